@@ -56,6 +56,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_FP32_VECTOR_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
 PEAK_HBM_GBPS = 8000.0
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
 WORKLOADS = {
     # name: (walls, grid, max_order, BASELINE.json config, scaling at N > 1)
     "cfg2": (50, 1024, 2, "configs[1]", "weak"),
@@ -178,6 +179,19 @@ def moving_transmitters(tx, n, step=0.01, seed=7):
         p = np.clip(p + rng.normal(0.0, step, 2), 0.05, 0.95)
         out.append(p.astype(np.float32))
     return out
+
+
+def dump_outputs(directory, power_map):
+    """--dump-outputs: what a caller of the timed path receives, as DIR/<name>.npy.  A map over DUMP_MAX_BYTES is cut to a
+    fixed, seeded sample of its rows (`power_map_rows`: their indices), so that two builds can be compared cell for cell."""
+    os.makedirs(directory, exist_ok=True)
+    power_map = np.ascontiguousarray(power_map, dtype=np.float32)
+    if power_map.nbytes > DUMP_MAX_BYTES:
+        n_rows = (DUMP_MAX_BYTES // 2) // (power_map.shape[1] * 4)
+        rows = np.sort(np.random.default_rng(1234).choice(power_map.shape[0], n_rows, replace=False))
+        np.save(os.path.join(directory, "power_map_rows.npy"), rows.astype(np.float64))
+        power_map = power_map[rows]
+    np.save(os.path.join(directory, "power_map.npy"), power_map)
 
 
 def launch_ranks(n, argv):
@@ -422,9 +436,13 @@ def main():
                     help="N > 1: priority of the stream the RCCL gather runs on beside the next sweep (lowest / default / highest): A/B")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the other modes / moving-TX / value+grad / parity legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the value map of the last timed step (rank 0: the assembled map) to DIR/*.npy, float32")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))  # before anything touches HIP
 
@@ -536,6 +554,8 @@ def main():
 
     wall, sequence_ms = timed(step, steps, warmup)
     ms_per_step = wall * 1e3 / steps
+    if args.dump_outputs and rank == 0:  # before anything else runs on the context: the map the last timed step left
+        dump_outputs(args.dump_outputs, shards.assemble(ctx.comm_get_gathered(world)) if gather else ctx.get_map())
     gather_cost = None
     if gather:  # what the RCCL gather adds to a step: the same steps without it (never the headline: the workload includes it)
         wall0, _ = timed(lambda: ctx.launch(params, tx), steps, warmup)
