@@ -56,6 +56,9 @@ D2D_DECLARE_MODE(MODE_SIG)
         default: return fn<MODE_SIG>(__VA_ARGS__);             \
     }
 
+static_assert(d2d_host::SWEEP_HARD == MODE_HARD && d2d_host::SWEEP_HSIG == MODE_HSIG && d2d_host::SWEEP_SIG == MODE_SIG,
+              "sweep_thresholds' modes are d2d::Mode");
+
 hipError_t launch_fwd(int mode, bool listed, bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     if (listed) { D2D_BY_MODE(launch_fwd_listed_m, stats, max_order, grid, lds, s, a) }
     D2D_BY_MODE(launch_fwd_m, stats, max_order, grid, lds, s, a)
@@ -178,9 +181,7 @@ struct d2d_ctx {
     int m = 0, n = 0;
     bool have_grid = false;
     DevBuf<float> d_X, d_Y, d_out;
-    DevBuf<unsigned long long> d_stats, d_shadow;
-    DevBuf<int> d_sched;                // patch schedule (its sort's histogram and cursors live behind d_shadow)
-    DevBuf<unsigned char> d_sched_key;
+    DevBuf<unsigned long long> d_stats;
 #ifdef D2D_AB_TIMELINE
     DevBuf<unsigned> d_timeline;
     long long timeline_n = 0;
@@ -188,8 +189,6 @@ struct d2d_ctx {
     bool tl_ring_on = false;
     long long tl_seq = 0;
 #endif
-    DevBuf<unsigned> d_cost;            // what every patch cost in the last culled sweep of this grid (ticks >> 6)
-    long long cost_tiles = 0;           // 0 = no history (scene, grid or candidate mask changed since)
     DevBuf<int> d_sched_override;       // diagnostic: a caller-supplied schedule (d2d_debug_set_schedule)
     long long sched_override_n = 0;
     bool use_cost_history = true;
@@ -262,46 +261,43 @@ struct d2d_ctx {
     long long fb_hint = 0;             // patches the last such launch left to the enumerating kernel
     float rl_vkey[6] = {-1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // validity parameters of the last launch with lists
     long long rl_launches = 0;         // launches with lists since the plan last changed (the read-back thins out: 1, 2, 3, then every 16th)
-    DevBuf<unsigned long long> d_rl_pool;
     DevBuf<float4> d_rl_box;           // bounding boxes of the leaf regions, then of the top regions (region_box_kernel)
     long long rl_box_key[4] = {-1, 0, 0, 0};  // grid version, leaf R, top R (0: one level) the boxes were built for
     long long grid_version = 0;        // bumped by d2d_set_grid
-    DevBuf<int> d_rl_next;             // [max_chunks]
-    DevBuf<int> d_rl_idx;              // first / cnt arrays of both levels, all orders
-    DevBuf<int> d_rl_meta;             // the queue of patches left to the enumerating kernel
-    int* rl_meta_ptr = nullptr;        // (inside d_shadow) [0] queue length, [1] pool head, [2 ..) leaf region flags
-    DevBuf<d2d::RegionLists> d_rl;     // the descriptor the sweep kernels read
-    d2d::RegionLists rl_host;          // what d_rl holds
     d2d_host::RegionPlan rl_plan;      // of the last launch that built lists (rl_plan.on) -- d2d_debug_region_stats
     int rl_max_order = 0;
-    bool rl_host_valid = false;
     // Pipelined preparation.  Everything a launch rebuilds before its sweep kernel (shadow masks, region lists, patch
-    // schedule) lives in two sets; the members above are the set of the current launch, `spare` is the other one (they
-    // are swapped at the start of every sweep launch).  The preparation of launch k+1 runs on aux_stream into set
-    // (k+1) mod 2 while the sweep kernel of launch k still reads set k mod 2 on the main stream: back-to-back launches
-    // (many transmitters, the benchmark) hide it completely.  The work history a schedule is sorted by is then two
-    // launches old instead of one.
+    // schedule) lives in a PrepSet: `cur` is the set of the current launch, spare_sets[] the others (they rotate at the
+    // start of every pipelined sweep launch).  The preparation of launch k+1 runs on aux_stream into its own set while the
+    // sweep kernel of launch k still reads another one on the main stream: back-to-back launches (many transmitters, the
+    // benchmark) hide it completely.  The work history a schedule is sorted by is then a few launches old instead of one.
     struct PrepSet {
-        DevBuf<unsigned long long> d_shadow, d_rl_pool;
-        DevBuf<int> d_sched, d_rl_next, d_rl_idx, d_rl_meta;
+        DevBuf<unsigned long long> d_shadow;  // shadow masks, then the schedule sort's histogram and cursors, then the lists' meta
+        DevBuf<int> d_sched;                  // patch schedule
         DevBuf<unsigned char> d_sched_key;
-        DevBuf<unsigned> d_cost;
-        DevBuf<d2d::RegionLists> d_rl;
-        d2d::RegionLists rl_host;
+        DevBuf<unsigned> d_cost;              // what every patch cost in the last culled sweep of this grid (ticks >> 6)
+        long long cost_tiles = 0;             // 0 = no history (scene, grid or candidate mask changed since)
+        DevBuf<unsigned long long> d_rl_pool;
+        DevBuf<int> d_rl_next;                // [max_chunks]
+        DevBuf<int> d_rl_idx;                 // first / cnt arrays of both levels, all orders
+        DevBuf<int> d_rl_meta;                // the queue of patches left to the enumerating kernel
+        int* rl_meta_ptr = nullptr;           // (inside d_shadow) [0] queue length, [1] pool head, [2 ..) leaf region flags
+        DevBuf<d2d::RegionLists> d_rl;        // the descriptor the sweep kernels read
+        d2d::RegionLists rl_host;             // what d_rl holds
         bool rl_host_valid = false;
-        long long cost_tiles = 0;
-        int* rl_meta_ptr = nullptr;
-        hipEvent_t ev_swept = nullptr;  // recorded on the main stream behind the sweep that read this set
+        hipEvent_t ev_swept = nullptr;        // recorded on the main stream behind the sweep that read this set
         bool swept_pending = false;
     };
+    PrepSet cur;
     static constexpr int N_SPARE = 2;   // three sets in all: the preparation runs freely ahead on its own streams (with two sets it
                                         // could not start before the sweep before last had finished, i.e. at the very moment the
                                         // previous sweep starts, and the sweep then waited for the tail of the chain: 0.111 ->
                                         // 0.107 ms per step at cfg2 once the sort had left the chain)
     PrepSet spare_sets[N_SPARE];        // [0] the oldest (next to be reused) .. [N_SPARE - 1] the previous launch's
-    PrepSet& spare = spare_sets[N_SPARE - 1];
-    hipEvent_t ev_swept = nullptr;      // (the current set's)
-    bool swept_pending = false;
+    template <class F> void for_each_set(F f) {
+        f(cur);
+        for (PrepSet& sp : spare_sets) f(sp);
+    }
     hipEvent_t ev_prep = nullptr;       // recorded on aux_stream behind a launch's preparation
     bool pipeline = true;
     long long unpiped_max_tiles = 256; // "unpiped_max_tiles": launches of orders <= 1 over at most this many patches prepare on the sweep's own stream (latency of a small call)
@@ -632,9 +628,9 @@ int d2d_create(int device, d2d_ctx** out) {
     if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence);
     if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming | hipEventDisableSystemFence);
     if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_swept, hipEventDisableTiming | hipEventDisableSystemFence);
-    for (int i = 0; i < d2d_ctx::N_SPARE; ++i)
-        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->spare_sets[i].ev_swept, hipEventDisableTiming | hipEventDisableSystemFence);
+    c->for_each_set([&](d2d_ctx::PrepSet& sp) {
+        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&sp.ev_swept, hipEventDisableTiming | hipEventDisableSystemFence);
+    });
     if (e1 == hipSuccess) e1 = hipHostMalloc(reinterpret_cast<void**>(&c->h_meta), 2 * sizeof(int), hipHostMallocDefault);
     if (e1 != hipSuccess) {
         delete c;
@@ -672,12 +668,8 @@ void d2d_destroy(d2d_ctx* c) {
     c->d_Y.release();
     c->d_out.release();
     c->d_stats.release();
-    c->d_shadow.release();
-    c->d_sched.release();
-    c->d_hidden.release(); c->d_rl_pool.release(); c->d_rl_box.release(); c->d_rl_next.release(); c->d_rl_idx.release(); c->d_rl_meta.release(); c->d_rl.release();
-    c->d_sched_key.release();
+    c->d_hidden.release(); c->d_rl_box.release();
     c->d_sched_override.release();
-    c->d_cost.release();
     c->d_heavy_list.release(); c->d_heavy_cnt.release(); c->d_heavy_done.release();
     c->d_pair.release();
     c->d_grad.release(); c->d_cot.release(); c->d_partial.release(); c->d_vjp.release();
@@ -695,14 +687,12 @@ void d2d_destroy(d2d_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-    if (c->ev_swept) (void)hipEventDestroy(c->ev_swept);
-    for (int i = 0; i < d2d_ctx::N_SPARE; ++i) {
-        d2d_ctx::PrepSet& sp = c->spare_sets[i];
+    c->for_each_set([](d2d_ctx::PrepSet& sp) {
         if (sp.ev_swept) (void)hipEventDestroy(sp.ev_swept);
         sp.d_shadow.release(); sp.d_rl_pool.release(); sp.d_sched.release(); sp.d_rl_next.release();
         sp.d_rl_idx.release(); sp.d_rl_meta.release(); sp.d_sched_key.release(); sp.d_cost.release();
         sp.d_rl.release();
-    }
+    });
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
     if (c->sort_stream) (void)hipStreamDestroy(c->sort_stream);
     if (c->scan_stream) { (void)hipStreamSynchronize(c->scan_stream); (void)hipStreamDestroy(c->scan_stream); }
@@ -767,8 +757,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->cust_C = -1;               // (a host-evaluated path function's rows belong to the paths of the previous scene)
     c->have_vjp = false;          // d_vjp was sized for (and computed from) the previous scene
     c->have_kernel_time = false;
-    c->cost_tiles = 0;  // the patch-cost history describes another sweep
-    for (int i = 0; i < d2d_ctx::N_SPARE; ++i) c->spare_sets[i].cost_tiles = 0;
+    c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
     c->hidden_valid = false;
     c->hidden_seen[0] = -1.0;
@@ -799,8 +788,7 @@ int d2d_set_candidate_mask(d2d_ctx* c, const uint8_t* allowed) {
         if (same) return D2D_OK;  // the mask in place already
     }
     c->cust_C = -1;     // (... and to the candidates of the previous mask)
-    c->cost_tiles = 0;  // the patch-cost history describes another sweep
-    for (int i = 0; i < d2d_ctx::N_SPARE; ++i) c->spare_sets[i].cost_tiles = 0;
+    c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     int rc = set_device(c);
     if (rc) return rc;
     if (allowed) c->allowed.assign(allowed, allowed + c->N);
@@ -876,8 +864,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->grid_reuses += 1;
     } else {
         c->have_grid = false;
-        c->cost_tiles = 0;  // the patch-cost history describes another sweep
-        for (int i = 0; i < d2d_ctx::N_SPARE; ++i) c->spare_sets[i].cost_tiles = 0;
+        c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
         c->grid_version += 1;  // ... and the regions' bounding boxes another grid
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
@@ -1157,35 +1144,58 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
     return D2D_OK;
 }
 
-static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsigned long long* d_stats, int grad_mode = 0) {
-    if (!c || !tx) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before a sweep");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before a sweep");
-    c->have_kernel_time = false;  // whatever this launch turns out to be, the previous launch's kernel time is stale
-    d2d_params p_custom;
-    if (p->fun_id == D2D_FUN_CUSTOM) {
-        // a host-evaluated path function (d2d_set_path_fun_values): the exhaustive value+grad kernel walks every candidate in the
-        // reference's order, which is the order the host's rows come in
-        if (!grad_mode) return fail(D2D_ERR_UNSUPPORTED, "fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only");
-        if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT) return opt_sweep_launch(c, p, tx, grad_mode);
-        long long want = 0;
-        for (int k = p->min_order; k <= p->max_order; ++k) {
-            long long ck = 1;
-            for (int i = 0; i < k; ++i) ck *= (i == 0) ? (long long)c->cw.size() : (long long)c->cw.size() - 1;
-            want += ck;
-        }
-        if (c->cust_C != want)
-            return fail(D2D_ERR_STATE, "d2d_set_path_fun_values holds %lld candidates, this sweep walks %lld", c->cust_C, want);
-        p_custom = *p;
-        p_custom.strict_nan = 1;
-        p = &p_custom;
+}  // extern "C"
+
+namespace {
+
+// ---- ImagePath sweeps: sweep_launch and its steps ------------------------------------------------------------------
+// What the steps of one launch share.  sweep_launch sets the inputs; take_prep_set and sweep_args the rest.
+struct Sweep {
+    const d2d_params* p;
+    const float* tx;
+    unsigned long long* d_stats;  // instrumented build (d2d_power_map_stats): its counters
+    int grad_mode;                // 0 values, 1 value+grad, 2 ... and the scene VJP
+    int tiles_x, tiles_y;
+    long long tiles;
+    bool piped = false;           // the preparation runs on aux_stream into a rotated set
+    bool set_was_swept = false;   // the set this launch takes was read by a sweep that may still be running (its ev_swept says when)
+    hipStream_t ps = nullptr;     // where this launch's preparation runs
+    d2d_host::SweepThresholds th;
+    bool txg = false, txg_culled = false;
+    dim3 grid_patches;            // one single-wave workgroup per 8 x 8 patch
+    d2d::SweepArgs a;
+};
+// The window of the shadow masks (certainly hit, parametric bins); the hidden masks reuse it.
+struct MaskWindow {
+    bool ok = false;
+    double in_lo = 0.0, in_hi = 0.0, dom_lo = 0.0, dom_w = 0.0;
+};
+// What the preparation steps found out.
+struct Prep {
+    bool zeroed = false;              // d_shadow's counters and list meta were zeroed with the shadow masks
+    MaskWindow win;
+    bool queue_impossible = false;    // no patch can be left to the enumerating kernel (the queue walker is not launched)
+    bool sched_from_history = false;  // the schedule's keys are measured (work history or list lengths), not the proxy
+};
+
+// a host-evaluated path function (d2d_set_path_fun_values): the exhaustive value+grad kernel walks every candidate in the
+// reference's order, which is the order the host's rows come in
+static int custom_fun_params(d2d_ctx* c, const d2d_params* p, d2d_params* out) {
+    long long want = 0;
+    for (int k = p->min_order; k <= p->max_order; ++k) {
+        long long ck = 1;
+        for (int i = 0; i < k; ++i) ck *= (i == 0) ? (long long)c->cw.size() : (long long)c->cw.size() - 1;
+        want += ck;
     }
-    if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT) {
-        if (d_stats) return fail(D2D_ERR_UNSUPPORTED, "the optimiser-based solvers have no instrumented build");
-        return opt_sweep_launch(c, p, tx, grad_mode);
-    }
+    if (c->cust_C != want)
+        return fail(D2D_ERR_STATE, "d2d_set_path_fun_values holds %lld candidates, this sweep walks %lld", c->cust_C, want);
+    *out = *p;
+    out->strict_nan = 1;
+    return D2D_OK;
+}
+
+// what an ImagePath sweep refuses from its arguments alone
+static int check_image_sweep(d2d_ctx* c, const d2d_params* p, const unsigned long long* d_stats) {
     if (p->solver != D2D_SOLVER_IMAGE) return fail(D2D_ERR_INVALID, "unknown solver %d", p->solver);
     if (p->max_order >= 1)
         for (int j = 0; j < c->N; ++j)
@@ -1195,62 +1205,49 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
                             "object %d has kind %d", j, (int)c->kind[j]);
     for (int j = 0; j < c->N; ++j)
         if (c->kind[j] == D2D_VERTEX) return fail(D2D_ERR_UNSUPPORTED, "Vertex objects need the MinPath/FermatPath solver");
-    if ((rc = set_device(c))) return rc;
-    if ((rc = upload_occl(c, p->patch))) return rc;
+    if (p->grid_role == D2D_GRID_TX && d_stats) return fail(D2D_ERR_UNSUPPORTED, "the instrumented build covers the RX-grid kernel only");
+    return D2D_OK;
+}
 
-    // Pipelined preparation (see d2d_ctx::PrepSet): this launch takes the set the launch before the previous one used,
-    // and builds into it on the side stream, which first waits for the sweep that read it last.
-    // (instrumented launches prepare on the main stream: their counters are zeroed there, and the list kernels add to them)
-    // (a lone call has no previous sweep to hide its preparation behind; preparing on the sweep stream whenever that stream is idle
-    // was measured: launch -> synchronise 0.146 -> 0.137 ms at 300^2, but back-to-back launches whose host runs ahead of the GPU
-    // only now and then lose 4-8 %: not kept)
-    // Small launches without region lists ("unpiped_max_tiles", orders <= 1): a grid of a few patches is all launch latency; its one
-    // preparation kernel (the shadow masks) takes microseconds and gains nothing from running beside a previous sweep, while the fork
-    // to the side stream and the join back cost two cross-stream events per launch.  They prepare on the sweep's own stream: the
-    // reference's own benchmark workload (basic_scene, scene.grid(n <= 50), orders 0..1) 45 -> 37.5 us launch -> synchronise, back-to-back
-    // launches unchanged at 24 us (scripts/small_launch_ab.py).  With lists (orders >= 2) a lone call gains the same 8 us but
-    // back-to-back launches lose 30 - 40 us (71 -> 104 us at 128^2): those stay pipelined.  A context that changes kind drains its
-    // streams once, like the "pipeline" option does.
-    const long long tiles_early = (long long)((c->n + d2d::TILE_W - 1) / d2d::TILE_W) * ((c->m + d2d::TILE_H - 1) / d2d::TILE_H);
-    const bool small = c->pipeline && p->max_order <= 1 && tiles_early <= c->unpiped_max_tiles;
+// Pipelined preparation (see d2d_ctx::PrepSet): this launch takes the set the launch before the previous one used,
+// and builds into it on the side stream, which first waits for the sweep that read it last.
+// (instrumented launches prepare on the main stream: their counters are zeroed there, and the list kernels add to them)
+// (a lone call has no previous sweep to hide its preparation behind; preparing on the sweep stream whenever that stream is idle
+// was measured: launch -> synchronise 0.146 -> 0.137 ms at 300^2, but back-to-back launches whose host runs ahead of the GPU
+// only now and then lose 4-8 %: not kept)
+// Small launches without region lists ("unpiped_max_tiles", orders <= 1): a grid of a few patches is all launch latency; its one
+// preparation kernel (the shadow masks) takes microseconds and gains nothing from running beside a previous sweep, while the fork
+// to the side stream and the join back cost two cross-stream events per launch.  They prepare on the sweep's own stream: the
+// reference's own benchmark workload (basic_scene, scene.grid(n <= 50), orders 0..1) 45 -> 37.5 us launch -> synchronise, back-to-back
+// launches unchanged at 24 us (scripts/small_launch_ab.py).  With lists (orders >= 2) a lone call gains the same 8 us but
+// back-to-back launches lose 30 - 40 us (71 -> 104 us at 128^2): those stay pipelined.  A context that changes kind drains its
+// streams once, like the "pipeline" option does.
+static int take_prep_set(d2d_ctx* c, Sweep& s) {
+    const bool small = c->pipeline && s.p->max_order <= 1 && s.tiles <= c->unpiped_max_tiles;
     if (small != c->last_small) {
         if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->aux_stream) HIP_TRY(hipStreamSynchronize(c->aux_stream));
         if (c->sort_stream) HIP_TRY(hipStreamSynchronize(c->sort_stream));
-        c->swept_pending = false;
-        for (int i = 0; i < d2d_ctx::N_SPARE; ++i) c->spare_sets[i].swept_pending = false;
+        c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.swept_pending = false; });
         c->last_small = small;
     }
-    const bool piped = c->pipeline && c->aux_stream != nullptr && d_stats == nullptr && !small;
-    bool set_was_swept = false;  // the set this launch takes was read by a sweep that may still be running (ev_swept says when it is through)
-    if (piped) {
+    s.piped = c->pipeline && c->aux_stream != nullptr && s.d_stats == nullptr && !small;
+    if (s.piped) {
         // rotate: the oldest set becomes the current one, the current one the newest spare
-        auto swap_with = [&](d2d_ctx::PrepSet& o) {
-            std::swap(c->d_shadow, o.d_shadow);
-            std::swap(c->d_rl_pool, o.d_rl_pool);
-            std::swap(c->d_sched, o.d_sched);
-            std::swap(c->d_rl_next, o.d_rl_next);
-            std::swap(c->d_rl_idx, o.d_rl_idx);
-            std::swap(c->d_rl_meta, o.d_rl_meta);
-            std::swap(c->d_sched_key, o.d_sched_key);
-            std::swap(c->d_cost, o.d_cost);
-            std::swap(c->d_rl, o.d_rl);
-            std::swap(c->rl_host, o.rl_host);
-            std::swap(c->rl_host_valid, o.rl_host_valid);
-            std::swap(c->cost_tiles, o.cost_tiles);
-            std::swap(c->rl_meta_ptr, o.rl_meta_ptr);
-            std::swap(c->ev_swept, o.ev_swept);
-            std::swap(c->swept_pending, o.swept_pending);
-        };
-        swap_with(c->spare_sets[0]);                                   // cur <- [0] (the oldest), [0] <- cur
-        for (int i = 0; i + 1 < d2d_ctx::N_SPARE; ++i) std::swap(c->spare_sets[i], c->spare_sets[i + 1]);  // .. which moves to the newest place
-        set_was_swept = c->swept_pending;
-        if (c->swept_pending) HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_swept, 0));
-        c->swept_pending = false;
+        std::swap(c->cur, c->spare_sets[0]);
+        for (int i = 0; i + 1 < d2d_ctx::N_SPARE; ++i) std::swap(c->spare_sets[i], c->spare_sets[i + 1]);
+        s.set_was_swept = c->cur.swept_pending;
+        if (c->cur.swept_pending) HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->cur.ev_swept, 0));
+        c->cur.swept_pending = false;
     }
-    hipStream_t const ps = piped ? c->aux_stream : c->stream;  // where this launch's preparation runs
+    s.ps = s.piped ? c->aux_stream : c->stream;
+    return D2D_OK;
+}
 
-    d2d::SweepArgs a;
+// the scalar SweepArgs: buffers of the scene and the grid, parameters, thresholds
+static int sweep_args(d2d_ctx* c, Sweep& s) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
     memset(&a, 0, sizeof a);
     a.occl = c->d_occl.p;
     a.refl = c->d_refl.p;
@@ -1263,609 +1260,600 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     a.out = c->d_out.p;
     a.m = c->m;
     a.n = c->n;
-    a.txx = tx[0];
-    a.txy = tx[1];
+    a.txx = s.tx[0];
+    a.txy = s.tx[1];
     a.min_order = p->min_order;
     a.max_order = p->max_order;
     a.alpha = p->alpha;
     a.tol = p->tol;
     a.seg_lo = -p->seg_tol;
     a.seg_hi = 1.0f + p->seg_tol;
-    // Filter thresholds: the soft window is where some activation of t is not exactly saturated
-    // to "outside": hard -> [-tol, 1+tol]; hard_sigmoid -> widened by 3/alpha; sigmoid -> by 89/alpha
-    // (exp(89) overflows fp32, 1/(1+inf) == 0).  1e-5 relative slack covers every rounding in the
-    // filter's own arithmetic (a few ulp).
-    double widen = 0.0;
-    int mode = d2d::MODE_HARD;
-    if (p->approx) {
-        mode = (p->act == D2D_ACT_HARD_SIGMOID) ? d2d::MODE_HSIG : d2d::MODE_SIG;
-        widen = ((mode == d2d::MODE_HSIG) ? 3.0 : 89.0) / (double)p->alpha;
-    }
-    const double widen_in = !p->approx ? 0.0 : ((mode == d2d::MODE_HSIG) ? 3.0 : 17.5) / (double)p->alpha * (1.0 + 1e-5);
-    // (sigmoid, forward sweeps: an occlusion test only enters the map through 1 - max_j sigmoid(z_j), and sigmoid(z) < 2^-25
-    // -- z < -17.33 -- leaves 1 - hit at exactly 1.0f, as no test at all would: the divide-free filter may drop what is
-    // certainly below -17.5 instead of what is certainly below -89.  The value+grad build keeps the wide window: it records
-    // which test carries the max.)
-    const double widen_flt = (mode == d2d::MODE_SIG && !grad_mode && c->sig_narrow_filter) ? 17.5 / (double)p->alpha : widen;
-    double lo = -((double)p->seg_tol + widen_flt);
-    double hi = 1.0 + (double)p->seg_tol + widen_flt;
-    a.flt_lo = (float)(lo * (1.0 + 1e-5) - 1e-30);
-    a.flt_hi = (float)(hi * (1.0 + 1e-5) + 1e-30);
-    // on_objects is exactly 0 / False once s < -widen or s > 1 + widen (same saturation argument)
-    a.on_lo = (float)(-widen * (1.0 + 1e-5) - 1e-30);
-    a.on_hi = (float)((1.0 + widen) * (1.0 + 1e-5) + 1e-30);
-    // loss certificate threshold (d2d_kernels.hpp): hard -> loss < tol decides; approx -> tol - loss must round to tol
-    a.loss_skip = -1.0f;
-    if (p->tol > 1e-30f && std::isfinite(p->tol)) {
-        if (!p->approx) a.loss_skip = p->tol * 0.999f;
-        else a.loss_skip = 0.49f * (p->tol - std::nextafterf(p->tol, 0.0f));
-    }
-    for (int k = 0; k <= D2D_MAX_ORDER; ++k) a.fnum[k] = integer_pow(p->r_coef, k);
-    a.h2 = p->height * p->height;
-    // sigmoid validity: an upper bound of |fun| lets the kernels skip contributions that cannot change the running sum
-    a.sig_l2f = 1e30f;
-    a.sig_mono = 1;
-    for (int k = p->min_order; k <= p->max_order; ++k) a.sig_mono = a.sig_mono && (a.fnum[k] >= 0.0f || p->fun_id != D2D_FUN_RECEIVED_POWER);
-    if (p->fun_id == D2D_FUN_ONE) {
-        a.sig_l2f = 0.0f;
-    } else if (p->fun_id == D2D_FUN_RECEIVED_POWER && a.h2 > 0.0f && std::isfinite(a.h2)) {
-        float fm = 0.0f;  // received_power = r_coef^k / (h^2 + r^2) <= |r_coef|^k / h^2
-        bool ok = true;
-        for (int k = p->min_order; k <= p->max_order; ++k) {
-            const float f = std::fabs(a.fnum[k]) / a.h2;
-            ok = ok && std::isfinite(f);
-            fm = std::fmax(fm, f);
-        }
-        if (ok && fm > 0.0f) a.sig_l2f = std::log2(fm) + 1e-3f;
-        else if (ok) a.sig_l2f = -1e30f;  // fun == 0 throughout
-    }
+    s.th = d2d_host::sweep_thresholds(*p, s.grad_mode != 0, c->sig_narrow_filter != 0);
+    a.flt_lo = s.th.flt_lo;
+    a.flt_hi = s.th.flt_hi;
+    a.on_lo = s.th.on_lo;
+    a.on_hi = s.th.on_hi;
+    a.loss_skip = s.th.loss_skip;
+    for (int k = 0; k <= D2D_MAX_ORDER; ++k) a.fnum[k] = s.th.fnum[k];
+    a.h2 = s.th.h2;
+    a.sig_l2f = s.th.sig_l2f;
+    a.sig_mono = s.th.sig_mono;
     a.fun_id = p->fun_id;
     a.cust_f = c->d_cust_f.p;
     a.cust_pb = c->d_cust_pb.p;
     a.cust_cells = (long)c->m * c->n;
-    if (p->fun_id == D2D_FUN_CUSTOM) a.sig_mono = 0;  // (values of any sign)
     a.out_mode = p->out_mode;
     a.patch = p->patch;
-    a.stats = d_stats;
-    a.wave_cycles = (d_stats && c->want_wave_cycles) ? d_stats + D2D_NUM_STATS : nullptr;
-
-    const int tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
-    const int tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    if (tiles > 0x7fffffffLL) return fail(D2D_ERR_INVALID, "grid too large: %lld tiles", tiles);
-    dim3 grid((unsigned)tiles);
-    dim3 grid_patches((unsigned)tiles);  // one single-wave workgroup per 8 x 8 patch
-    const bool txg = p->grid_role == D2D_GRID_TX;
-    // first-segment shadow coverage (RX grids: the fixed end point is the transmitter)
-    a.shadow = nullptr;
-    a.shadow_dperp = 0.0f;
-    a.pair = nullptr;
-    a.pair_dperp = 0.0f;
-    a.pair_prefix_ok = 0;
-    bool prep_zeroed = false;
-    bool m_masks_ok = false;  // the masks' certified window and bins (set with the shadow masks below)
-    double m_in_lo = 0.0, m_in_hi = 0.0, m_dom_lo = 0.0, m_dom_w = 0.0;
-    // A step of the backward scan with un == 0 (the line to the image parallel to the wall, geometry.py:1105) leaves a
-    // zero-length segment, loss >= 1 (0.999 with roundings): is such a path exactly invalid under this tol / activation?
-    const double x_deg = (double)p->tol - 0.999;  // tol - loss at best
-    const bool degenerate_invalid = !p->approx ? (p->tol <= 0.5f)
-                                    : (mode == d2d::MODE_HSIG ? ((double)p->alpha * x_deg + 3.0 <= -1e-3) : ((double)p->alpha * x_deg <= -89.5));
+    a.stats = s.d_stats;
+    a.wave_cycles = (s.d_stats && c->want_wave_cycles) ? s.d_stats + D2D_NUM_STATS : nullptr;
+    if (s.tiles > 0x7fffffffLL) return fail(D2D_ERR_INVALID, "grid too large: %lld tiles", s.tiles);
+    s.grid_patches = dim3((unsigned)s.tiles);
+    s.txg = p->grid_role == D2D_GRID_TX;
     // TX grid: culled kernels -- unless a degenerate path can count.  Their culling walks the chain from the FIXED end (images of
     // the receiver, first the wall next to the cell), which is the exact chain's LAST step: where an earlier exact step hits
     // un == 0 the exact points are not the geometric ones the culling reasons about (RX grids cull along the exact chain's own
     // order and stop at its poles).  Found by scripts/fuzz_parity.py (seed 4003, case 1295: sigmoid, alpha = 10, tol = 0.5 --
     // a zero-length segment still leaves sigmoid(-5) -- walls on a lattice); tests/test_gpu_forward.py keeps the case.
-    const bool txg_culled = txg && !c->txg_exhaustive && !(grad_mode && p->strict_nan) && degenerate_invalid;
-    if (txg && !c->txg_exhaustive && !(grad_mode && p->strict_nan) && !degenerate_invalid) ++c->txg_fallbacks;
-    if ((!txg || txg_culled) && c->N >= 2 && p->max_order >= 1) {
-        // [N] masks, then the {histogram, cursors} of the patch schedule's counting sort, then what the region lists need
-        // zeroed per launch ({queue length, pool head}, one flag per leaf region): one memset for all of it
-        const size_t rl_regions = (size_t)((tiles_x + c->region_size - 1) / c->region_size) * (size_t)((tiles_y + c->region_size - 1) / c->region_size);
-        // (a multiple of 256 bytes: the runtime fills odd tails with a second kernel)
-        const size_t zero_words = ((size_t)c->N + d2d::SCHED_KEYS + (2 + rl_regions + 1) / 2 + 31) & ~(size_t)31;
-        if ((rc = c->d_shadow.ensure(zero_words))) return rc;
-        if (!c->prep_fused) {
-            hipLaunchKernelGGL(d2d::zero_words_kernel, dim3((unsigned)((zero_words + 255) / 256)), dim3(256), 0, ps, c->d_shadow.p, (long)zero_words);
-            HIP_TRY(hipEventRecord(c->ev_fork, ps));  // (the schedule's sort may start here, on a stream of its own)
-        }
-        prep_zeroed = true;
-        // window where a test is certainly "hit" (hard) / exactly saturated to 1 (approx): shrink [-tol, 1+tol] by widen
-        const double in_lo = -(double)p->seg_tol + widen_in, in_hi = 1.0 + (double)p->seg_tol - widen_in;
-        float ext = std::fmax(std::fmax(c->scene_absmax, c->grid_absmax), std::fmax(std::fabs(tx[0]), std::fabs(tx[1])));
-        bool pair_ext_ok = false;
-        const bool masks_ok = in_hi > in_lo + 1e-3 && std::isfinite(ext) && ext > 0.0f;
-        // bins span the parametric window in which on_objects is not exactly 0 (+ a little)
-        const double dom_lo = (double)a.on_lo - 2e-3, dom_hi = (double)a.on_hi + 2e-3;
-        const double dom_w = (dom_hi - dom_lo) / 64.0;
-        const float dperp = 4096.0f * 1.1920929e-07f * (masks_ok ? ext : 1.0f) * (float)(p->max_order + 1);
-        if (c->prep_fused) {
-            // one kernel: the masks (stored, not OR-ed: nothing to zero in front) and the zeroing of everything behind them
-            const long n_zero = (long)zero_words - c->N;
-            hipLaunchKernelGGL(d2d::shadow_fill_kernel, dim3((unsigned)(c->N + (n_zero + 255) / 256)), dim3(256), 0, ps, c->d_occl.p, c->d_refl.p,
-                               c->d_kind.p, c->N, tx[0], tx[1], (float)(in_lo + 1e-4), (float)(in_hi - 1e-4), dperp, (float)dom_lo, (float)dom_w,
-                               masks_ok ? 1 : 0, c->d_shadow.p, c->d_shadow.p + c->N, n_zero);
+    const bool txg_cullable = s.txg && !c->txg_exhaustive && !(s.grad_mode && p->strict_nan);
+    s.txg_culled = txg_cullable && s.th.degenerate_invalid;
+    if (txg_cullable && !s.th.degenerate_invalid) ++c->txg_fallbacks;
+    return D2D_OK;
+}
+
+// (a sweep that reads the old masks may still be in flight on the main stream)
+static int wait_spare_sweeps(d2d_ctx* c, hipStream_t st) {
+    for (d2d_ctx::PrepSet& sp : c->spare_sets)
+        if (sp.swept_pending) HIP_TRY(hipStreamWaitEvent(st, sp.ev_swept, 0));
+    return D2D_OK;
+}
+
+// wall-to-wall masks for the segments between two interaction points (orders >= 2): no end point involved,
+// so they depend on the scene and the validity mode only and are kept until one of those changes
+static int prep_pair_masks(d2d_ctx* c, Sweep& s, const MaskWindow& w, float ext) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
+    int rc;
+    bool pair_ext_ok = false;
+    if (p->max_order >= 2 && c->N >= 3 && c->N <= 256 && c->use_pair_masks && std::isfinite(c->scene_absmax) && c->scene_absmax > 0.0f) {
+        const float pdperp = 4096.0f * 1.1920929e-07f * c->scene_absmax * (float)(D2D_MAX_ORDER + 1);
+        const float key[6] = {p->patch, p->seg_tol, (float)p->approx, (float)p->act, p->alpha, pdperp};
+        if (!c->pair_valid || std::memcmp(key, c->pair_key, sizeof(key)) != 0) {
+            const size_t n2 = (size_t)c->N * c->N;
+            if ((rc = c->d_pair.ensure(n2))) return rc;
+            if (s.piped && (rc = wait_spare_sweeps(c, s.ps))) return rc;
+            HIP_TRY(hipMemsetAsync(c->d_pair.p, 0, n2 * sizeof(unsigned long long), s.ps));
+            const long long waves = (long long)c->N * c->N * c->N;
+            hipLaunchKernelGGL(d2d::pair_shadow_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s.ps, c->d_occl.p,
+                               c->d_refl.p, c->d_kind.p, c->N, (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), pdperp,
+                               (float)w.dom_lo, (float)(w.dom_w * 8.0), c->d_pair.p);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(c->ev_fork, ps));  // (the sort of a big launch needs its counters zeroed: it may start here)
+            std::memcpy(c->pair_key, key, sizeof(key));
+            c->pair_valid = true;
         }
-        m_masks_ok = masks_ok; m_in_lo = in_lo; m_in_hi = in_hi; m_dom_lo = dom_lo; m_dom_w = dom_w;
-        if (masks_ok) {
-            if (!c->prep_fused) {
-                const int pairs = c->N * c->N;
-                hipLaunchKernelGGL(d2d::shadow_tx_kernel, dim3((unsigned)pairs), dim3(64), 0, ps, c->d_occl.p,
-                                   c->d_refl.p, c->d_kind.p, c->N, tx[0], tx[1], (float)(in_lo + 1e-4), (float)(in_hi - 1e-4), dperp,
-                                   (float)dom_lo, (float)dom_w, c->d_shadow.p);
-                HIP_TRY(hipGetLastError());
-            }
-            a.shadow = c->d_shadow.p;
-            a.shadow_dperp = dperp;
-            a.shadow_lo = (float)dom_lo;
-            a.shadow_inv = (float)(1.0 / dom_w);
-            // wall-to-wall masks for the segments between two interaction points (orders >= 2): no end point involved,
-            // so they depend on the scene and the validity mode only and are kept until one of those changes
-            if (p->max_order >= 2 && c->N >= 3 && c->N <= 256 && c->use_pair_masks && std::isfinite(c->scene_absmax) && c->scene_absmax > 0.0f) {
-                const float pdperp = 4096.0f * 1.1920929e-07f * c->scene_absmax * (float)(D2D_MAX_ORDER + 1);
-                const float key[6] = {p->patch, p->seg_tol, (float)p->approx, (float)p->act, p->alpha, pdperp};
-                if (!c->pair_valid || std::memcmp(key, c->pair_key, sizeof(key)) != 0) {
-                    const size_t n2 = (size_t)c->N * c->N;
-                    if ((rc = c->d_pair.ensure(n2))) return rc;
-                    // (a sweep that reads the old masks may still be in flight on the main stream)
-                    for (int i = 0; piped && i < d2d_ctx::N_SPARE; ++i)
-                        if (c->spare_sets[i].swept_pending) HIP_TRY(hipStreamWaitEvent(ps, c->spare_sets[i].ev_swept, 0));
-                    HIP_TRY(hipMemsetAsync(c->d_pair.p, 0, n2 * sizeof(unsigned long long), ps));
-                    const long long waves = (long long)c->N * c->N * c->N;
-                    hipLaunchKernelGGL(d2d::pair_shadow_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ps, c->d_occl.p,
-                                       c->d_refl.p, c->d_kind.p, c->N, (float)(in_lo + 1e-4), (float)(in_hi - 1e-4), pdperp,
-                                       (float)dom_lo, (float)(dom_w * 8.0), c->d_pair.p);
-                    HIP_TRY(hipGetLastError());
-                    std::memcpy(c->pair_key, key, sizeof(key));
-                    c->pair_valid = true;
-                }
-                a.pair = c->d_pair.p;
-                a.pair_dperp = pdperp;
-                pair_ext_ok = ext <= 8.0f * c->scene_absmax;  // interaction points of a valid path stay within pdperp of their walls
-            }
-            // a candidate with un == 0 in some step has a zero-length segment, loss >= 1: is it exactly invalid?
-            a.shadow_prefix_ok = degenerate_invalid ? 1 : 0;
-            a.pair_prefix_ok = (a.pair && pair_ext_ok && a.shadow_prefix_ok) ? 1 : 0;
+        a.pair = c->d_pair.p;
+        a.pair_dperp = pdperp;
+        pair_ext_ok = ext <= 8.0f * c->scene_absmax;  // interaction points of a valid path stay within pdperp of their walls
+    }
+    // a candidate with un == 0 in some step has a zero-length segment, loss >= 1: is it exactly invalid?
+    a.shadow_prefix_ok = s.th.degenerate_invalid ? 1 : 0;
+    a.pair_prefix_ok = (a.pair && pair_ext_ok && a.shadow_prefix_ok) ? 1 : 0;
+    return D2D_OK;
+}
+
+// first-segment shadow coverage (RX grids: the fixed end point is the transmitter) and the pair masks
+static int prep_masks(d2d_ctx* c, Sweep& s, Prep& pr) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
+    int rc;
+    if (!((!s.txg || s.txg_culled) && c->N >= 2 && p->max_order >= 1)) return D2D_OK;
+    // [N] masks, then the {histogram, cursors} of the patch schedule's counting sort, then what the region lists need
+    // zeroed per launch ({queue length, pool head}, one flag per leaf region): one memset for all of it
+    const size_t rl_regions = (size_t)((s.tiles_x + c->region_size - 1) / c->region_size) * (size_t)((s.tiles_y + c->region_size - 1) / c->region_size);
+    // (a multiple of 256 bytes: the runtime fills odd tails with a second kernel)
+    const size_t zero_words = ((size_t)c->N + d2d::SCHED_KEYS + (2 + rl_regions + 1) / 2 + 31) & ~(size_t)31;
+    if ((rc = c->cur.d_shadow.ensure(zero_words))) return rc;
+    if (!c->prep_fused) {
+        hipLaunchKernelGGL(d2d::zero_words_kernel, dim3((unsigned)((zero_words + 255) / 256)), dim3(256), 0, s.ps, c->cur.d_shadow.p, (long)zero_words);
+        HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the schedule's sort may start here, on a stream of its own)
+    }
+    pr.zeroed = true;
+    // window where a test is certainly "hit" (hard) / exactly saturated to 1 (approx): shrink [-tol, 1+tol] by widen
+    MaskWindow& w = pr.win;
+    w.in_lo = -(double)p->seg_tol + s.th.widen_in;
+    w.in_hi = 1.0 + (double)p->seg_tol - s.th.widen_in;
+    const float ext = std::fmax(std::fmax(c->scene_absmax, c->grid_absmax), std::fmax(std::fabs(s.tx[0]), std::fabs(s.tx[1])));
+    w.ok = w.in_hi > w.in_lo + 1e-3 && std::isfinite(ext) && ext > 0.0f;
+    // bins span the parametric window in which on_objects is not exactly 0 (+ a little)
+    w.dom_lo = (double)a.on_lo - 2e-3;
+    const double dom_hi = (double)a.on_hi + 2e-3;
+    w.dom_w = (dom_hi - w.dom_lo) / 64.0;
+    const float dperp = 4096.0f * 1.1920929e-07f * (w.ok ? ext : 1.0f) * (float)(p->max_order + 1);
+    if (c->prep_fused) {
+        // one kernel: the masks (stored, not OR-ed: nothing to zero in front) and the zeroing of everything behind them
+        const long n_zero = (long)zero_words - c->N;
+        hipLaunchKernelGGL(d2d::shadow_fill_kernel, dim3((unsigned)(c->N + (n_zero + 255) / 256)), dim3(256), 0, s.ps, c->d_occl.p, c->d_refl.p,
+                           c->d_kind.p, c->N, s.tx[0], s.tx[1], (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), dperp, (float)w.dom_lo,
+                           (float)w.dom_w, w.ok ? 1 : 0, c->cur.d_shadow.p, c->cur.d_shadow.p + c->N, n_zero);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the sort of a big launch needs its counters zeroed: it may start here)
+    }
+    if (!w.ok) return D2D_OK;
+    if (!c->prep_fused) {
+        const int pairs = c->N * c->N;
+        hipLaunchKernelGGL(d2d::shadow_tx_kernel, dim3((unsigned)pairs), dim3(64), 0, s.ps, c->d_occl.p,
+                           c->d_refl.p, c->d_kind.p, c->N, s.tx[0], s.tx[1], (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), dperp,
+                           (float)w.dom_lo, (float)w.dom_w, c->cur.d_shadow.p);
+        HIP_TRY(hipGetLastError());
+    }
+    a.shadow = c->cur.d_shadow.p;
+    a.shadow_dperp = dperp;
+    a.shadow_lo = (float)w.dom_lo;
+    a.shadow_inv = (float)(1.0 / w.dom_w);
+    return prep_pair_masks(c, s, w, ext);
+}
+
+// last-segment masks: which bins of which wall are hidden from a whole leaf region (forward RX-grid sweeps)
+// (launches of a few hundred patches are latency-bound: one more dependent load per culling step costs them more than
+// the masks save -- 64^2 cells: 0.085 -> 0.097 ms with them, 128^2 0.072 -> 0.076, 200^2 equal, 300^2 0.091 -> 0.086)
+static int prep_hidden_masks(d2d_ctx* c, Sweep& s, const Prep& pr, const d2d_host::RegionPlan& rp, d2d::RegionLevel& leaf) {
+    const d2d_params* p = s.p;
+    const MaskWindow& w = pr.win;
+    int rc;
+    if (!(w.ok && s.a.shadow && c->use_hidden_masks && s.tiles >= c->hidden_min_tiles && std::isfinite(c->scene_absmax) &&
+          std::isfinite(c->grid_absmax) && (size_t)rp.leaf.regions * (size_t)c->N <= ((size_t)1 << 28)))
+        return D2D_OK;
+    const float hdperp = 4096.0f * 1.1920929e-07f * std::fmax(c->scene_absmax, c->grid_absmax) * (float)(D2D_MAX_ORDER + 1);
+    const double key[12] = {(double)c->grid_version, (double)rp.leaf.R, (double)c->m, (double)c->n, (double)p->patch, (double)p->seg_tol,
+                            (double)(p->approx * 4 + p->act + (s.txg ? 16 : 0)), (double)p->alpha, (double)hdperp, w.dom_lo, w.dom_w, (double)c->N};
+    if (hdperp > 0.0f && !(c->hidden_valid && std::memcmp(key, c->hidden_key, sizeof key) == 0)) {
+        if (std::memcmp(key, c->hidden_seen, sizeof key) == 0) {  // the second launch in a row with this key: build
+            const size_t nh = (size_t)rp.leaf.regions * (size_t)c->N;
+            if ((rc = c->d_hidden.ensure(nh))) return rc;
+            if (s.piped && (rc = wait_spare_sweeps(c, s.ps))) return rc;
+            hipLaunchKernelGGL(d2d::hidden_region_kernel, dim3((unsigned)nh), dim3(64), 0, s.ps, c->d_occl.p, c->d_refl.p, c->d_kind.p, c->N,
+                               c->d_rl_box.p, (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), hdperp, (float)w.dom_lo, (float)w.dom_w,
+                               c->d_hidden.p, s.txg ? 1 : 0);
+            HIP_TRY(hipGetLastError());
+            std::memcpy(c->hidden_key, key, sizeof key);
+            c->hidden_valid = true;
+            c->hidden_builds += 1;
+        } else {
+            std::memcpy(c->hidden_seen, key, sizeof key);
+            c->hidden_valid = false;
         }
     }
-    // region candidate lists (orders >= 2): the culled RX-grid kernels (forward, instrumented, value+grad) read them
-    a.rl = nullptr;
-    a.fb_n = nullptr;
-    a.fb_list = nullptr;
-    bool queue_impossible = false;
-    if ((!txg || txg_culled) && c->use_region_lists && p->max_order >= 2 && c->cw.size() >= 2 && c->N <= 4095 && !(grad_mode && p->strict_nan)) {
-        // "region_budget_mb" bounds the device memory of ALL list pools: the pipeline keeps one per rotating set
-        const long long pool_cap_mb = std::max<long long>(1, c->region_budget_mb / (piped ? 1 + d2d_ctx::N_SPARE : 1));
-        // how the previous launch's lists fared (read back without waiting: a launch or two late is early enough)
-        if (c->meta_pending && hipEventQuery(c->ev_meta) == hipSuccess) {
-            c->meta_pending = false;
-            c->fb_hint = c->h_meta[0];
-            if ((long long)c->h_meta[1] + c->pend_static > c->pend_chunks && c->rl_pool_mb < pool_cap_mb)
-                c->rl_pool_mb = std::min(pool_cap_mb, c->rl_pool_mb * 4);  // the pool ran out: a bigger one from now on
-        }
-        // third-order lists over a big scene start with 1 GB per set: configs[3]'s hard_sigmoid lists are 577 MB, and the ONE launch
-        // that finds a 256 MB pool too small takes 8.7 s instead of 0.04 (its patches enumerate) -- 288 GB of HBM are there to be used
-        if (!c->rl_pool_by_option && p->max_order >= 3 && c->cw.size() >= 64 && c->rl_pool_mb < 1024) c->rl_pool_mb = 1024;
-        if (c->rl_pool_mb > pool_cap_mb) c->rl_pool_mb = pool_cap_mb;
-        d2d_host::RegionPlan rp =
-            d2d_host::region_plan(tiles_x, tiles_y, (long long)c->cw.size(), p->min_order, p->max_order, (int)c->region_size,
-                                  (int)c->region_size_top, (int)c->region_slices, c->rl_pool_mb << 20, d2d::RL_CHUNK);
-        const size_t lds_l = (size_t)(3 * c->N + 1) * sizeof(float4) + 512;                                         // tables + culling queue
-        const size_t lds_r = (size_t)(3 * c->N + 1) * sizeof(float4) + (size_t)d2d::RL_GATHER * sizeof(unsigned long long);  // tables + gather buffer
-        if (rp.on && lds_l <= d2d_host::LDS_LIMIT && lds_r <= d2d_host::LDS_LIMIT) {
-            // the pool is the one big allocation of the library: when the device cannot give it, this launch enumerates
-            // (same results) and later launches ask for a quarter
-            if (c->d_rl_pool.ensure((size_t)rp.max_chunks * d2d::RL_CHUNK) != D2D_OK || c->d_rl_next.ensure((size_t)rp.max_chunks) != D2D_OK) {
-                (void)hipGetLastError();
-                c->d_rl_pool.release();
-                c->d_rl_next.release();
-                c->rl_pool_mb = std::max<long long>(1, c->rl_pool_mb / 4);
-                rp.on = false;
-            }
-        }
-        if (rp.on && lds_l <= d2d_host::LDS_LIMIT && lds_r <= d2d_host::LDS_LIMIT) {
-            const int orders = p->max_order - rp.k_lo + 1;
-            const size_t per_order = (size_t)rp.leaf.slots + (size_t)rp.top.slots;
-            if ((rc = c->d_rl_idx.ensure(per_order * (size_t)orders))) return rc;
-            // meta (zeroed with the shadow masks above): [0] queue length, [1] pool head, [2 ..) leaf region flags
-            int* const meta = reinterpret_cast<int*>(c->d_shadow.p + c->N + d2d::SCHED_KEYS);
-            c->rl_meta_ptr = meta;
-            if ((rc = c->d_rl_meta.ensure((size_t)tiles))) return rc;  // the queue of patches left to the enumerating kernel
-            if ((rc = c->d_rl.ensure(1))) return rc;
-            {
-                // the regions' bounding boxes depend on the grid only
-                const long long key[4] = {c->grid_version, rp.leaf.R, rp.top.R, (long long)c->m * 0x100000000ll + c->n};
-                const size_t nbox = (size_t)rp.leaf.regions + (size_t)rp.top.regions;
-                if (std::memcmp(key, c->rl_box_key, sizeof key) != 0 || c->d_rl_box.n < nbox) {
-                    if ((rc = c->d_rl_box.ensure(nbox))) return rc;
-                    hipLaunchKernelGGL(d2d::region_box_kernel, dim3((unsigned)rp.leaf.regions), dim3(256), 0, ps, c->d_X.p, c->d_Y.p,
-                                       c->m, c->n, rp.leaf.R, rp.leaf.regions_x, c->d_rl_box.p);
-                    hipLaunchKernelGGL(d2d::region_box_kernel, dim3((unsigned)rp.top.regions), dim3(256), 0, ps, c->d_X.p, c->d_Y.p,
-                                       c->m, c->n, rp.top.R, rp.top.regions_x, c->d_rl_box.p + rp.leaf.regions);
-                    HIP_TRY(hipGetLastError());
-                    std::memcpy(c->rl_box_key, key, sizeof key);
-                }
-            }
-            auto fill = [](d2d::RegionLevel& l, const d2d_host::RegionLevelPlan& lp_) {
-                l.S = lp_.S;
-                l.R = lp_.R;
-                l.regions_x = lp_.regions_x;
-                l.regions_y = lp_.regions_y;
-            };
-            d2d::RegionLists rl;
-            d2d::RegionLevel top;
-            memset(&rl, 0, sizeof rl);
-            memset(&top, 0, sizeof top);
-            fill(rl.leaf, rp.leaf);
-            fill(top, rp.top);
-            rl.leaf.box = c->d_rl_box.p;
-            top.box = c->d_rl_box.p + rp.leaf.regions;
-            // last-segment masks: which bins of which wall are hidden from a whole leaf region (forward RX-grid sweeps)
-            // (launches of a few hundred patches are latency-bound: one more dependent load per culling step costs them more than
-            // the masks save -- 64^2 cells: 0.085 -> 0.097 ms with them, 128^2 0.072 -> 0.076, 200^2 equal, 300^2 0.091 -> 0.086)
-            if ((!txg || txg_culled) && m_masks_ok && a.shadow && c->use_hidden_masks && tiles >= c->hidden_min_tiles && std::isfinite(c->scene_absmax) && std::isfinite(c->grid_absmax) &&
-                (size_t)rp.leaf.regions * (size_t)c->N <= ((size_t)1 << 28)) {
-                const float hdperp = 4096.0f * 1.1920929e-07f * std::fmax(c->scene_absmax, c->grid_absmax) * (float)(D2D_MAX_ORDER + 1);
-                const double key[12] = {(double)c->grid_version, (double)rp.leaf.R, (double)c->m, (double)c->n, (double)p->patch, (double)p->seg_tol,
-                                        (double)(p->approx * 4 + p->act + (txg ? 16 : 0)), (double)p->alpha, (double)hdperp, m_dom_lo, m_dom_w, (double)c->N};
-                if (hdperp > 0.0f && !(c->hidden_valid && std::memcmp(key, c->hidden_key, sizeof key) == 0)) {
-                    if (std::memcmp(key, c->hidden_seen, sizeof key) == 0) {  // the second launch in a row with this key: build
-                        const size_t nh = (size_t)rp.leaf.regions * (size_t)c->N;
-                        if ((rc = c->d_hidden.ensure(nh))) return rc;
-                        // (a sweep that reads the old masks may still be in flight on the main stream)
-                        for (int i = 0; piped && i < d2d_ctx::N_SPARE; ++i)
-                            if (c->spare_sets[i].swept_pending) HIP_TRY(hipStreamWaitEvent(ps, c->spare_sets[i].ev_swept, 0));
-                        hipLaunchKernelGGL(d2d::hidden_region_kernel, dim3((unsigned)nh), dim3(64), 0, ps, c->d_occl.p, c->d_refl.p, c->d_kind.p, c->N,
-                                           c->d_rl_box.p, (float)(m_in_lo + 1e-4), (float)(m_in_hi - 1e-4), hdperp, (float)m_dom_lo, (float)m_dom_w,
-                                           c->d_hidden.p, txg ? 1 : 0);
-                        HIP_TRY(hipGetLastError());
-                        std::memcpy(c->hidden_key, key, sizeof key);
-                        c->hidden_valid = true;
-                        c->hidden_builds += 1;
-                    } else {
-                        std::memcpy(c->hidden_seen, key, sizeof key);
-                        c->hidden_valid = false;
-                    }
-                }
-                if (c->hidden_valid && std::memcmp(key, c->hidden_key, sizeof key) == 0) {
-                    rl.leaf.hidden = c->d_hidden.p;
-                    rl.leaf.hidden_dperp = hdperp;
-                }
-            }
-            int* at = c->d_rl_idx.p;
-            int chunk_at = 0;
-            for (int k = rp.k_lo; k <= p->max_order; ++k) {
-                rl.leaf.cnt[k] = at; at += rp.leaf.slots;
-                rl.leaf.chunk0[k] = chunk_at; chunk_at += (int)rp.leaf.slots;
-                top.cnt[k] = at; at += rp.top.slots;
-                top.chunk0[k] = chunk_at; chunk_at += (int)rp.top.slots;
-            }
-            rl.lp.pool = c->d_rl_pool.p;
-            rl.lp.next = c->d_rl_next.p;
-            rl.lp.head = meta + 1;
-            rl.lp.n_static = (int)rp.n_static;
-            rl.lp.max_chunks = (int)rp.max_chunks;
-            rl.flag = meta + 2;
-            a.fb_n = meta;
-            a.fb_list = c->d_rl_meta.p;
-            if (!c->rl_host_valid || std::memcmp(&rl, &c->rl_host, sizeof rl) != 0) {
-                // written by a kernel that takes the descriptor by value: stream-ordered, and nothing reads host memory
-                // after this call returns (a copy from a pageable member would be staged synchronously and drain `ps`)
-                c->rl_host = rl;
-                c->rl_host_valid = true;
-                hipLaunchKernelGGL(d2d::write_region_lists_kernel, dim3(1), dim3(1), 0, ps, c->d_rl.p, rl);
-                HIP_TRY(hipGetLastError());
-            }
-            d2d::SweepArgs al = a;
-            al.fb_n = nullptr;
-            al.cullq_off = (int)((size_t)(3 * c->N + 1) * sizeof(float4));
-            for (int k = rp.k_lo; k <= p->max_order; ++k) {
-                HIP_TRY(d2d::launch_region_lists(k, false, txg, dim3((unsigned)rp.top.slots), lds_l, ps, al, top, rl.lp));
-                HIP_TRY(d2d::launch_region_refine(k, false, txg, dim3((unsigned)rp.leaf.regions), lds_r, ps, al, rl.leaf, top, rl.lp, rl.flag));
-            }
-            a.rl = c->d_rl.p;
-            c->rl_plan = rp;
-            c->rl_max_order = p->max_order;
-            // (the lists' lengths follow the validity parameters as much as the plan: a context that goes from hard to hard_sigmoid
-            // validity on the same grid -- bench.py's configs[3] legs -- must look at its first launches again: without this the
-            // overflow of the hard_sigmoid lists was noticed sixteen launches late, each of them seconds long)
-            const float vkey[6] = {(float)mode, p->alpha, p->tol, p->patch, p->seg_tol, (float)(p->min_order * 16 + p->max_order)};
-            const bool same_params = std::memcmp(vkey, c->rl_vkey, sizeof vkey) == 0;
-            std::memcpy(c->rl_vkey, vkey, sizeof vkey);
-            c->rl_launches = (same_params && c->rl_meta_static == rp.n_static && c->rl_meta_chunks == rp.max_chunks) ? c->rl_launches + 1 : 1;
-            c->rl_meta_static = rp.n_static;
-            c->rl_meta_chunks = rp.max_chunks;
-            {
-                // Can a patch be left to the enumerating kernel at all?  Only a cell or end point that is not comfortably
-                // finite or a list that does not fit can do that; if even "every candidate survives everywhere" fits the
-                // pool, the queue stays empty and the launch that would walk it is not made.
-                double worst = 0.0;  // entries of all lists of one region
-                for (int k = rp.k_lo; k <= p->max_order; ++k) worst += (double)c->cw.size() * std::pow((double)c->cw.size() - 1.0, k - 1);
-                const double worst_chunks = worst * (double)(rp.leaf.regions + rp.top.regions) / d2d::RL_CHUNK + 2.0 * (double)rp.n_static;
-                queue_impossible = c->grid_all_finite && std::fabs(tx[0]) < 1e18f && std::fabs(tx[1]) < 1e18f &&
-                                   worst_chunks < (double)rp.max_chunks;
-            }
+    if (c->hidden_valid && std::memcmp(key, c->hidden_key, sizeof key) == 0) {
+        leaf.hidden = c->d_hidden.p;
+        leaf.hidden_dperp = hdperp;
+    }
+    return D2D_OK;
+}
+
+// region candidate lists (orders >= 2): the culled RX-grid kernels (forward, instrumented, value+grad) read them
+static int prep_region_lists(d2d_ctx* c, Sweep& s, Prep& pr) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
+    d2d_ctx::PrepSet& cur = c->cur;
+    int rc;
+    if (!((!s.txg || s.txg_culled) && c->use_region_lists && p->max_order >= 2 && c->cw.size() >= 2 && c->N <= 4095 &&
+          !(s.grad_mode && p->strict_nan)))
+        return D2D_OK;
+    // "region_budget_mb" bounds the device memory of ALL list pools: the pipeline keeps one per rotating set
+    const long long pool_cap_mb = std::max<long long>(1, c->region_budget_mb / (s.piped ? 1 + d2d_ctx::N_SPARE : 1));
+    // how the previous launch's lists fared (read back without waiting: a launch or two late is early enough)
+    if (c->meta_pending && hipEventQuery(c->ev_meta) == hipSuccess) {
+        c->meta_pending = false;
+        c->fb_hint = c->h_meta[0];
+        if ((long long)c->h_meta[1] + c->pend_static > c->pend_chunks && c->rl_pool_mb < pool_cap_mb)
+            c->rl_pool_mb = std::min(pool_cap_mb, c->rl_pool_mb * 4);  // the pool ran out: a bigger one from now on
+    }
+    // third-order lists over a big scene start with 1 GB per set: configs[3]'s hard_sigmoid lists are 577 MB, and the ONE launch
+    // that finds a 256 MB pool too small takes 8.7 s instead of 0.04 (its patches enumerate) -- 288 GB of HBM are there to be used
+    if (!c->rl_pool_by_option && p->max_order >= 3 && c->cw.size() >= 64 && c->rl_pool_mb < 1024) c->rl_pool_mb = 1024;
+    if (c->rl_pool_mb > pool_cap_mb) c->rl_pool_mb = pool_cap_mb;
+    d2d_host::RegionPlan rp =
+        d2d_host::region_plan(s.tiles_x, s.tiles_y, (long long)c->cw.size(), p->min_order, p->max_order, (int)c->region_size,
+                              (int)c->region_size_top, (int)c->region_slices, c->rl_pool_mb << 20, d2d::RL_CHUNK);
+    const size_t lds_l = (size_t)(3 * c->N + 1) * sizeof(float4) + 512;                                         // tables + culling queue
+    const size_t lds_r = (size_t)(3 * c->N + 1) * sizeof(float4) + (size_t)d2d::RL_GATHER * sizeof(unsigned long long);  // tables + gather buffer
+    if (!rp.on || lds_l > d2d_host::LDS_LIMIT || lds_r > d2d_host::LDS_LIMIT) return D2D_OK;
+    // the pool is the one big allocation of the library: when the device cannot give it, this launch enumerates
+    // (same results) and later launches ask for a quarter
+    if (cur.d_rl_pool.ensure((size_t)rp.max_chunks * d2d::RL_CHUNK) != D2D_OK || cur.d_rl_next.ensure((size_t)rp.max_chunks) != D2D_OK) {
+        (void)hipGetLastError();
+        cur.d_rl_pool.release();
+        cur.d_rl_next.release();
+        c->rl_pool_mb = std::max<long long>(1, c->rl_pool_mb / 4);
+        return D2D_OK;
+    }
+    const int orders = p->max_order - rp.k_lo + 1;
+    const size_t per_order = (size_t)rp.leaf.slots + (size_t)rp.top.slots;
+    if ((rc = cur.d_rl_idx.ensure(per_order * (size_t)orders))) return rc;
+    // meta (zeroed with the shadow masks above): [0] queue length, [1] pool head, [2 ..) leaf region flags
+    int* const meta = reinterpret_cast<int*>(cur.d_shadow.p + c->N + d2d::SCHED_KEYS);
+    cur.rl_meta_ptr = meta;
+    if ((rc = cur.d_rl_meta.ensure((size_t)s.tiles))) return rc;  // the queue of patches left to the enumerating kernel
+    if ((rc = cur.d_rl.ensure(1))) return rc;
+    {
+        // the regions' bounding boxes depend on the grid only
+        const long long key[4] = {c->grid_version, rp.leaf.R, rp.top.R, (long long)c->m * 0x100000000ll + c->n};
+        const size_t nbox = (size_t)rp.leaf.regions + (size_t)rp.top.regions;
+        if (std::memcmp(key, c->rl_box_key, sizeof key) != 0 || c->d_rl_box.n < nbox) {
+            if ((rc = c->d_rl_box.ensure(nbox))) return rc;
+            hipLaunchKernelGGL(d2d::region_box_kernel, dim3((unsigned)rp.leaf.regions), dim3(256), 0, s.ps, c->d_X.p, c->d_Y.p,
+                               c->m, c->n, rp.leaf.R, rp.leaf.regions_x, c->d_rl_box.p);
+            hipLaunchKernelGGL(d2d::region_box_kernel, dim3((unsigned)rp.top.regions), dim3(256), 0, s.ps, c->d_X.p, c->d_Y.p,
+                               c->m, c->n, rp.top.R, rp.top.regions_x, c->d_rl_box.p + rp.leaf.regions);
+            HIP_TRY(hipGetLastError());
+            std::memcpy(c->rl_box_key, key, sizeof key);
         }
     }
-    if (!a.rl) c->rl_plan.on = false;
-    // dearest-first patch schedule for the culled kernels
-    a.sched = nullptr;
-    a.n_heavy = 0;
-    bool sched_from_history = false;
-    if ((!txg || txg_culled) && !(grad_mode && p->strict_nan) && p->max_order >= 2 && c->cw.size() >= 2 && tiles >= c->sched_min_tiles) {
-        if ((rc = c->d_sched.ensure((size_t)tiles))) return rc;
-        if ((rc = c->d_sched_key.ensure((size_t)tiles))) return rc;
-        if (!prep_zeroed) {
-            if ((rc = c->d_shadow.ensure((size_t)c->N + d2d::SCHED_KEYS))) return rc;
-            HIP_TRY(hipMemsetAsync(c->d_shadow.p + c->N, 0, d2d::SCHED_KEYS * sizeof(unsigned long long), ps));
+    auto fill = [](d2d::RegionLevel& l, const d2d_host::RegionLevelPlan& lp_) {
+        l.S = lp_.S;
+        l.R = lp_.R;
+        l.regions_x = lp_.regions_x;
+        l.regions_y = lp_.regions_y;
+    };
+    d2d::RegionLists rl;
+    d2d::RegionLevel top;
+    memset(&rl, 0, sizeof rl);
+    memset(&top, 0, sizeof top);
+    fill(rl.leaf, rp.leaf);
+    fill(top, rp.top);
+    rl.leaf.box = c->d_rl_box.p;
+    top.box = c->d_rl_box.p + rp.leaf.regions;
+    if ((rc = prep_hidden_masks(c, s, pr, rp, rl.leaf))) return rc;
+    int* at = cur.d_rl_idx.p;
+    int chunk_at = 0;
+    for (int k = rp.k_lo; k <= p->max_order; ++k) {
+        rl.leaf.cnt[k] = at; at += rp.leaf.slots;
+        rl.leaf.chunk0[k] = chunk_at; chunk_at += (int)rp.leaf.slots;
+        top.cnt[k] = at; at += rp.top.slots;
+        top.chunk0[k] = chunk_at; chunk_at += (int)rp.top.slots;
+    }
+    rl.lp.pool = cur.d_rl_pool.p;
+    rl.lp.next = cur.d_rl_next.p;
+    rl.lp.head = meta + 1;
+    rl.lp.n_static = (int)rp.n_static;
+    rl.lp.max_chunks = (int)rp.max_chunks;
+    rl.flag = meta + 2;
+    a.fb_n = meta;
+    a.fb_list = cur.d_rl_meta.p;
+    if (!cur.rl_host_valid || std::memcmp(&rl, &cur.rl_host, sizeof rl) != 0) {
+        // written by a kernel that takes the descriptor by value: stream-ordered, and nothing reads host memory
+        // after this call returns (a copy from a pageable member would be staged synchronously and drain `ps`)
+        cur.rl_host = rl;
+        cur.rl_host_valid = true;
+        hipLaunchKernelGGL(d2d::write_region_lists_kernel, dim3(1), dim3(1), 0, s.ps, cur.d_rl.p, rl);
+        HIP_TRY(hipGetLastError());
+    }
+    d2d::SweepArgs al = a;
+    al.fb_n = nullptr;
+    al.cullq_off = (int)((size_t)(3 * c->N + 1) * sizeof(float4));
+    for (int k = rp.k_lo; k <= p->max_order; ++k) {
+        HIP_TRY(d2d::launch_region_lists(k, false, s.txg, dim3((unsigned)rp.top.slots), lds_l, s.ps, al, top, rl.lp));
+        HIP_TRY(d2d::launch_region_refine(k, false, s.txg, dim3((unsigned)rp.leaf.regions), lds_r, s.ps, al, rl.leaf, top, rl.lp, rl.flag));
+    }
+    a.rl = cur.d_rl.p;
+    c->rl_plan = rp;
+    c->rl_max_order = p->max_order;
+    // (the lists' lengths follow the validity parameters as much as the plan: a context that goes from hard to hard_sigmoid
+    // validity on the same grid -- bench.py's configs[3] legs -- must look at its first launches again: without this the
+    // overflow of the hard_sigmoid lists was noticed sixteen launches late, each of them seconds long)
+    const float vkey[6] = {(float)s.th.mode, p->alpha, p->tol, p->patch, p->seg_tol, (float)(p->min_order * 16 + p->max_order)};
+    const bool same_params = std::memcmp(vkey, c->rl_vkey, sizeof vkey) == 0;
+    std::memcpy(c->rl_vkey, vkey, sizeof vkey);
+    c->rl_launches = (same_params && c->rl_meta_static == rp.n_static && c->rl_meta_chunks == rp.max_chunks) ? c->rl_launches + 1 : 1;
+    c->rl_meta_static = rp.n_static;
+    c->rl_meta_chunks = rp.max_chunks;
+    // Can a patch be left to the enumerating kernel at all?  Only a cell or end point that is not comfortably
+    // finite or a list that does not fit can do that; if even "every candidate survives everywhere" fits the
+    // pool, the queue stays empty and the launch that would walk it is not made.
+    double worst = 0.0;  // entries of all lists of one region
+    for (int k = rp.k_lo; k <= p->max_order; ++k) worst += (double)c->cw.size() * std::pow((double)c->cw.size() - 1.0, k - 1);
+    const double worst_chunks = worst * (double)(rp.leaf.regions + rp.top.regions) / d2d::RL_CHUNK + 2.0 * (double)rp.n_static;
+    pr.queue_impossible = c->grid_all_finite && std::fabs(s.tx[0]) < 1e18f && std::fabs(s.tx[1]) < 1e18f &&
+                          worst_chunks < (double)rp.max_chunks;
+    return D2D_OK;
+}
+
+// dearest-first patch schedule for the culled kernels; then which work history the sweep writes
+static int prep_schedule(d2d_ctx* c, Sweep& s, Prep& pr) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
+    d2d_ctx::PrepSet& cur = c->cur;
+    const long long tiles = s.tiles;
+    int rc;
+    if ((!s.txg || s.txg_culled) && !(s.grad_mode && p->strict_nan) && p->max_order >= 2 && c->cw.size() >= 2 && tiles >= c->sched_min_tiles) {
+        if ((rc = cur.d_sched.ensure((size_t)tiles))) return rc;
+        if ((rc = cur.d_sched_key.ensure((size_t)tiles))) return rc;
+        if (!pr.zeroed) {
+            if ((rc = cur.d_shadow.ensure((size_t)c->N + d2d::SCHED_KEYS))) return rc;
+            HIP_TRY(hipMemsetAsync(cur.d_shadow.p + c->N, 0, d2d::SCHED_KEYS * sizeof(unsigned long long), s.ps));
         }
-        int* hist = reinterpret_cast<int*>(c->d_shadow.p + c->N);  // [SCHED_KEYS] counts, [SCHED_KEYS] cursors
+        int* hist = reinterpret_cast<int*>(cur.d_shadow.p + c->N);  // [SCHED_KEYS] counts, [SCHED_KEYS] cursors
         // cost key: what the patch cost last time, when this context has swept the same grid before (optimisation
         // loops, repeated maps); otherwise a proxy computed from the geometry
-        const bool from_history = c->cost_tiles == tiles && c->use_cost_history && c->sched_key_mode != 1;
+        const bool from_history = cur.cost_tiles == tiles && c->use_cost_history && c->sched_key_mode != 1;
         // no (usable) history: the lengths of the region lists this launch has just built, if any, else the geometric proxy
         const bool from_lists = !from_history && a.rl != nullptr && c->sched_key_mode != 2;
-        sched_from_history = from_history || from_lists;
+        pr.sched_from_history = from_history || from_lists;
         if (!from_history && !from_lists)
-            hipLaunchKernelGGL(d2d::patch_cost_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, ps, a, c->d_sched_key.p);
-        {
-            // keys from the work history depend on nothing this launch has built: the sort then runs on the side stream,
-            // beside the shadow masks and the region lists, behind the memset of its counters
-            const bool one_wg = c->prep_fused && tiles <= d2d::SORT1_MAX;  // the whole sort in one workgroup's LDS: nothing zeroed, nothing to wait for
-            const bool side = from_history && (prep_zeroed || (one_wg && piped)) && c->use_aux && (piped ? c->sort_stream : c->aux_stream) != nullptr;
-            hipStream_t ss = side ? (piped ? c->sort_stream : c->aux_stream) : ps;
-            // (ev_fork sits on `ps` behind the zeroing; without the pipeline `ps` is the main stream, i.e. also behind the
-            // previous sweep, whose work counters the sort reads)
-            if (side && (!one_wg || !piped)) HIP_TRY(hipStreamWaitEvent(ss, c->ev_fork, 0));
-            // (the one-workgroup sort waits for nothing this launch builds -- only for the sweep that last read this set's schedule)
-            if (side && one_wg && piped && set_was_swept) HIP_TRY(hipStreamWaitEvent(ss, c->ev_swept, 0));
-            if (one_wg) {
-                hipLaunchKernelGGL(d2d::patch_sort_kernel, dim3(1), dim3(d2d::SORT1_THREADS), 0, ss, c->d_sched_key.p,
-                                   from_history ? c->d_cost.p : (const unsigned*)nullptr, c->d_sched.p, (long)tiles,
-                                   from_lists ? a.rl : (const d2d::RegionLists*)nullptr, tiles_x, c->rl_plan.k_lo, p->max_order);
-            } else {
-                const unsigned sort_blocks = (unsigned)((tiles + 256 * d2d::SCHED_PER_THREAD - 1) / (256 * d2d::SCHED_PER_THREAD));
-                hipLaunchKernelGGL(d2d::patch_hist_kernel, dim3(sort_blocks), dim3(256), 0, ss, c->d_sched_key.p,
-                                   from_history ? c->d_cost.p : (const unsigned*)nullptr, hist, (long)tiles,
-                                   from_lists ? a.rl : (const d2d::RegionLists*)nullptr, tiles_x, c->rl_plan.k_lo, p->max_order);
-                hipLaunchKernelGGL(d2d::patch_order_kernel, dim3(sort_blocks), dim3(256), 0, ss, c->d_sched_key.p, hist,
-                                   hist + d2d::SCHED_KEYS, c->d_sched.p, (long)tiles);
-            }
-            if (side) {
-                HIP_TRY(hipEventRecord(c->ev_join, ss));
-                HIP_TRY(hipStreamWaitEvent(ps, c->ev_join, 0));
-            }
+            hipLaunchKernelGGL(d2d::patch_cost_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s.ps, a, cur.d_sched_key.p);
+        // keys from the work history depend on nothing this launch has built: the sort then runs on the side stream,
+        // beside the shadow masks and the region lists, behind the memset of its counters
+        const bool one_wg = c->prep_fused && tiles <= d2d::SORT1_MAX;  // the whole sort in one workgroup's LDS: nothing zeroed, nothing to wait for
+        const bool side = from_history && (pr.zeroed || (one_wg && s.piped)) && c->use_aux && (s.piped ? c->sort_stream : c->aux_stream) != nullptr;
+        hipStream_t ss = side ? (s.piped ? c->sort_stream : c->aux_stream) : s.ps;
+        // (ev_fork sits on `ps` behind the zeroing; without the pipeline `ps` is the main stream, i.e. also behind the
+        // previous sweep, whose work counters the sort reads)
+        if (side && (!one_wg || !s.piped)) HIP_TRY(hipStreamWaitEvent(ss, c->ev_fork, 0));
+        // (the one-workgroup sort waits for nothing this launch builds -- only for the sweep that last read this set's schedule)
+        if (side && one_wg && s.piped && s.set_was_swept) HIP_TRY(hipStreamWaitEvent(ss, cur.ev_swept, 0));
+        const unsigned* cost_in = from_history ? cur.d_cost.p : (const unsigned*)nullptr;
+        const d2d::RegionLists* lists_in = from_lists ? a.rl : (const d2d::RegionLists*)nullptr;
+        if (one_wg) {
+            hipLaunchKernelGGL(d2d::patch_sort_kernel, dim3(1), dim3(d2d::SORT1_THREADS), 0, ss, cur.d_sched_key.p, cost_in, cur.d_sched.p,
+                               (long)tiles, lists_in, s.tiles_x, c->rl_plan.k_lo, p->max_order);
+        } else {
+            const unsigned sort_blocks = (unsigned)((tiles + 256 * d2d::SCHED_PER_THREAD - 1) / (256 * d2d::SCHED_PER_THREAD));
+            hipLaunchKernelGGL(d2d::patch_hist_kernel, dim3(sort_blocks), dim3(256), 0, ss, cur.d_sched_key.p, cost_in, hist, (long)tiles,
+                               lists_in, s.tiles_x, c->rl_plan.k_lo, p->max_order);
+            hipLaunchKernelGGL(d2d::patch_order_kernel, dim3(sort_blocks), dim3(256), 0, ss, cur.d_sched_key.p, hist,
+                               hist + d2d::SCHED_KEYS, cur.d_sched.p, (long)tiles);
+        }
+        if (side) {
+            HIP_TRY(hipEventRecord(c->ev_join, ss));
+            HIP_TRY(hipStreamWaitEvent(s.ps, c->ev_join, 0));
         }
         HIP_TRY(hipGetLastError());
-        a.sched = c->d_sched.p;
+        a.sched = cur.d_sched.p;
     }
-    if (c->sched_override_n == tiles && !txg) a.sched = c->d_sched_override.p;
-    a.cost_out = nullptr;
-    if (a.sched && !d_stats) {
-        if ((rc = c->d_cost.ensure((size_t)tiles))) return rc;
-        a.cost_out = c->d_cost.p;  // the kernels launched below count the work of every patch
-        c->cost_tiles = tiles;     // (stream order: the next launch's key kernel runs after this sweep)
+    if (c->sched_override_n == tiles && !s.txg) a.sched = c->d_sched_override.p;
+    if (a.sched && !s.d_stats) {
+        if ((rc = cur.d_cost.ensure((size_t)tiles))) return rc;
+        a.cost_out = cur.d_cost.p;  // the kernels launched below count the work of every patch
+        cur.cost_tiles = tiles;     // (stream order: the next launch's key kernel runs after this sweep)
     }
-    if (txg && d_stats) return fail(D2D_ERR_UNSUPPORTED, "the instrumented build covers the RX-grid kernel only");
-    if (piped) {
-        // the sweep waits for this launch's preparation; the set is busy until the sweep is through (d2d_swept below)
-        HIP_TRY(hipEventRecord(c->ev_prep, ps));
+    return D2D_OK;
+}
+
+// behind a LISTED launch: how the lists fared, read back without waiting (see prep_region_lists)
+static int read_back_meta(d2d_ctx* c) {
+    if (!c->meta_pending && c->h_meta && (c->rl_launches <= 3 || c->rl_launches % 16 == 0)) {
+        HIP_TRY(hipMemcpyAsync(c->h_meta, c->cur.rl_meta_ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_meta, c->stream));
+        c->meta_pending = true;
+        c->pend_static = c->rl_meta_static;  // the plan THIS launch's counters belong to
+        c->pend_chunks = c->rl_meta_chunks;
+    }
+    return D2D_OK;
+}
+
+// The sweep kernel, launch(a, grid); behind a LISTED one (a.rl) the patches it left to the enumerating build (usually none):
+// a few workgroups walk the queue, launch(args without lists, schedule or cut patches, their grid); then the read-back of
+// how the lists fared.
+template <class Launch>
+static int sweep_and_walk(d2d_ctx* c, const Sweep& s, const Prep& pr, const d2d::SweepArgs& a, dim3 grid, Launch launch) {
+    HIP_TRY(launch(a, grid));
+    if (!a.rl || pr.queue_impossible) return D2D_OK;
+    d2d::SweepArgs af = a;
+    af.rl = nullptr; af.sched = nullptr; af.n_heavy = 0;
+    HIP_TRY(launch(af, dim3((unsigned)std::min<long long>(s.tiles, std::max<long long>(256, c->fb_hint)))));
+    return read_back_meta(c);
+}
+
+// everything before this is preparation (memsets, shadow masks, schedule); what follows is the sweep kernel itself
+static int sweep_begin(d2d_ctx* c, const Sweep& s) {
+    if (s.piped) {
+        // the sweep waits for this launch's preparation; the set is busy until the sweep is through (sweep_done)
+        HIP_TRY(hipEventRecord(c->ev_prep, s.ps));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_prep, 0));
     }
-    // everything above is preparation (memsets, shadow masks, schedule); what follows is the sweep kernel itself
     c->have_kernel_time = false;
     if (c->time_kernel) HIP_TRY(hipEventRecord(c->evk0, c->stream));
-#define D2D_KERNEL_DONE()                                        \
-    do {                                                         \
-        if (c->time_kernel) {                                    \
-            HIP_TRY(hipEventRecord(c->evk1, c->stream));         \
-            c->have_kernel_time = true;                          \
-        }                                                        \
-        if (c->pipeline && c->aux_stream != nullptr) {           \
-            /* (also behind a launch that prepared on the sweep stream: a later pipelined launch may take its set) */ \
-            HIP_TRY(hipEventRecord(c->ev_swept, c->stream));     \
-            c->swept_pending = true;                             \
-        }                                                        \
-    } while (0)
-    // behind a LISTED launch: how the lists fared, read back without waiting (see above)
-    auto read_back_meta = [&]() -> int {
-        if (!c->meta_pending && c->h_meta && (c->rl_launches <= 3 || c->rl_launches % 16 == 0)) {
-            HIP_TRY(hipMemcpyAsync(c->h_meta, c->rl_meta_ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipEventRecord(c->ev_meta, c->stream));
-            c->meta_pending = true;
-            c->pend_static = c->rl_meta_static;  // the plan THIS launch's counters belong to
-            c->pend_chunks = c->rl_meta_chunks;
-        }
-        return D2D_OK;
-    };
-    const dim3 grid_queue((unsigned)std::min<long long>(tiles, std::max<long long>(256, c->fb_hint)));
-    if (txg_culled && !grad_mode) {
+    return D2D_OK;
+}
+
+// behind the sweep kernel(s)
+static int sweep_done(d2d_ctx* c) {
+    if (c->time_kernel) {
+        HIP_TRY(hipEventRecord(c->evk1, c->stream));
+        c->have_kernel_time = true;
+    }
+    if (c->pipeline && c->aux_stream != nullptr) {
+        // (also behind a launch that prepared on the sweep stream: a later pipelined launch may take its set)
+        HIP_TRY(hipEventRecord(c->cur.ev_swept, c->stream));
+        c->cur.swept_pending = true;
+    }
+    return D2D_OK;
+}
+
+// TX grid, values only: culled, or exhaustive (the "txg_exhaustive" option, or a degenerate path can count)
+static int launch_txg_values(d2d_ctx* c, Sweep& s, const Prep& pr) {
+    const int mode = s.th.mode, max_order = s.p->max_order;
+    int rc;
+    if (s.txg_culled) {
         const size_t lds_t = (size_t)(3 * c->N + 1) * sizeof(float4);
         if (lds_t > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
-        a.grad = nullptr; a.cot = nullptr; a.partial = nullptr;
-        HIP_TRY(d2d::launch_txg(mode, a.rl != nullptr, false, p->max_order, grid, lds_t, c->stream, a));
-        if (a.rl && !queue_impossible) {  // the patches the listed kernel left behind (usually none)
-            d2d::SweepArgs af = a;
-            af.rl = nullptr; af.sched = nullptr;
-            HIP_TRY(d2d::launch_txg(mode, false, false, p->max_order, grid_queue, lds_t, c->stream, af));
-            if ((rc = read_back_meta())) return rc;
-        }
-        D2D_KERNEL_DONE();
-        return D2D_OK;
-    }
-    if (txg && !grad_mode) {
-        // TX grid, values only, exhaustive ("txg_exhaustive" option): the per-lane-image code path without the adjoint
+        rc = sweep_and_walk(c, s, pr, s.a, s.grid_patches, [&](const d2d::SweepArgs& x, dim3 g) {
+            return d2d::launch_txg(mode, x.rl != nullptr, false, max_order, g, lds_t, c->stream, x);
+        });
+        if (rc) return rc;
+    } else {
+        // the per-lane-image code path without the adjoint
         const size_t lds0 = (size_t)(4 * c->N + 4) * sizeof(float);
-        a.grad = nullptr; a.cot = nullptr; a.partial = nullptr;
-        HIP_TRY(d2d::launch_vg(mode, true, false, grid, lds0, c->stream, a));
-        D2D_KERNEL_DONE();
-        return D2D_OK;
+        HIP_TRY(d2d::launch_vg(mode, true, false, s.grid_patches, lds0, c->stream, s.a));
     }
-    if (grad_mode) {
-        const size_t cells = (size_t)c->m * c->n;
-        if (p->out_mode == D2D_OUT_ADD && !c->have_grad) return fail(D2D_ERR_STATE, "D2D_OUT_ADD needs a previous value+grad sweep on this grid");
-        if (grad_mode == 2 && p->out_mode == D2D_OUT_ADD && c->have_vjp) {
-            // a scene VJP accumulated over several transmitters must come from sweeps of one kind (an ImagePath sweep has no
-            // phi part) and must still be this rank's own partial sum
-            if (c->vjp_has_phi)
-                return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP comes from a MinPath / FermatPath sweep; an ImagePath sweep cannot be added to it");
-            if (c->vjp_reduced)
-                return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP has been all-reduced over ranks; fetch it, then start a new sum (D2D_OUT_OVERWRITE)");
+    return sweep_done(c);
+}
+
+// The NaN scan (d2d_nanscan.hpp) on stream st
+static int launch_scan(d2d_ctx* c, const Sweep& s, hipStream_t st, const d2d::SweepArgs& as) {
+    // two levels (a workgroup of 16 waves per region of 4 x 4 patches) when the region's list fits beside the tables
+    const size_t lds_r = (size_t)(3 * c->N) * sizeof(float4) + (size_t)d2d::NAN_LCAP * sizeof(unsigned long long) +
+                         (size_t)(2 * d2d::NAN_W + 1) * (size_t)((c->N + 31) / 32) * sizeof(unsigned) + 16;
+    // (+ the kernel's static LDS: boxes, counters, the region's probe queue, its cells and their flag words)
+    const size_t lds_static = 512 + (size_t)d2d::NAN_WQCAP * sizeof(unsigned long long) + (size_t)d2d::NAN_W * (64 * sizeof(float2) + 16);
+    const bool regions = c->nan_scan_mode != 2 && lds_r + lds_static <= d2d_host::LDS_LIMIT && c->N <= 4095;
+    const size_t lds_n = regions ? lds_r : (size_t)(3 * c->N) * sizeof(float4) + (size_t)c->N * sizeof(int) + 16;
+    if (lds_n > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the NaN scan's LDS table", c->N);
+    unsigned long long* ns = nullptr;
+    if (c->nan_scan_stats) {
+        int rc;
+        if ((rc = c->d_nan_stats.ensure(8))) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_nan_stats.p, 0, 8 * sizeof(unsigned long long), st));
+        ns = c->d_nan_stats.p;
+    }
+    const dim3 grid_regions((unsigned)(((s.tiles_x + d2d::NAN_R - 1) / d2d::NAN_R) * ((s.tiles_y + d2d::NAN_RY - 1) / d2d::NAN_RY)));
+    d2d::SweepArgs ac = as;
+    ac.nan_wqcap = c->nan_wqcap > 0 ? (int)c->nan_wqcap : d2d::NAN_WQCAP;  // (the kernel takes them as they are: never 0)
+    ac.nan_rb = c->nan_rb > 0 ? (int)c->nan_rb : d2d::NAN_RB;
+    // (the region kernel's debug instance -- run-time buffer sizes, counters -- only when a test asked for either)
+    const bool dbg = c->nan_wqcap > 0 || c->nan_rb > 0 || c->nan_scan_stats;
+    HIP_TRY(d2d::launch_nan_scan(s.p->approx != 0, s.txg, s.p->max_order, regions, dbg, regions ? grid_regions : s.grid_patches, lds_n, st, ac, ns));
+    return D2D_OK;
+}
+
+// Value + gradient (+ the scene VJP's partial sums and their reduction, grad_mode 2)
+static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
+    const int mode = s.th.mode, grad_mode = s.grad_mode;
+    const bool txg = s.txg;
+    int rc = D2D_OK;
+    const size_t cells = (size_t)c->m * c->n;
+    if (p->out_mode == D2D_OUT_ADD && !c->have_grad) return fail(D2D_ERR_STATE, "D2D_OUT_ADD needs a previous value+grad sweep on this grid");
+    if (grad_mode == 2 && p->out_mode == D2D_OUT_ADD && c->have_vjp) {
+        // a scene VJP accumulated over several transmitters must come from sweeps of one kind (an ImagePath sweep has no
+        // phi part) and must still be this rank's own partial sum
+        if (c->vjp_has_phi)
+            return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP comes from a MinPath / FermatPath sweep; an ImagePath sweep cannot be added to it");
+        if (c->vjp_reduced)
+            return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP has been all-reduced over ranks; fetch it, then start a new sum (D2D_OUT_OVERWRITE)");
+    }
+    if ((rc = c->d_grad.ensure(2 * cells))) return rc;
+    c->have_grad = true;
+    a.grad = c->d_grad.p;
+    a.cot = c->have_cot ? c->d_cot.p : nullptr;
+    const int n_elem = 4 * c->N + 2;
+    if (grad_mode == 2) {
+        if ((rc = c->d_partial.ensure((size_t)s.tiles * n_elem))) return rc;
+        if ((rc = c->d_vjp.ensure((size_t)n_elem + (size_t)c->N))) return rc;  // [4N] end points, [2] fixed point, [N] phi
+        a.partial = c->d_partial.p;
+    }
+    if (p->out_mode == D2D_OUT_OVERWRITE) c->have_vjp = false;
+    // (hard validity with fun = 1: nothing is differentiated through the path; order 0 alone: only path_length's own trap)
+    const bool scan = !p->strict_nan && (!txg || s.txg_culled) && c->nan_scan && (p->approx || p->fun_id != D2D_FUN_ONE) &&
+                      ((p->max_order >= 1 && !c->cw.empty()) || (p->min_order <= 0 && p->fun_id != D2D_FUN_ONE));
+    // The culled sweep writes the gradients of the candidates it evaluates; the reference's autodiff NaN positions -- an exact
+    // zero in the backward scan of ANY candidate, valid or not -- come from a pass of their own (d2d_nanscan.hpp), which
+    // poisons the cells and the patches' rows of VJP partial sums the way the exhaustive kernel (strict_nan) would have
+    // written them.  It reads the scene's tables and the grid only: it runs BESIDE the sweep on a stream of its own and
+    // leaves flags that nan_apply_kernel applies once both are through ("nan_scan_async" = 0: behind the sweep, as in round 4).
+    // Every size check of the sweeps below comes BEFORE the scan is forked onto its own stream: nothing may fail between the
+    // fork and the join (a scan left running would read tables that a later d2d_set_scene rewrites).
+    const bool culled_rx = !txg && !p->strict_nan;
+    const size_t lds_tab = (size_t)(4 * c->N + 1) * sizeof(float4);  // tables, adjoint table
+    const size_t lds_culled = culled_rx ? lds_tab + 512 : lds_tab;    // (+ the culling queue)
+    if ((culled_rx || s.txg_culled) && lds_culled > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
+    bool scan_beside = false;
+    // ... and should a launch fail behind the fork all the same (a HIP error), the scan is waited for before the error is returned
+    struct ScanJoin {
+        d2d_ctx* c;
+        bool armed = false;
+        ~ScanJoin() {
+            if (armed && c->scan_stream) (void)hipStreamSynchronize(c->scan_stream);
         }
-        if ((rc = c->d_grad.ensure(2 * cells))) return rc;
-        c->have_grad = true;
-        a.grad = c->d_grad.p;
-        a.cot = c->have_cot ? c->d_cot.p : nullptr;
-        a.partial = nullptr;
-        const int n_elem = 4 * c->N + 2;
-        if (grad_mode == 2) {
-            if ((rc = c->d_partial.ensure((size_t)tiles * n_elem))) return rc;
-            if ((rc = c->d_vjp.ensure((size_t)n_elem + (size_t)c->N))) return rc;  // [4N] end points, [2] fixed point, [N] phi
-            a.partial = c->d_partial.p;
+    } scan_join{c};
+    const int rw = 1 + (c->N + 31) / 32;
+    if (scan && c->nan_scan_async) {
+        if (c->scan_stream == nullptr || c->scan_stream_prio != c->nan_scan_prio) {
+            if (c->scan_stream) { HIP_TRY(hipStreamSynchronize(c->scan_stream)); HIP_TRY(hipStreamDestroy(c->scan_stream)); c->scan_stream = nullptr; }
+            int prio_lo = 0, prio_hi = 0;
+            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+            HIP_TRY(hipStreamCreateWithPriority(&c->scan_stream, hipStreamNonBlocking, c->nan_scan_prio ? prio_hi : prio_lo));
+            c->scan_stream_prio = c->nan_scan_prio;
         }
-        if (p->out_mode == D2D_OUT_OVERWRITE) c->have_vjp = false;
+        if (!c->ev_scan_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_fork, hipEventDisableTiming | hipEventDisableSystemFence));
+        if (!c->ev_scan_done) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_done, hipEventDisableTiming | hipEventDisableSystemFence));
+        if ((rc = c->d_nan_cells.ensure((size_t)s.tiles))) return rc;
+        if (grad_mode == 2 && (rc = c->d_nan_rows.ensure((size_t)s.tiles * rw))) return rc;
+        d2d::SweepArgs as = a;
+        as.nan_cell_bits = c->d_nan_cells.p;
+        as.nan_row_bits = grad_mode == 2 ? c->d_nan_rows.p : nullptr;
+        as.nan_row_words = rw;
+        // (the previous launch's nan_apply_kernel has read the flags: stream order through the fork event)
+        HIP_TRY(hipEventRecord(c->ev_scan_fork, c->stream));
+        HIP_TRY(hipStreamWaitEvent(c->scan_stream, c->ev_scan_fork, 0));
+        scan_join.armed = true;
+        if ((rc = launch_scan(c, s, c->scan_stream, as))) return rc;
+        HIP_TRY(hipEventRecord(c->ev_scan_done, c->scan_stream));
+        scan_beside = true;
+    }
+    if (culled_rx) {
+        // culled value+grad sweep (default)
+        a.cullq_off = (int)lds_tab;
+        rc = sweep_and_walk(c, s, pr, a, s.grid_patches, [&](const d2d::SweepArgs& x, dim3 g) {
+            return d2d::launch_fwd_grad(mode, x.rl != nullptr, p->max_order, g, lds_culled, c->stream, x);
+        });
+    } else if (s.txg_culled) {
+        // TX grid, culled value+grad sweep
+        rc = sweep_and_walk(c, s, pr, a, s.grid_patches, [&](const d2d::SweepArgs& x, dim3 g) {
+            return d2d::launch_txg(mode, x.rl != nullptr, true, p->max_order, g, lds_culled, c->stream, x);
+        });
+    } else {
         const size_t lds = (size_t)(4 * c->N + 4) * sizeof(float);
-        // (hard validity with fun = 1: nothing is differentiated through the path; order 0 alone: only path_length's own trap)
-        const bool scan = !p->strict_nan && (!txg || txg_culled) && c->nan_scan && (p->approx || p->fun_id != D2D_FUN_ONE) &&
-                          ((p->max_order >= 1 && !c->cw.empty()) || (p->min_order <= 0 && p->fun_id != D2D_FUN_ONE));
-        // The culled sweep writes the gradients of the candidates it evaluates; the reference's autodiff NaN positions -- an exact
-        // zero in the backward scan of ANY candidate, valid or not -- come from a pass of their own (d2d_nanscan.hpp), which
-        // poisons the cells and the patches' rows of VJP partial sums the way the exhaustive kernel (strict_nan) would have
-        // written them.  It reads the scene's tables and the grid only: it runs BESIDE the sweep on a stream of its own and
-        // leaves flags that nan_apply_kernel applies once both are through ("nan_scan_async" = 0: behind the sweep, as in round 4).
-        auto launch_scan = [&](hipStream_t st, const d2d::SweepArgs& as) -> int {
-            // two levels (a workgroup of 16 waves per region of 4 x 4 patches) when the region's list fits beside the tables
-            const size_t lds_r = (size_t)(3 * c->N) * sizeof(float4) + (size_t)d2d::NAN_LCAP * sizeof(unsigned long long) +
-                                 (size_t)(2 * d2d::NAN_W + 1) * (size_t)((c->N + 31) / 32) * sizeof(unsigned) + 16;
-            // (+ the kernel's static LDS: boxes, counters, the region's probe queue, its cells and their flag words)
-            const size_t lds_static = 512 + (size_t)d2d::NAN_WQCAP * sizeof(unsigned long long) + (size_t)d2d::NAN_W * (64 * sizeof(float2) + 16);
-            const bool regions = c->nan_scan_mode != 2 && lds_r + lds_static <= d2d_host::LDS_LIMIT && c->N <= 4095;
-            const size_t lds_n = regions ? lds_r : (size_t)(3 * c->N) * sizeof(float4) + (size_t)c->N * sizeof(int) + 16;
-            if (lds_n > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the NaN scan's LDS table", c->N);
-            unsigned long long* ns = nullptr;
-            if (c->nan_scan_stats) {
-                int rc2;
-                if ((rc2 = c->d_nan_stats.ensure(8))) return rc2;
-                HIP_TRY(hipMemsetAsync(c->d_nan_stats.p, 0, 8 * sizeof(unsigned long long), st));
-                ns = c->d_nan_stats.p;
-            }
-            const dim3 grid_regions((unsigned)(((tiles_x + d2d::NAN_R - 1) / d2d::NAN_R) * ((tiles_y + d2d::NAN_RY - 1) / d2d::NAN_RY)));
-            d2d::SweepArgs ac = as;
-            ac.nan_wqcap = c->nan_wqcap > 0 ? (int)c->nan_wqcap : d2d::NAN_WQCAP;  // (the kernel takes them as they are: never 0)
-            ac.nan_rb = c->nan_rb > 0 ? (int)c->nan_rb : d2d::NAN_RB;
-            // (the region kernel's debug instance -- run-time buffer sizes, counters -- only when a test asked for either)
-            const bool dbg = c->nan_wqcap > 0 || c->nan_rb > 0 || c->nan_scan_stats;
-            HIP_TRY(d2d::launch_nan_scan(p->approx != 0, txg, p->max_order, regions, dbg, regions ? grid_regions : grid_patches, lds_n, st, ac, ns));
-            return D2D_OK;
-        };
-        // every size check of the sweeps below comes BEFORE the scan is forked onto its own stream: nothing may fail between the
-        // fork and the join (a scan left running would read tables that a later d2d_set_scene rewrites)
-        if (!txg && !p->strict_nan) {
-            if ((size_t)(4 * c->N + 1) * sizeof(float4) + 512 > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
-        } else if (txg_culled) {
-            if ((size_t)(4 * c->N + 1) * sizeof(float4) > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
-        }
-        bool scan_beside = false;
-        // ... and should a launch fail behind the fork all the same (a HIP error), the scan is waited for before the error is returned
-        struct ScanJoin {
-            d2d_ctx* c;
-            bool armed = false;
-            ~ScanJoin() {
-                if (armed && c->scan_stream) (void)hipStreamSynchronize(c->scan_stream);
-            }
-        } scan_join{c};
-        if (scan && c->nan_scan_async) {
-            if (c->scan_stream == nullptr || c->scan_stream_prio != c->nan_scan_prio) {
-                if (c->scan_stream) { HIP_TRY(hipStreamSynchronize(c->scan_stream)); HIP_TRY(hipStreamDestroy(c->scan_stream)); c->scan_stream = nullptr; }
-                int prio_lo = 0, prio_hi = 0;
-                (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-                HIP_TRY(hipStreamCreateWithPriority(&c->scan_stream, hipStreamNonBlocking, c->nan_scan_prio ? prio_hi : prio_lo));
-                c->scan_stream_prio = c->nan_scan_prio;
-            }
-            if (!c->ev_scan_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_fork, hipEventDisableTiming | hipEventDisableSystemFence));
-            if (!c->ev_scan_done) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_done, hipEventDisableTiming | hipEventDisableSystemFence));
-            const int rw = 1 + (c->N + 31) / 32;
-            if ((rc = c->d_nan_cells.ensure((size_t)tiles))) return rc;
-            if (grad_mode == 2 && (rc = c->d_nan_rows.ensure((size_t)tiles * rw))) return rc;
-            d2d::SweepArgs as = a;
-            as.nan_cell_bits = c->d_nan_cells.p;
-            as.nan_row_bits = grad_mode == 2 ? c->d_nan_rows.p : nullptr;
-            as.nan_row_words = rw;
-            // (the previous launch's nan_apply_kernel has read the flags: stream order through the fork event)
-            HIP_TRY(hipEventRecord(c->ev_scan_fork, c->stream));
-            HIP_TRY(hipStreamWaitEvent(c->scan_stream, c->ev_scan_fork, 0));
-            scan_join.armed = true;
-            if ((rc = launch_scan(c->scan_stream, as))) return rc;
-            HIP_TRY(hipEventRecord(c->ev_scan_done, c->scan_stream));
-            scan_beside = true;
-        }
-        if (!txg && !p->strict_nan) {
-            // culled value+grad sweep (default)
-            const size_t lds2 = (size_t)(4 * c->N + 1) * sizeof(float4) + 512;  // tables, adjoint table, culling queue
-            if (lds2 > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
-            a.cullq_off = (int)((size_t)(4 * c->N + 1) * sizeof(float4));
-            HIP_TRY(d2d::launch_fwd_grad(mode, a.rl != nullptr, p->max_order, grid_patches, lds2, c->stream, a));
-            if (a.rl && !queue_impossible) {  // the patches the listed kernel left behind (usually none): a few workgroups walk the queue
-                d2d::SweepArgs af = a;
-                af.rl = nullptr; af.sched = nullptr; af.n_heavy = 0;
-                HIP_TRY(d2d::launch_fwd_grad(mode, false, p->max_order, dim3((unsigned)std::min<long long>(tiles, std::max<long long>(256, c->fb_hint))),
-                                             lds2, c->stream, af));
-                if ((rc = read_back_meta())) return rc;
-            }
-        } else if (txg_culled) {
-            // TX grid, culled value+grad sweep
-            const size_t lds2 = (size_t)(4 * c->N + 1) * sizeof(float4);
-            if (lds2 > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
-            HIP_TRY(d2d::launch_txg(mode, a.rl != nullptr, true, p->max_order, grid_patches, lds2, c->stream, a));
-            if (a.rl && !queue_impossible) {  // the patches the listed kernel left behind (usually none)
-                d2d::SweepArgs af = a;
-                af.rl = nullptr; af.sched = nullptr;
-                HIP_TRY(d2d::launch_txg(mode, false, true, p->max_order, grid_queue, lds2, c->stream, af));
-                if ((rc = read_back_meta())) return rc;
-            }
-        } else {
-            HIP_TRY(d2d::launch_vg(mode, txg, true, grid, lds, c->stream, a));
-        }
-        if (scan_beside) {
-            d2d::SweepArgs as = a;
-            as.nan_cell_bits = c->d_nan_cells.p;
-            as.nan_row_bits = grad_mode == 2 ? c->d_nan_rows.p : nullptr;
-            as.nan_row_words = 1 + (c->N + 31) / 32;
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_scan_done, 0));
-            scan_join.armed = false;  // joined: the main stream is behind the scan from here on
-            HIP_TRY(d2d::launch_nan_apply(c->stream, as, (long)tiles));
-        } else if (scan) {
-            if ((rc = launch_scan(c->stream, a))) return rc;
-        }
-        D2D_KERNEL_DONE();
-        if (grad_mode == 2) {
-            const long rows = (long)tiles;  // one row of partials per patch
-            if ((rc = join_comm(c, 2))) return rc;  // the previous step's all-reduce has finished with d_vjp
-            const int accumulate = (p->out_mode == D2D_OUT_ADD && c->have_vjp) ? 1 : 0;
-            c->vjp_has_phi = false;
-            c->vjp_reduced = false;
-            hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)n_elem), dim3(256), 0, c->stream, c->d_partial.p,
-                               rows, n_elem, c->d_vjp.p, accumulate);
-            HIP_TRY(hipGetLastError());
-            c->have_vjp = true;
-        }
-        return D2D_OK;
+        HIP_TRY(d2d::launch_vg(mode, txg, true, s.grid_patches, lds, c->stream, a));
     }
+    if (rc) return rc;
+    if (scan_beside) {
+        d2d::SweepArgs as = a;
+        as.nan_cell_bits = c->d_nan_cells.p;
+        as.nan_row_bits = grad_mode == 2 ? c->d_nan_rows.p : nullptr;
+        as.nan_row_words = rw;
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_scan_done, 0));
+        scan_join.armed = false;  // joined: the main stream is behind the scan from here on
+        HIP_TRY(d2d::launch_nan_apply(c->stream, as, (long)s.tiles));
+    } else if (scan) {
+        if ((rc = launch_scan(c, s, c->stream, a))) return rc;
+    }
+    if ((rc = sweep_done(c))) return rc;
+    if (grad_mode == 2) {
+        const long rows = (long)s.tiles;  // one row of partials per patch
+        if ((rc = join_comm(c, 2))) return rc;  // the previous step's all-reduce has finished with d_vjp
+        const int accumulate = (p->out_mode == D2D_OUT_ADD && c->have_vjp) ? 1 : 0;
+        c->vjp_has_phi = false;
+        c->vjp_reduced = false;
+        hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)n_elem), dim3(256), 0, c->stream, c->d_partial.p,
+                           rows, n_elem, c->d_vjp.p, accumulate);
+        HIP_TRY(hipGetLastError());
+        c->have_vjp = true;
+    }
+    return D2D_OK;
+}
+
+// RX grid, values (or the instrumented build): candidate by candidate (coop), every patch shared by 4 waves (split), or
+// one wave per patch with the dearest patches cut in four
+static int launch_rx_values(d2d_ctx* c, Sweep& s, const Prep& pr) {
+    const d2d_params* p = s.p;
+    d2d::SweepArgs& a = s.a;
+    const int mode = s.th.mode;
+    const long long tiles = s.tiles;
+    const bool stats = s.d_stats != nullptr;
+    int rc;
     const size_t tab_lds = d2d_host::tab_lds_bytes(c->N);  // tables (+ adjoint table) + one culling queue
     if (tab_lds > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table (max ~2400)", c->N);
     // Launches that hold only a few patches per SIMD are bound by their dearest patch: share every patch between
-    // D2D_SPLIT_W waves there (power_fwd_split_kernel).  Big grids are throughput-bound: one wave per patch.
-    constexpr int D2D_SPLIT_W = d2d::SPLIT_W;
-    const d2d_host::SplitLds sl = d2d_host::split_lds_bytes(c->N, D2D_SPLIT_W, d2d::SPLIT_LIST);
-    const size_t split_base = sl.base, split_lds = sl.total;  // ... + one culling queue per wave
+    // SPLIT_W waves there (power_fwd_split_kernel).  Big grids are throughput-bound: one wave per patch.
+    const d2d_host::SplitLds sl = d2d_host::split_lds_bytes(c->N, d2d::SPLIT_W, d2d::SPLIT_LIST);  // ... + one culling queue per wave
     // (sigmoid validity: a wave that adds to a list instead of the running sum loses the sum's absorption shortcut, sig_zc_of --
     // measured at 64^2 .. 640^2 cells of cfg2's scene the shared patches take 7.5 .. 11.6 ms, one wave per patch 5.4 .. 7.8)
     // (measured with the last-segment masks in place, sweep kernel, ms -- 4 waves per patch / one: hard 512^2 0.068 / 0.072,
     // 640^2 0.080 / 0.065; hard_sigmoid 384^2 0.141 / 0.123 (8 waves candidate by candidate: 0.104), 512^2 0.136 / 0.121,
     // 640^2 0.117 / 0.097: hard launches share their patches up to 5120 of them, hard_sigmoid ones only candidate by candidate)
     const long long split_lim = c->split_max_tiles >= 0 ? c->split_max_tiles : (mode == d2d::MODE_HARD ? 5120 : 0);
-    const bool split = p->max_order >= 2 && c->cw.size() >= 2 && split_lds <= d2d_host::LDS_LIMIT && tiles <= split_lim &&
+    const bool split = p->max_order >= 2 && c->cw.size() >= 2 && sl.total <= d2d_host::LDS_LIMIT && tiles <= split_lim &&
                        (mode != d2d::MODE_SIG || c->split_sigmoid);
     // the smallest launches (the grids of the reference's own examples): W waves per patch, candidate by candidate
     // (power_fwd_coop_kernel).  Measured on cfg2's scene, ms per sweep kernel, best other kernel first:
@@ -1873,7 +1861,7 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     //   hsig  128^2 0.204 -> 0.119 (16)         320^2 0.180 -> 0.163 (8)   384^2 0.136 -> 0.106 (8)   448^2 0.138 / 0.134
     //   sig   128^2 6.48 -> 1.28 (16)   200^2 6.26 -> 1.93 (16)   320^2 6.20 -> 3.07 (8)   512^2 5.35 -> 4.35 (4)   640^2 5.6 / 6.3
     int coop_w = 0;
-    if (p->max_order >= 2 && c->cw.size() >= 2 && a.rl != nullptr && !d_stats && c->coop_waves != 0) {
+    if (p->max_order >= 2 && c->cw.size() >= 2 && a.rl != nullptr && !stats && c->coop_waves != 0) {
         const bool sig = mode == d2d::MODE_SIG;
         const long long lim = c->coop_max_tiles >= 0 ? c->coop_max_tiles : (mode == d2d::MODE_HARD ? 640 : (sig ? 4096 : 2304));
         if (c->coop_waves > 0) coop_w = (int)c->coop_waves;
@@ -1883,8 +1871,8 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
         if (d2d_host::coop_lds_bytes(c->N, coop_w, d2d::COOP_C) + 4096 > d2d_host::LDS_LIMIT ||  /* (+ the kernel's static LDS: masks, chunks, floor) */ tiles > lim || (c->coop_waves < 0 && c->split_max_tiles >= 0 && tiles > c->split_max_tiles)) coop_w = 0;
     }
     // the dearest patches of a bigger launch are cut in four (see power_fwd_kernel); they are only known with a work history
-    dim3 grid_fwd = grid_patches;
-    if (!split && !coop_w && !d_stats && p->max_order == 2 && c->cw.size() >= 2 && a.sched == c->d_sched.p && sched_from_history && c->heavy_split != 0) {
+    dim3 grid_fwd = s.grid_patches;
+    if (!split && !coop_w && !stats && p->max_order == 2 && c->cw.size() >= 2 && a.sched == c->cur.d_sched.p && pr.sched_from_history && c->heavy_split != 0) {
         const long long P = d2d::HEAVY_PARTS;
         // -1 (default): launches that are only a few patch latencies long (fewer than 4 patches per wave slot of the chip)
         // are bound by their dearest patches: one patch in 93 is cut there (measured best at 1024^2), else 64 patches
@@ -1919,18 +1907,14 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
             grid_fwd = dim3((unsigned)(tiles + (P - 1) * H));
         }
     }
-    a.cullq_off = (int)(split ? split_base : (size_t)(4 * c->N + 1) * sizeof(float4));
+    a.cullq_off = (int)(split ? sl.base : (size_t)(4 * c->N + 1) * sizeof(float4));
     c->last_shape_waves = coop_w ? coop_w : (split ? 4 : 1);
     c->last_shape_coop = coop_w ? 1 : 0;
-    if (coop_w) HIP_TRY(d2d::launch_fwd_coop(mode, p->max_order, coop_w, grid_patches, d2d_host::coop_lds_bytes(c->N, coop_w, d2d::COOP_C), c->stream, a));
-    else if (split) HIP_TRY(d2d::launch_fwd_split(mode, a.rl != nullptr, d_stats != nullptr, p->max_order, grid_patches, split_lds, c->stream, a));
-    else {
-        // one patch per wave, fwd_waves waves per workgroup (fewer, bigger workgroups are dispatched faster)
-        // (0: 4 when a single-wave workgroup's LDS would keep a CU below 32 waves, else 1; STATS and the enumerating build: 1)
-        unsigned wpb = c->fwd_waves > 0 ? (unsigned)c->fwd_waves : ((tab_lds * 32 > 160 * 1024) ? 4u : 1u);
-        if (!a.rl || d_stats) wpb = 1;
-        const dim3 g((grid_fwd.x + wpb - 1) / wpb, wpb);
+    // one patch per wave, fwd_waves waves per workgroup (fewer, bigger workgroups are dispatched faster)
+    // (0: 4 when a single-wave workgroup's LDS would keep a CU below 32 waves, else 1; STATS and the enumerating build: 1)
+    const unsigned wpb_listed = c->fwd_waves > 0 ? (unsigned)c->fwd_waves : ((tab_lds * 32 > 160 * 1024) ? 4u : 1u);
 #ifdef D2D_AB_TIMELINE  // diagnostic build: one start / end stamp per workgroup, read back by d2d_debug_get_work
+    if (!coop_w && !split) {
         if (c->tl_ring_on) {
             // ... or only the first start / the end of every launch (an unperturbed pipelined sequence: scripts/launch_gaps.py)
             a.tl_ring = c->d_tl_ring.p;
@@ -1939,25 +1923,68 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
             if ((rc = c->d_timeline.ensure(2 * (size_t)grid_fwd.x + 64))) return rc;
             HIP_TRY(hipMemsetAsync(c->d_timeline.p, 0, (2 * (size_t)grid_fwd.x + 64) * sizeof(unsigned), c->stream));
             c->timeline_n = 2 * (long long)grid_fwd.x;
-            if (!d_stats) a.grad = reinterpret_cast<float*>(c->d_timeline.p);
+            if (!stats) a.grad = reinterpret_cast<float*>(c->d_timeline.p);
         }
+    }
 #endif
-        HIP_TRY(d2d::launch_fwd(mode, a.rl != nullptr, d_stats != nullptr, p->max_order, g, tab_lds + (wpb - 1) * 512, c->stream, a));
+    // (the queue walker -- x without lists -- is the split or the one-wave-per-patch kernel)
+    rc = sweep_and_walk(c, s, pr, a, grid_fwd, [&](const d2d::SweepArgs& x, dim3 g) {
+        const bool listed = x.rl != nullptr;
+        if (coop_w && listed) return d2d::launch_fwd_coop(mode, p->max_order, coop_w, g, d2d_host::coop_lds_bytes(c->N, coop_w, d2d::COOP_C), c->stream, x);
+        if (split) return d2d::launch_fwd_split(mode, listed, stats, p->max_order, g, sl.total, c->stream, x);
+        const unsigned wpb = (listed && !stats) ? wpb_listed : 1u;
+        const hipError_t e = d2d::launch_fwd(mode, listed, stats, p->max_order, dim3((g.x + wpb - 1) / wpb, wpb), tab_lds + (wpb - 1) * 512, c->stream, x);
 #ifdef D2D_AB_TIMELINE
-        if (c->tl_ring_on) hipLaunchKernelGGL(d2d::tl_end_kernel, dim3(1), dim3(1), 0, c->stream, c->d_tl_ring.p, a.tl_seq);
+        if (c->tl_ring_on && &x == &a) hipLaunchKernelGGL(d2d::tl_end_kernel, dim3(1), dim3(1), 0, c->stream, c->d_tl_ring.p, a.tl_seq);
 #endif
-    }
-    if (a.rl && !queue_impossible) {  // the patches the listed kernel left behind (usually none): a few workgroups walk the queue
-        d2d::SweepArgs af = a;
-        af.rl = nullptr; af.sched = nullptr; af.n_heavy = 0;
-        const dim3 gq((unsigned)std::min<long long>(tiles, std::max<long long>(256, c->fb_hint)));
-        if (split) HIP_TRY(d2d::launch_fwd_split(mode, false, d_stats != nullptr, p->max_order, gq, split_lds, c->stream, af));
-        else HIP_TRY(d2d::launch_fwd(mode, false, d_stats != nullptr, p->max_order, gq, tab_lds, c->stream, af));
-        if ((rc = read_back_meta())) return rc;
-    }
-    D2D_KERNEL_DONE();
-    return D2D_OK;
+        return e;
+    });
+    if (rc) return rc;
+    return sweep_done(c);
 }
+
+static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsigned long long* d_stats, int grad_mode = 0) {
+    if (!c || !tx) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before a sweep");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before a sweep");
+    c->have_kernel_time = false;  // whatever this launch turns out to be, the previous launch's kernel time is stale
+    if (p->fun_id == D2D_FUN_CUSTOM && !grad_mode) return fail(D2D_ERR_UNSUPPORTED, "fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only");
+    if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT) {
+        if (d_stats) return fail(D2D_ERR_UNSUPPORTED, "the optimiser-based solvers have no instrumented build");
+        return opt_sweep_launch(c, p, tx, grad_mode);
+    }
+    d2d_params p_custom;
+    if (p->fun_id == D2D_FUN_CUSTOM) {
+        if ((rc = custom_fun_params(c, p, &p_custom))) return rc;
+        p = &p_custom;
+    }
+    if ((rc = check_image_sweep(c, p, d_stats))) return rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = upload_occl(c, p->patch))) return rc;
+
+    Sweep s;
+    s.p = p;
+    s.tx = tx;
+    s.d_stats = d_stats;
+    s.grad_mode = grad_mode;
+    s.tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
+    s.tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
+    s.tiles = (long long)s.tiles_x * s.tiles_y;
+    Prep pr;
+    if ((rc = take_prep_set(c, s)) || (rc = sweep_args(c, s))) return rc;
+    if ((rc = prep_masks(c, s, pr)) || (rc = prep_region_lists(c, s, pr))) return rc;
+    if (!s.a.rl) c->rl_plan.on = false;
+    if ((rc = prep_schedule(c, s, pr)) || (rc = sweep_begin(c, s))) return rc;
+    if (grad_mode) return launch_value_grad(c, s, pr);
+    if (s.txg) return launch_txg_values(c, s, pr);
+    return launch_rx_values(c, s, pr);
+}
+
+}  // namespace
+
+extern "C" {
 
 int d2d_power_map_launch(d2d_ctx* c, const d2d_params* p, const float* tx) { return sweep_launch(c, p, tx, nullptr); }
 
@@ -2099,8 +2126,7 @@ int d2d_set_option(d2d_ctx* c, const char* name, int64_t value) {
         // (the two sets must not be mixed up by a switch in mid-flight)
         if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->aux_stream) HIP_TRY(hipStreamSynchronize(c->aux_stream));
-        c->swept_pending = false;
-        for (int i = 0; i < d2d_ctx::N_SPARE; ++i) c->spare_sets[i].swept_pending = false;
+        c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.swept_pending = false; });
         c->pipeline = value != 0;
     }
     else if (!strcmp(name, "unpiped_max_tiles")) {
@@ -2211,8 +2237,8 @@ int d2d_debug_get_work(d2d_ctx* c, uint32_t* work, int64_t n) {
         return (int)0;
     }
 #endif
-    if (!c->d_cost.p || c->cost_tiles != n) return fail(D2D_ERR_STATE, "no work history of %lld patches", (long long)n);
-    HIP_TRY(hipMemcpyAsync(work, c->d_cost.p, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    if (!c->cur.d_cost.p || c->cur.cost_tiles != n) return fail(D2D_ERR_STATE, "no work history of %lld patches", (long long)n);
+    HIP_TRY(hipMemcpyAsync(work, c->cur.d_cost.p, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return D2D_OK;
 }
@@ -2238,11 +2264,11 @@ int d2d_debug_region_stats(d2d_ctx* c, int64_t* out) {
     if (!c->rl_plan.on) return D2D_OK;
     const d2d_host::RegionPlan& rp = c->rl_plan;
     std::vector<int> meta(2 + (size_t)rp.leaf.regions);
-    HIP_TRY(hipMemcpyAsync(meta.data(), c->rl_meta_ptr, meta.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(meta.data(), c->cur.rl_meta_ptr, meta.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     const int orders = c->rl_max_order - rp.k_lo + 1;
     const size_t per_order = (size_t)rp.leaf.slots + (size_t)rp.top.slots;
     std::vector<int> idx(per_order * (size_t)orders);
-    HIP_TRY(hipMemcpyAsync(idx.data(), c->d_rl_idx.p, idx.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(idx.data(), c->cur.d_rl_idx.p, idx.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     out[0] = meta[1] + rp.n_static;
     out[1] = rp.max_chunks;
@@ -2260,9 +2286,9 @@ int d2d_debug_get_schedule(d2d_ctx* c, int32_t* order, uint8_t* key, int64_t n) 
     if (!c || !order || !key) return fail(D2D_ERR_INVALID, "NULL argument");
     int rc = set_device(c);
     if (rc) return rc;
-    if (!c->d_sched.p || !c->d_sched_key.p || (size_t)n > c->d_sched.n) return fail(D2D_ERR_STATE, "no schedule of %lld patches has been built", (long long)n);
-    HIP_TRY(hipMemcpyAsync(order, c->d_sched.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(key, c->d_sched_key.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (!c->cur.d_sched.p || !c->cur.d_sched_key.p || (size_t)n > c->cur.d_sched.n) return fail(D2D_ERR_STATE, "no schedule of %lld patches has been built", (long long)n);
+    HIP_TRY(hipMemcpyAsync(order, c->cur.d_sched.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(key, c->cur.d_sched_key.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return D2D_OK;
 }

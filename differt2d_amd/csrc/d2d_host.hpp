@@ -1,7 +1,7 @@
 // Host-only logic of libd2d.so that needs neither a device nor the HIP headers: candidate enumeration (the stand-in for
-// differt-core's Rust graph iterator, differt2d/scene.py:153-175), parameter validation, lax.integer_pow, and the
-// buffer-size arithmetic of the sweep launches (LDS tables, the contribution lists of the patches cut in four and their
-// 4 GiB guard).  d2d.hip uses these functions as they are; tests/native/d2d_host_san.cpp compiles the same header with
+// differt-core's Rust graph iterator, differt2d/scene.py:153-175), parameter validation, lax.integer_pow, the
+// scalar thresholds of a sweep, and the buffer-size arithmetic of the sweep launches (LDS tables, the contribution lists
+// of the patches cut in four and their 4 GiB guard).  d2d.hip uses these functions as they are; tests/native/d2d_host_san.cpp compiles the same header with
 // g++ -fsanitize=address,undefined and tests/test_host_sanitizers.py drives it (sanitizers run on the CPU build only).
 #pragma once
 #include <stdint.h>
@@ -216,6 +216,75 @@ inline HeavyPlan heavy_plan(long long tiles, long long Nc, long long heavy_split
     hp.list_floats = H * parts * cap * 64;
     hp.cnt_ints = H * parts * 64 + H * parts;
     return hp;
+}
+
+// ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
+enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
+struct SweepThresholds {
+    int mode = SWEEP_HARD;
+    double widen = 0.0, widen_in = 0.0, widen_flt = 0.0;
+    float flt_lo = 0.0f, flt_hi = 0.0f, on_lo = 0.0f, on_hi = 0.0f;
+    float loss_skip = -1.0f;
+    float fnum[D2D_MAX_ORDER + 1] = {};
+    float h2 = 0.0f;
+    float sig_l2f = 1e30f;
+    int sig_mono = 1;
+    bool degenerate_invalid = false;
+};
+// The thresholds of the culling tests and shortcuts of an ImagePath sweep with parameters p (checked by check_params).
+// grad: a value+grad sweep; sig_narrow_filter: the "sig_narrow_filter" option.
+inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad, bool sig_narrow_filter) {
+    SweepThresholds t;
+    // Filter thresholds: the soft window is where some activation of t is not exactly saturated
+    // to "outside": hard -> [-tol, 1+tol]; hard_sigmoid -> widened by 3/alpha; sigmoid -> by 89/alpha
+    // (exp(89) overflows fp32, 1/(1+inf) == 0).  1e-5 relative slack covers every rounding in the
+    // filter's own arithmetic (a few ulp).
+    if (p.approx) {
+        t.mode = (p.act == D2D_ACT_HARD_SIGMOID) ? SWEEP_HSIG : SWEEP_SIG;
+        t.widen = ((t.mode == SWEEP_HSIG) ? 3.0 : 89.0) / (double)p.alpha;
+    }
+    t.widen_in = !p.approx ? 0.0 : ((t.mode == SWEEP_HSIG) ? 3.0 : 17.5) / (double)p.alpha * (1.0 + 1e-5);
+    // (sigmoid, forward sweeps: an occlusion test only enters the map through 1 - max_j sigmoid(z_j), and sigmoid(z) < 2^-25
+    // -- z < -17.33 -- leaves 1 - hit at exactly 1.0f, as no test at all would: the divide-free filter may drop what is
+    // certainly below -17.5 instead of what is certainly below -89.  The value+grad build keeps the wide window: it records
+    // which test carries the max.)
+    t.widen_flt = (t.mode == SWEEP_SIG && !grad && sig_narrow_filter) ? 17.5 / (double)p.alpha : t.widen;
+    const double lo = -((double)p.seg_tol + t.widen_flt);
+    const double hi = 1.0 + (double)p.seg_tol + t.widen_flt;
+    t.flt_lo = (float)(lo * (1.0 + 1e-5) - 1e-30);
+    t.flt_hi = (float)(hi * (1.0 + 1e-5) + 1e-30);
+    // on_objects is exactly 0 / False once s < -widen or s > 1 + widen (same saturation argument)
+    t.on_lo = (float)(-t.widen * (1.0 + 1e-5) - 1e-30);
+    t.on_hi = (float)((1.0 + t.widen) * (1.0 + 1e-5) + 1e-30);
+    // loss certificate threshold (d2d_kernels.hpp): hard -> loss < tol decides; approx -> tol - loss must round to tol
+    if (p.tol > 1e-30f && std::isfinite(p.tol)) {
+        if (!p.approx) t.loss_skip = p.tol * 0.999f;
+        else t.loss_skip = 0.49f * (p.tol - std::nextafterf(p.tol, 0.0f));
+    }
+    for (int k = 0; k <= D2D_MAX_ORDER; ++k) t.fnum[k] = integer_pow(p.r_coef, k);
+    t.h2 = p.height * p.height;
+    // sigmoid validity: an upper bound of |fun| lets the kernels skip contributions that cannot change the running sum
+    for (int k = p.min_order; k <= p.max_order; ++k) t.sig_mono = t.sig_mono && (t.fnum[k] >= 0.0f || p.fun_id != D2D_FUN_RECEIVED_POWER);
+    if (p.fun_id == D2D_FUN_ONE) {
+        t.sig_l2f = 0.0f;
+    } else if (p.fun_id == D2D_FUN_RECEIVED_POWER && t.h2 > 0.0f && std::isfinite(t.h2)) {
+        float fm = 0.0f;  // received_power = r_coef^k / (h^2 + r^2) <= |r_coef|^k / h^2
+        bool ok = true;
+        for (int k = p.min_order; k <= p.max_order; ++k) {
+            const float f = std::fabs(t.fnum[k]) / t.h2;
+            ok = ok && std::isfinite(f);
+            fm = std::fmax(fm, f);
+        }
+        if (ok && fm > 0.0f) t.sig_l2f = std::log2(fm) + 1e-3f;
+        else if (ok) t.sig_l2f = -1e30f;  // fun == 0 throughout
+    }
+    if (p.fun_id == D2D_FUN_CUSTOM) t.sig_mono = 0;  // (values of any sign)
+    // A step of the backward scan with un == 0 (the line to the image parallel to the wall, geometry.py:1105) leaves a
+    // zero-length segment, loss >= 1 (0.999 with roundings): is such a path exactly invalid under this tol / activation?
+    const double x_deg = (double)p.tol - 0.999;  // tol - loss at best
+    t.degenerate_invalid = !p.approx ? (p.tol <= 0.5f)
+                                     : (t.mode == SWEEP_HSIG ? ((double)p.alpha * x_deg + 3.0 <= -1e-3) : ((double)p.alpha * x_deg <= -89.5));
+    return t;
 }
 
 // ---- region candidate lists (region_list_kernel / region_refine_kernel) ----------------------------------------------

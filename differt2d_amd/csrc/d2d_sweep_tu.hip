@@ -2,6 +2,8 @@
 // per-mode launcher that d2d_launch.cpp's dispatchers call.  Compiled several times by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 5 region lists (mode 0 only), 9 fwd_coop,
 //   6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2 taken from the region lists (LISTED), 10 NaN scan (mode 0 only)}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}
+#include <type_traits>
+
 #include "d2d_launch.hpp"
 #if D2D_TU_FAMILY == 10
 #include "d2d_nanscan.hpp"
@@ -15,20 +17,21 @@ namespace d2d {
 
 constexpr int TU_MODE = D2D_TU_MODE;
 
+// the kernels' MAXK for a launch of orders up to max_order (2 also covers orders 0 and 1): f(std::integral_constant<int, MAXK>)
+template <class F>
+static void by_maxk(int max_order, F f) {
+    if (max_order <= 2) f(std::integral_constant<int, 2>{});
+    else if (max_order == 3) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
 #if D2D_TU_FAMILY == 0
 template <int MODE> hipError_t launch_fwd_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
-    if (stats) {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, 2>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, 3>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, 4>), grid, block, lds, s, a);
-    } else {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 2>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 3>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 4>), grid, block, lds, s, a);
-    }
+    if (stats) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, decltype(K)::value>), grid, block, lds, s, a); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, decltype(K)::value>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 1
@@ -36,9 +39,7 @@ template <int MODE> hipError_t launch_fwd_grad_m(int max_order, dim3 grid, size_
 template <>
 hipError_t launch_fwd_grad_m<TU_MODE>(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
-    if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 2, true>), grid, block, lds, s, a);
-    else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 3, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 4, true>), grid, block, lds, s, a);
+    by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, decltype(K)::value, true>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 2
@@ -46,15 +47,8 @@ template <int MODE> hipError_t launch_fwd_split_m(bool stats, int max_order, dim
 template <>
 hipError_t launch_fwd_split_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64 * SPLIT_W);
-    if (stats) {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, 2, SPLIT_W>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, 3, SPLIT_W>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, 4, SPLIT_W>), grid, block, lds, s, a);
-    } else {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, 2, SPLIT_W>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, 3, SPLIT_W>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, 4, SPLIT_W>), grid, block, lds, s, a);
-    }
+    if (stats) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, decltype(K)::value, SPLIT_W>), grid, block, lds, s, a); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, decltype(K)::value, SPLIT_W>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 3
@@ -62,25 +56,10 @@ template <int MODE> hipError_t launch_txg_m(bool listed, bool grad, int max_orde
 template <>
 hipError_t launch_txg_m<TU_MODE>(bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
-    if (listed) {
-        if (grad) {
-            if (max_order <= 2) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 2, true, true>), grid, block, lds, s, a);
-            else if (max_order == 3) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 3, true, true>), grid, block, lds, s, a);
-            else hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 4, true, true>), grid, block, lds, s, a);
-        } else {
-            if (max_order <= 2) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 2, false, true>), grid, block, lds, s, a);
-            else if (max_order == 3) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 3, false, true>), grid, block, lds, s, a);
-            else hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 4, false, true>), grid, block, lds, s, a);
-        }
-    } else if (grad) {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 2, true>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 3, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 4, true>), grid, block, lds, s, a);
-    } else {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 2>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 3>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, 4>), grid, block, lds, s, a);
-    }
+    if (listed && grad) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, decltype(K)::value, true, true>), grid, block, lds, s, a); });
+    else if (listed) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, decltype(K)::value, false, true>), grid, block, lds, s, a); });
+    else if (grad) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, decltype(K)::value, true>), grid, block, lds, s, a); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_txg_kernel<TU_MODE, decltype(K)::value>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 4
@@ -100,19 +79,9 @@ hipError_t launch_fwd_listed_m<TU_MODE>(bool stats, int max_order, dim3 grid, si
     const bool wide = grid.y == 4;  // (grid.y carries the waves per workgroup: 1 or 4)
     const dim3 block(wide ? 256 : 64);
     grid.y = 1;
-    if (stats) {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, 2, false, true>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, 3, false, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, 4, false, true>), grid, block, lds, s, a);
-    } else if (wide) {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 2, false, true, 4>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 3, false, true, 4>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 4, false, true, 4>), grid, block, lds, s, a);
-    } else {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 2, false, true>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 3, false, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 4, false, true>), grid, block, lds, s, a);
-    }
+    if (stats) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, true, decltype(K)::value, false, true>), grid, block, lds, s, a); });
+    else if (wide) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, decltype(K)::value, false, true, 4>), grid, block, lds, s, a); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, decltype(K)::value, false, true>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 7
@@ -120,9 +89,7 @@ template <int MODE> hipError_t launch_fwd_grad_listed_m(int max_order, dim3 grid
 template <>
 hipError_t launch_fwd_grad_listed_m<TU_MODE>(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
-    if (max_order <= 2) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 2, true, true>), grid, block, lds, s, a);
-    else if (max_order == 3) hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 3, true, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, 4, true, true>), grid, block, lds, s, a);
+    by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_kernel<TU_MODE, false, decltype(K)::value, true, true>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 8
@@ -130,15 +97,8 @@ template <int MODE> hipError_t launch_fwd_split_listed_m(bool stats, int max_ord
 template <>
 hipError_t launch_fwd_split_listed_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64 * SPLIT_W);
-    if (stats) {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, 2, SPLIT_W, true>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, 3, SPLIT_W, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, 4, SPLIT_W, true>), grid, block, lds, s, a);
-    } else {
-        if (max_order <= 2) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, 2, SPLIT_W, true>), grid, block, lds, s, a);
-        else if (max_order == 3) hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, 3, SPLIT_W, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, 4, SPLIT_W, true>), grid, block, lds, s, a);
-    }
+    if (stats) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, true, decltype(K)::value, SPLIT_W, true>), grid, block, lds, s, a); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_split_kernel<TU_MODE, false, decltype(K)::value, SPLIT_W, true>), grid, block, lds, s, a); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 9
@@ -146,9 +106,7 @@ template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid
 template <int W>
 static void launch_fwd_coop_w(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64 * W);
-    if (max_order <= 2) hipLaunchKernelGGL((power_fwd_coop_kernel<TU_MODE, 2, W>), grid, block, lds, s, a);
-    else if (max_order == 3) hipLaunchKernelGGL((power_fwd_coop_kernel<TU_MODE, 3, W>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((power_fwd_coop_kernel<TU_MODE, 4, W>), grid, block, lds, s, a);
+    by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_fwd_coop_kernel<TU_MODE, decltype(K)::value, W>), grid, block, lds, s, a); });
 }
 template <>
 hipError_t launch_fwd_coop_m<TU_MODE>(int max_order, int W, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
@@ -159,81 +117,47 @@ hipError_t launch_fwd_coop_m<TU_MODE>(int max_order, int W, dim3 grid, size_t ld
 }
 #elif D2D_TU_FAMILY == 5
 // region_list_kernel / region_refine_kernel <K, GRAD>: independent of the validity mode (compiled once, -DD2D_TU_MODE=0)
+// (`grad` is unused: the value+grad sweeps read the forward sweeps' lists, their NaN positions come from d2d_nanscan.hpp)
 hipError_t launch_region_lists(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RegionLevel& lv,
                                const ListPool& lp) {
     const dim3 block(64);
-#define D2D_RL(KK, G, T) hipLaunchKernelGGL((region_list_kernel<KK, G, T>), grid, block, lds, s, a, lv, lp)
-#define D2D_RL_K(G, T)            \
-    do {                          \
-        if (K == 2) D2D_RL(2, G, T);      \
-        else if (K == 3) D2D_RL(3, G, T); \
-        else D2D_RL(4, G, T);             \
-    } while (0)
-    (void)grad;  // (the value+grad sweeps read the forward sweeps' lists: their NaN positions come from d2d_nanscan.hpp)
-    if (txg) D2D_RL_K(false, true);
-    else D2D_RL_K(false, false);
-#undef D2D_RL_K
-#undef D2D_RL
+    if (txg) by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_list_kernel<decltype(KK)::value, false, true>), grid, block, lds, s, a, lv, lp); });
+    else by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_list_kernel<decltype(KK)::value, false, false>), grid, block, lds, s, a, lv, lp); });
     return hipGetLastError();
 }
 hipError_t launch_region_refine(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RegionLevel& lv,
                                 const RegionLevel& parent, const ListPool& lp, int* flag) {
     const dim3 block(64);
-#define D2D_RR(KK, G, T) hipLaunchKernelGGL((region_refine_kernel<KK, G, T>), grid, block, lds, s, a, lv, parent, lp, flag)
-#define D2D_RR_K(G, T)            \
-    do {                          \
-        if (K == 2) D2D_RR(2, G, T);      \
-        else if (K == 3) D2D_RR(3, G, T); \
-        else D2D_RR(4, G, T);             \
-    } while (0)
-    (void)grad;
-    if (txg) D2D_RR_K(false, true);
-    else D2D_RR_K(false, false);
-#undef D2D_RR_K
-#undef D2D_RR
+    if (txg) by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_refine_kernel<decltype(KK)::value, false, true>), grid, block, lds, s, a, lv, parent, lp, flag); });
+    else by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_refine_kernel<decltype(KK)::value, false, false>), grid, block, lds, s, a, lv, parent, lp, flag); });
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 10
 // nan_scan_kernel<APPROX, TXG, MAXK>: depends on hard / approx only (compiled once, -DD2D_TU_MODE=0)
+// regions: nan_scan_region_kernel, and its DBG instance (run-time buffer sizes and counters -- tests; the product launches DBG = false)
+template <bool APPROX, bool TXG>
+static void launch_nan_scan_regions(int max_order, bool dbg, dim3 grid, dim3 block, size_t lds, hipStream_t s, const SweepArgs& a, unsigned long long* stats) {
+    if (dbg) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((nan_scan_region_kernel<APPROX, TXG, decltype(K)::value, true>), grid, block, lds, s, a, stats); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((nan_scan_region_kernel<APPROX, TXG, decltype(K)::value>), grid, block, lds, s, a, stats); });
+}
+template <bool APPROX, bool TXG>
+static void launch_nan_scan_patches(int max_order, dim3 grid, dim3 block, size_t lds, hipStream_t s, const SweepArgs& a, unsigned long long* stats) {
+    by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((nan_scan_kernel<APPROX, TXG, decltype(K)::value>), grid, block, lds, s, a, stats); });
+}
 hipError_t launch_nan_scan(bool approx, bool txg, int max_order, bool regions, bool dbg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a,
                            unsigned long long* stats) {
     const dim3 block(regions ? 64 * NAN_W : 64);
-#define D2D_NS(KERNEL, ...)                                                                                   \
-    do {                                                                                                      \
-        if (max_order <= 2) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, 2>), grid, block, lds, s, a, stats);      \
-        else if (max_order == 3) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, 3>), grid, block, lds, s, a, stats); \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, 4>), grid, block, lds, s, a, stats);                     \
-    } while (0)
-    // (the region kernel's DBG instance: run-time buffer sizes and counters -- tests; the product launches DBG = false)
-#define D2D_NSR(A, T)                                                                                                      \
-    do {                                                                                                                   \
-        if (dbg) {                                                                                                         \
-            if (max_order <= 2) hipLaunchKernelGGL((nan_scan_region_kernel<A, T, 2, true>), grid, block, lds, s, a, stats); \
-            else if (max_order == 3) hipLaunchKernelGGL((nan_scan_region_kernel<A, T, 3, true>), grid, block, lds, s, a, stats); \
-            else hipLaunchKernelGGL((nan_scan_region_kernel<A, T, 4, true>), grid, block, lds, s, a, stats);               \
-        } else {                                                                                                           \
-            D2D_NS(nan_scan_region_kernel, A, T);                                                                          \
-        }                                                                                                                  \
-    } while (0)
     if (regions) {
-        if (approx) {
-            if (txg) D2D_NSR(true, true);
-            else D2D_NSR(true, false);
-        } else {
-            if (txg) D2D_NSR(false, true);
-            else D2D_NSR(false, false);
-        }
+        if (approx && txg) launch_nan_scan_regions<true, true>(max_order, dbg, grid, block, lds, s, a, stats);
+        else if (approx) launch_nan_scan_regions<true, false>(max_order, dbg, grid, block, lds, s, a, stats);
+        else if (txg) launch_nan_scan_regions<false, true>(max_order, dbg, grid, block, lds, s, a, stats);
+        else launch_nan_scan_regions<false, false>(max_order, dbg, grid, block, lds, s, a, stats);
     } else {
-        if (approx) {
-            if (txg) D2D_NS(nan_scan_kernel, true, true);
-            else D2D_NS(nan_scan_kernel, true, false);
-        } else {
-            if (txg) D2D_NS(nan_scan_kernel, false, true);
-            else D2D_NS(nan_scan_kernel, false, false);
-        }
+        if (approx && txg) launch_nan_scan_patches<true, true>(max_order, grid, block, lds, s, a, stats);
+        else if (approx) launch_nan_scan_patches<true, false>(max_order, grid, block, lds, s, a, stats);
+        else if (txg) launch_nan_scan_patches<false, true>(max_order, grid, block, lds, s, a, stats);
+        else launch_nan_scan_patches<false, false>(max_order, grid, block, lds, s, a, stats);
     }
-#undef D2D_NSR
-#undef D2D_NS
     return hipGetLastError();
 }
 hipError_t launch_nan_apply(hipStream_t s, const SweepArgs& a, long tiles) {

@@ -1,5 +1,5 @@
 // C entry points over differt2d_amd/csrc/d2d_host.hpp -- the host-only logic of libd2d.so (candidate enumeration,
-// parameter validation, launch buffer sizes) -- for the CPU sanitizer build:
+// parameter validation, sweep thresholds, launch buffer sizes) -- for the CPU sanitizer build:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared -fPIC
 // (tests/test_host_sanitizers.py).  The product compiles the very same header into libd2d.so with hipcc.
 #include "../../differt2d_amd/csrc/d2d_host.hpp"
@@ -55,6 +55,16 @@ void san_region_plan(int tiles_x, int tiles_y, long long Nc, int min_order, int 
     out12[1] = rp.top.R; out12[2] = rp.top.S; out12[3] = rp.top.regions; out12[4] = rp.top.slots;
     out12[5] = rp.leaf.R; out12[6] = rp.leaf.S; out12[7] = rp.leaf.regions; out12[8] = rp.leaf.slots;
     out12[9] = rp.n_static; out12[10] = rp.max_chunks; out12[11] = rp.k_lo;
+}
+
+// d: widen, widen_in, widen_flt; f: flt_lo, flt_hi, on_lo, on_hi, loss_skip, h2, sig_l2f, fnum[0 .. D2D_MAX_ORDER];
+// i: mode, sig_mono, degenerate_invalid
+void san_sweep_thresholds(const d2d_params* p, int grad, int sig_narrow_filter, double* d3, float* f12, int* i3) {
+    const d2d_host::SweepThresholds t = d2d_host::sweep_thresholds(*p, grad != 0, sig_narrow_filter != 0);
+    d3[0] = t.widen; d3[1] = t.widen_in; d3[2] = t.widen_flt;
+    f12[0] = t.flt_lo; f12[1] = t.flt_hi; f12[2] = t.on_lo; f12[3] = t.on_hi; f12[4] = t.loss_skip; f12[5] = t.h2; f12[6] = t.sig_l2f;
+    for (int k = 0; k <= D2D_MAX_ORDER; ++k) f12[7 + k] = t.fnum[k];
+    i3[0] = t.mode; i3[1] = t.sig_mono; i3[2] = t.degenerate_invalid ? 1 : 0;
 }
 
 }  // extern "C"
