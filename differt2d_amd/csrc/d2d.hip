@@ -172,6 +172,7 @@ struct d2d_ctx {
     int bc_steps = -1;
     double bc_b1 = 0.0, bc_b2 = 0.0;    // ... and the decay rates the tabulated bias corrections belong to
     double opt_lr = 0.1, opt_b1 = 0.9, opt_b2 = 0.999, opt_eps = 1e-8;  // d2d_set_optimizer (optax.adam's defaults, optimize.py:83)
+    int opt_kind = D2D_OPT_ADAM;  // D2D_OPT_SGD*: opt_b1 holds the momentum, opt_b2 the Nesterov flag (include/d2d.h)
     std::vector<float> theta0;  // [C][D2D_MAX_ORDER] as set by d2d_set_theta0
     DevBuf<int> d_scand, d_sorder;
     // trace scratch
@@ -412,11 +413,23 @@ d2d::ObjTables obj_tables(d2d_ctx* c) {
 }
 
 // optax.adam(0.1) defaults (optimize.py:83): b1 = 0.9, b2 = 0.999, eps = 1e-8 -- or what d2d_set_optimizer said; bias
-// corrections 1 - b^t tabulated in double precision and rounded to fp32 (the oracle does the same).
+// corrections 1 - b^t tabulated in double precision and rounded to fp32 (the oracle does the same).  SGD has no tables.
 int adam_cfg(d2d_ctx* c, const d2d_params* p, d2d::AdamCfg* A) {
     const int steps = p->steps;
     if (steps < 1 || steps > 1000000) return fail(D2D_ERR_INVALID, "steps must lie in 1..1e6, got %d", steps);
     if (p->many < 0 || p->many > 4096) return fail(D2D_ERR_INVALID, "many must lie in 0..4096, got %d", p->many);
+    if (c->opt_kind != D2D_OPT_ADAM) {
+        // optax.sgd: momentum and learning rate are Python floats, weakly typed (rounded to fp32 where they meet an fp32 array)
+        A->solver = p->solver;
+        A->steps = steps;
+        A->many = p->many > 1 ? p->many : 1;
+        A->lr = (float)c->opt_lr;
+        A->sgd = 1;
+        A->momentum = (c->opt_kind == D2D_OPT_SGD_MOMENTUM) ? 1 : 0;
+        A->nesterov = (A->momentum && c->opt_b2 != 0.0) ? 1 : 0;
+        A->decay = A->momentum ? (float)c->opt_b1 : 0.0f;
+        return D2D_OK;
+    }
     if (c->bc_steps != steps || c->bc_b1 != c->opt_b1 || c->bc_b2 != c->opt_b2) {
         std::vector<float> b1((size_t)steps + 1), b2((size_t)steps + 1);
         for (int t = 1; t <= steps; ++t) {
@@ -444,6 +457,7 @@ int adam_cfg(d2d_ctx* c, const d2d_params* p, d2d::AdamCfg* A) {
     A->b1 = (float)c->opt_b1;
     A->b2 = (float)c->opt_b2;
     A->eps = (float)c->opt_eps;
+    A->sgd = 0;
     // optax.scale_by_adam: (1 - decay) is a Python float (double arithmetic) multiplied into an fp32 array
     A->omb1 = (float)(1.0 - c->opt_b1);
     A->omb2 = (float)(1.0 - c->opt_b2);
@@ -1054,7 +1068,7 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
             if (p->out_mode == D2D_OUT_OVERWRITE) c->have_vjp = false;
         }
         c->have_grad = true;
-        // reverse mode: the trajectories of the solver (4 floats per step and unknown) go through HBM
+        // reverse mode: the trajectories of the solver (Adam: 4 floats per step and unknown, SGD: 1) go through HBM
         d2d::OptRevArgs ra;
         memset(&ra, 0, sizeof ra);
         long long chunk_cells = 0;
@@ -1063,7 +1077,7 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
             for (int64_t i = 0; i < C; ++i) {
                 int nu = 0;
                 for (int q = 0; q < order[(size_t)i]; ++q) nu += c->kind[cand[(size_t)i * D2D_MAX_ORDER + q]] != D2D_VERTEX ? 1 : 0;
-                off[(size_t)i + 1] = off[(size_t)i] + 4ll * steps_of(p) * nu;
+                off[(size_t)i + 1] = off[(size_t)i] + (long long)d2d::traj_floats_per_step(a.A.sgd != 0) * steps_of(p) * nu;
             }
             const long long per_cell = std::max<long long>(1, off[(size_t)C]);  // floats per cell, all candidates
             const long long cells_pad = ((long long)a.cells + 63) / 64 * 64;
@@ -1134,11 +1148,13 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
     const bool side_by_side = c->opt_parallel && C >= 2 && C <= 65535 && (long long)C * a.cells <= (1ll << 26);
     if (side_by_side) {
         if ((rc = c->d_contrib.ensure((size_t)C * (size_t)a.cells))) return rc;
-        hipLaunchKernelGGL(d2d::power_opt_cand_kernel, dim3(blocks, (unsigned)C), dim3(64), 0, c->stream, a, c->d_contrib.p);
+        if (a.A.sgd) hipLaunchKernelGGL(d2d::power_opt_cand_kernel<true>, dim3(blocks, (unsigned)C), dim3(64), 0, c->stream, a, c->d_contrib.p);
+        else hipLaunchKernelGGL(d2d::power_opt_cand_kernel<false>, dim3(blocks, (unsigned)C), dim3(64), 0, c->stream, a, c->d_contrib.p);
         hipLaunchKernelGGL(d2d::opt_reduce_kernel, dim3((unsigned)((a.cells + 255) / 256)), dim3(256), 0, c->stream, c->d_contrib.p,
                            (int)C, a.cells, c->d_out.p, p->out_mode);
     } else {
-        hipLaunchKernelGGL(d2d::power_opt_kernel, dim3(blocks), dim3(64), 0, c->stream, a);
+        if (a.A.sgd) hipLaunchKernelGGL(d2d::power_opt_kernel<true>, dim3(blocks), dim3(64), 0, c->stream, a);
+        else hipLaunchKernelGGL(d2d::power_opt_kernel<false>, dim3(blocks), dim3(64), 0, c->stream, a);
     }
     HIP_TRY(hipGetLastError());
     return D2D_OK;
@@ -2335,10 +2351,23 @@ int d2d_set_theta0(d2d_ctx* c, const float* theta0, int64_t n_rows) {
 
 int d2d_set_optimizer(d2d_ctx* c, int32_t kind, double learning_rate, double b1, double b2, double eps) {
     if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (kind != D2D_OPT_ADAM) return fail(D2D_ERR_UNSUPPORTED, "optimizer kind %d is not native (D2D_OPT_ADAM is)", (int)kind);
+    if (kind == D2D_OPT_SGD || kind == D2D_OPT_SGD_MOMENTUM) {
+        if (!std::isfinite(learning_rate)) return fail(D2D_ERR_INVALID, "SGD needs a finite learning rate (got %g)", learning_rate);
+        if (kind == D2D_OPT_SGD_MOMENTUM && (!(b1 >= 0.0 && b1 < 1.0) || !(b2 == 0.0 || b2 == 1.0)))
+            return fail(D2D_ERR_INVALID, "SGD with momentum needs a momentum in [0, 1) and a Nesterov flag of 0 or 1 (got %g, %g)", b1, b2);
+        c->opt_kind = kind;
+        c->opt_lr = learning_rate;
+        c->opt_b1 = (kind == D2D_OPT_SGD_MOMENTUM) ? b1 : 0.0;
+        c->opt_b2 = (kind == D2D_OPT_SGD_MOMENTUM) ? b2 : 0.0;
+        c->opt_eps = 0.0;
+        return D2D_OK;
+    }
+    if (kind != D2D_OPT_ADAM)
+        return fail(D2D_ERR_UNSUPPORTED, "optimizer kind %d is not native (D2D_OPT_ADAM, D2D_OPT_SGD and D2D_OPT_SGD_MOMENTUM are)", (int)kind);
     if (!std::isfinite(learning_rate) || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps >= 0.0) || !std::isfinite(eps))
         return fail(D2D_ERR_INVALID, "Adam needs a finite learning rate, decay rates in [0, 1) and eps >= 0 (got %g, %g, %g, %g)", learning_rate, b1,
                     b2, eps);
+    c->opt_kind = kind;
     c->opt_lr = learning_rate;
     c->opt_b1 = b1;
     c->opt_b2 = b2;
@@ -2429,7 +2458,9 @@ int d2d_trace_paths(d2d_ctx* c, const d2d_params* p, const float* tx, const floa
     a.seg_lo = -p->seg_tol;
     a.seg_hi = 1.0f + p->seg_tol;
     const unsigned blocks = (unsigned)((n + 63) / 64);
-    hipLaunchKernelGGL(d2d::trace_kernel, dim3(blocks), dim3(64), 0, c->stream, a);
+    // (the image-method and validation paths never reach the solver: the Adam instance serves them)
+    if (opt && a.A.sgd) hipLaunchKernelGGL(d2d::trace_kernel<true>, dim3(blocks), dim3(64), 0, c->stream, a);
+    else hipLaunchKernelGGL(d2d::trace_kernel<false>, dim3(blocks), dim3(64), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(xys, c->d_txys.p, n * NP * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(loss, c->d_tloss.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -3995,19 +3995,40 @@ __device__ __forceinline__ void image_solve(const ObjTables& T, int k, const int
         }
 }
 
-// ---- MinPath / FermatPath: Adam on the parametric coordinates ------------------------------------------
+// ---- MinPath / FermatPath: Adam (or SGD) on the parametric coordinates ----------------------------------
 // geometry.py:1117-1288, optimize.py:44-97 with optax.adam(0.1): mu = b1 mu + (1-b1) g; nu = b2 nu + (1-b2) g^2;
 // x += -lr * (mu / (1 - b1^t)) / (sqrt(nu / (1 - b2^t)) + eps).  The gradient of the objective w.r.t. theta is
 // derived by hand (reverse mode through parametric_to_cartesian and evaluate_cartesian / path_length).
-struct AdamCfg {
+// The solver loops are templates on the optimiser (bool SGD): the Adam instances are the code above, untouched; the SGD
+// instances run sgd_step (below) and serve plain SGD, momentum and Nesterov momentum through wave-uniform flags.
+struct AdamCfg {  // the optimiser's configuration (Adam's fields, and SGD's)
     int solver;  // D2D_SOLVER_MINPATH or D2D_SOLVER_FERMAT
     int steps;
     int many;    // number of random starts; the start whose recorded loss is smallest wins (optimize.py:136-182)
-    const float* __restrict__ bc1;  // [steps] 1 - b1^t
-    const float* __restrict__ bc2;  // [steps] 1 - b2^t
+    const float* __restrict__ bc1;  // [steps] 1 - b1^t   (Adam only)
+    const float* __restrict__ bc2;  // [steps] 1 - b2^t   (Adam only)
     float lr, b1, b2, eps;
     float omb1, omb2;  // 1 - b1, 1 - b2 evaluated in double precision and rounded (optax: Python floats, weakly typed)
+    int sgd;           // 0 Adam, 1 SGD (the template parameter of the kernel that runs; checked by the launchers)
+    int momentum;      // SGD: 1 with optax.trace (momentum given, 0.0 included), 0 for momentum=None (no state at all)
+    int nesterov;      // SGD with momentum: Nesterov's variant
+    float decay;       // SGD with momentum: the trace's decay, rounded to fp32 (a weakly typed Python float)
 };
+
+// Floats per step and unknown of the trajectory the reverse sweep records (d2d_optrev.hpp: opt_run_t): Adam's
+// (theta_t, g_t, mu_{t+1}, nu_{t+1}); SGD's adjoint is linear in its state and needs theta_t alone.
+constexpr int traj_floats_per_step(bool sgd) { return sgd ? 1 : 4; }
+
+// optax 0.2.4 sgd(learning_rate, momentum, nesterov) = chain(trace(momentum, nesterov) if momentum is not None, scale(-lr)):
+//   trace: f(a, t) = a + decay * t;  m' = f(g, m);  u = f(g, m') if nesterov else m'   (the trace starts at zeros)
+// Returns u (the update before scale(-lr)) and advances the trace m; momentum=None returns g and leaves m alone.  V is
+// float or a Dual (the forward-tangent kernel).
+template <class V>
+__device__ __forceinline__ V sgd_step(const AdamCfg& A, const V& g, V& m) {
+    if (!A.momentum) return g;
+    m = g + A.decay * m;
+    return A.nesterov ? g + A.decay * m : m;
+}
 
 __device__ __forceinline__ void theta_to_points(const ObjTables& T, int k, const int (&cd)[D2D_MAX_ORDER],
                                                 const float (&theta)[D2D_MAX_ORDER], float txx, float txy, float rxx, float rxy,
@@ -4134,7 +4155,8 @@ __device__ __forceinline__ float objective_grad(const ObjTables& T, int solver, 
     return loss;
 }
 
-// One Adam run from theta0: final theta in `th`, returns the objective recorded at the last step (before the last update).
+// One Adam (SGD) run from theta0: final theta in `th`, returns the objective recorded at the last step (before the last update).
+template <bool SGD>
 __device__ __forceinline__ float opt_run(const ObjTables& T, const AdamCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
                                          const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
                                          float (&th)[D2D_MAX_ORDER]) {
@@ -4151,14 +4173,20 @@ __device__ __forceinline__ float opt_run(const ObjTables& T, const AdamCfg& A, i
     for (int t = 0; t < A.steps; ++t) {
         theta_to_points(T, k, cd, th, txx, txy, rxx, rxy, px, py);
         last = objective_grad(T, A.solver, k, cd, px, py, g);
-        const float c1 = A.bc1[t], c2 = A.bc2[t];
+        if constexpr (SGD) {
 #pragma unroll
-        for (int q = 0; q < D2D_MAX_ORDER; ++q) {
-            if (q < nu_) {
-                mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
-                nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
-                float mh = mu[q] / c1, nh = nu[q] / c2;
-                th[q] = th[q] + (-A.lr) * (mh / (sqrtf(nh) + A.eps));
+            for (int q = 0; q < D2D_MAX_ORDER; ++q)
+                if (q < nu_) th[q] = th[q] + (-A.lr) * sgd_step(A, g[q], mu[q]);
+        } else {
+            const float c1 = A.bc1[t], c2 = A.bc2[t];
+#pragma unroll
+            for (int q = 0; q < D2D_MAX_ORDER; ++q) {
+                if (q < nu_) {
+                    mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
+                    nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
+                    float mh = mu[q] / c1, nh = nu[q] / c2;
+                    th[q] = th[q] + (-A.lr) * (mh / (sqrtf(nh) + A.eps));
+                }
             }
         }
     }
@@ -4166,13 +4194,14 @@ __device__ __forceinline__ float opt_run(const ObjTables& T, const AdamCfg& A, i
 }
 
 // Returns the path points and the loss the reference attaches to the path. theta0: [many][D2D_MAX_ORDER].
+template <bool SGD>
 __device__ __forceinline__ float opt_solve(const ObjTables& T, const AdamCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
                                            const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
                                            float (&px)[NP], float (&py)[NP]) {
     float best[D2D_MAX_ORDER], th[D2D_MAX_ORDER];
-    float best_loss = opt_run(T, A, k, cd, theta0, txx, txy, rxx, rxy, best);
+    float best_loss = opt_run<SGD>(T, A, k, cd, theta0, txx, txy, rxx, rxy, best);
     for (int m = 1; m < A.many; ++m) {  // jnp.argmin: the first minimum wins; NaN losses win like in jnp.argmin
-        float l = opt_run(T, A, k, cd, theta0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
+        float l = opt_run<SGD>(T, A, k, cd, theta0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
         const bool better = (l < best_loss) || (l != l && best_loss == best_loss);
         best_loss = better ? l : best_loss;
 #pragma unroll
@@ -4210,6 +4239,7 @@ struct TraceArgs {
 // One thread per (tx/rx pair, candidate).  Serves Scene.all_paths / all_valid_paths / accumulate_over_paths
 // (scene.py:1156-1334), {Image,Min,Fermat}Path.from_tx_objects_rx and Path.is_valid / on_objects /
 // intersects_with_objects (geometry.py:821-963) of the host mirror.
+template <bool SGD>
 __global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= (long)a.P * a.C) return;
@@ -4235,7 +4265,7 @@ __global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
     } else if (k == 0) {
         image_solve(a.T, 0, cd, txx, txy, rxx, rxy, px, py);  // geometry.py:1178-1180 / 1268-1270
     } else {
-        loss = opt_solve(a.T, a.A, k, cd, a.theta0 + (long)c * a.A.many * D2D_MAX_ORDER, txx, txy, rxx, rxy, px, py);
+        loss = opt_solve<SGD>(a.T, a.A, k, cd, a.theta0 + (long)c * a.A.many * D2D_MAX_ORDER, txx, txy, rxx, rxy, px, py);
     }
     float on, hit, valid;
     literal_validity(a.T, L, k, cd, px, py, loss, a.tol, a.seg_lo, a.seg_hi, on, hit, valid);
@@ -4280,6 +4310,7 @@ struct OptSweepArgs {
 };
 
 // valid * fun of one (cell, candidate): solve, validate, evaluate (scene.py:1892-1918 with an optimiser-based path class)
+template <bool SGD>
 __device__ __forceinline__ float opt_contribution(const OptSweepArgs& a, int c, float txx, float txy, float rxx, float rxy) {
     const Truth L{a.mode, a.alpha};
     const int k = a.order[c];
@@ -4290,7 +4321,7 @@ __device__ __forceinline__ float opt_contribution(const OptSweepArgs& a, int c, 
     float px[NP], py[NP];
     float loss = 0.0f;
     if (k == 0) image_solve(a.T, 0, cd, txx, txy, rxx, rxy, px, py);
-    else loss = opt_solve(a.T, a.A, k, cd, th0, txx, txy, rxx, rxy, px, py);
+    else loss = opt_solve<SGD>(a.T, a.A, k, cd, th0, txx, txy, rxx, rxy, px, py);
     float on, hit, valid;
     literal_validity(a.T, L, k, cd, px, py, loss, a.tol, a.seg_lo, a.seg_hi, on, hit, valid);
     const float r = literal_length(k, px, py);
@@ -4309,6 +4340,7 @@ __device__ __forceinline__ float opt_contribution(const OptSweepArgs& a, int c, 
 
 #ifdef D2D_AUX_KERNELS
 // One cell per lane, the candidates one after the other (any number of candidates).
+template <bool SGD>
 __global__ void __launch_bounds__(64) power_opt_kernel(OptSweepArgs a) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.cells) return;
@@ -4316,7 +4348,7 @@ __global__ void __launch_bounds__(64) power_opt_kernel(OptSweepArgs a) {
     const float txx = a.grid_is_tx ? gx_ : a.txx, txy = a.grid_is_tx ? gy_ : a.txy;
     const float rxx = a.grid_is_tx ? a.txx : gx_, rxy = a.grid_is_tx ? a.txy : gy_;
     float acc = 0.0f;
-    for (int c = 0; c < a.C; ++c) acc = acc + opt_contribution(a, c, txx, txy, rxx, rxy);
+    for (int c = 0; c < a.C; ++c) acc = acc + opt_contribution<SGD>(a, c, txx, txy, rxx, rxy);
     if (a.out_mode == D2D_OUT_ADD) a.out[idx] = a.out[idx] + acc;
     else a.out[idx] = acc;
 }
@@ -4324,6 +4356,7 @@ __global__ void __launch_bounds__(64) power_opt_kernel(OptSweepArgs a) {
 // The same with the candidates spread over blockIdx.y: every (cell, candidate) is `steps` SEQUENTIAL Adam iterations, so
 // a 300^2 grid with 7 candidates only fills the chip when the candidates run side by side (1.4 -> 10 waves per SIMD).
 // Contributions go to contrib[c][cell]; opt_reduce_kernel adds them in candidate order: the same fp32 sum.
+template <bool SGD>
 __global__ void __launch_bounds__(64) power_opt_cand_kernel(OptSweepArgs a, float* __restrict__ contrib) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.cells) return;
@@ -4331,7 +4364,7 @@ __global__ void __launch_bounds__(64) power_opt_cand_kernel(OptSweepArgs a, floa
     const float gx_ = a.X[idx], gy_ = a.Y[idx];
     const float txx = a.grid_is_tx ? gx_ : a.txx, txy = a.grid_is_tx ? gy_ : a.txy;
     const float rxx = a.grid_is_tx ? a.txx : gx_, rxy = a.grid_is_tx ? a.txy : gy_;
-    contrib[(long)c * a.cells + idx] = opt_contribution(a, c, txx, txy, rxx, rxy);
+    contrib[(long)c * a.cells + idx] = opt_contribution<SGD>(a, c, txx, txy, rxx, rxy);
 }
 
 __global__ void __launch_bounds__(256) opt_reduce_kernel(const float* __restrict__ contrib, int C, long cells, float* __restrict__ out,

@@ -6,7 +6,8 @@
 namespace d2d {
 
 hipError_t launch_opt_grad(const OptGradArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL(power_opt_grad_kernel, grid, dim3(64), lds, stream, a);
+    if (a.s.A.sgd) hipLaunchKernelGGL(power_opt_grad_kernel<true>, grid, dim3(64), lds, stream, a);
+    else hipLaunchKernelGGL(power_opt_grad_kernel<false>, grid, dim3(64), lds, stream, a);
     return hipGetLastError();
 }
 

@@ -410,8 +410,8 @@ __device__ __forceinline__ Dual<B> dobjective_grad(int solver, const DObj<B> (&o
     return loss;
 }
 
-// One Adam run (the Dual of opt_run): final theta in th[], returns the objective recorded at the last step.
-template <int K, int B>
+// One Adam (SGD) run (the Dual of opt_run): final theta in th[], returns the objective recorded at the last step.
+template <int K, int B, bool SGD>
 __device__ __forceinline__ Dual<B> dopt_run(const AdamCfg& A, const DObj<B> (&ob)[K > 0 ? K : 1], const float* __restrict__ theta0,
                                             const Dual<B>& ax_, const Dual<B>& ay_, const Dual<B>& bx_, const Dual<B>& by_,
                                             Dual<B> (&th)[K > 0 ? K : 1]) {
@@ -429,14 +429,20 @@ __device__ __forceinline__ Dual<B> dopt_run(const AdamCfg& A, const DObj<B> (&ob
     for (int t = 0; t < A.steps; ++t) {
         dpoints<K, B>(ob, th, ax_, ay_, bx_, by_, px, py);
         last = dobjective_grad<K, B>(A.solver, ob, px, py, g);
-        const float c1 = A.bc1[t], c2 = A.bc2[t];
+        if constexpr (SGD) {
 #pragma unroll
-        for (int q = 0; q < KK; ++q) {
-            if (q < nu_) {
-                mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
-                nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
-                const Dual<B> mh = mu[q] / c1, nh = nu[q] / c2;
-                th[q] = th[q] + (-A.lr) * (mh / (dsqrt(nh) + A.eps));
+            for (int q = 0; q < KK; ++q)
+                if (q < nu_) th[q] = th[q] + (-A.lr) * sgd_step(A, g[q], mu[q]);
+        } else {
+            const float c1 = A.bc1[t], c2 = A.bc2[t];
+#pragma unroll
+            for (int q = 0; q < KK; ++q) {
+                if (q < nu_) {
+                    mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
+                    nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
+                    const Dual<B> mh = mu[q] / c1, nh = nu[q] / c2;
+                    th[q] = th[q] + (-A.lr) * (mh / (dsqrt(nh) + A.eps));
+                }
             }
         }
     }
@@ -530,7 +536,7 @@ __device__ __forceinline__ Dual<B> dcontribution(const OptGradArgs& a, const int
 // Everything for one (cell, candidate of order K): directional derivatives of valid * fun, B directions at a time.
 //   grx, gry      += d / d cell
 //   row[5 N + 2]  += cot * d / d (object end points [4 N], fixed end point [2], phi [N])   (LDS, wave-uniform targets)
-template <int K, int B>
+template <int K, int B, bool SGD>
 __device__ __forceinline__ void opt_grad_candidate(const OptGradArgs& a, int c, const int (&cd)[D2D_MAX_ORDER], float cellx, float celly,
                                                    float cot, bool active, float& grx, float& gry, float* row) {
     constexpr int KK = K > 0 ? K : 1;
@@ -545,9 +551,9 @@ __device__ __forceinline__ void opt_grad_candidate(const OptGradArgs& a, int c, 
     float best_loss = 0.0f;  // what the winning run recorded at its last step (MinPath's path loss, geometry.py:1284-1288)
     if (K > 0) {
         float th[D2D_MAX_ORDER];
-        best_loss = opt_run(s.T, s.A, K, cd, th0, txx, txy, rxx, rxy, best_th);
+        best_loss = opt_run<SGD>(s.T, s.A, K, cd, th0, txx, txy, rxx, rxy, best_th);
         for (int m = 1; m < s.A.many; ++m) {
-            const float l = opt_run(s.T, s.A, K, cd, th0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
+            const float l = opt_run<SGD>(s.T, s.A, K, cd, th0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
             const bool better = (l < best_loss) || (l != l && best_loss == best_loss);
             best_loss = better ? l : best_loss;
             best_m = better ? m : best_m;
@@ -612,7 +618,7 @@ __device__ __forceinline__ void opt_grad_candidate(const OptGradArgs& a, int c, 
         Dual<B> loss = dconst<B>(0.0f);
         if (K > 0) {
             if (b0 < n_theta) {
-                loss = dopt_run<K, B>(s.A, ob, th0 + best_m * D2D_MAX_ORDER, ax_, ay_, bx_, by_, th);
+                loss = dopt_run<K, B, SGD>(s.A, ob, th0 + best_m * D2D_MAX_ORDER, ax_, ay_, bx_, by_, th);
             } else {
                 // none of these directions moves theta: the solver's outputs are constants here
 #pragma unroll
@@ -647,6 +653,7 @@ __device__ __forceinline__ void opt_grad_candidate(const OptGradArgs& a, int c, 
 constexpr int OPTGRAD_B = 9;  // tangents carried at a time: an order-1 candidate's 4 + 5 directions in one Adam pass
 
 // One (cell, candidate) per lane; candidate = blockIdx.y (wave-uniform), as power_opt_cand_kernel.
+template <bool SGD>
 __global__ void __launch_bounds__(64) power_opt_grad_kernel(OptGradArgs a) {
     extern __shared__ float row[];  // [5 N + 2]
     const OptSweepArgs& s = a.s;
@@ -669,14 +676,14 @@ __global__ void __launch_bounds__(64) power_opt_grad_kernel(OptGradArgs a) {
     float grx = 0.0f, gry = 0.0f;
     float* r = a.partial ? row : nullptr;
     switch (k) {  // wave-uniform
-        case 0: opt_grad_candidate<0, OPTGRAD_B>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
-        case 1: opt_grad_candidate<1, OPTGRAD_B>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
-        case 2: opt_grad_candidate<2, OPTGRAD_B>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
-        case 3: opt_grad_candidate<3, OPTGRAD_B>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
-        default: opt_grad_candidate<4, OPTGRAD_B>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
+        case 0: opt_grad_candidate<0, OPTGRAD_B, SGD>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
+        case 1: opt_grad_candidate<1, OPTGRAD_B, SGD>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
+        case 2: opt_grad_candidate<2, OPTGRAD_B, SGD>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
+        case 3: opt_grad_candidate<3, OPTGRAD_B, SGD>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
+        default: opt_grad_candidate<4, OPTGRAD_B, SGD>(a, c, cd, cellx, celly, cot, active, grx, gry, r); break;
     }
     if (active) {
-        a.contrib[(long)c * s.cells + idx] = opt_contribution(s, c, txx, txy, rxx, rxy);  // the forward sweep's own value
+        a.contrib[(long)c * s.cells + idx] = opt_contribution<SGD>(s, c, txx, txy, rxx, rxy);  // the forward sweep's own value
         a.gcontrib[((long)c * s.cells + idx) * 2] = grx;
         a.gcontrib[((long)c * s.cells + idx) * 2 + 1] = gry;
     }

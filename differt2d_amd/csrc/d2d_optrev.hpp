@@ -6,10 +6,11 @@
 // the same by hand:
 //
 //   forward   the solver's own loop (opt_run_t<true>: the very code of the forward sweep) writes its trajectory
-//             (theta_t, g_t, mu_{t+1}, nu_{t+1} per step, 16 bytes per unknown) to HBM, one (cell, candidate) per lane, lanes
-//             of a wave on consecutive addresses;
+//             (theta_t, g_t, mu_{t+1}, nu_{t+1} per step, 16 bytes per unknown; SGD: theta_t alone, 4 bytes) to HBM, one
+//             (cell, candidate) per lane, lanes of a wave on consecutive addresses;
 //   reverse   the adjoint of valid * fun w.r.t. the final points (hand derived, jnp.minimum / maximum ties split as JAX's
-//             JVP rules do), then the steps backwards: the adjoint of the Adam update (mu, nu, theta) and, for the
+//             JVP rules do), then the steps backwards: the adjoint of the Adam update (mu, nu, theta) -- or of SGD's
+//             (trace, theta), a linear recurrence that needs no stored state --, and, for the
 //             gradient g_t = d objective / d theta inside it, the vector-Jacobian products  v^T d g / d (theta, tx, rx,
 //             objects)  =  d / d eps  grad_{all inputs} objective(theta + eps v)  (mixed partials commute): ONE forward
 //             tangent (Dual<1>, seeded with v = gbar_t in theta) carried through the hand-derived reverse-mode gradient
@@ -56,9 +57,9 @@ struct OptRevArgs {
 };
 
 // ---- the solver's loop, optionally recording its trajectory (the forward sweep's opt_run is opt_run_t<false>) ---------
-// tr: this lane's slot of the candidate's trajectory; entry (t, q, which) at tr[((t * nu + q) * 4 + which) * stride],
-// which = 0 theta_t, 1 g_t, 2 mu_{t+1}, 3 nu_{t+1}
-template <bool STORE>
+// tr: this lane's slot of the candidate's trajectory; entry (t, q, which) at tr[((t * nu + q) * W + which) * stride] with
+// W = traj_floats_per_step(SGD) (d2d_kernels.hpp).  Adam: which = 0 theta_t, 1 g_t, 2 mu_{t+1}, 3 nu_{t+1}; SGD: theta_t only
+template <bool STORE, bool SGD>
 __device__ __forceinline__ float opt_run_t(const ObjTables& T, const AdamCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
                                            const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
                                            float (&th)[D2D_MAX_ORDER], float* __restrict__ tr, long stride) {
@@ -75,6 +76,16 @@ __device__ __forceinline__ float opt_run_t(const ObjTables& T, const AdamCfg& A,
     for (int t = 0; t < A.steps; ++t) {
         theta_to_points(T, k, cd, th, txx, txy, rxx, rxy, px, py);
         last = objective_grad(T, A.solver, k, cd, px, py, g);
+        if constexpr (SGD) {
+#pragma unroll
+            for (int q = 0; q < D2D_MAX_ORDER; ++q) {
+                if (q < nu_) {
+                    if (STORE) tr[(long)(t * nu_ + q) * stride] = th[q];
+                    th[q] = th[q] + (-A.lr) * sgd_step(A, g[q], mu[q]);
+                }
+            }
+            continue;
+        }
         const float c1 = A.bc1[t], c2 = A.bc2[t];
 #pragma unroll
         for (int q = 0; q < D2D_MAX_ORDER; ++q) {
@@ -316,7 +327,8 @@ __device__ __forceinline__ float seg_test(int mode, float alpha, float lo, float
 // Returns the contribution itself (the forward sweep's float code on the same final theta: the value map is bit-identical).
 // CUST: the instance that serves a host-evaluated path function (D2D_FUN_CUSTOM; its loads and selects cost the fused
 // functions' instance 3 % at cfg5 when they share one)
-template <int K, bool CUST>
+// SGD: the optimiser (d2d_kernels.hpp: sgd_step); else Adam
+template <int K, bool CUST, bool SGD>
 __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, const int (&cd)[D2D_MAX_ORDER], float cellx, float celly,
                                                    float cot, bool active, long lane_cell, long idx, float& grx, float& gry, float* row) {
     constexpr int KK = K > 0 ? K : 1;
@@ -342,15 +354,15 @@ __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, 
         int best_m = 0;
         if (s.A.many > 1) {
             float tmp[D2D_MAX_ORDER];
-            float best_loss = opt_run_t<false>(T, s.A, K, cd, th0, txx, txy, rxx, rxy, tmp, nullptr, 0);
+            float best_loss = opt_run_t<false, SGD>(T, s.A, K, cd, th0, txx, txy, rxx, rxy, tmp, nullptr, 0);
             for (int m = 1; m < s.A.many; ++m) {
-                const float l = opt_run_t<false>(T, s.A, K, cd, th0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, tmp, nullptr, 0);
+                const float l = opt_run_t<false, SGD>(T, s.A, K, cd, th0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, tmp, nullptr, 0);
                 const bool better = (l < best_loss) || (l != l && best_loss == best_loss);
                 best_loss = better ? l : best_loss;
                 best_m = better ? m : best_m;
             }
         }
-        loss = opt_run_t<true>(T, s.A, K, cd, th0 + best_m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th, tr, stride);
+        loss = opt_run_t<true, SGD>(T, s.A, K, cd, th0 + best_m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th, tr, stride);
     }
     float px[NP], py[NP];
     if (K == 0) image_solve(T, 0, cd, txx, txy, rxx, rxy, px, py);
@@ -579,28 +591,48 @@ __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, 
         }
         const int which = (s.A.solver == D2D_SOLVER_FERMAT) ? OBJ_LENGTH : OBJ_INTERACTION;
         for (int t = s.A.steps - 1; t >= 0; --t) {
-            const float c1 = s.A.bc1[t], c2 = s.A.bc2[t];
             float gbar[KK], tht[KK];
+            if constexpr (SGD) {
+                // theta' = theta + (-lr) u;  u = g (momentum=None), m' (trace) or g + decay m' (Nesterov);  m' = g + decay m.
+                // mub carries the adjoint of the trace m_{t+1} backwards; nothing of the forward values is needed but theta_t.
 #pragma unroll
-            for (int q = 0; q < KK; ++q) {
-                gbar[q] = tht[q] = 0.0f;
-                if (q < nu_) {
-                    const float* e = tr + ((long)(t * nu_ + q) * 4) * stride;
-                    tht[q] = e[0];
-                    const float gt = e[stride], mu1 = e[2 * stride], nu1 = e[3 * stride];
-                    const float mh = mu1 / c1, nh = nu1 / c2;
-                    const float sq = sqrtf(nh);
-                    const float den = sq + s.A.eps;
-                    // theta' = theta + (-lr) * (mh / den)
-                    const float ub = (-s.A.lr) * thb[q];
-                    const float mhb = ub / den;
-                    const float denb = -(ub * mh) / (den * den);
-                    const float nhb = denb * (0.5f / sq);  // sqrt'(0) = inf: 0 * inf = NaN, as jnp.sqrt's rule
-                    const float m1b = mub[q] + mhb / c1;
-                    const float n1b = nub[q] + nhb / c2;
-                    gbar[q] = s.A.omb1 * m1b + s.A.omb2 * ((2.0f * gt) * n1b);
-                    mub[q] = s.A.b1 * m1b;
-                    nub[q] = s.A.b2 * n1b;
+                for (int q = 0; q < KK; ++q) {
+                    gbar[q] = tht[q] = 0.0f;
+                    if (q < nu_) {
+                        tht[q] = tr[(long)(t * nu_ + q) * stride];
+                        const float ub = (-s.A.lr) * thb[q];
+                        if (!s.A.momentum) {
+                            gbar[q] = ub;
+                        } else {
+                            const float m1b = s.A.nesterov ? mub[q] + s.A.decay * ub : mub[q] + ub;
+                            gbar[q] = s.A.nesterov ? ub + m1b : m1b;
+                            mub[q] = s.A.decay * m1b;
+                        }
+                    }
+                }
+            } else {
+                const float c1 = s.A.bc1[t], c2 = s.A.bc2[t];
+#pragma unroll
+                for (int q = 0; q < KK; ++q) {
+                    gbar[q] = tht[q] = 0.0f;
+                    if (q < nu_) {
+                        const float* e = tr + ((long)(t * nu_ + q) * 4) * stride;
+                        tht[q] = e[0];
+                        const float gt = e[stride], mu1 = e[2 * stride], nu1 = e[3 * stride];
+                        const float mh = mu1 / c1, nh = nu1 / c2;
+                        const float sq = sqrtf(nh);
+                        const float den = sq + s.A.eps;
+                        // theta' = theta + (-lr) * (mh / den)
+                        const float ub = (-s.A.lr) * thb[q];
+                        const float mhb = ub / den;
+                        const float denb = -(ub * mh) / (den * den);
+                        const float nhb = denb * (0.5f / sq);  // sqrt'(0) = inf: 0 * inf = NaN, as jnp.sqrt's rule
+                        const float m1b = mub[q] + mhb / c1;
+                        const float n1b = nub[q] + nhb / c2;
+                        gbar[q] = s.A.omb1 * m1b + s.A.omb2 * ((2.0f * gt) * n1b);
+                        mub[q] = s.A.b1 * m1b;
+                        nub[q] = s.A.b2 * n1b;
+                    }
                 }
             }
             D1 seed[KK];
@@ -666,7 +698,7 @@ __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, 
 // One (cell, candidate) per lane; candidate = c_first + blockIdx.y (wave-uniform, all of order K: the enumeration is by ascending
 // order, so every order is a contiguous range and gets a launch -- and a register allocation -- of its own), cells
 // [cell0, cell0 + chunk_cells).
-template <int K, bool CUST>
+template <int K, bool CUST, bool SGD>
 __global__ void __launch_bounds__(64) power_opt_rev_kernel(OptRevArgs ra, int c_first) {
     extern __shared__ float row[];  // [5 N + 2]
     const OptGradArgs& a = ra.g;
@@ -688,7 +720,7 @@ __global__ void __launch_bounds__(64) power_opt_rev_kernel(OptRevArgs ra, int c_
     for (int i = 0; i < D2D_MAX_ORDER; ++i) cd[i] = s.cand[c * D2D_MAX_ORDER + i];
     float grx = 0.0f, gry = 0.0f;
     float* r = a.partial ? row : nullptr;
-    const float v = opt_rev_candidate<K, CUST>(ra, c, cd, cellx, celly, cot, active, lane_cell, idx, grx, gry, r);
+    const float v = opt_rev_candidate<K, CUST, SGD>(ra, c, cd, cellx, celly, cot, active, lane_cell, idx, grx, gry, r);
     if (active) {
         a.contrib[(long)c * s.cells + idx] = v;
         a.gcontrib[((long)c * s.cells + idx) * 2] = grx;

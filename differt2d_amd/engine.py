@@ -366,13 +366,21 @@ class Context:
 
     def set_optimizer(self, optimizer=None):
         """The optimiser of the MinPath / FermatPath solvers for the next sweeps (include/d2d.h: d2d_set_optimizer).  ``None`` =
-        the reference's default, ``optax.adam(0.1)``; else an :class:`differt2d_amd.optimize.Adam`."""
-        from .optimize import Adam, default_optimizer
+        the reference's default, ``optax.adam(0.1)``; else an :class:`differt2d_amd.optimize.Adam` or
+        :class:`differt2d_amd.optimize.SGD`."""
+        from .optimize import SGD, Adam, default_optimizer
 
         o = default_optimizer() if optimizer is None else optimizer
+        if isinstance(o, SGD):
+            if o.momentum is None:
+                L.check(self._lib.d2d_set_optimizer(self._ctx, L.D2D_OPT_SGD, float(o.learning_rate), 0.0, 0.0, 0.0))
+            else:  # b1 = momentum, b2 = Nesterov flag
+                nesterov = 1.0 if o.nesterov else 0.0
+                L.check(self._lib.d2d_set_optimizer(self._ctx, L.D2D_OPT_SGD_MOMENTUM, float(o.learning_rate), float(o.momentum), nesterov, 0.0))
+            return
         if not isinstance(o, Adam):
             raise L.D2DUnsupported(-4, f"optimizer {optimizer!r} is not native: differt2d_amd.optimize.adam(learning_rate, b1, b2, eps) is")
-        L.check(self._lib.d2d_set_optimizer(self._ctx, 0, float(o.learning_rate), float(o.b1), float(o.b2), float(o.eps)))
+        L.check(self._lib.d2d_set_optimizer(self._ctx, L.D2D_OPT_ADAM, float(o.learning_rate), float(o.b1), float(o.b2), float(o.eps)))
 
     def trace_paths(self, params: L.Params, tx, rx, candidates, xys_in=None, loss_in=None, theta0=None):
         """Solves (or validates ``xys_in``) every candidate for every (tx, rx) pair on the GPU.

@@ -469,8 +469,9 @@ def draw_theta0(objects_per_candidate, key, theta0=None, many: int = 1, per_cand
 
 def _opt_kwargs(kwargs):
     """(steps, many, theta0, optimizer) from ``path_cls_kwargs`` (reference optimize.py:44-52, 136-143).  ``optimizer``: None
-    (the reference's default, ``optax.adam(0.1)``) or ``differt2d_amd.optimize.adam(learning_rate, b1, b2, eps)``."""
-    from .optimize import Adam
+    (the reference's default, ``optax.adam(0.1)``), ``differt2d_amd.optimize.adam(learning_rate, b1, b2, eps)`` or
+    ``differt2d_amd.optimize.sgd(learning_rate, momentum, nesterov)``."""
+    from .optimize import SGD, Adam
 
     kw = dict(kwargs)
     steps = int(kw.pop("steps", 100))
@@ -479,9 +480,9 @@ def _opt_kwargs(kwargs):
     if many < 1:
         raise ValueError("many must be >= 1")
     optimizer = kw.pop("optimizer", None)
-    if optimizer is not None and not isinstance(optimizer, Adam):
-        raise L.D2DUnsupported(-4, f"optimizer {optimizer!r} is not native: differt2d_amd.optimize.adam(learning_rate, b1, b2, eps) is "
-                                   "(the reference's default is optax.adam(0.1))")
+    if optimizer is not None and not isinstance(optimizer, (Adam, SGD)):
+        raise L.D2DUnsupported(-4, f"optimizer {optimizer!r} is not native: differt2d_amd.optimize.adam(learning_rate, b1, b2, eps) and "
+                                   "sgd(learning_rate, momentum, nesterov) are (the reference's default is optax.adam(0.1))")
     if kw:
         raise TypeError(f"unexpected keyword arguments: {sorted(kw)}")
     return steps, many, theta0, optimizer
@@ -509,7 +510,7 @@ class _OptPath(Path):
 
 
 class FermatPath(_OptPath):
-    """Path minimising its length (reference geometry.py:1117-1204): Adam on the parametric coordinates, on the GPU."""
+    """Path minimising its length (reference geometry.py:1117-1204): Adam (or SGD) on the parametric coordinates, on the GPU."""
 
     solver = "fermat"
 

@@ -5,13 +5,14 @@ Two layers, as in the reference:
 
 * The MinPath / FermatPath solvers.  The reference hands the path classes' objective -- the path's length or its interaction
   losses as a function of the parametric coordinates -- to :func:`minimize` (geometry.py:1172-1204, 1256-1288); here that loop IS
-  the GPU kernel (`d2d::power_opt_kernel` and the reverse sweep behind it, differt2d_amd/csrc) for those objectives and for the
-  optimiser the reference defaults to, Adam -- with any hyper-parameters: pass ``optimizer=adam(...)`` in ``path_cls_kwargs``
-  where the reference takes ``optimizer=optax.adam(...)``.  No sweep ever calls the functions below.
+  the GPU kernel (`d2d::power_opt_kernel` and the reverse sweep behind it, differt2d_amd/csrc) for those objectives and for
+  two optimisers: the one the reference defaults to, Adam, and SGD (plain, momentum, Nesterov) -- with any hyper-parameters:
+  pass ``optimizer=adam(...)`` or ``optimizer=sgd(...)`` in ``path_cls_kwargs`` where the reference takes
+  ``optimizer=optax.adam(...)`` / ``optax.sgd(...)``.  No sweep ever calls the functions below.
 * :func:`minimize`, :func:`minimize_random_uniform`, :func:`minimize_many_random_uniform` as CALLABLES for a user's own Python
   objective (optimize.py:44-182): a host utility, like the reference's (which is plain JAX on whatever backend), with the same
-  signatures, the same update rule (``optax.adam``, fp32, optax's order of operations -- the one `oracle/ref.py:616-638` and the
-  kernels follow), the same initial guesses (``jax.random.uniform`` on the Threefry key: differt2d_amd/random.py) and the
+  signatures, the same update rule (``optax.adam`` or ``optax.sgd``, fp32, optax's order of operations -- the one
+  `oracle/ref.py:616-638` and the kernels follow), the same initial guesses (``jax.random.uniform`` on the Threefry key: differt2d_amd/random.py) and the
   reference's return convention (the loss evaluated BEFORE the last update, optimize.py:86-97).  The objective's gradient comes
   from the NumPy recording tape of differt2d_amd/fun_grad.py (JAX's conventions at ties, ``where``, ``sqrt'(0)``), or from
   ``fun.value_and_grad(x, *args)`` when the user supplies one.  The reference's known answers (tests/test_optimize.py:27-74 and
@@ -23,7 +24,7 @@ from typing import Any, Callable, Optional
 
 import numpy as np
 
-__all__ = ["Adam", "adam", "default_optimizer", "minimize", "minimize_random_uniform", "minimize_many_random_uniform"]
+__all__ = ["Adam", "adam", "SGD", "sgd", "default_optimizer", "minimize", "minimize_random_uniform", "minimize_many_random_uniform"]
 
 F = np.float32
 
@@ -41,6 +42,30 @@ class Adam:
 def adam(learning_rate: float = 0.1, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8) -> Adam:
     """Same signature as ``optax.adam`` for the arguments the native solver has."""
     return Adam(float(learning_rate), float(b1), float(b2), float(eps))
+
+
+@dataclass(frozen=True)
+class SGD:
+    """``optax.sgd(learning_rate, momentum, nesterov)`` (optax 0.2.4).
+
+    ``momentum=None``: ``scale(-lr)``, no state.  A float (``0.0`` included): ``chain(trace(momentum, nesterov), scale(-lr))``
+    -- a different optimiser from ``None``: a trace of decay 0 still carries a NaN of the previous step forward."""
+
+    learning_rate: float = 0.1
+    momentum: Optional[float] = None
+    nesterov: bool = False
+
+
+def sgd(learning_rate: float = 0.1, momentum: Optional[float] = None, nesterov: bool = False) -> SGD:
+    """Same signature as ``optax.sgd`` for the arguments the native solver has (``momentum`` in [0, 1) or None)."""
+    lr = float(learning_rate)
+    if not np.isfinite(lr):
+        raise ValueError(f"the learning rate must be finite, got {learning_rate!r}")
+    if momentum is not None:
+        momentum = float(momentum)
+        if not (0.0 <= momentum < 1.0):
+            raise ValueError(f"momentum must lie in [0, 1) or be None, got {momentum!r}")
+    return SGD(lr, momentum, bool(nesterov))
 
 
 def default_optimizer() -> Adam:
@@ -66,12 +91,13 @@ def _value_and_grad(fun: Callable, x: np.ndarray, args: tuple):
     return F(out.value), (np.zeros_like(x) if g is None else np.asarray(g, F).reshape(x.shape))
 
 
-def minimize(fun: Callable, x0, args: tuple = (), steps: int = 100, optimizer: Optional[Adam] = None):
+def minimize(fun: Callable, x0, args: tuple = (), steps: int = 100, optimizer=None):
     """Minimizes a scalar function of one or more variables (reference optimize.py:44-97).
 
     Returns ``(x, loss)``: the solution after ``steps`` updates and the loss evaluated before the last of them (the
     reference's ``losses[-1]`` of a ``lax.scan`` whose body evaluates, then updates).  ``optimizer``: an :class:`Adam`
-    (:func:`adam`); anything else is refused -- the reference takes any ``optax.GradientTransformation``, this library has Adam.
+    (:func:`adam`) or an :class:`SGD` (:func:`sgd`); anything else is refused -- the reference takes any
+    ``optax.GradientTransformation``, this library has these two.
 
     >>> import numpy as np
     >>> def f(x, offset=1.0):
@@ -85,10 +111,12 @@ def minimize(fun: Callable, x0, args: tuple = (), steps: int = 100, optimizer: O
     True
     """
     opt = optimizer or default_optimizer()
+    if isinstance(opt, SGD):
+        return _minimize_sgd(fun, x0, tuple(args), int(steps), opt)
     if not isinstance(opt, Adam):
         from ._lib import D2DUnsupported
 
-        raise D2DUnsupported(-4, f"optimizer {type(opt).__name__}: only differt2d_amd.optimize.adam(...) is implemented")
+        raise D2DUnsupported(-4, f"optimizer {type(opt).__name__}: only differt2d_amd.optimize.adam(...) and sgd(...) are implemented")
     x = np.array(x0, F)
     mu, nu = np.zeros_like(x), np.zeros_like(x)
     # optax.scale_by_adam + scale(-lr) in fp32; the constants 1 - b and 1 - b**t are formed in double and cast, this order of
@@ -104,6 +132,26 @@ def minimize(fun: Callable, x0, args: tuple = (), steps: int = 100, optimizer: O
             mh = mu / F(1.0 - b1**t)
             nh = nu / F(1.0 - b2**t)
             x = (x + lr * (mh / (np.sqrt(nh) + eps))).astype(F)
+    return x, loss
+
+
+def _minimize_sgd(fun: Callable, x0, args: tuple, steps: int, opt: SGD):
+    """:func:`minimize` with ``optax.sgd`` in fp32: trace ``m' = g + c(momentum) * m`` (from zeros), ``u = g + c(momentum) * m'``
+    with Nesterov else ``m'`` (``u = g`` for momentum None), ``x = x + c(-lr) * u`` -- the kernels' sgd_step."""
+    x = np.array(x0, F)
+    m = np.zeros_like(x)
+    lr = F(-float(opt.learning_rate))
+    d = None if opt.momentum is None else F(opt.momentum)
+    loss = F(np.nan)
+    for _ in range(steps):
+        loss, g = _value_and_grad(fun, x, args)
+        with np.errstate(all="ignore"):
+            if d is None:
+                u = g
+            else:
+                m = (g + d * m).astype(F)
+                u = (g + d * m).astype(F) if opt.nesterov else m
+            x = (x + lr * u).astype(F)
     return x, loss
 
 

@@ -195,14 +195,21 @@ int d2d_set_theta0(d2d_ctx* ctx, const float* theta0, int64_t n_rows);
 /* The optimiser of the MinPath / FermatPath solvers for the NEXT sweeps and traces (differt2d/optimize.py:44-51: any
  * optax.GradientTransformation; default optax.adam(learning_rate=0.1), optimize.py:83).  Native: Adam with any
  * hyper-parameters (optax.adam(learning_rate, b1, b2, eps), eps_root = 0) -- they are Python floats on the reference's
- * side, hence doubles here; the gradients through the solver (reverse mode and forward tangents) follow them.  Any other
- * kind: D2D_ERR_UNSUPPORTED. */
+ * side, hence doubles here; the gradients through the solver (reverse mode and forward tangents) follow them.
+ *   D2D_OPT_ADAM           optax.adam(learning_rate, b1, b2, eps): decay rates in [0, 1), eps >= 0 and finite.
+ *   D2D_OPT_SGD            optax.sgd(learning_rate) (momentum=None: x += -lr * g, no state); b1, b2, eps are ignored.
+ *   D2D_OPT_SGD_MOMENTUM   optax.sgd(learning_rate, momentum=b1, nesterov=b2): b1 = the momentum in [0, 1) (0 included: a
+ *                          trace of decay 0 still carries a NaN forward, unlike D2D_OPT_SGD), b2 = the Nesterov flag, 0 or
+ *                          1; eps is ignored.
+ * The learning rate must be finite.  Any other kind: D2D_ERR_UNSUPPORTED. */
 #define D2D_OPT_ADAM 0
+#define D2D_OPT_SGD 1
+#define D2D_OPT_SGD_MOMENTUM 2
 int d2d_set_optimizer(d2d_ctx* ctx, int32_t kind, double learning_rate, double b1, double b2, double eps);
 
 /* Launches the fused forward sweep for transmitter tx[2] on the ctx stream (asynchronous).
  * Inputs and outputs stay resident in HBM. params->solver selects ImagePath (fused image-method kernel) or
- * MinPath / FermatPath (per-cell Adam loop of params->steps iterations, hand-derived gradient). */
+ * MinPath / FermatPath (per-cell optimiser loop of params->steps iterations, hand-derived gradient). */
 int d2d_power_map_launch(d2d_ctx* ctx, const d2d_params* params, const float* tx);
 
 /* ---- value + gradient (replaces grad=True / value_and_grad=True of the sweep, differt2d/scene.py:1920-1923,
