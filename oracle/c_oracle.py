@@ -58,6 +58,14 @@ class OrcOptParams(C.Structure):
     ]
 
 
+class OrcOptimizer(C.Structure):
+    _fields_ = [
+        ("opt", C.c_int32),
+        ("momentum", C.c_double),
+        ("nesterov", C.c_int32),
+    ]
+
+
 FUN_IDS = {"received_power": 0, "length_squared": 1, "length": 2, "one": 3}
 ACT_IDS = {"hard_sigmoid": 0, "sigmoid": 1}
 
@@ -99,10 +107,15 @@ def lib():
         L.orc_opt_power_map.restype = C.c_int
         L.orc_opt_power_map.argtypes = [C.c_int, dp, up, dp, C.c_int, C.POINTER(OrcOptParams), dp, dp, dp, C.c_long, ip, ip, C.c_long,
                                         dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int, C.c_int]
+        L.orc_opt_power_map_opt.restype = C.c_int
+        L.orc_opt_power_map_opt.argtypes = [C.c_int, dp, up, dp, C.c_int, C.POINTER(OrcOptParams), C.POINTER(OrcOptimizer), dp, dp, dp,
+                                            C.c_long, ip, ip, C.c_long, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int, C.c_int]
         L.orc_opt_objective.restype = C.c_int
         L.orc_opt_objective.argtypes = [C.c_int, dp, up, dp, C.c_int, C.c_int, dp, dp, ip, C.c_int, dp, dp, dp]
         L.orc_opt_adam_step.restype = C.c_int
         L.orc_opt_adam_step.argtypes = [C.c_int, C.POINTER(OrcOptParams), C.c_int, C.c_double, dp, dp, dp]
+        L.orc_opt_sgd_step.restype = C.c_int
+        L.orc_opt_sgd_step.argtypes = [C.c_int, C.POINTER(OrcOptParams), C.POINTER(OrcOptimizer), C.c_double, dp, dp]
         _lib = L
     return _lib
 
@@ -218,6 +231,7 @@ def max_threads():
 
 # ---------------------------------------------------------------------- MinPath / FermatPath sweeps (oracle/d2d_oracle_opt.c)
 SOLVER_IDS = {"min": 1, "fermat": 2}
+OPT_ADAM, OPT_SGD, OPT_SGD_TRACE = 0, 1, 2  # orc_opt_optimizer.opt
 
 
 def _opt_scene(kinds, xys, phis, dtype):
@@ -245,9 +259,24 @@ def _opt_cands(cands, theta0s):
 
 
 def make_opt_params(solver="min", steps=100, approx=False, function="hard_sigmoid", alpha=100.0, tol=1e-2, patch=0.0, seg_tol=0.005,
-                    fun="received_power", r_coef=0.5, height=0.1, lr=0.1, b1=0.9, b2=0.999, eps=1e-8, grid_role="rx", g_ulps=0):
-    return OrcOptParams(int(bool(approx)), ACT_IDS[function], FUN_IDS[fun], alpha, tol, patch, seg_tol, r_coef, height,
-                        SOLVER_IDS[solver], int(steps), lr, b1, b2, eps, 1 if grid_role == "tx" else 0, int(g_ulps))
+                    fun="received_power", r_coef=0.5, height=0.1, lr=0.1, b1=0.9, b2=0.999, eps=1e-8, grid_role="rx", g_ulps=0,
+                    optimizer="adam", momentum=None, nesterov=False):
+    """(orc_opt_params, orc_opt_optimizer).  ``optimizer``: "adam" (lr, b1, b2, eps; the reference's default) or "sgd"
+    (optax.sgd(lr, momentum, nesterov): no trace for momentum None, a trace for any momentum, 0.0 included)."""
+    if optimizer == "adam":
+        opt = OPT_ADAM
+    elif optimizer == "sgd":
+        opt = OPT_SGD if momentum is None else OPT_SGD_TRACE
+    else:
+        raise ValueError(f"optimizer {optimizer!r}: 'adam' or 'sgd'")
+    p = OrcOptParams(int(bool(approx)), ACT_IDS[function], FUN_IDS[fun], alpha, tol, patch, seg_tol, r_coef, height,
+                     SOLVER_IDS[solver], int(steps), lr, b1, b2, eps, 1 if grid_role == "tx" else 0, int(g_ulps))
+    return p, OrcOptimizer(opt, 0.0 if momentum is None else float(momentum), int(bool(nesterov)))
+
+
+def sgd_kwargs(lr, momentum=None, nesterov=False):
+    """The keywords of make_opt_params (and of every function here that takes them) for optax.sgd(lr, momentum, nesterov)."""
+    return dict(optimizer="sgd", lr=lr, momentum=momentum, nesterov=nesterov)
 
 
 def opt_power_map(kinds, xys, phis, fixed, X, Y, cands, theta0s, dtype="float32", grad=False, with_paths=False, nthreads=0,
@@ -265,15 +294,15 @@ def opt_power_map(kinds, xys, phis, fixed, X, Y, cands, theta0s, dtype="float32"
     ci, ck, th = _opt_cands(cands, theta0s)
     Xc = np.ascontiguousarray(np.asarray(X, np.float32), dtype=np.float64)
     Yc = np.ascontiguousarray(np.asarray(Y, np.float32), dtype=np.float64)
-    p = make_opt_params(**kw)
+    p, o = make_opt_params(**kw)
     value = np.empty(Xc.shape, np.float64)
     g = np.empty(Xc.shape + (2,), np.float64) if grad else None
     snaps = np.ascontiguousarray([p.steps] if snaps is None else snaps, dtype=np.int32)
     pts = np.empty(Xc.shape + (len(cands), snaps.size, ORC_MAX_ORDER, 2), np.float64) if with_paths else None
     loss = np.empty(Xc.shape + (len(cands),), np.float64) if with_paths else None
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    rc = lib().orc_opt_power_map(2 if (fp32_tangents and grad and not f64) else int(f64), xys.reshape(-1) if xys.size else np.zeros(1), kinds if kinds.size else np.zeros(1, np.uint8),
-                                 sincos.reshape(-1) if sincos.size else np.zeros(1), int(kinds.size), C.byref(p),
+    rc = lib().orc_opt_power_map_opt(2 if (fp32_tangents and grad and not f64) else int(f64), xys.reshape(-1) if xys.size else np.zeros(1), kinds if kinds.size else np.zeros(1, np.uint8),
+                                 sincos.reshape(-1) if sincos.size else np.zeros(1), int(kinds.size), C.byref(p), C.byref(o),
                                  np.ascontiguousarray(np.asarray(fixed, np.float32), dtype=np.float64), Xc.reshape(-1), Yc.reshape(-1), Xc.size,
                                  ci.reshape(-1), ck, len(cands), th.reshape(-1), value.reshape(-1), ptr(g), ptr(pts), ptr(loss), snaps, int(snaps.size), nthreads)
     if rc != 0:
@@ -301,10 +330,22 @@ def opt_objective(kinds, xys, phis, tx, rx, cand, theta, solver="min", dtype="fl
 
 def opt_adam_step(t, g, x, mu, nu, dtype="float32", **kw):
     """One optax.adam update (oracle/ref.py:616-638's order) -> (x, mu, nu)."""
-    p = make_opt_params(**kw)
+    p, o = make_opt_params(**kw)
+    if o.opt != OPT_ADAM:
+        raise ValueError("opt_adam_step: an Adam update")
     x, mu, nu = (np.array([float(v)]) for v in (x, mu, nu))
     lib().orc_opt_adam_step(int(np.dtype(dtype) == np.float64), C.byref(p), int(t), float(g), x, mu, nu)
     return float(x[0]), float(mu[0]), float(nu[0])
+
+
+def opt_sgd_step(g, x, m, dtype="float32", **kw):
+    """One optax.sgd update (oracle/ref.py's sgd_minimize order; ``kw`` with optimizer="sgd") -> (x, m); m is the trace."""
+    p, o = make_opt_params(**kw)
+    x, m = (np.array([float(v)]) for v in (x, m))
+    rc = lib().orc_opt_sgd_step(int(np.dtype(dtype) == np.float64), C.byref(p), C.byref(o), float(g), x, m)
+    if rc != 0:
+        raise RuntimeError(f"orc_opt_sgd_step failed: {rc}")
+    return float(x[0]), float(m[0])
 
 
 def opt_conditioning(kinds, xys, phis, fixed, X, Y, cands, theta0s, steps, tol_pts=2e-5, tol_val=2e-3, with_grad=False, **kw):

@@ -11,7 +11,9 @@
  *   objective, FermatPath       differt2d/geometry.py:1117-1204: path_length (:176-203); recorded loss = sum of
  *                               evaluate_cartesian at the final points (:1204)
  *   minimize                    differt2d/optimize.py:44-97: `steps` x { loss, g = value_and_grad(objective)(theta);
- *                               theta += optax.adam(0.1) update }, optax 0.2.4's scale_by_adam, in oracle/ref.py:616-638's order
+ *                               theta += update } with the update of optax 0.2.4's adam (the reference's default,
+ *                               optax.adam(0.1): scale_by_adam, in oracle/ref.py's adam_minimize order) or sgd (trace(momentum,
+ *                               nesterov) + scale(-lr), or scale(-lr) alone without momentum: oracle/ref.py's sgd_minimize order)
  *   validity, path function     as oracle/d2d_oracle.c (geometry.py:821-963, logic.py:218-537, utils.py:17-54); a Vertex
  *                               contains every point and intersects nothing (:397-414)
  *   accumulation                differt2d/scene.py:1892-1918; the initial guesses theta0[candidate] are shared by all cells
@@ -32,7 +34,9 @@
  * in the reference): second-order forward jets of the objective in (theta, cell) give d g / d cell = H_theta,cell +
  * H_theta,theta d theta / d cell inside the loop; first-order duals afterwards.  The reference's reverse-mode NaN conventions
  * that forward mode does not show by itself are stated as rules: normalize() of a zero-length vector inside a differentiated
- * objective / loss (geometry.py:227-228 behind a where) and sqrt'(0) of Adam's second moment when g == 0 exactly.
+ * objective / loss (geometry.py:227-228 behind a where) and sqrt'(0) of Adam's second moment when g == 0 exactly.  SGD's
+ * update is linear in g: its tangent is the same recurrence on the derivatives, and no NaN arises in it that the values do not
+ * carry (a NaN gradient stays in a momentum trace for good, a decay-0 one included: 0 * NaN = NaN, as in optax).
  *
  * Build: oracle/Makefile (gcc -O2 -ffp-contract=off -fopenmp).
  */
@@ -54,18 +58,52 @@
 #define ORC_RIS 1
 #define ORC_VERTEX 2
 
+#define ORC_OPT_PARAMS_FIELDS                                                                                                    \
+    int32_t approx;   /* 0: jnp.logical_*, 1: min / max / activation */                                                       \
+    int32_t act;      /* 0: hard_sigmoid, 1: sigmoid */                                                                        \
+    int32_t fun_id;   /* 0 received_power, 1 length**2, 2 length, 3 one */                                                     \
+    double alpha, tol, patch, seg_tol, r_coef, height; /* python floats in the reference: cast to the working precision (xp.c) */ \
+    int32_t solver;   /* 1: MinPath, 2: FermatPath */                                                                          \
+    int32_t steps;    /* >= 1 */                                                                                               \
+    double lr, b1, b2, eps; /* optax.adam(0.1): 0.1, 0.9, 0.999, 1e-8 (b1, b2, eps: Adam only; lr: every optimiser) */        \
+    int32_t grid_is_tx;                                                                                                         \
+    int32_t g_ulps; /* conditioning probe: every objective gradient moved by this many units in the last place (0: as        \
+                       computed) -- what another implementation of the same derivative (a reverse pass, a hand-derived       \
+                       formula) differs by */
+
 typedef struct orc_opt_params {
-    int32_t approx;   /* 0: jnp.logical_*, 1: min / max / activation */
-    int32_t act;      /* 0: hard_sigmoid, 1: sigmoid */
-    int32_t fun_id;   /* 0 received_power, 1 length**2, 2 length, 3 one */
-    double alpha, tol, patch, seg_tol, r_coef, height; /* python floats in the reference: cast to the working precision (xp.c) */
-    int32_t solver;   /* 1: MinPath, 2: FermatPath */
-    int32_t steps;    /* >= 1 */
-    double lr, b1, b2, eps; /* optax.adam(0.1): 0.1, 0.9, 0.999, 1e-8 */
-    int32_t grid_is_tx;
-    int32_t g_ulps; /* conditioning probe: every objective gradient moved by this many units in the last place (0: as computed) --
-                       what another implementation of the same derivative (a reverse pass, a hand-derived formula) differs by */
+    ORC_OPT_PARAMS_FIELDS
 } orc_opt_params;
+
+/* The optimiser of the solver loop, beside orc_opt_params (whose layout is the one the Adam-only entry points have always read:
+ * orc_opt_power_map and orc_opt_adam_step run Adam, orc_opt_power_map_opt and orc_opt_sgd_step take one of these). */
+typedef struct orc_opt_optimizer {
+    int32_t opt;      /* ORC_OPT_ADAM (b1, b2, eps of orc_opt_params), ORC_OPT_SGD (optax.sgd, momentum None), ORC_OPT_SGD_TRACE */
+    double momentum;  /* ORC_OPT_SGD_TRACE: the trace's decay, 0 included */
+    int32_t nesterov; /* ORC_OPT_SGD_TRACE: 1 = Nesterov */
+} orc_opt_optimizer;
+
+#define ORC_OPT_ADAM 0
+#define ORC_OPT_SGD 1
+#define ORC_OPT_SGD_TRACE 2
+
+/* what the body below reads: the parameters and the optimiser in one */
+typedef struct orc_opt_cfg {
+    ORC_OPT_PARAMS_FIELDS
+    int32_t opt;
+    double momentum;
+    int32_t nesterov;
+} orc_opt_cfg;
+
+static orc_opt_cfg orc_opt_make_cfg(const orc_opt_params* p, const orc_opt_optimizer* o) {
+    orc_opt_cfg c;
+    memset(&c, 0, sizeof c);
+    memcpy(&c, p, sizeof *p); /* (the same leading fields, from one macro: the same layout) */
+    c.opt = o ? o->opt : ORC_OPT_ADAM;
+    c.momentum = o ? o->momentum : 0.0;
+    c.nesterov = o ? o->nesterov : 0;
+    return c;
+}
 
 #define ORC_OPT_INSTANCE
 /* five instances of the body below: {fp32, fp64} x {lean: first-order jets in theta only (value maps), full: second-order
@@ -119,13 +157,24 @@ typedef struct orc_opt_params {
  * updates, 1 <= snaps[s] <= steps) and loss [ncell][C] or NULL (the recorded loss): what the trajectory agreement of the
  * conditioning mask is taken from.
  */
+int orc_opt_power_map_opt(int f64, const double* xys, const uint8_t* kind, const double* sincos, int N, const orc_opt_params* p_,
+                          const orc_opt_optimizer* o, const double* fixed, const double* X, const double* Y, long ncell,
+                          const int32_t* cands, const int32_t* cand_k, long C, const double* theta0, double* value, double* grad,
+                          double* pts, double* loss, const int32_t* snaps, int n_snap, int nthreads) {
+    const orc_opt_cfg cfg = orc_opt_make_cfg(p_, o);
+    const orc_opt_cfg* p = &cfg;
+#define ORC_OPT_ARGS xys, kind, sincos, N, p, fixed, X, Y, ncell, cands, cand_k, C, theta0, value, grad, pts, loss, snaps, n_snap, nthreads
+    if (grad) return f64 == 1 ? orc_opt_power_map_f64g(ORC_OPT_ARGS) : (f64 == 2 ? orc_opt_power_map_f32t(ORC_OPT_ARGS) : orc_opt_power_map_f32g(ORC_OPT_ARGS));
+    return f64 ? orc_opt_power_map_f64(ORC_OPT_ARGS) : orc_opt_power_map_f32(ORC_OPT_ARGS);
+}
+
+/* (Adam: the entry point before orc_opt_optimizer existed) */
 int orc_opt_power_map(int f64, const double* xys, const uint8_t* kind, const double* sincos, int N, const orc_opt_params* p,
                       const double* fixed, const double* X, const double* Y, long ncell, const int32_t* cands,
                       const int32_t* cand_k, long C, const double* theta0, double* value, double* grad, double* pts,
                       double* loss, const int32_t* snaps, int n_snap, int nthreads) {
-#define ORC_OPT_ARGS xys, kind, sincos, N, p, fixed, X, Y, ncell, cands, cand_k, C, theta0, value, grad, pts, loss, snaps, n_snap, nthreads
-    if (grad) return f64 == 1 ? orc_opt_power_map_f64g(ORC_OPT_ARGS) : (f64 == 2 ? orc_opt_power_map_f32t(ORC_OPT_ARGS) : orc_opt_power_map_f32g(ORC_OPT_ARGS));
-    return f64 ? orc_opt_power_map_f64(ORC_OPT_ARGS) : orc_opt_power_map_f32(ORC_OPT_ARGS);
+    return orc_opt_power_map_opt(f64, xys, kind, sincos, N, p, NULL, fixed, X, Y, ncell, cands, cand_k, C, theta0, value, grad, pts,
+                                 loss, snaps, n_snap, nthreads);
 }
 
 /* The objective and its theta-gradient at given parameters (pins the dual-number gradient against autodiff of ref.py) and one
@@ -137,8 +186,17 @@ int orc_opt_objective(int f64, const double* xys, const uint8_t* kind, const dou
                : orc_opt_objective_f32(xys, kind, sincos, N, solver, tx, rx, cand, k, theta, value, g);
 }
 
-int orc_opt_adam_step(int f64, const orc_opt_params* p, int t, double g, double* x, double* mu, double* nu) {
-    return f64 ? orc_opt_adam_step_f64(p, t, g, x, mu, nu) : orc_opt_adam_step_f32(p, t, g, x, mu, nu);
+int orc_opt_adam_step(int f64, const orc_opt_params* p_, int t, double g, double* x, double* mu, double* nu) {
+    const orc_opt_cfg cfg = orc_opt_make_cfg(p_, NULL);
+    return f64 ? orc_opt_adam_step_f64(&cfg, t, g, x, mu, nu) : orc_opt_adam_step_f32(&cfg, t, g, x, mu, nu);
+}
+
+/* One SGD update given g (o->opt ORC_OPT_SGD or ORC_OPT_SGD_TRACE, the learning rate p->lr; m: the trace, untouched without one):
+ * pins the update against ref.sgd_minimize and differt2d_amd.optimize.sgd bit for bit, tests/test_oracle_opt_c.py. */
+int orc_opt_sgd_step(int f64, const orc_opt_params* p_, const orc_opt_optimizer* o, double g, double* x, double* m) {
+    if (!o || (o->opt != ORC_OPT_SGD && o->opt != ORC_OPT_SGD_TRACE)) return -1;
+    const orc_opt_cfg cfg = orc_opt_make_cfg(p_, o);
+    return f64 ? orc_opt_sgd_step_f64(&cfg, g, x, m) : orc_opt_sgd_step_f32(&cfg, g, x, m);
 }
 
 #else /* ------------------------------------------------------------------------------------------------ the body, per precision */
@@ -389,11 +447,11 @@ int SFX(orc_opt_objective)(const double* xys, const uint8_t* kind, const double*
 }
 
 /* optax.scale_by_adam + scale(-lr) in oracle/ref.py:616-638's order; t = 1, 2, ...  Returns the update's pieces in place. */
-static inline void SFX(adam_consts)(const orc_opt_params* p, int t, REAL* c1, REAL* c2) {
+static inline void SFX(adam_consts)(const orc_opt_cfg* p, int t, REAL* c1, REAL* c2) {
     *c1 = (REAL)(1.0 - pow(p->b1, (double)t));
     *c2 = (REAL)(1.0 - pow(p->b2, (double)t));
 }
-int SFX(orc_opt_adam_step)(const orc_opt_params* p, int t, double g_, double* x_, double* mu_, double* nu_) {
+int SFX(orc_opt_adam_step)(const orc_opt_cfg* p, int t, double g_, double* x_, double* mu_, double* nu_) {
     REAL c1, c2, g = (REAL)g_, x = (REAL)*x_, mu = (REAL)*mu_, nu = (REAL)*nu_;
     SFX(adam_consts)(p, t, &c1, &c2);
     mu = (REAL)p->b1 * mu + (REAL)(1.0 - p->b1) * g;
@@ -404,8 +462,26 @@ int SFX(orc_opt_adam_step)(const orc_opt_params* p, int t, double g_, double* x_
     return 0;
 }
 
+/* optax.sgd in oracle/ref.py's sgd_minimize order: m' = g + c(momentum) m, u = g + c(momentum) m' with Nesterov else m' (u = g
+ * without a trace), x + c(-lr) u.  The tangent of the same update is sgd_tangent below. */
+static inline REAL SFX(sgd_update)(const orc_opt_cfg* p, REAL g, REAL x, REAL* m) {
+    REAL u = g;
+    if (p->opt == ORC_OPT_SGD_TRACE) {
+        const REAL d = (REAL)p->momentum;
+        *m = g + d * *m;
+        u = p->nesterov ? g + d * *m : *m;
+    }
+    return x + (REAL)(-p->lr) * u;
+}
+int SFX(orc_opt_sgd_step)(const orc_opt_cfg* p, double g_, double* x_, double* m_) {
+    REAL m = (REAL)*m_;
+    const REAL x = SFX(sgd_update)(p, (REAL)g_, (REAL)*x_, &m);
+    *x_ = (double)x; *m_ = (double)m;
+    return 0;
+}
+
 /* ---- validity and path function on first-order duals w.r.t. the cell (J_nv = 2 or 0), as oracle/d2d_oracle_grad.c ---- */
-static inline JET SFX(activation)(JET x, const orc_opt_params* p) {
+static inline JET SFX(activation)(JET x, const orc_opt_cfg* p) {
     JET z = jmulc((REAL)p->alpha, x);
     if (p->act == 0) return jdiv(jmin(jmax(jadd(z, jc((REAL)3)), jc((REAL)0)), jc((REAL)6)), jc((REAL)6));
     JET r = jc((REAL)1 / ((REAL)1 + EXP(-z.v))); /* lax.logistic; JVP y (1 - y) */
@@ -417,9 +493,9 @@ static inline JET SFX(activation)(JET x, const orc_opt_params* p) {
 static inline JET SFX(t_and)(JET a, JET b, int approx) { return approx ? jmin(a, b) : jc((a.v != 0 && b.v != 0) ? (REAL)1 : (REAL)0); }
 static inline JET SFX(t_or)(JET a, JET b, int approx) { return approx ? jmax(a, b) : jc((a.v != 0 || b.v != 0) ? (REAL)1 : (REAL)0); }
 static inline JET SFX(t_not)(JET a, int approx) { return approx ? jsub(jc((REAL)1), a) : jc(a.v != 0 ? (REAL)0 : (REAL)1); }
-static inline JET SFX(t_ge)(JET x, JET y, const orc_opt_params* p) { return p->approx ? activation(jsub(x, y), p) : jc(x.v >= y.v ? (REAL)1 : (REAL)0); }
-static inline JET SFX(t_le)(JET x, JET y, const orc_opt_params* p) { return p->approx ? activation(jsub(y, x), p) : jc(x.v <= y.v ? (REAL)1 : (REAL)0); }
-static inline JET SFX(t_lt)(JET x, JET y, const orc_opt_params* p) { return p->approx ? activation(jsub(y, x), p) : jc(x.v < y.v ? (REAL)1 : (REAL)0); }
+static inline JET SFX(t_ge)(JET x, JET y, const orc_opt_cfg* p) { return p->approx ? activation(jsub(x, y), p) : jc(x.v >= y.v ? (REAL)1 : (REAL)0); }
+static inline JET SFX(t_le)(JET x, JET y, const orc_opt_cfg* p) { return p->approx ? activation(jsub(y, x), p) : jc(x.v <= y.v ? (REAL)1 : (REAL)0); }
+static inline JET SFX(t_lt)(JET x, JET y, const orc_opt_cfg* p) { return p->approx ? activation(jsub(y, x), p) : jc(x.v < y.v ? (REAL)1 : (REAL)0); }
 #define t_and SFX(t_and)
 #define t_or SFX(t_or)
 #define t_not SFX(t_not)
@@ -427,13 +503,13 @@ static inline JET SFX(t_lt)(JET x, JET y, const orc_opt_params* p) { return p->a
 #define t_le SFX(t_le)
 #define t_lt SFX(t_lt)
 
-static inline JET SFX(seg_test)(JET num, JET den, const orc_opt_params* p) { /* geometry.py:163-171 */
+static inline JET SFX(seg_test)(JET num, JET den, const orc_opt_cfg* p) { /* geometry.py:163-171 */
     const int den_is_zero = (den.v == (REAL)0);
     JET t = den_is_zero ? jc((REAL)INFINITY) : jdiv(num, den);
     return t_and(t_ge(t, jc((REAL)(-p->seg_tol)), p), t_le(t, jc((REAL)1 + (REAL)p->seg_tol), p), p->approx);
 }
 #define seg_test SFX(seg_test)
-static inline JET SFX(wall_hits)(const OBJ* w, JET p3x, JET p3y, JET p4x, JET p4y, const orc_opt_params* p) { /* geometry.py:82-173 */
+static inline JET SFX(wall_hits)(const OBJ* w, JET p3x, JET p3y, JET p4x, JET p4y, const orc_opt_cfg* p) { /* geometry.py:82-173 */
     const REAL Ax = w->p2x - w->p1x, Ay = w->p2y - w->p1y;
     JET Bx = jsub(p3x, p4x), By = jsub(p3y, p4y);
     JET Cx = jsub(jc(w->p1x), p3x), Cy = jsub(jc(w->p1y), p3y);
@@ -458,7 +534,7 @@ static inline REAL SFX(ipow)(REAL x, int n) { /* lax.integer_pow */
 /* One (cell, candidate): the contribution valid * fun as a first-order dual w.r.t. the cell.  cellv: 0 = the cell is the
  * receiver (rx), 1 = the transmitter.  With with_grad the loop carries (theta, cell) second-order jets. */
 static JET SFX(eval_candidate)(const OBJ* O, int N, const int32_t* cand, int k, REAL txx, REAL txy, REAL rxx, REAL rxy, int cell_is_tx,
-                               const double* theta0, const orc_opt_params* p, int with_grad, double* pts_out, double* loss_out,
+                               const double* theta0, const orc_opt_cfg* p, int with_grad, double* pts_out, double* loss_out,
                                const int32_t* snaps, int n_snap) {
     const int n = n_unknowns(O, cand, k);
 #if !JSECOND
@@ -502,8 +578,8 @@ static JET SFX(eval_candidate)(const OBJ* O, int N, const int32_t* cand, int k, 
                     dlast[c] = f.g[n + c];
                     for (int i = 0; i < n; ++i) dlast[c] += f.g[i] * dth[i][c];
                 }
-            REAL c1, c2;
-            SFX(adam_consts)(p, t, &c1, &c2);
+            REAL c1 = (REAL)1, c2 = (REAL)1;
+            if (p->opt == ORC_OPT_ADAM) SFX(adam_consts)(p, t, &c1, &c2);
             TREAL dgs[ORC_MAX_ORDER][2]; /* d g_i / d cell, with d theta_t / d cell of THIS step for every unknown */
             for (int i = 0; i < n; ++i) {
                 dgs[i][0] = dgs[i][1] = 0.0;
@@ -521,7 +597,23 @@ static JET SFX(eval_candidate)(const OBJ* O, int N, const int32_t* cand, int k, 
                     g = (sizeof(REAL) == 4) ? (REAL)nextafterf((float)g, p->g_ulps > 0 ? INFINITY : -INFINITY)
                                             : (REAL)nextafter((double)g, p->g_ulps > 0 ? INFINITY : -INFINITY);
                 const TREAL* dg = dgs[i];
-                /* oracle/ref.py:633-637 */
+                if (p->opt != ORC_OPT_ADAM) {
+                    /* oracle/ref.py's sgd_minimize; the tangent is the same linear recurrence: d m' = d g + c(momentum) d m, d u =
+                     * d g + c(momentum) d m' (Nesterov) else d m', d theta += c(-lr) d u (mu holds the trace) */
+                    th[i] = SFX(sgd_update)(p, g, th[i], &mu[i]);
+                    if (with_grad)
+                        for (int c = 0; c < 2; ++c) {
+                            TREAL du = dg[c];
+                            if (p->opt == ORC_OPT_SGD_TRACE) {
+                                const TREAL d = (TREAL)(REAL)p->momentum;
+                                dmu[i][c] = dg[c] + d * dmu[i][c];
+                                du = p->nesterov ? dg[c] + d * dmu[i][c] : dmu[i][c];
+                            }
+                            dth[i][c] += (TREAL)(REAL)(-p->lr) * du;
+                        }
+                    continue;
+                }
+                /* oracle/ref.py's adam_minimize */
                 const REAL b1 = (REAL)p->b1, b2 = (REAL)p->b2, ob1 = (REAL)(1.0 - p->b1), ob2 = (REAL)(1.0 - p->b2);
                 mu[i] = b1 * mu[i] + ob1 * g;
                 const REAL gg = g * g;
@@ -625,11 +717,11 @@ static JET SFX(eval_candidate)(const OBJ* O, int N, const int32_t* cand, int k, 
     return out;
 }
 
-int SFX(orc_opt_power_map)(const double* xys, const uint8_t* kind, const double* sincos, int N, const orc_opt_params* p,
+int SFX(orc_opt_power_map)(const double* xys, const uint8_t* kind, const double* sincos, int N, const orc_opt_cfg* p,
                            const double* fixed, const double* X, const double* Y, long ncell, const int32_t* cands,
                            const int32_t* cand_k, long C, const double* theta0, double* value, double* grad, double* pts,
                            double* loss, const int32_t* snaps, int n_snap, int nthreads) {
-    if (N < 0 || p->steps < 1 || (p->solver != 1 && p->solver != 2)) return -1;
+    if (N < 0 || p->steps < 1 || (p->solver != 1 && p->solver != 2) || p->opt < ORC_OPT_ADAM || p->opt > ORC_OPT_SGD_TRACE) return -1;
     OBJ* O = (OBJ*)malloc(sizeof(OBJ) * (N > 0 ? N : 1));
     for (int j = 0; j < N; ++j) SFX(make_obj)(&O[j], kind[j], xys + 4 * j, sincos + 2 * j, (REAL)p->patch);
 #ifdef _OPENMP

@@ -638,6 +638,53 @@ def adam_minimize(value_and_grad, x0, steps=100, lr=0.1, b1=0.9, b2=0.999, eps=1
     return x, loss
 
 
+# optax.sgd instead of Adam in opt_path / opt_path_diff while set (None: Adam, _ADAM): dict(lr=, momentum=, nesterov=)
+_SGD = None
+
+
+class sgd_hyper:
+    """``with sgd_hyper(lr=0.01, momentum=0.3, nesterov=False): ...`` -- opt_path / opt_path_diff inside run optax.sgd
+    (sgd_minimize) instead of Adam."""
+
+    def __init__(self, lr, momentum=None, nesterov=False):
+        self.kw = dict(lr=lr, momentum=momentum, nesterov=nesterov)
+
+    def __enter__(self):
+        global _SGD
+        self.old, _SGD = _SGD, self.kw
+
+    def __exit__(self, *exc):
+        global _SGD
+        _SGD = self.old
+
+
+def sgd_minimize(value_and_grad, x0, steps=100, lr=0.1, momentum=None, nesterov=False, xp=NUMPY):
+    """adam_minimize's signature with optax.sgd inside (optax 0.2.4: chain(trace(momentum, nesterov), scale(-lr)), or
+    scale(-lr) alone for momentum None; the trace starts at zeros): m' = g + c(momentum) m, u = g + c(momentum) m' with
+    Nesterov else m', x = x + c(-lr) u.  A momentum of 0.0 keeps its trace: 0 * NaN = NaN carries a NaN gradient forward.
+    Returns (x_final, loss evaluated BEFORE the last update)."""
+    x = list(x0)
+    m = [xp.zeros_like(v) for v in x]
+    loss = None
+    for _ in range(steps):
+        loss, g = value_and_grad(x)
+        for i in range(len(x)):
+            if momentum is None:
+                u = g[i]
+            else:
+                m[i] = g[i] + xp.c(momentum) * m[i]
+                u = g[i] + xp.c(momentum) * m[i] if nesterov else m[i]
+            x[i] = x[i] + xp.c(-lr) * u
+    return x, loss
+
+
+def _minimize(value_and_grad, x0, steps, xp):
+    """The solver loop of opt_path / opt_path_diff: sgd_minimize while _SGD is set, else adam_minimize with _ADAM."""
+    if _SGD is not None:
+        return sgd_minimize(value_and_grad, x0, steps=steps, xp=xp, **_SGD)
+    return adam_minimize(value_and_grad, x0, steps=steps, xp=xp, **_ADAM)
+
+
 # --- validity (geometry.py:821-963) ---------------------------------------------------
 
 
@@ -824,7 +871,7 @@ def opt_path(solver, tx, objs, rx, theta0, steps, xp=NUMPY):
         return loss.detach(), [gi.detach() for gi in g]
 
     x0 = [torch.full(batch, float(theta0[i]), dtype=tb.tdtype) for i in range(n_unknowns)]
-    x, last_loss = adam_minimize(vg, x0, steps=steps, xp=tb, **_ADAM)
+    x, last_loss = _minimize(vg, x0, steps, tb)
     pts = parametric_to_cartesian(t_objs, x, t_tx, t_rx, tb)
     if solver == "fermat":
         loss = path_loss(t_objs, pts, tb)  # geometry.py:1204
@@ -856,7 +903,7 @@ def opt_path_diff(solver, tx, objs, rx, theta0, steps, tb):
         return loss, list(g)
 
     x0 = [torch.full(tuple(batch), float(theta0[i]), dtype=tb.tdtype).requires_grad_(True) for i in range(n_unknowns)]
-    x, last_loss = adam_minimize(vg, x0, steps=steps, xp=tb, **_ADAM)
+    x, last_loss = _minimize(vg, x0, steps, tb)
     pts = parametric_to_cartesian(objs, x, tx, rx, tb)
     loss = path_loss(objs, pts, tb) if solver == "fermat" else last_loss  # geometry.py:1204 / :1284-1288
     return [p.expand(*batch, 2) for p in pts], loss

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Randomised differential test of the MinPath / FermatPath sweeps (GPU box): the solver kernels (K4) against
 oracle/d2d_oracle_opt.c on random scenes of Wall / RIS / Vertex objects -- value maps and, every other case, per-cell gradients
-through the Adam loop -- orders 1..2 (order 3 in small scenes), both solvers, all validity modes, both grid roles.
+through the solver loop -- orders 1..2 (order 3 in small scenes), both solvers, all validity modes, both grid roles, with
+Adam (the reference's default) or SGD (plain, momentum, Nesterov, momentum 0.0: --optimizer sgd; mixed: either, per case).
 
 Sequential fp32 Adam steps are not reproducible to the last bit between two gradient implementations and chaotic where a
 solve has not settled, so cells are compared where the ORACLE ALONE calls the sweep well conditioned (CO.opt_conditioning:
 every candidate's trajectory agrees between its fp64 run, its fp32 run and fp32 runs from inputs one ulp away); there the GPU
 sits within 1e-5 of the map's scale (+ 1e-5 relative) of the fp64 oracle, or within four times the oracle's own fp32 distance.
 
-usage: python scripts/fuzz_opt.py [n_cases] [seed]"""
+usage: python scripts/fuzz_opt.py [--optimizer {adam,sgd,mixed}] [n_cases] [seed]"""
 
 import os
 import sys
@@ -23,6 +24,24 @@ from differt2d_amd.engine import Context  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 
 F = np.float32
+SGD_KINDS = ("plain", "momentum", "nesterov", "momentum0")
+
+
+def random_sgd(rng, solver):
+    """An optax.sgd for one case: (lr, momentum, nesterov).  Ranges where the oracle's own iteration is not chaotic: SGD does not
+    normalise its step, and once lr times the objective's curvature exceeds 2 a solve jumps about and no two precisions follow
+    it.  MinPath's residual has a curvature of order 1 / distance**2 next to a wall: lr in [5e-4, 2e-3] (tests/test_oracle_opt_c.py:
+    at lr 0.005 .. 0.01 most order-2 solves of the RIS scene are chaotic after 50 steps); FermatPath's path length is tamer:
+    lr in [2e-3, 1e-2].  Momentum in [0.1, 0.5]: a heavy trace at a large rate is chaotic too (tests/test_gpu_opt_sgd.py: 0.8 at
+    lr 0.01)."""
+    lo, hi = (5e-4, 2e-3) if solver == "min" else (2e-3, 1e-2)
+    lr = float(F(np.exp(rng.uniform(np.log(lo), np.log(hi)))))
+    kind = SGD_KINDS[int(rng.integers(0, len(SGD_KINDS)))]
+    if kind == "plain":
+        return kind, (lr, None, False)
+    if kind == "momentum0":
+        return kind, (lr, 0.0, False)
+    return kind, (lr, float(F(rng.uniform(0.1, 0.5))), kind == "nesterov")
 
 
 def random_case(rng):
@@ -52,10 +71,14 @@ def random_case(rng):
     return kinds, xys, phis, fixed, X, Y, kw, min_order, max_order, cands, theta0
 
 
-def check_case(ctx, case, kinds, xys, phis, fixed, X, Y, kw, min_order, max_order, cands, theta0, with_grad, role):
+def check_case(ctx, case, kinds, xys, phis, fixed, X, Y, kw, min_order, max_order, cands, theta0, with_grad, role, sgd_spec=None):
+    from differt2d_amd.optimize import sgd
+
     th = [t[: sum(kinds[int(i)] != 2 for i in c)] for c, t in zip(cands, theta0)]
+    okw = {} if sgd_spec is None else CO.sgd_kwargs(*sgd_spec)
     cond = CO.opt_conditioning(kinds, xys, phis, fixed, X, Y, cands, th, kw["steps"], with_grad=with_grad,
-                               grid_role="tx" if role == L.GRID_TX else "rx", **{k: v for k, v in kw.items() if k != "steps"})
+                               grid_role="tx" if role == L.GRID_TX else "rx", **{k: v for k, v in kw.items() if k != "steps"}, **okw)
+    ctx.set_optimizer(None if sgd_spec is None else sgd(sgd_spec[0], momentum=sgd_spec[1], nesterov=sgd_spec[2]))
     ctx.set_scene(xys, kinds, phis)
     ctx.set_theta0(theta0)
     gkw = dict(kw, min_order=min_order, max_order=max_order, grid_role=role)
@@ -98,14 +121,16 @@ def check_case(ctx, case, kinds, xys, phis, fixed, X, Y, kw, min_order, max_orde
         # (oracle/ref.py under torch) on that cell: within twice ITS distance from fp64
         if gbad.any() and gbad.sum() <= 32:
             from oracle import ref as R
+            from contextlib import nullcontext
 
             rkw = dict(solver=kw["solver"], steps=kw["steps"], approx=kw["approx"], alpha=kw["alpha"], tol=kw["tol"], patch=kw["patch"], fun=kw["fun"],
                        grid_role="tx" if role == L.GRID_TX else "rx", **({"function": kw["function"]} if kw["approx"] else {}))
             wb = np.argwhere(gbad)
             print(f"  .. case {case}: {len(wb)} cells to the reverse-mode yardstick", flush=True)
             Xc, Yc = X[wb[:, 0], wb[:, 1]][None], Y[wb[:, 0], wb[:, 1]][None]  # (one batched call per precision)
-            t = {dt: R.opt_value_and_grads(kinds, np.asarray(xys, np.float64), phis, fixed, Xc, Yc, cands, th, dtype=dt, **rkw)["grad_cell"][0]
-                 for dt in ("float64", "float32")}
+            with R.sgd_hyper(*sgd_spec) if sgd_spec is not None else nullcontext():
+                t = {dt: R.opt_value_and_grads(kinds, np.asarray(xys, np.float64), phis, fixed, Xc, Yc, cands, th, dtype=dt, **rkw)["grad_cell"][0]
+                     for dt in ("float64", "float32")}
             for i, w in enumerate(map(tuple, wb)):
                 # (as vectors, and five times the reference chain's own fp32-reverse-mode distance: two different backward passes in
                 # fp32 -- torch's and the kernels' -- sit at different multiples of the same rounding; seed 2 case 193, sigmoid in deep
@@ -119,8 +144,14 @@ def check_case(ctx, case, kinds, xys, phis, fixed, X, Y, kw, min_order, max_orde
 
 
 def main():
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    import argparse
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--optimizer", choices=("adam", "sgd", "mixed"), default="adam")
+    ap.add_argument("n_cases", nargs="?", type=int, default=200)
+    ap.add_argument("seed", nargs="?", type=int, default=0)
+    args = ap.parse_args()
+    n_cases, seed = args.n_cases, args.seed
     rng = np.random.default_rng(seed)
     bad = n_stable = n_cells = n_grad = 0
     t0 = time.time()
@@ -128,15 +159,19 @@ def main():
         for case in range(n_cases):
             kinds, xys, phis, fixed, X, Y, kw, lo, hi, cands, theta0 = random_case(rng)
             role = L.GRID_TX if case % 3 == 2 else L.GRID_RX
-            msgs, s, c, g = check_case(ctx, case, kinds, xys, phis, fixed, X, Y, kw, lo, hi, cands, theta0, case % 2 == 1, role)
+            opt, sgd_spec = "adam", None
+            # (drawn from a generator of their own: the Adam cases of a seed stay the cases they always were)
+            if args.optimizer == "sgd" or (args.optimizer == "mixed" and case % 2 == 0):
+                opt, sgd_spec = random_sgd(np.random.default_rng([seed, case]), kw["solver"])
+            msgs, s, c, g = check_case(ctx, case, kinds, xys, phis, fixed, X, Y, kw, lo, hi, cands, theta0, case % 2 == 1, role, sgd_spec)
             n_stable, n_cells, n_grad = n_stable + s, n_cells + c, n_grad + g
             if msgs:
                 bad += 1
                 print(f"MISMATCH case {case} seed {seed} {'TX' if role == L.GRID_TX else 'RX'}-grid: kinds={kinds.tolist()} grid={X.shape} orders {lo}..{hi} "
-                      f"kw={kw}: " + "; ".join(msgs), flush=True)
+                      f"kw={kw} optimizer {opt} {sgd_spec}: " + "; ".join(msgs), flush=True)
             if case % 100 == 99:
                 print(f"  .. {case + 1} cases, {bad} mismatches, {n_stable} of {n_cells} cells well conditioned, {n_grad} gradients compared, {time.time() - t0:.0f} s", flush=True)
-    print(f"opt fuzz: {n_cases} cases, {bad} mismatches, {n_stable} of {n_cells} cells well conditioned (values compared there), "
+    print(f"opt fuzz ({args.optimizer}): {n_cases} cases, {bad} mismatches, {n_stable} of {n_cells} cells well conditioned (values compared there), "
           f"{n_grad} per-cell gradients compared, {time.time() - t0:.1f} s (seed {seed})")
     sys.exit(1 if bad else 0)
 

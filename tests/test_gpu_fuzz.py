@@ -75,3 +75,12 @@ def test_cut_in_four_handover_is_stable_under_repetition():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "stress_heavy.py"), "150"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "stress: 0 mismatching maps" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+
+
+def test_sgd_solver_fuzz_against_the_c_oracle():
+    """scripts/fuzz_opt.py --optimizer sgd: the same random cases with SGD -- plain, momentum, Nesterov or momentum 0.0, at a
+    learning rate and momentum where the oracle's iteration is not chaotic -- against the C oracle's SGD restatement."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_opt.py"), "--optimizer", "sgd", "20", "2027"],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    assert " 0 mismatches" in out.stdout

@@ -10,6 +10,8 @@ import pytest
 
 from test_gpu_opt import _gpu_opt_grads, _opt_case, _oracle_objs, _oracle_stable, _ris_scene, _scene_tables, _tight
 
+from oracle.ref import sgd_minimize
+
 pytestmark = pytest.mark.gpu
 
 F = np.float32
@@ -19,25 +21,6 @@ F = np.float32
 # momentum 0.8, MinPath's iteration is chaotic on some cells: a one-ulp change of theta0 moves the oracle's own fp32 gradient
 # by orders of magnitude there, and no fp32 evaluation can be held to the _tight bar.)
 SPECS = {"plain": (0.01, None, False), "momentum": (0.005, 0.3, False), "nesterov": (0.005, 0.5, True)}
-
-
-def sgd_minimize(value_and_grad, x0, steps=100, lr=0.1, momentum=None, nesterov=False, xp=None):
-    """oracle/ref.py: adam_minimize's signature with optax.sgd inside (optax 0.2.4: chain(trace(momentum, nesterov),
-    scale(-lr)), or scale(-lr) alone for momentum None; the trace starts at zeros): m' = g + c(momentum) m, u = g +
-    c(momentum) m' with Nesterov else m', x = x + c(-lr) u.  Returns (x_final, loss evaluated BEFORE the last update)."""
-    x = list(x0)
-    m = [xp.zeros_like(v) for v in x]
-    loss = None
-    for _ in range(steps):
-        loss, g = value_and_grad(x)
-        for i in range(len(x)):
-            if momentum is None:
-                u = g[i]
-            else:
-                m[i] = g[i] + xp.c(momentum) * m[i]
-                u = g[i] + xp.c(momentum) * m[i] if nesterov else m[i]
-            x[i] = x[i] + xp.c(-lr) * u
-    return x, loss
 
 
 def _sgd_oracle(monkeypatch, name):
