@@ -414,16 +414,16 @@ d2d::ObjTables obj_tables(d2d_ctx* c) {
 
 // optax.adam(0.1) defaults (optimize.py:83): b1 = 0.9, b2 = 0.999, eps = 1e-8 -- or what d2d_set_optimizer said; bias
 // corrections 1 - b^t tabulated in double precision and rounded to fp32 (the oracle does the same).  SGD has no tables.
-int adam_cfg(d2d_ctx* c, const d2d_params* p, d2d::AdamCfg* A) {
+int opt_cfg(d2d_ctx* c, const d2d_params* p, d2d::OptCfg* A) {
     const int steps = p->steps;
     if (steps < 1 || steps > 1000000) return fail(D2D_ERR_INVALID, "steps must lie in 1..1e6, got %d", steps);
     if (p->many < 0 || p->many > 4096) return fail(D2D_ERR_INVALID, "many must lie in 0..4096, got %d", p->many);
-    if (c->opt_kind != D2D_OPT_ADAM) {
-        // optax.sgd: momentum and learning rate are Python floats, weakly typed (rounded to fp32 where they meet an fp32 array)
-        A->solver = p->solver;
-        A->steps = steps;
-        A->many = p->many > 1 ? p->many : 1;
-        A->lr = (float)c->opt_lr;
+    A->solver = p->solver;
+    A->steps = steps;
+    A->many = p->many > 1 ? p->many : 1;
+    // the hyper-parameters are Python floats on the reference's side (weakly typed: rounded to fp32 where they meet an fp32 array)
+    A->lr = (float)c->opt_lr;
+    if (c->opt_kind != D2D_OPT_ADAM) {  // optax.sgd
         A->sgd = 1;
         A->momentum = (c->opt_kind == D2D_OPT_SGD_MOMENTUM) ? 1 : 0;
         A->nesterov = (A->momentum && c->opt_b2 != 0.0) ? 1 : 0;
@@ -447,13 +447,8 @@ int adam_cfg(d2d_ctx* c, const d2d_params* p, d2d::AdamCfg* A) {
         c->bc_b1 = c->opt_b1;
         c->bc_b2 = c->opt_b2;
     }
-    A->solver = p->solver;
-    A->steps = steps;
-    A->many = p->many > 1 ? p->many : 1;
     A->bc1 = c->d_bc1.p;
     A->bc2 = c->d_bc2.p;
-    // the hyper-parameters are Python floats on the reference's side (weakly typed: rounded to fp32 where they meet an fp32 array)
-    A->lr = (float)c->opt_lr;
     A->b1 = (float)c->opt_b1;
     A->b2 = (float)c->opt_b2;
     A->eps = (float)c->opt_eps;
@@ -462,6 +457,16 @@ int adam_cfg(d2d_ctx* c, const d2d_params* p, d2d::AdamCfg* A) {
     A->omb1 = (float)(1.0 - c->opt_b1);
     A->omb2 = (float)(1.0 - c->opt_b2);
     return D2D_OK;
+}
+
+// the validity chain's parameters of the solver sweeps' arguments (d2d::OptSweepArgs, d2d::TraceArgs)
+template <class Args>
+void set_validity(Args& a, const d2d_params* p) {
+    a.mode = p->approx ? (p->act == D2D_ACT_HARD_SIGMOID ? d2d::MODE_HSIG : d2d::MODE_SIG) : d2d::MODE_HARD;
+    a.alpha = p->alpha;
+    a.tol = p->tol;
+    a.seg_lo = -p->seg_tol;
+    a.seg_hi = 1.0f + p->seg_tol;
 }
 
 int check_params(const d2d_params* p) {
@@ -953,19 +958,39 @@ int d2d_debug_grid_reuses(d2d_ctx* c, int64_t* count) {
     return D2D_OK;
 }
 
-// MinPath / FermatPath sweep: explicit candidate list (these sweeps have few candidates), theta0 per candidate.
-// grad_mode: 0 values; 1 + per-cell gradient; 2 + scene VJP (d2d_optgrad.hpp: tangents carried through the Adam loop).
-static inline long long steps_of(const d2d_params* p) { return p->steps; }
+}  // extern "C"
 
-static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, int grad_mode) {
+namespace {
+
+// ---- MinPath / FermatPath sweeps: opt_sweep_launch and its steps; an explicit candidate list, theta0 per candidate ---
+// What the steps of one launch share: opt_sweep_launch sets the inputs, the steps the rest.
+struct OptSweep {
+    const d2d_params* p;
+    const float* tx;
+    int grad_mode;                    // 0 values; 1 + per-cell gradient; 2 + scene VJP
+    int64_t C = 0;
+    std::vector<int32_t> cand, order;  // [C][D2D_MAX_ORDER], [C]: by ascending order
+    unsigned blocks = 0;              // 64-lane workgroups over the grid
+    int n_elem = 0;                   // scene VJP row: [4N] object end points, [2] fixed end point, [N] phi
+    d2d::OptSweepArgs a;
+    d2d::OptGradArgs g;               // value+grad sweeps
+    d2d::OptRevArgs ra;               // ... in reverse mode (option opt_grad_mode 0)
+    long long chunk_cells = 0;        // reverse mode: cells per launch (the trajectory store holds that many)
+};
+
+// enumerate the candidates; check theta0 and upload both
+static int opt_candidates(d2d_ctx* c, OptSweep& s) {
+    const d2d_params* p = s.p;
     int rc;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = upload_occl(c, p->patch))) return rc;
     int64_t C = 0;
     if ((rc = d2d_count_candidates(c->N, c->allowed.data(), p->min_order, p->max_order, &C))) return rc;
     if (C > (1 << 22)) return fail(D2D_ERR_UNSUPPORTED, "%lld candidates are too many for an optimiser-based sweep", (long long)C);
-    std::vector<int32_t> cand((size_t)C * D2D_MAX_ORDER + 1), order((size_t)C + 1);
+    std::vector<int32_t>& cand = s.cand;
+    std::vector<int32_t>& order = s.order;
+    cand.assign((size_t)C * D2D_MAX_ORDER + 1, 0);
+    order.assign((size_t)C + 1, 0);
     if ((rc = d2d_enumerate_candidates(c->N, c->allowed.data(), p->min_order, p->max_order, cand.data(), order.data(), C))) return rc;
+    s.C = C;
     bool need_theta = false;
     for (int64_t i = 0; i < C; ++i)
         for (int q = 0; q < order[(size_t)i]; ++q)
@@ -980,27 +1005,28 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
     HIP_TRY(hipMemcpyAsync(c->d_scand.p, cand.data(), cand.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_sorder.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_theta0.p, th.data(), th.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors go out of scope
-    d2d::OptSweepArgs a;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // th goes out of scope
+    return D2D_OK;
+}
+
+static int opt_args(d2d_ctx* c, OptSweep& s) {
+    const d2d_params* p = s.p;
+    d2d::OptSweepArgs& a = s.a;
     memset(&a, 0, sizeof a);
     a.T = obj_tables(c);
-    if ((rc = adam_cfg(c, p, &a.A))) return rc;
+    if (int rc = opt_cfg(c, p, &a.A)) return rc;
     a.cand = c->d_scand.p;
     a.order = c->d_sorder.p;
     a.theta0 = c->d_theta0.p;
-    a.C = (int)C;
+    a.C = (int)s.C;
     a.X = c->d_X.p;
     a.Y = c->d_Y.p;
     a.out = c->d_out.p;
     a.cells = (long)c->m * c->n;
-    a.txx = tx[0];
-    a.txy = tx[1];
+    a.txx = s.tx[0];
+    a.txy = s.tx[1];
     a.grid_is_tx = (p->grid_role == D2D_GRID_TX) ? 1 : 0;
-    a.mode = p->approx ? (p->act == D2D_ACT_HARD_SIGMOID ? d2d::MODE_HSIG : d2d::MODE_SIG) : d2d::MODE_HARD;
-    a.alpha = p->alpha;
-    a.tol = p->tol;
-    a.seg_lo = -p->seg_tol;
-    a.seg_hi = 1.0f + p->seg_tol;
+    set_validity(a, p);
     for (int k = 0; k <= D2D_MAX_ORDER; ++k) a.fnum[k] = integer_pow(p->r_coef, k);
     a.h2 = p->height * p->height;
     a.fun_id = p->fun_id;
@@ -1008,161 +1034,184 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
     if (p->fun_id == D2D_FUN_CUSTOM) {
         // a host-evaluated path function: rows in this enumeration's order, chained through the reverse pass over the stored
         // trajectory (the forward-tangent variant carries no seed for them)
-        if (!grad_mode || c->opt_grad_mode != 0)
+        if (!s.grad_mode || c->opt_grad_mode != 0)
             return fail(D2D_ERR_UNSUPPORTED, "fun_id D2D_FUN_CUSTOM with an optimiser-based solver needs the reverse-mode value+grad sweep (option opt_grad_mode 0)");
-        if (c->cust_C != (long long)C)
-            return fail(D2D_ERR_STATE, "d2d_set_path_fun_values holds %lld candidates, this sweep walks %lld", c->cust_C, (long long)C);
+        if (c->cust_C != (long long)s.C)
+            return fail(D2D_ERR_STATE, "d2d_set_path_fun_values holds %lld candidates, this sweep walks %lld", c->cust_C, (long long)s.C);
         a.cust_f = c->d_cust_f.p;
         a.cust_pb = c->d_cust_pb.p;
     }
-    const unsigned blocks = (unsigned)((a.cells + 63) / 64);
-    if (grad_mode) {
-        // one (cell, candidate) per lane, the candidates side by side; value, per-cell gradient and VJP partial sums go
-        // through per-candidate scratch and are reduced in candidate order
-        if (C > 65535 || (long long)C * a.cells > (1ll << 28))
-            return fail(D2D_ERR_UNSUPPORTED, "%lld candidates x %lld cells exceed the gradient sweep's scratch (2^28 contributions)",
-                        (long long)C, (long long)a.cells);
-        const int n_elem = 5 * c->N + 2;  // [4N] object end points, [2] fixed end point, [N] phi
-        if (C == 0) {
-            // no candidate at all (order 2 in a scene of one object): the map, its gradient and the scene VJP are zero -- the
-            // reference's loop over no candidates (scene.py:1892-1918); found by scripts/fuzz_opt.py
-            if (p->out_mode == D2D_OUT_ADD && !c->have_grad) return fail(D2D_ERR_STATE, "D2D_OUT_ADD needs a previous value+grad sweep on this grid");
-            if ((rc = c->d_grad.ensure(2 * (size_t)a.cells))) return rc;
-            c->have_grad = true;
-            HIP_TRY(d2d::launch_opt_grad_reduce(nullptr, nullptr, 0, a.cells, c->d_out.p, c->d_grad.p, p->out_mode, c->stream));
-            if (grad_mode == 2) {
-                if ((rc = c->d_vjp.ensure((size_t)n_elem))) return rc;
-                if ((rc = join_comm(c, 2))) return rc;
-                if (!(p->out_mode == D2D_OUT_ADD && c->have_vjp)) {
-                    HIP_TRY(hipMemsetAsync(c->d_vjp.p, 0, (size_t)n_elem * sizeof(double), c->stream));
-                    c->vjp_has_phi = true;
-                    c->vjp_reduced = false;
-                }
-                c->have_vjp = true;
-            }
-            return D2D_OK;
-        }
-        if (p->out_mode == D2D_OUT_ADD && !c->have_grad) return fail(D2D_ERR_STATE, "D2D_OUT_ADD needs a previous value+grad sweep on this grid");
-        if (grad_mode == 2 && p->out_mode == D2D_OUT_ADD && c->have_vjp) {
-            if (!c->vjp_has_phi)
-                return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP comes from an ImagePath sweep; a MinPath / FermatPath sweep cannot be added to it");
-            if (c->vjp_reduced)
-                return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP has been all-reduced over ranks; fetch it, then start a new sum (D2D_OUT_OVERWRITE)");
-        }
-        if ((rc = c->d_contrib.ensure((size_t)C * (size_t)a.cells))) return rc;
-        if ((rc = c->d_gcontrib.ensure(2 * (size_t)C * (size_t)a.cells))) return rc;
-        if ((rc = c->d_grad.ensure(2 * (size_t)a.cells))) return rc;
-        d2d::OptGradArgs g;
-        memset(&g, 0, sizeof g);
-        g.s = a;
-        g.patch = p->patch;
-        g.cot = c->have_cot ? c->d_cot.p : nullptr;
-        g.contrib = c->d_contrib.p;
-        g.gcontrib = c->d_gcontrib.p;
-        g.partial = nullptr;
-        const size_t rows = (size_t)C * blocks;
-        if (grad_mode == 2) {
-            if ((rc = c->d_partial.ensure(rows * (size_t)n_elem))) return rc;
-            if ((rc = c->d_vjp.ensure((size_t)n_elem))) return rc;
-            g.partial = c->d_partial.p;
-            if (p->out_mode == D2D_OUT_OVERWRITE) c->have_vjp = false;
-        }
-        c->have_grad = true;
-        // reverse mode: the trajectories of the solver (Adam: 4 floats per step and unknown, SGD: 1) go through HBM
-        d2d::OptRevArgs ra;
-        memset(&ra, 0, sizeof ra);
-        long long chunk_cells = 0;
-        if (c->opt_grad_mode == 0) {
-            std::vector<long long> off((size_t)C + 1, 0);
-            for (int64_t i = 0; i < C; ++i) {
-                int nu = 0;
-                for (int q = 0; q < order[(size_t)i]; ++q) nu += c->kind[cand[(size_t)i * D2D_MAX_ORDER + q]] != D2D_VERTEX ? 1 : 0;
-                off[(size_t)i + 1] = off[(size_t)i] + (long long)d2d::traj_floats_per_step(a.A.sgd != 0) * steps_of(p) * nu;
-            }
-            const long long per_cell = std::max<long long>(1, off[(size_t)C]);  // floats per cell, all candidates
-            const long long cells_pad = ((long long)a.cells + 63) / 64 * 64;
-            // The budget: "opt_traj_mb", but never more than half of what the device has free right now (other ranks may share
-            // it; the store that is resident already counts as free) -- and when even that cannot be had, chunks of half the
-            // cells, down to one wave's worth, before giving up (a hard error where round 2's forward tangents ran)
-            long long budget = std::max<long long>(c->opt_traj_mb, 1) << 20;
-            {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                    const long long avail = (long long)free_b + (long long)(c->d_traj.n * sizeof(float));
-                    budget = std::min<long long>(budget, std::max<long long>(avail / 2, 64ll << 20));
-                } else {
-                    (void)hipGetLastError();
-                }
-            }
-            chunk_cells = std::min<long long>(cells_pad, std::max<long long>(64, budget / (4 * per_cell) / 64 * 64));
-            while (c->d_traj.ensure((size_t)(chunk_cells * per_cell)) != D2D_OK) {
-                (void)hipGetLastError();
-                if (chunk_cells <= 64) return fail(D2D_ERR_HIP, "the solver's trajectory store does not fit the device even for 64 cells (%lld floats per cell)", per_cell);
-                chunk_cells = std::max<long long>(64, chunk_cells / 2 / 64 * 64);
-            }
-            if ((rc = c->d_traj_off.ensure((size_t)C + 1))) return rc;
-            HIP_TRY(hipMemcpyAsync(c->d_traj_off.p, off.data(), ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));  // (the host vector goes out of scope)
-            ra.g = g;
-            ra.traj = c->d_traj.p;
-            ra.traj_off = c->d_traj_off.p;
-            ra.total_blocks = blocks;
-        }
-        if (c->time_kernel) HIP_TRY(hipEventRecord(c->evk0, c->stream));
-        if (c->opt_grad_mode == 0) {
-            for (long long cell0 = 0; cell0 < (long long)a.cells; cell0 += chunk_cells) {
-                ra.cell0 = (long)cell0;
-                ra.chunk_cells = (long)std::min<long long>(chunk_cells, (long long)a.cells - cell0);
-                ra.stride = (long)((ra.chunk_cells + 63) / 64 * 64);
-                for (int64_t c0 = 0; c0 < C;) {  // one launch per order: a contiguous range of the enumeration
-                    int64_t c1 = c0 + 1;
-                    while (c1 < C && order[(size_t)c1] == order[(size_t)c0]) ++c1;
-                    HIP_TRY(d2d::launch_opt_rev(order[(size_t)c0], ra, (int)c0, dim3((unsigned)(ra.stride / 64), (unsigned)(c1 - c0)),
-                                                (size_t)n_elem * sizeof(float), c->stream));
-                    c0 = c1;
-                }
-            }
-        } else {
-            HIP_TRY(d2d::launch_opt_grad(g, dim3(blocks, (unsigned)C), (size_t)n_elem * sizeof(float), c->stream));
-        }
-        if (c->time_kernel) {
-            HIP_TRY(hipEventRecord(c->evk1, c->stream));
-            c->have_kernel_time = true;
-        }
-        HIP_TRY(d2d::launch_opt_grad_reduce(c->d_contrib.p, c->d_gcontrib.p, (int)C, a.cells, c->d_out.p, c->d_grad.p, p->out_mode, c->stream));
-        if (grad_mode == 2) {
-            if ((rc = join_comm(c, 2))) return rc;  // the previous step's all-reduce has finished with d_vjp
-            // a VJP accumulated over several transmitters (D2D_OUT_ADD) must come from sweeps of one kind (the image-method
-            // sweeps have no phi part) and must still be this rank's own partial sum
-            const int accumulate = (p->out_mode == D2D_OUT_ADD && c->have_vjp) ? 1 : 0;
-            c->vjp_reduced = false;
-            hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)n_elem), dim3(256), 0, c->stream, c->d_partial.p, (long)rows, n_elem,
-                               c->d_vjp.p, accumulate);
-            HIP_TRY(hipGetLastError());
-            c->have_vjp = true;
+    s.blocks = (unsigned)((a.cells + 63) / 64);
+    s.n_elem = 5 * c->N + 2;
+    return D2D_OK;
+}
+
+// no candidate at all (order 2 in a scene of one object): the map, its gradient and the scene VJP are zero -- the
+// reference's loop over no candidates (scene.py:1892-1918); found by scripts/fuzz_opt.py
+static int opt_grad_zero(d2d_ctx* c, const OptSweep& s) {
+    const d2d_params* p = s.p;
+    int rc;
+    if (p->out_mode == D2D_OUT_ADD && !c->have_grad) return fail(D2D_ERR_STATE, "D2D_OUT_ADD needs a previous value+grad sweep on this grid");
+    if ((rc = c->d_grad.ensure(2 * (size_t)s.a.cells))) return rc;
+    c->have_grad = true;
+    HIP_TRY(d2d::launch_opt_grad_reduce(nullptr, nullptr, 0, s.a.cells, c->d_out.p, c->d_grad.p, p->out_mode, c->stream));
+    if (s.grad_mode == 2) {
+        if ((rc = c->d_vjp.ensure((size_t)s.n_elem))) return rc;
+        if ((rc = join_comm(c, 2))) return rc;
+        if (!(p->out_mode == D2D_OUT_ADD && c->have_vjp)) {
+            HIP_TRY(hipMemsetAsync(c->d_vjp.p, 0, (size_t)s.n_elem * sizeof(double), c->stream));
             c->vjp_has_phi = true;
+            c->vjp_reduced = false;
         }
+        c->have_vjp = true;
+    }
+    return D2D_OK;
+}
+
+// the D2D_OUT_ADD state checks; per-candidate scratch (value, per-cell gradient, VJP partial sums), reduced in candidate order
+static int opt_grad_buffers(d2d_ctx* c, OptSweep& s) {
+    const d2d_params* p = s.p;
+    int rc;
+    if (p->out_mode == D2D_OUT_ADD && !c->have_grad) return fail(D2D_ERR_STATE, "D2D_OUT_ADD needs a previous value+grad sweep on this grid");
+    if (s.grad_mode == 2 && p->out_mode == D2D_OUT_ADD && c->have_vjp) {
+        if (!c->vjp_has_phi)
+            return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP comes from an ImagePath sweep; a MinPath / FermatPath sweep cannot be added to it");
+        if (c->vjp_reduced)
+            return fail(D2D_ERR_STATE, "D2D_OUT_ADD: the resident scene VJP has been all-reduced over ranks; fetch it, then start a new sum (D2D_OUT_OVERWRITE)");
+    }
+    const size_t C = (size_t)s.C, cells = (size_t)s.a.cells;
+    if ((rc = c->d_contrib.ensure(C * cells))) return rc;
+    if ((rc = c->d_gcontrib.ensure(2 * C * cells))) return rc;
+    if ((rc = c->d_grad.ensure(2 * cells))) return rc;
+    d2d::OptGradArgs& g = s.g;
+    memset(&g, 0, sizeof g);
+    g.s = s.a;
+    g.patch = p->patch;
+    g.cot = c->have_cot ? c->d_cot.p : nullptr;
+    g.contrib = c->d_contrib.p;
+    g.gcontrib = c->d_gcontrib.p;
+    g.partial = nullptr;
+    if (s.grad_mode == 2) {
+        if ((rc = c->d_partial.ensure(C * s.blocks * (size_t)s.n_elem))) return rc;
+        if ((rc = c->d_vjp.ensure((size_t)s.n_elem))) return rc;
+        g.partial = c->d_partial.p;
+        if (p->out_mode == D2D_OUT_OVERWRITE) c->have_vjp = false;
+    }
+    c->have_grad = true;
+    return D2D_OK;
+}
+
+// reverse mode: the solver's trajectories go through HBM, in chunks of cells (d2d_host::opt_chunk_cells); when even the
+// first chunk cannot be had, chunks of half the cells, down to one wave's worth, before giving up
+static int opt_traj_store(d2d_ctx* c, OptSweep& s) {
+    const int64_t C = s.C;
+    std::vector<long long> off((size_t)C + 1, 0);
+    for (int64_t i = 0; i < C; ++i) {
+        int nu = 0;
+        for (int q = 0; q < s.order[(size_t)i]; ++q) nu += c->kind[s.cand[(size_t)i * D2D_MAX_ORDER + q]] != D2D_VERTEX ? 1 : 0;
+        off[(size_t)i + 1] = off[(size_t)i] + (long long)d2d::traj_floats_per_step(s.a.A.sgd != 0) * s.p->steps * nu;
+    }
+    const long long per_cell = std::max<long long>(1, off[(size_t)C]);  // floats per cell, all candidates
+    size_t free_b = 0, total_b = 0;
+    const bool mem_known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    if (!mem_known) (void)hipGetLastError();
+    long long& chunk_cells = s.chunk_cells;
+    chunk_cells = d2d_host::opt_chunk_cells(s.a.cells, per_cell, c->opt_traj_mb, mem_known, (long long)free_b, (long long)(c->d_traj.n * sizeof(float)));
+    while (c->d_traj.ensure((size_t)(chunk_cells * per_cell)) != D2D_OK) {
+        (void)hipGetLastError();
+        if (chunk_cells <= 64) return fail(D2D_ERR_HIP, "the solver's trajectory store does not fit the device even for 64 cells (%lld floats per cell)", per_cell);
+        chunk_cells = std::max<long long>(64, chunk_cells / 2 / 64 * 64);
+    }
+    int rc;
+    if ((rc = c->d_traj_off.ensure((size_t)C + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_traj_off.p, off.data(), ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the host vector goes out of scope)
+    d2d::OptRevArgs& ra = s.ra;
+    memset(&ra, 0, sizeof ra);
+    ra.g = s.g;
+    ra.traj = c->d_traj.p;
+    ra.traj_off = c->d_traj_off.p;
+    ra.total_blocks = s.blocks;
+    return D2D_OK;
+}
+
+// the value+grad kernels (reverse mode: chunk x order launches), then the reduction of values and per-cell gradients
+static int opt_grad_launch(d2d_ctx* c, OptSweep& s) {
+    const size_t lds = (size_t)s.n_elem * sizeof(float);
+    if (c->time_kernel) HIP_TRY(hipEventRecord(c->evk0, c->stream));
+    if (c->opt_grad_mode == 0) {
+        d2d::OptRevArgs& ra = s.ra;
+        for (long long cell0 = 0; cell0 < (long long)s.a.cells; cell0 += s.chunk_cells) {
+            ra.cell0 = (long)cell0;
+            ra.chunk_cells = (long)std::min<long long>(s.chunk_cells, (long long)s.a.cells - cell0);
+            ra.stride = (long)((ra.chunk_cells + 63) / 64 * 64);
+            for (int64_t c0 = 0; c0 < s.C;) {  // one launch per order: a contiguous range of the enumeration
+                int64_t c1 = c0 + 1;
+                while (c1 < s.C && s.order[(size_t)c1] == s.order[(size_t)c0]) ++c1;
+                HIP_TRY(d2d::launch_opt_rev(s.order[(size_t)c0], ra, (int)c0, dim3((unsigned)(ra.stride / 64), (unsigned)(c1 - c0)), lds, c->stream));
+                c0 = c1;
+            }
+        }
+    } else {
+        HIP_TRY(d2d::launch_opt_grad(s.g, dim3(s.blocks, (unsigned)s.C), lds, c->stream));
+    }
+    if (c->time_kernel) {
+        HIP_TRY(hipEventRecord(c->evk1, c->stream));
+        c->have_kernel_time = true;
+    }
+    HIP_TRY(d2d::launch_opt_grad_reduce(c->d_contrib.p, c->d_gcontrib.p, (int)s.C, s.a.cells, c->d_out.p, c->d_grad.p, s.p->out_mode, c->stream));
+    return D2D_OK;
+}
+
+// the scene VJP: the workgroups' partial sums, reduced in a fixed order
+static int opt_vjp_reduce(d2d_ctx* c, const OptSweep& s) {
+    if (int rc = join_comm(c, 2)) return rc;  // the previous step's all-reduce has finished with d_vjp
+    // a VJP accumulated over several transmitters (D2D_OUT_ADD) must come from sweeps of one kind (the image-method
+    // sweeps have no phi part) and must still be this rank's own partial sum
+    const int accumulate = (s.p->out_mode == D2D_OUT_ADD && c->have_vjp) ? 1 : 0;
+    c->vjp_reduced = false;
+    hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)s.n_elem), dim3(256), 0, c->stream, c->d_partial.p, (long)((size_t)s.C * s.blocks),
+                       s.n_elem, c->d_vjp.p, accumulate);
+    HIP_TRY(hipGetLastError());
+    c->have_vjp = true;
+    c->vjp_has_phi = true;
+    return D2D_OK;
+}
+
+// values only: the candidates side by side while the contributions fit a modest scratch buffer (and the grid's y dimension)
+static int opt_value_launch(d2d_ctx* c, const OptSweep& s) {
+    const d2d::OptSweepArgs& a = s.a;
+    const int64_t C = s.C;
+    const bool side_by_side = c->opt_parallel && C >= 2 && C <= 65535 && (long long)C * a.cells <= (1ll << 26);
+    if (!side_by_side) {
+        HIP_TRY(d2d::launch_opt(a, dim3(s.blocks), nullptr, c->stream));
         return D2D_OK;
     }
-    // candidates side by side while the contributions fit a modest scratch buffer (and the grid's y dimension)
-    const bool side_by_side = c->opt_parallel && C >= 2 && C <= 65535 && (long long)C * a.cells <= (1ll << 26);
-    if (side_by_side) {
-        if ((rc = c->d_contrib.ensure((size_t)C * (size_t)a.cells))) return rc;
-        if (a.A.sgd) hipLaunchKernelGGL(d2d::power_opt_cand_kernel<true>, dim3(blocks, (unsigned)C), dim3(64), 0, c->stream, a, c->d_contrib.p);
-        else hipLaunchKernelGGL(d2d::power_opt_cand_kernel<false>, dim3(blocks, (unsigned)C), dim3(64), 0, c->stream, a, c->d_contrib.p);
-        hipLaunchKernelGGL(d2d::opt_reduce_kernel, dim3((unsigned)((a.cells + 255) / 256)), dim3(256), 0, c->stream, c->d_contrib.p,
-                           (int)C, a.cells, c->d_out.p, p->out_mode);
-    } else {
-        if (a.A.sgd) hipLaunchKernelGGL(d2d::power_opt_kernel<true>, dim3(blocks), dim3(64), 0, c->stream, a);
-        else hipLaunchKernelGGL(d2d::power_opt_kernel<false>, dim3(blocks), dim3(64), 0, c->stream, a);
-    }
+    if (int rc = c->d_contrib.ensure((size_t)C * (size_t)a.cells)) return rc;
+    HIP_TRY(d2d::launch_opt(a, dim3(s.blocks, (unsigned)C), c->d_contrib.p, c->stream));
+    hipLaunchKernelGGL(d2d::opt_reduce_kernel, dim3((unsigned)((a.cells + 255) / 256)), dim3(256), 0, c->stream, c->d_contrib.p, (int)C, a.cells,
+                       c->d_out.p, s.p->out_mode);
     HIP_TRY(hipGetLastError());
     return D2D_OK;
 }
 
-}  // extern "C"
-
-namespace {
+static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, int grad_mode) {
+    OptSweep s;
+    s.p = p;
+    s.tx = tx;
+    s.grad_mode = grad_mode;
+    int rc;
+    if ((rc = set_device(c)) || (rc = upload_occl(c, p->patch)) || (rc = opt_candidates(c, s)) || (rc = opt_args(c, s))) return rc;
+    if (!grad_mode) return opt_value_launch(c, s);
+    if (s.C > 65535 || (long long)s.C * s.a.cells > (1ll << 28))
+        return fail(D2D_ERR_UNSUPPORTED, "%lld candidates x %lld cells exceed the gradient sweep's scratch (2^28 contributions)",
+                    (long long)s.C, (long long)s.a.cells);
+    if (s.C == 0) return opt_grad_zero(c, s);
+    if ((rc = opt_grad_buffers(c, s))) return rc;
+    if (c->opt_grad_mode == 0 && (rc = opt_traj_store(c, s))) return rc;
+    if ((rc = opt_grad_launch(c, s))) return rc;
+    return grad_mode == 2 ? opt_vjp_reduce(c, s) : D2D_OK;
+}
 
 // ---- ImagePath sweeps: sweep_launch and its steps ------------------------------------------------------------------
 // What the steps of one launch share.  sweep_launch sets the inputs; take_prep_set and sweep_args the rest.
@@ -2431,7 +2480,7 @@ int d2d_trace_paths(d2d_ctx* c, const d2d_params* p, const float* tx, const floa
     a.T = obj_tables(c);
     a.solver = p->solver;
     if (opt) {
-        if ((rc = adam_cfg(c, p, &a.A))) return rc;
+        if ((rc = opt_cfg(c, p, &a.A))) return rc;
         const size_t nth = (size_t)C * (size_t)a.A.many * D2D_MAX_ORDER;
         if ((rc = c->d_theta0.ensure(nth + 1))) return rc;
         if (theta0) HIP_TRY(hipMemcpyAsync(c->d_theta0.p, theta0, nth * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -2452,16 +2501,8 @@ int d2d_trace_paths(d2d_ctx* c, const d2d_params* p, const float* tx, const floa
     a.on = c->d_ton.p;
     a.hit = c->d_thit.p;
     a.length = c->d_tlen.p;
-    a.mode = p->approx ? (p->act == D2D_ACT_HARD_SIGMOID ? d2d::MODE_HSIG : d2d::MODE_SIG) : d2d::MODE_HARD;
-    a.alpha = p->alpha;
-    a.tol = p->tol;
-    a.seg_lo = -p->seg_tol;
-    a.seg_hi = 1.0f + p->seg_tol;
-    const unsigned blocks = (unsigned)((n + 63) / 64);
-    // (the image-method and validation paths never reach the solver: the Adam instance serves them)
-    if (opt && a.A.sgd) hipLaunchKernelGGL(d2d::trace_kernel<true>, dim3(blocks), dim3(64), 0, c->stream, a);
-    else hipLaunchKernelGGL(d2d::trace_kernel<false>, dim3(blocks), dim3(64), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
+    set_validity(a, p);
+    HIP_TRY(d2d::launch_trace(a, dim3((unsigned)((n + 63) / 64)), c->stream));
     HIP_TRY(hipMemcpyAsync(xys, c->d_txys.p, n * NP * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(loss, c->d_tloss.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(valid, c->d_tvalid.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

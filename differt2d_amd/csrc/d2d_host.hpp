@@ -6,6 +6,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <string>
@@ -285,6 +286,20 @@ inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad, bool sig
     t.degenerate_invalid = !p.approx ? (p.tol <= 0.5f)
                                      : (t.mode == SWEEP_HSIG ? ((double)p.alpha * x_deg + 3.0 <= -1e-3) : ((double)p.alpha * x_deg <= -89.5));
     return t;
+}
+
+// ---- trajectory store of the reverse-mode MinPath / FermatPath sweep (d2d.hip: opt_traj_store) ----------------------
+// Cells per chunk of the grid's `cells` for a store of floats_per_cell floats per cell (all candidates; taken as at least 1):
+// the budget is traj_mb MiB ("opt_traj_mb", at least 1), but never more than half of what the device has free (free_bytes,
+// plus resident_bytes: the store that is resident already counts as free) -- nor less than 64 MiB by that rule -- when
+// mem_known (hipMemGetInfo answered).  Whole waves of 64 cells, at least one, at most the grid rounded up to whole waves.
+inline long long opt_chunk_cells(long long cells, long long floats_per_cell, long long traj_mb, bool mem_known, long long free_bytes,
+                                 long long resident_bytes) {
+    const long long per_cell = std::max<long long>(1, floats_per_cell);
+    const long long cells_pad = (cells + 63) / 64 * 64;
+    long long budget = std::max<long long>(traj_mb, 1) << 20;
+    if (mem_known) budget = std::min<long long>(budget, std::max<long long>((free_bytes + resident_bytes) / 2, 64ll << 20));
+    return std::min<long long>(cells_pad, std::max<long long>(64, budget / (4 * per_cell) / 64 * 64));
 }
 
 // ---- region candidate lists (region_list_kernel / region_refine_kernel) ----------------------------------------------

@@ -3999,9 +3999,9 @@ __device__ __forceinline__ void image_solve(const ObjTables& T, int k, const int
 // geometry.py:1117-1288, optimize.py:44-97 with optax.adam(0.1): mu = b1 mu + (1-b1) g; nu = b2 nu + (1-b2) g^2;
 // x += -lr * (mu / (1 - b1^t)) / (sqrt(nu / (1 - b2^t)) + eps).  The gradient of the objective w.r.t. theta is
 // derived by hand (reverse mode through parametric_to_cartesian and evaluate_cartesian / path_length).
-// The solver loops are templates on the optimiser (bool SGD): the Adam instances are the code above, untouched; the SGD
-// instances run sgd_step (below) and serve plain SGD, momentum and Nesterov momentum through wave-uniform flags.
-struct AdamCfg {  // the optimiser's configuration (Adam's fields, and SGD's)
+// The solver loop is a template on the optimiser (bool SGD): the SGD instances run sgd_step (below) and serve plain SGD,
+// momentum and Nesterov momentum through wave-uniform flags.
+struct OptCfg {  // the optimiser's configuration (Adam's fields, and SGD's)
     int solver;  // D2D_SOLVER_MINPATH or D2D_SOLVER_FERMAT
     int steps;
     int many;    // number of random starts; the start whose recorded loss is smallest wins (optimize.py:136-182)
@@ -4015,7 +4015,7 @@ struct AdamCfg {  // the optimiser's configuration (Adam's fields, and SGD's)
     float decay;       // SGD with momentum: the trace's decay, rounded to fp32 (a weakly typed Python float)
 };
 
-// Floats per step and unknown of the trajectory the reverse sweep records (d2d_optrev.hpp: opt_run_t): Adam's
+// Floats per step and unknown of the trajectory the reverse sweep records (opt_run<true, SGD>): Adam's
 // (theta_t, g_t, mu_{t+1}, nu_{t+1}); SGD's adjoint is linear in its state and needs theta_t alone.
 constexpr int traj_floats_per_step(bool sgd) { return sgd ? 1 : 4; }
 
@@ -4024,10 +4024,27 @@ constexpr int traj_floats_per_step(bool sgd) { return sgd ? 1 : 4; }
 // Returns u (the update before scale(-lr)) and advances the trace m; momentum=None returns g and leaves m alone.  V is
 // float or a Dual (the forward-tangent kernel).
 template <class V>
-__device__ __forceinline__ V sgd_step(const AdamCfg& A, const V& g, V& m) {
+__device__ __forceinline__ V sgd_step(const OptCfg& A, const V& g, V& m) {
     if (!A.momentum) return g;
     m = g + A.decay * m;
     return A.nesterov ? g + A.decay * m : m;
+}
+
+// sqrt of the optimiser's value type (d2d_optgrad.hpp: the overload on Dual<B>)
+__device__ __forceinline__ float vsqrt(float x) { return sqrtf(x); }
+
+// One step of one unknown: theta and the state (mu: Adam's first moment or SGD's trace; nu: Adam's second moment) from the
+// gradient g; c1, c2: Adam's bias corrections 1 - b1^t, 1 - b2^t.  V is float or a Dual (the forward-tangent kernel).
+template <bool SGD, class V>
+__device__ __forceinline__ void opt_step(const OptCfg& A, float c1, float c2, const V& g, V& th, V& mu, V& nu) {
+    if constexpr (SGD) {
+        th = th + (-A.lr) * sgd_step(A, g, mu);
+    } else {
+        mu = A.b1 * mu + A.omb1 * g;
+        nu = A.b2 * nu + A.omb2 * (g * g);
+        const V mh = mu / c1, nh = nu / c2;
+        th = th + (-A.lr) * (mh / (vsqrt(nh) + A.eps));
+    }
 }
 
 __device__ __forceinline__ void theta_to_points(const ObjTables& T, int k, const int (&cd)[D2D_MAX_ORDER],
@@ -4155,11 +4172,15 @@ __device__ __forceinline__ float objective_grad(const ObjTables& T, int solver, 
     return loss;
 }
 
-// One Adam (SGD) run from theta0: final theta in `th`, returns the objective recorded at the last step (before the last update).
-template <bool SGD>
-__device__ __forceinline__ float opt_run(const ObjTables& T, const AdamCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
+// One Adam (SGD) run from theta0: final theta in `th`, returns the objective recorded at the last step (before the last
+// update).  STORE: records the trajectory the reverse sweep (d2d_optrev.hpp) walks back; tr is this lane's slot of the
+// candidate's trajectory, entry (t, q, which) at tr[((t * nu + q) * W + which) * stride] with W = traj_floats_per_step(SGD).
+// Adam: which = 0 theta_t, 1 g_t, 2 mu_{t+1}, 3 nu_{t+1}; SGD: theta_t only.
+template <bool STORE, bool SGD>
+__device__ __forceinline__ float opt_run(const ObjTables& T, const OptCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
                                          const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
-                                         float (&th)[D2D_MAX_ORDER]) {
+                                         float (&th)[D2D_MAX_ORDER], float* __restrict__ tr = nullptr, long stride = 0) {
+    constexpr int W = traj_floats_per_step(SGD);
     float px[NP], py[NP];
     float mu[D2D_MAX_ORDER], nu[D2D_MAX_ORDER], g[D2D_MAX_ORDER];
     int nu_ = 0;
@@ -4173,19 +4194,17 @@ __device__ __forceinline__ float opt_run(const ObjTables& T, const AdamCfg& A, i
     for (int t = 0; t < A.steps; ++t) {
         theta_to_points(T, k, cd, th, txx, txy, rxx, rxy, px, py);
         last = objective_grad(T, A.solver, k, cd, px, py, g);
-        if constexpr (SGD) {
+        const float c1 = SGD ? 1.0f : A.bc1[t], c2 = SGD ? 1.0f : A.bc2[t];
 #pragma unroll
-            for (int q = 0; q < D2D_MAX_ORDER; ++q)
-                if (q < nu_) th[q] = th[q] + (-A.lr) * sgd_step(A, g[q], mu[q]);
-        } else {
-            const float c1 = A.bc1[t], c2 = A.bc2[t];
-#pragma unroll
-            for (int q = 0; q < D2D_MAX_ORDER; ++q) {
-                if (q < nu_) {
-                    mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
-                    nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
-                    float mh = mu[q] / c1, nh = nu[q] / c2;
-                    th[q] = th[q] + (-A.lr) * (mh / (sqrtf(nh) + A.eps));
+        for (int q = 0; q < D2D_MAX_ORDER; ++q) {
+            if (q < nu_) {
+                float* e = STORE ? tr + (long)(t * nu_ + q) * W * stride : nullptr;
+                if (STORE) e[0] = th[q];
+                if (STORE && !SGD) e[stride] = g[q];
+                opt_step<SGD>(A, c1, c2, g[q], th[q], mu[q], nu[q]);
+                if (STORE && !SGD) {
+                    e[2 * stride] = mu[q];
+                    e[3 * stride] = nu[q];
                 }
             }
         }
@@ -4193,28 +4212,72 @@ __device__ __forceinline__ float opt_run(const ObjTables& T, const AdamCfg& A, i
     return last;
 }
 
-// Returns the path points and the loss the reference attaches to the path. theta0: [many][D2D_MAX_ORDER].
+// Runs every start of theta0 ([many][D2D_MAX_ORDER]) and picks the winner as jnp.argmin does (optimize.py:136-182): the
+// first minimum of the recorded losses wins, a NaN loss wins.  Its theta in `best`, its index in best_m; returns its loss.
 template <bool SGD>
-__device__ __forceinline__ float opt_solve(const ObjTables& T, const AdamCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
-                                           const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
-                                           float (&px)[NP], float (&py)[NP]) {
+__device__ __forceinline__ float opt_best(const ObjTables& T, const OptCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
+                                          const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
+                                          float (&best_th)[D2D_MAX_ORDER], int& best_m) {
     float best[D2D_MAX_ORDER], th[D2D_MAX_ORDER];
-    float best_loss = opt_run<SGD>(T, A, k, cd, theta0, txx, txy, rxx, rxy, best);
-    for (int m = 1; m < A.many; ++m) {  // jnp.argmin: the first minimum wins; NaN losses win like in jnp.argmin
-        float l = opt_run<SGD>(T, A, k, cd, theta0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
+    float best_loss = opt_run<false, SGD>(T, A, k, cd, theta0, txx, txy, rxx, rxy, best);
+    int bm = 0;
+    for (int m = 1; m < A.many; ++m) {
+        float l = opt_run<false, SGD>(T, A, k, cd, theta0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
         const bool better = (l < best_loss) || (l != l && best_loss == best_loss);
         best_loss = better ? l : best_loss;
+        bm = better ? m : bm;
 #pragma unroll
         for (int q = 0; q < D2D_MAX_ORDER; ++q) best[q] = better ? th[q] : best[q];
     }
+#pragma unroll
+    for (int q = 0; q < D2D_MAX_ORDER; ++q) best_th[q] = best[q];
+    best_m = bm;
+    return best_loss;
+}
+
+// Returns the path points and the loss the reference attaches to the path. theta0: [many][D2D_MAX_ORDER].
+template <bool SGD>
+__device__ __forceinline__ float opt_solve(const ObjTables& T, const OptCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
+                                           const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
+                                           float (&px)[NP], float (&py)[NP]) {
+    float best[D2D_MAX_ORDER];
+    int best_m;
+    const float best_loss = opt_best<SGD>(T, A, k, cd, theta0, txx, txy, rxx, rxy, best, best_m);
     theta_to_points(T, k, cd, best, txx, txy, rxx, rxy, px, py);
     if (A.solver == D2D_SOLVER_FERMAT) return interaction_loss(T, k, cd, px, py);  // geometry.py:1204
     return best_loss;                                                               // geometry.py:1284-1288
 }
 
+// fun (utils.py:17-54, geometry.py:811-819) of a path of order k and length r: received power (fnum[k]: its numerator),
+// length squared, length, else 1.  V is float or a Dual.
+template <class V>
+__device__ __forceinline__ V opt_fun(int fun_id, const float (&fnum)[D2D_MAX_ORDER + 1], float h2, int k, const V& r) {
+    V f;
+    if (fun_id == D2D_FUN_RECEIVED_POWER) {
+        float num = fnum[0];
+#pragma unroll
+        for (int q = 1; q <= D2D_MAX_ORDER; ++q)
+            if (q == k) num = fnum[q];
+        f = num / (h2 + r * r);
+    } else if (fun_id == D2D_FUN_LENGTH_SQUARED) f = r * r;
+    else if (fun_id == D2D_FUN_LENGTH) f = r;
+    else f = V{} + 1.0f;  // (a Dual: a constant)
+    return f;
+}
+// Its adjoint w.r.t. r given f = opt_fun(...) and fbar = d / d f (0 where fun is a constant)
+__device__ __forceinline__ float opt_fun_rbar(int fun_id, float h2, float r, float f, float fbar) {
+    if (fun_id == D2D_FUN_RECEIVED_POWER) {
+        const float Dn = h2 + r * r;
+        return -(fbar * (f / Dn)) * (2.0f * r);
+    }
+    if (fun_id == D2D_FUN_LENGTH_SQUARED) return fbar * (2.0f * r);
+    if (fun_id == D2D_FUN_LENGTH) return fbar;
+    return 0.0f;
+}
+
 struct TraceArgs {
     ObjTables T;
-    AdamCfg A;
+    OptCfg A;
     int solver;
     const int* __restrict__ cand;   // [C][D2D_MAX_ORDER]
     const int* __restrict__ order;  // [C]
@@ -4282,13 +4345,19 @@ __global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
     if (a.length) a.length[tid] = r;
 }
 
+// the configured optimiser's instance (A zeroed, for an ImagePath trace: the Adam instance, which never runs the solver)
+static hipError_t launch_trace(const TraceArgs& a, dim3 grid, hipStream_t stream) {
+    if (a.A.sgd) hipLaunchKernelGGL(trace_kernel<true>, grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(trace_kernel<false>, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
 #endif  // D2D_AUX_KERNELS
 
 // Grid sweep for the optimiser-based solvers: one RX cell per lane, candidates walked in the reference's order
 // (scene.py:1892-1918); theta0 is per candidate and shared by every cell, as in the reference (scene.py:1887-1890).
 struct OptSweepArgs {
     ObjTables T;
-    AdamCfg A;
+    OptCfg A;
     const int* __restrict__ cand;      // [C][D2D_MAX_ORDER]   (explicit list: these sweeps have few candidates)
     const int* __restrict__ order;     // [C]
     const float* __restrict__ theta0;  // [C][D2D_MAX_ORDER]
@@ -4325,17 +4394,7 @@ __device__ __forceinline__ float opt_contribution(const OptSweepArgs& a, int c, 
     float on, hit, valid;
     literal_validity(a.T, L, k, cd, px, py, loss, a.tol, a.seg_lo, a.seg_hi, on, hit, valid);
     const float r = literal_length(k, px, py);
-    float f;
-    if (a.fun_id == D2D_FUN_RECEIVED_POWER) {
-        float num = a.fnum[0];
-#pragma unroll
-        for (int q = 1; q <= D2D_MAX_ORDER; ++q)
-            if (q == k) num = a.fnum[q];
-        f = num / (a.h2 + r * r);
-    } else if (a.fun_id == D2D_FUN_LENGTH_SQUARED) f = r * r;
-    else if (a.fun_id == D2D_FUN_LENGTH) f = r;
-    else f = 1.0f;
-    return valid * f;
+    return valid * opt_fun(a.fun_id, a.fnum, a.h2, k, r);
 }
 
 #ifdef D2D_AUX_KERNELS
@@ -4365,6 +4424,15 @@ __global__ void __launch_bounds__(64) power_opt_cand_kernel(OptSweepArgs a, floa
     const float txx = a.grid_is_tx ? gx_ : a.txx, txy = a.grid_is_tx ? gy_ : a.txy;
     const float rxx = a.grid_is_tx ? a.txx : gx_, rxy = a.grid_is_tx ? a.txy : gy_;
     contrib[(long)c * a.cells + idx] = opt_contribution<SGD>(a, c, txx, txy, rxx, rxy);
+}
+
+// the instance of the configured optimiser: power_opt_cand_kernel given contrib, else power_opt_kernel
+static hipError_t launch_opt(const OptSweepArgs& a, dim3 grid, float* contrib, hipStream_t stream) {
+    if (contrib && a.A.sgd) hipLaunchKernelGGL(power_opt_cand_kernel<true>, grid, dim3(64), 0, stream, a, contrib);
+    else if (contrib) hipLaunchKernelGGL(power_opt_cand_kernel<false>, grid, dim3(64), 0, stream, a, contrib);
+    else if (a.A.sgd) hipLaunchKernelGGL(power_opt_kernel<true>, grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(power_opt_kernel<false>, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
 }
 
 __global__ void __launch_bounds__(256) opt_reduce_kernel(const float* __restrict__ contrib, int C, long cells, float* __restrict__ out,

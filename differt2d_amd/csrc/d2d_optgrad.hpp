@@ -133,6 +133,7 @@ D2D_DUAL_FN Dual<B> dsqrt(const Dual<B>& a) {
     for (int i = 0; i < B; ++i) r.d[i] = a.d[i] * h;
     return r;
 }
+D2D_DUAL_FN Dual<B> vsqrt(const Dual<B>& a) { return dsqrt(a); }  // opt_step's sqrt (d2d_kernels.hpp: the float overload)
 // jnp.where(c, a, b)
 D2D_DUAL_FN Dual<B> dwhere(bool c, const Dual<B>& a, const Dual<B>& b) { return c ? a : b; }
 // jnp.minimum / jnp.maximum: NaN-propagating values; tangent of the selected argument, ties split evenly
@@ -412,7 +413,7 @@ __device__ __forceinline__ Dual<B> dobjective_grad(int solver, const DObj<B> (&o
 
 // One Adam (SGD) run (the Dual of opt_run): final theta in th[], returns the objective recorded at the last step.
 template <int K, int B, bool SGD>
-__device__ __forceinline__ Dual<B> dopt_run(const AdamCfg& A, const DObj<B> (&ob)[K > 0 ? K : 1], const float* __restrict__ theta0,
+__device__ __forceinline__ Dual<B> dopt_run(const OptCfg& A, const DObj<B> (&ob)[K > 0 ? K : 1], const float* __restrict__ theta0,
                                             const Dual<B>& ax_, const Dual<B>& ay_, const Dual<B>& bx_, const Dual<B>& by_,
                                             Dual<B> (&th)[K > 0 ? K : 1]) {
     constexpr int KK = K > 0 ? K : 1;
@@ -429,22 +430,10 @@ __device__ __forceinline__ Dual<B> dopt_run(const AdamCfg& A, const DObj<B> (&ob
     for (int t = 0; t < A.steps; ++t) {
         dpoints<K, B>(ob, th, ax_, ay_, bx_, by_, px, py);
         last = dobjective_grad<K, B>(A.solver, ob, px, py, g);
-        if constexpr (SGD) {
+        const float c1 = SGD ? 1.0f : A.bc1[t], c2 = SGD ? 1.0f : A.bc2[t];
 #pragma unroll
-            for (int q = 0; q < KK; ++q)
-                if (q < nu_) th[q] = th[q] + (-A.lr) * sgd_step(A, g[q], mu[q]);
-        } else {
-            const float c1 = A.bc1[t], c2 = A.bc2[t];
-#pragma unroll
-            for (int q = 0; q < KK; ++q) {
-                if (q < nu_) {
-                    mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
-                    nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
-                    const Dual<B> mh = mu[q] / c1, nh = nu[q] / c2;
-                    th[q] = th[q] + (-A.lr) * (mh / (dsqrt(nh) + A.eps));
-                }
-            }
-        }
+        for (int q = 0; q < KK; ++q)
+            if (q < nu_) opt_step<SGD>(A, c1, c2, g[q], th[q], mu[q], nu[q]);
     }
     return last;
 }
@@ -465,17 +454,7 @@ __device__ __forceinline__ Dual<B> dcontribution(const OptGradArgs& a, const int
                                                  const int (&gdir)[B]) {
     const OptSweepArgs& s = a.s;
     // fun (utils.py:17-54, geometry.py:811-819)
-    const Dual<B> r = dlength<K, B>(px, py);
-    Dual<B> f;
-    if (s.fun_id == D2D_FUN_RECEIVED_POWER) {
-        float num = s.fnum[0];
-#pragma unroll
-        for (int q = 1; q <= D2D_MAX_ORDER; ++q)
-            if (q == K) num = s.fnum[q];
-        f = num / (s.h2 + r * r);
-    } else if (s.fun_id == D2D_FUN_LENGTH_SQUARED) f = r * r;
-    else if (s.fun_id == D2D_FUN_LENGTH) f = r;
-    else f = dconst<B>(1.0f);
+    const Dual<B> f = opt_fun(s.fun_id, s.fnum, s.h2, K, dlength<K, B>(px, py));
     if (s.mode == MODE_HARD) {
         // jnp.logical_* on booleans: no gradient through validity; valid from the forward float chain
         const Truth L{s.mode, s.alpha};
@@ -549,18 +528,7 @@ __device__ __forceinline__ void opt_grad_candidate(const OptGradArgs& a, int c, 
     int best_m = 0;
     float best_th[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f};
     float best_loss = 0.0f;  // what the winning run recorded at its last step (MinPath's path loss, geometry.py:1284-1288)
-    if (K > 0) {
-        float th[D2D_MAX_ORDER];
-        best_loss = opt_run<SGD>(s.T, s.A, K, cd, th0, txx, txy, rxx, rxy, best_th);
-        for (int m = 1; m < s.A.many; ++m) {
-            const float l = opt_run<SGD>(s.T, s.A, K, cd, th0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th);
-            const bool better = (l < best_loss) || (l != l && best_loss == best_loss);
-            best_loss = better ? l : best_loss;
-            best_m = better ? m : best_m;
-#pragma unroll
-            for (int q = 0; q < D2D_MAX_ORDER; ++q) best_th[q] = better ? th[q] : best_th[q];
-        }
-    }
+    if (K > 0) best_loss = opt_best<SGD>(s.T, s.A, K, cd, th0, txx, txy, rxx, rxy, best_th, best_m);
     // ---- the directions, ordered: cell, fixed point, the candidate's own objects (each once), then the others
     // slot -> global direction; the first n_theta slots move theta
     int objs[KK];

@@ -5,7 +5,7 @@
 // length, :1117-1204) in REVERSE mode: jax.grad of a scan is a backward scan over the stored trajectory.  This file does
 // the same by hand:
 //
-//   forward   the solver's own loop (opt_run_t<true>: the very code of the forward sweep) writes its trajectory
+//   forward   the solver's own loop (opt_run<true>: the very code of the forward sweep) writes its trajectory
 //             (theta_t, g_t, mu_{t+1}, nu_{t+1} per step, 16 bytes per unknown; SGD: theta_t alone, 4 bytes) to HBM, one
 //             (cell, candidate) per lane, lanes of a wave on consecutive addresses;
 //   reverse   the adjoint of valid * fun w.r.t. the final points (hand derived, jnp.minimum / maximum ties split as JAX's
@@ -55,58 +55,6 @@ struct OptRevArgs {
     long stride;                        // chunk_cells rounded up to whole waves: every lane of the launch owns a trajectory slot
     long total_blocks;                  // workgroups per candidate over the WHOLE grid (rows of the VJP partial sums)
 };
-
-// ---- the solver's loop, optionally recording its trajectory (the forward sweep's opt_run is opt_run_t<false>) ---------
-// tr: this lane's slot of the candidate's trajectory; entry (t, q, which) at tr[((t * nu + q) * W + which) * stride] with
-// W = traj_floats_per_step(SGD) (d2d_kernels.hpp).  Adam: which = 0 theta_t, 1 g_t, 2 mu_{t+1}, 3 nu_{t+1}; SGD: theta_t only
-template <bool STORE, bool SGD>
-__device__ __forceinline__ float opt_run_t(const ObjTables& T, const AdamCfg& A, int k, const int (&cd)[D2D_MAX_ORDER],
-                                           const float* __restrict__ theta0, float txx, float txy, float rxx, float rxy,
-                                           float (&th)[D2D_MAX_ORDER], float* __restrict__ tr, long stride) {
-    float px[NP], py[NP];
-    float mu[D2D_MAX_ORDER], nu[D2D_MAX_ORDER], g[D2D_MAX_ORDER];
-    int nu_ = 0;
-#pragma unroll
-    for (int i = 0; i < D2D_MAX_ORDER; ++i) {
-        th[i] = theta0[i];
-        mu[i] = nu[i] = 0.0f;
-        if (i < k && T.kind[cd[i]] != D2D_VERTEX) ++nu_;
-    }
-    float last = 0.0f;
-    for (int t = 0; t < A.steps; ++t) {
-        theta_to_points(T, k, cd, th, txx, txy, rxx, rxy, px, py);
-        last = objective_grad(T, A.solver, k, cd, px, py, g);
-        if constexpr (SGD) {
-#pragma unroll
-            for (int q = 0; q < D2D_MAX_ORDER; ++q) {
-                if (q < nu_) {
-                    if (STORE) tr[(long)(t * nu_ + q) * stride] = th[q];
-                    th[q] = th[q] + (-A.lr) * sgd_step(A, g[q], mu[q]);
-                }
-            }
-            continue;
-        }
-        const float c1 = A.bc1[t], c2 = A.bc2[t];
-#pragma unroll
-        for (int q = 0; q < D2D_MAX_ORDER; ++q) {
-            if (q < nu_) {
-                if (STORE) {
-                    tr[((long)(t * nu_ + q) * 4 + 0) * stride] = th[q];
-                    tr[((long)(t * nu_ + q) * 4 + 1) * stride] = g[q];
-                }
-                mu[q] = A.b1 * mu[q] + A.omb1 * g[q];
-                nu[q] = A.b2 * nu[q] + A.omb2 * (g[q] * g[q]);
-                if (STORE) {
-                    tr[((long)(t * nu_ + q) * 4 + 2) * stride] = mu[q];
-                    tr[((long)(t * nu_ + q) * 4 + 3) * stride] = nu[q];
-                }
-                float mh = mu[q] / c1, nh = nu[q] / c2;
-                th[q] = th[q] + (-A.lr) * (mh / (sqrtf(nh) + A.eps));
-            }
-        }
-    }
-    return last;
-}
 
 // ---- the objective's gradient w.r.t. ALL its inputs, on Dual<1> --------------------------------------------------------
 enum { OBJ_INTERACTION = 0, OBJ_LENGTH = 1 };  // sum of evaluate_cartesian (geometry.py:641-650, 698-711); path_length (:176-203)
@@ -327,7 +275,7 @@ __device__ __forceinline__ float seg_test(int mode, float alpha, float lo, float
 // Returns the contribution itself (the forward sweep's float code on the same final theta: the value map is bit-identical).
 // CUST: the instance that serves a host-evaluated path function (D2D_FUN_CUSTOM; its loads and selects cost the fused
 // functions' instance 3 % at cfg5 when they share one)
-// SGD: the optimiser (d2d_kernels.hpp: sgd_step); else Adam
+// SGD: the optimiser (d2d_kernels.hpp: opt_step); else Adam
 template <int K, bool CUST, bool SGD>
 __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, const int (&cd)[D2D_MAX_ORDER], float cellx, float celly,
                                                    float cot, bool active, long lane_cell, long idx, float& grx, float& gry, float* row) {
@@ -352,17 +300,8 @@ __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, 
     float loss = 0.0f;
     if (K > 0) {
         int best_m = 0;
-        if (s.A.many > 1) {
-            float tmp[D2D_MAX_ORDER];
-            float best_loss = opt_run_t<false, SGD>(T, s.A, K, cd, th0, txx, txy, rxx, rxy, tmp, nullptr, 0);
-            for (int m = 1; m < s.A.many; ++m) {
-                const float l = opt_run_t<false, SGD>(T, s.A, K, cd, th0 + m * D2D_MAX_ORDER, txx, txy, rxx, rxy, tmp, nullptr, 0);
-                const bool better = (l < best_loss) || (l != l && best_loss == best_loss);
-                best_loss = better ? l : best_loss;
-                best_m = better ? m : best_m;
-            }
-        }
-        loss = opt_run_t<true, SGD>(T, s.A, K, cd, th0 + best_m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th, tr, stride);
+        if (s.A.many > 1) opt_best<SGD>(T, s.A, K, cd, th0, txx, txy, rxx, rxy, th, best_m);  // then the winner again, recorded
+        loss = opt_run<true, SGD>(T, s.A, K, cd, th0 + best_m * D2D_MAX_ORDER, txx, txy, rxx, rxy, th, tr, stride);
     }
     float px[NP], py[NP];
     if (K == 0) image_solve(T, 0, cd, txx, txy, rxx, rxy, px, py);
@@ -372,16 +311,8 @@ __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, 
     float on, hit, valid;
     literal_validity(T, L, K, cd, px, py, loss, s.tol, s.seg_lo, s.seg_hi, on, hit, valid);
     const float r = literal_length(K, px, py);
-    float num = s.fnum[0];
-#pragma unroll
-    for (int q = 1; q <= D2D_MAX_ORDER; ++q)
-        if (q == K) num = s.fnum[q];
-    float f;
-    if (s.fun_id == D2D_FUN_RECEIVED_POWER) f = num / (s.h2 + r * r);
-    else if (s.fun_id == D2D_FUN_LENGTH_SQUARED) f = r * r;
-    else if (s.fun_id == D2D_FUN_LENGTH) f = r;
-    else if (CUST && s.fun_id == D2D_FUN_CUSTOM) f = s.cust_f[(long)c * s.cells + idx];  // d2d_set_path_fun_values: the host's fun on the traced path
-    else f = 1.0f;
+    const float f = (CUST && s.fun_id == D2D_FUN_CUSTOM) ? s.cust_f[(long)c * s.cells + idx]  // d2d_set_path_fun_values: the host's fun on the traced path
+                                                         : opt_fun(s.fun_id, s.fnum, s.h2, K, r);
     const float contribution = valid * f;
 
     // ---- reverse of valid * f w.r.t. the final points, the recorded loss and the objects -------------------------------
@@ -393,13 +324,7 @@ __device__ __forceinline__ float opt_rev_candidate(const OptRevArgs& ra, int c, 
 #pragma unroll
     for (int i = 0; i < KK; ++i) obx[i] = oby[i] = tbx[i] = tby[i] = nbx[i] = nby[i] = spb[i] = cpb[i] = 0.0f;
     const float fbar = valid;
-    float rbar;
-    if (s.fun_id == D2D_FUN_RECEIVED_POWER) {
-        const float Dn = s.h2 + r * r;
-        rbar = -(fbar * (f / Dn)) * (2.0f * r);
-    } else if (s.fun_id == D2D_FUN_LENGTH_SQUARED) rbar = fbar * (2.0f * r);
-    else if (s.fun_id == D2D_FUN_LENGTH) rbar = fbar;
-    else rbar = 0.0f;
+    const float rbar = opt_fun_rbar(s.fun_id, s.h2, r, f, fbar);
     if (CUST && s.fun_id == D2D_FUN_CUSTOM) {
         // the host's d fun / d xys (its derivative w.r.t. the end points as arguments of `fun` folded into rows 0 and K + 1)
         const float* pb = s.cust_pb + ((long)c * s.cells + idx) * (2 * (D2D_MAX_ORDER + 2));

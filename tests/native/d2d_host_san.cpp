@@ -1,5 +1,5 @@
 // C entry points over differt2d_amd/csrc/d2d_host.hpp -- the host-only logic of libd2d.so (candidate enumeration,
-// parameter validation, sweep thresholds, launch buffer sizes) -- for the CPU sanitizer build:
+// parameter validation, sweep thresholds, launch buffer sizes, the reverse sweep's trajectory chunks) -- for the CPU sanitizer build:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared -fPIC
 // (tests/test_host_sanitizers.py).  The product compiles the very same header into libd2d.so with hipcc.
 #include "../../differt2d_amd/csrc/d2d_host.hpp"
@@ -65,6 +65,11 @@ void san_sweep_thresholds(const d2d_params* p, int grad, int sig_narrow_filter, 
     f12[0] = t.flt_lo; f12[1] = t.flt_hi; f12[2] = t.on_lo; f12[3] = t.on_hi; f12[4] = t.loss_skip; f12[5] = t.h2; f12[6] = t.sig_l2f;
     for (int k = 0; k <= D2D_MAX_ORDER; ++k) f12[7 + k] = t.fnum[k];
     i3[0] = t.mode; i3[1] = t.sig_mono; i3[2] = t.degenerate_invalid ? 1 : 0;
+}
+
+long long san_opt_chunk_cells(long long cells, long long floats_per_cell, long long traj_mb, int mem_known, long long free_bytes,
+                              long long resident_bytes) {
+    return d2d_host::opt_chunk_cells(cells, floats_per_cell, traj_mb, mem_known != 0, free_bytes, resident_bytes);
 }
 
 }  // extern "C"

@@ -282,7 +282,7 @@ def test_sgd_trajectory_matches_the_c_oracle_after_few_steps(solver, steps):
 
 
 def _chunks(per_cell_floats, cells, traj_mb):
-    """opt_sweep_launch's chunking (differt2d_amd/csrc/d2d.hip): cells per chunk for a trajectory budget of traj_mb MiB."""
+    """d2d_host::opt_chunk_cells (differt2d_amd/csrc/d2d_host.hpp): cells per chunk for a trajectory budget of traj_mb MiB."""
     cells_pad = (cells + 63) // 64 * 64
     return min(cells_pad, max(64, (traj_mb << 20) // (4 * per_cell_floats) // 64 * 64))
 

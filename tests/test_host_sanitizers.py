@@ -2,7 +2,7 @@
 
 * the C oracle's sanitizer build (`make -C oracle asan`: -fsanitize=address,undefined) sweeps small and degenerate inputs;
 * the host-only logic of libd2d.so -- differt2d_amd/csrc/d2d_host.hpp: candidate enumeration, parameter validation, the
-  sweep thresholds, the LDS / heavy-list size arithmetic with its 4 GiB guard -- compiled with g++ -fsanitize=address,undefined
+  sweep thresholds, the LDS / heavy-list size arithmetic with its 4 GiB guard, the reverse sweep's trajectory chunks -- compiled with g++ -fsanitize=address,undefined
   (tests/native/d2d_host_san.cpp) and driven through ctypes with edge cases.
 
 Both run in a child process with libasan preloaded (an instrumented library cannot be loaded into a plain python
@@ -272,6 +272,33 @@ def test_libd2d_host_logic_under_asan_and_ubsan(asan, tmp_path):
         for kw, grad, narrow, want_d, want_f, want_i in recorded:
             d, f, i = thresholds(params(**kw), grad, narrow)
             assert d.view(np.uint64).tolist() == want_d and f.view(np.uint32).tolist() == want_f and i.tolist() == want_i, (kw, grad, narrow)
+        # ---- cells per chunk of the reverse sweep's trajectory store (opt_chunk_cells): edge inputs, then recorded values
+        L.san_opt_chunk_cells.argtypes = [C.c_longlong] * 3 + [C.c_int] + [C.c_longlong] * 2
+        L.san_opt_chunk_cells.restype = C.c_longlong
+        chunk = L.san_opt_chunk_cells
+        for cells in (1, 10, 63, 64, 65, 810, 90000, 2**31 - 1):
+            pad = -(-cells // 64) * 64
+            for per_cell in (0, 1, 400, 123457, 2**40):
+                for mb in (1, 7, 16384, 262144):
+                    for known, free, resident in ((0, 0, 0), (1, 0, 0), (1, 1 << 20, 0), (1, 300 << 20, 4096), (1, 2**61, 2**61)):
+                        n = chunk(cells, per_cell, mb, known, free, resident)
+                        assert n % 64 == 0 and 64 <= n <= pad, (cells, per_cell, mb, known, free, resident, n)
+                        budget = min(mb << 20, max((free + resident) // 2, 64 << 20)) if known else mb << 20
+                        assert n == pad or n * 4 * max(per_cell, 1) <= budget or n == 64, (cells, per_cell, mb, n)
+        assert chunk(10, 400, 1, 0, 0, 0) == 64 and chunk(10, 0, 1, 1, 0, 0) == 64                  # fewer than 64 cells: one wave
+        assert chunk(90000, 2**40, 1, 0, 0, 0) == 64                                               # a budget below one wave: one wave
+        assert chunk(90000, 400, 16384, 1, 0, 0) == 64 * ((64 << 20) // 1600 // 64)                # nothing free: the 64 MiB floor
+        assert chunk(90000, 400, 16384, 1, 2**61, 2**61) == chunk(90000, 400, 16384, 0, 0, 0)      # plenty free: opt_traj_mb decides
+        recorded = [   # (cells, floats per cell, opt_traj_mb, memory known, free bytes, resident bytes) -> the inline code's chunk
+            (810, 0, 1, 0, 0, 0, 832), (810, 0, 16384, 1, 0, 0, 832), (810, 400, 1, 0, 0, 0, 640), (810, 400, 1, 1, 0, 0, 640),
+            (810, 4000, 1, 0, 0, 0, 64), (810, 123457, 16384, 1, 0, 0, 128), (810, 123457, 16384, 1, 314572800, 4096, 256),
+            (25600, 0, 1, 1, 0, 0, 25600), (25600, 4000, 16384, 1, 0, 0, 4160), (25600, 4000, 16384, 1, 314572800, 4096, 9792),
+            (90000, 0, 1, 0, 0, 0, 90048), (90000, 400, 16384, 1, 0, 0, 41920), (90000, 123457, 16384, 0, 0, 0, 34752),
+            (90000, 123457, 16384, 1, 268435456000, 1073741824, 34752), (1000000, 0, 1, 1, 0, 0, 262144),
+            (1000000, 0, 16384, 0, 0, 0, 1000000), (1000000, 400, 16384, 1, 314572800, 4096, 98304),
+        ]
+        for *args, want in recorded:
+            assert chunk(*args) == want, (args, want)
         print("HOST-SAN-OK")
     """
     out = _run_child(code, asan)
