@@ -151,12 +151,11 @@ struct d2d_ctx {
     DevBuf<unsigned long long> d_hidden;
     bool hidden_valid = false;
     double hidden_key[12] = {0}, hidden_seen[12] = {0};
-    bool use_hidden_masks = true;       // "hidden_masks" option (A/B and tests; same results)
+    bool use_hidden_masks = true;       // "hidden_masks" option (tests: the reference that never builds them; same results)
     long long hidden_min_tiles = 400;   // ... for launches of at least this many patches ("hidden_min_tiles" option)
     long long hidden_builds = 0;        // diagnostic
     float pair_key[6] = {0, 0, 0, 0, 0, 0};  // patch, seg_tol, approx, act, alpha, dperp
     bool use_pair_masks = true;
-    int sig_narrow_filter = 1;  // option "sig_narrow_filter": 0 = the filter's window at -89, 1 = at -17.5 (same bits)
     // scene (device)
     DevBuf<float4> d_occl, d_refl, d_flt;
     DevBuf<int> d_cw;
@@ -194,7 +193,6 @@ struct d2d_ctx {
     long long sched_override_n = 0;
     bool use_cost_history = true;
     long long fwd_waves = 0;            // patches (= waves) per workgroup of the LISTED forward sweep kernel: 1, 4, or 0 = by the table's size
-    long long sched_key_mode = 0;       // schedule keys: 0 work history if there is one, else list lengths, else the proxy; 1 never the history; 2 never the lists
     bool txg_exhaustive = false;        // TX-grid value sweeps with the exhaustive kernel (A/B and tests)
     long long sched_min_tiles = 2048;   // launches with fewer patches keep the identity schedule
     uint64_t grid_token = 0;  // the caller's version token of the resident grid (valid with have_grid; 0: none, see grid_shadow)
@@ -222,14 +220,9 @@ struct d2d_ctx {
     long long nan_scan_mode = 1;        // ... 1: two levels (regions of 4 x 4 patches, then patches), 2: one wave per patch (A/B and tests; same flags)
     bool nan_scan_stats = false;        // "nan_scan_stats" option: count probes / flagged cells / flagged patches (d2d_debug_nan_scan)
     DevBuf<unsigned long long> d_nan_stats;
-    // the scan BESIDE the sweep ("nan_scan_async", default on): on a stream of its own, its flags applied by nan_apply_kernel once
-    // both are through (sweep 0.14 ms + scan 0.26 ms one behind the other at cfg3)
-    bool nan_scan_async = true;
     size_t lds_max = d2d_host::LDS_MAX;  // dynamic LDS a launch without a choice may take (gfx950: the CU's 160 KB less 4 KB of static LDS, d2d_host.hpp; d2d_create lowers it to what the device reports)
     long long nan_wqcap = 0, nan_rb = 0;  // "nan_scan_wqcap" / "nan_scan_rb": the region scan's queue entries / batches per round in use (0: all; tests)
-    long long nan_scan_prio = 0;        // "nan_scan_prio": 0 the scan stream has the lowest priority, 1 the highest (A/B)
-    hipStream_t scan_stream = nullptr;  // created at the first use
-    long long scan_stream_prio = -1;
+    hipStream_t scan_stream = nullptr;  // created at the first use, at the lowest priority
     hipEvent_t ev_scan_fork = nullptr, ev_scan_done = nullptr;
     DevBuf<unsigned long long> d_nan_cells;  // [patches]
     DevBuf<unsigned> d_nan_rows;             // [patches][1 + ceil(N / 32)]
@@ -253,7 +246,6 @@ struct d2d_ctx {
     hipStream_t aux_stream = nullptr;  // the patch schedule's sort runs here, beside the shadow masks and the region lists
     hipStream_t sort_stream = nullptr; // .. and here when aux_stream carries the whole preparation (pipeline)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool use_aux = true;
     int* h_meta = nullptr;             // pinned: {patches left to the enumerating kernel, pool chunks handed out} of the last launch with lists
     hipEvent_t ev_meta = nullptr;
     bool meta_pending = false;
@@ -303,7 +295,6 @@ struct d2d_ctx {
     bool pipeline = true;
     long long unpiped_max_tiles = 256; // "unpiped_max_tiles": launches of orders <= 1 over at most this many patches prepare on the sweep's own stream (latency of a small call)
     bool last_small = false;           // ... what the previous launch was (a change of kind drains both streams first)
-    bool prep_fused = true;             // shadow masks + zeroing in one kernel, the schedule's sort in one workgroup ("prep_fused" option; 0: round 2's chain)
     // RCCL (one communicator per ctx, collectives run on the ctx stream)
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
@@ -610,9 +601,6 @@ int d2d_create(int device, d2d_ctx** out) {
     if (device < 0 || device >= n) return fail(D2D_ERR_NO_DEVICE, "device %d out of range (0..%d)", device, n - 1);
     d2d_ctx* c = new d2d_ctx();
     c->device = device;
-    if (const char* v = getenv("D2D_SCHED_MIN_TILES")) c->sched_min_tiles = atoll(v);  // tuning knob
-    if (const char* v = getenv("D2D_HEAVY_SPLIT")) c->heavy_split = atoll(v);
-    if (const char* v = getenv("D2D_SPLIT_MAX_TILES")) c->split_max_tiles = atoll(v);  // tuning knob (0: never)
     hipError_t e1 = hipSetDevice(device);
     if (e1 == hipSuccess) {
         // The kernels are gfx950 code objects and size their LDS for a CU with 160 KB: say so HERE, in words, instead of failing a
@@ -641,7 +629,7 @@ int d2d_create(int device, d2d_ctx** out) {
         // the side stream carries short dependent chains that run beside a sweep kernel which fills the chip: highest priority
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        e1 = hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, getenv("D2D_AUX_PRIO_OFF") ? prio_lo : prio_hi);
+        e1 = hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, prio_hi);
         if (e1 == hipSuccess) e1 = hipStreamCreateWithPriority(&c->sort_stream, hipStreamNonBlocking, prio_hi);
     }
     if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence);
@@ -1333,7 +1321,7 @@ static int sweep_args(d2d_ctx* c, Sweep& s) {
     a.tol = p->tol;
     a.seg_lo = -p->seg_tol;
     a.seg_hi = 1.0f + p->seg_tol;
-    s.th = d2d_host::sweep_thresholds(*p, s.grad_mode != 0, c->sig_narrow_filter != 0);
+    s.th = d2d_host::sweep_thresholds(*p, s.grad_mode != 0);
     a.flt_lo = s.th.flt_lo;
     a.flt_hi = s.th.flt_hi;
     a.on_lo = s.th.on_lo;
@@ -1417,10 +1405,6 @@ static int prep_masks(d2d_ctx* c, Sweep& s, Prep& pr) {
     // (a multiple of 256 bytes: the runtime fills odd tails with a second kernel)
     const size_t zero_words = ((size_t)c->N + d2d::SCHED_KEYS + (2 + rl_regions + 1) / 2 + 31) & ~(size_t)31;
     if ((rc = c->cur.d_shadow.ensure(zero_words))) return rc;
-    if (!c->prep_fused) {
-        hipLaunchKernelGGL(d2d::zero_words_kernel, dim3((unsigned)((zero_words + 255) / 256)), dim3(256), 0, s.ps, c->cur.d_shadow.p, (long)zero_words);
-        HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the schedule's sort may start here, on a stream of its own)
-    }
     pr.zeroed = true;
     // window where a test is certainly "hit" (hard) / exactly saturated to 1 (approx): shrink [-tol, 1+tol] by widen
     MaskWindow& w = pr.win;
@@ -1433,23 +1417,14 @@ static int prep_masks(d2d_ctx* c, Sweep& s, Prep& pr) {
     const double dom_hi = (double)a.on_hi + 2e-3;
     w.dom_w = (dom_hi - w.dom_lo) / 64.0;
     const float dperp = 4096.0f * 1.1920929e-07f * (w.ok ? ext : 1.0f) * (float)(p->max_order + 1);
-    if (c->prep_fused) {
-        // one kernel: the masks (stored, not OR-ed: nothing to zero in front) and the zeroing of everything behind them
-        const long n_zero = (long)zero_words - c->N;
-        hipLaunchKernelGGL(d2d::shadow_fill_kernel, dim3((unsigned)(c->N + (n_zero + 255) / 256)), dim3(256), 0, s.ps, c->d_occl.p, c->d_refl.p,
-                           c->d_kind.p, c->N, s.tx[0], s.tx[1], (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), dperp, (float)w.dom_lo,
-                           (float)w.dom_w, w.ok ? 1 : 0, c->cur.d_shadow.p, c->cur.d_shadow.p + c->N, n_zero);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the sort of a big launch needs its counters zeroed: it may start here)
-    }
+    // one kernel: the masks (stored, not OR-ed: nothing to zero in front) and the zeroing of everything behind them
+    const long n_zero = (long)zero_words - c->N;
+    hipLaunchKernelGGL(d2d::shadow_fill_kernel, dim3((unsigned)(c->N + (n_zero + 255) / 256)), dim3(256), 0, s.ps, c->d_occl.p, c->d_refl.p,
+                       c->d_kind.p, c->N, s.tx[0], s.tx[1], (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), dperp, (float)w.dom_lo,
+                       (float)w.dom_w, w.ok ? 1 : 0, c->cur.d_shadow.p, c->cur.d_shadow.p + c->N, n_zero);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the sort of a big launch needs its counters zeroed: it may start here)
     if (!w.ok) return D2D_OK;
-    if (!c->prep_fused) {
-        const int pairs = c->N * c->N;
-        hipLaunchKernelGGL(d2d::shadow_tx_kernel, dim3((unsigned)pairs), dim3(64), 0, s.ps, c->d_occl.p,
-                           c->d_refl.p, c->d_kind.p, c->N, s.tx[0], s.tx[1], (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), dperp,
-                           (float)w.dom_lo, (float)w.dom_w, c->cur.d_shadow.p);
-        HIP_TRY(hipGetLastError());
-    }
     a.shadow = c->cur.d_shadow.p;
     a.shadow_dperp = dperp;
     a.shadow_lo = (float)w.dom_lo;
@@ -1639,16 +1614,16 @@ static int prep_schedule(d2d_ctx* c, Sweep& s, Prep& pr) {
         int* hist = reinterpret_cast<int*>(cur.d_shadow.p + c->N);  // [SCHED_KEYS] counts, [SCHED_KEYS] cursors
         // cost key: what the patch cost last time, when this context has swept the same grid before (optimisation
         // loops, repeated maps); otherwise a proxy computed from the geometry
-        const bool from_history = cur.cost_tiles == tiles && c->use_cost_history && c->sched_key_mode != 1;
+        const bool from_history = cur.cost_tiles == tiles && c->use_cost_history;
         // no (usable) history: the lengths of the region lists this launch has just built, if any, else the geometric proxy
-        const bool from_lists = !from_history && a.rl != nullptr && c->sched_key_mode != 2;
+        const bool from_lists = !from_history && a.rl != nullptr;
         pr.sched_from_history = from_history || from_lists;
         if (!from_history && !from_lists)
             hipLaunchKernelGGL(d2d::patch_cost_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s.ps, a, cur.d_sched_key.p);
         // keys from the work history depend on nothing this launch has built: the sort then runs on the side stream,
         // beside the shadow masks and the region lists, behind the memset of its counters
-        const bool one_wg = c->prep_fused && tiles <= d2d::SORT1_MAX;  // the whole sort in one workgroup's LDS: nothing zeroed, nothing to wait for
-        const bool side = from_history && (pr.zeroed || (one_wg && s.piped)) && c->use_aux && (s.piped ? c->sort_stream : c->aux_stream) != nullptr;
+        const bool one_wg = tiles <= d2d::SORT1_MAX;  // the whole sort in one workgroup's LDS: nothing zeroed, nothing to wait for
+        const bool side = from_history && (pr.zeroed || (one_wg && s.piped)) && (s.piped ? c->sort_stream : c->aux_stream) != nullptr;
         hipStream_t ss = side ? (s.piped ? c->sort_stream : c->aux_stream) : s.ps;
         // (ev_fork sits on `ps` behind the zeroing; without the pipeline `ps` is the main stream, i.e. also behind the
         // previous sweep, whose work counters the sort reads)
@@ -1815,14 +1790,13 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
     // zero in the backward scan of ANY candidate, valid or not -- come from a pass of their own (d2d_nanscan.hpp), which
     // poisons the cells and the patches' rows of VJP partial sums the way the exhaustive kernel (strict_nan) would have
     // written them.  It reads the scene's tables and the grid only: it runs BESIDE the sweep on a stream of its own and
-    // leaves flags that nan_apply_kernel applies once both are through ("nan_scan_async" = 0: behind the sweep, as in round 4).
+    // leaves flags that nan_apply_kernel applies once both are through.
     // Every size check of the sweeps below comes BEFORE the scan is forked onto its own stream: nothing may fail between the
     // fork and the join (a scan left running would read tables that a later d2d_set_scene rewrites).
     const bool culled_rx = !txg && !p->strict_nan;
     const size_t lds_tab = (size_t)(4 * c->N + 1) * sizeof(float4);  // tables, adjoint table
     const size_t lds_culled = culled_rx ? lds_tab + 512 : lds_tab;    // (+ the culling queue)
     if ((culled_rx || s.txg_culled) && lds_culled > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
-    bool scan_beside = false;
     // ... and should a launch fail behind the fork all the same (a HIP error), the scan is waited for before the error is returned
     struct ScanJoin {
         d2d_ctx* c;
@@ -1832,13 +1806,11 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         }
     } scan_join{c};
     const int rw = 1 + (c->N + 31) / 32;
-    if (scan && c->nan_scan_async) {
-        if (c->scan_stream == nullptr || c->scan_stream_prio != c->nan_scan_prio) {
-            if (c->scan_stream) { HIP_TRY(hipStreamSynchronize(c->scan_stream)); HIP_TRY(hipStreamDestroy(c->scan_stream)); c->scan_stream = nullptr; }
+    if (scan) {
+        if (c->scan_stream == nullptr) {
             int prio_lo = 0, prio_hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            HIP_TRY(hipStreamCreateWithPriority(&c->scan_stream, hipStreamNonBlocking, c->nan_scan_prio ? prio_hi : prio_lo));
-            c->scan_stream_prio = c->nan_scan_prio;
+            HIP_TRY(hipStreamCreateWithPriority(&c->scan_stream, hipStreamNonBlocking, prio_lo));
         }
         if (!c->ev_scan_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_fork, hipEventDisableTiming | hipEventDisableSystemFence));
         if (!c->ev_scan_done) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_done, hipEventDisableTiming | hipEventDisableSystemFence));
@@ -1854,7 +1826,6 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         scan_join.armed = true;
         if ((rc = launch_scan(c, s, c->scan_stream, as))) return rc;
         HIP_TRY(hipEventRecord(c->ev_scan_done, c->scan_stream));
-        scan_beside = true;
     }
     if (culled_rx) {
         // culled value+grad sweep (default)
@@ -1872,7 +1843,7 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         HIP_TRY(d2d::launch_vg(mode, txg, true, s.grid_patches, lds, c->stream, a));
     }
     if (rc) return rc;
-    if (scan_beside) {
+    if (scan) {
         d2d::SweepArgs as = a;
         as.nan_cell_bits = c->d_nan_cells.p;
         as.nan_row_bits = grad_mode == 2 ? c->d_nan_rows.p : nullptr;
@@ -1880,8 +1851,6 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_scan_done, 0));
         scan_join.armed = false;  // joined: the main stream is behind the scan from here on
         HIP_TRY(d2d::launch_nan_apply(c->stream, as, (long)s.tiles));
-    } else if (scan) {
-        if ((rc = launch_scan(c, s, c->stream, a))) return rc;
     }
     if ((rc = sweep_done(c))) return rc;
     if (grad_mode == 2) {
@@ -2185,8 +2154,6 @@ int d2d_set_option(d2d_ctx* c, const char* name, int64_t value) {
     else if (!strcmp(name, "heavy_split")) c->heavy_split = value;
     else if (!strcmp(name, "time_kernel")) c->time_kernel = value != 0;
     else if (!strcmp(name, "cost_history")) c->use_cost_history = value != 0;
-    else if (!strcmp(name, "sched_key_mode")) c->sched_key_mode = value;
-    else if (!strcmp(name, "side_stream")) c->use_aux = value != 0;
     else if (!strcmp(name, "pipeline")) {
         // (the two sets must not be mixed up by a switch in mid-flight)
         if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2203,7 +2170,6 @@ int d2d_set_option(d2d_ctx* c, const char* name, int64_t value) {
         c->fwd_waves = value;
     }
     else if (!strcmp(name, "pair_masks")) c->use_pair_masks = value != 0;
-    else if (!strcmp(name, "sig_narrow_filter")) c->sig_narrow_filter = (int)value;
 #ifdef D2D_AB_TIMELINE
     else if (!strcmp(name, "tl_ring")) {
         c->tl_ring_on = value != 0;
@@ -2227,7 +2193,6 @@ int d2d_set_option(d2d_ctx* c, const char* name, int64_t value) {
         if (c->comm_stream) return fail(D2D_ERR_STATE, "comm_prio must be set before the first collective creates the communication stream");
         c->comm_prio = value > 0 ? 1 : (value < 0 ? -1 : 0);
     }
-    else if (!strcmp(name, "nan_scan_async")) c->nan_scan_async = value != 0;
     else if (!strcmp(name, "nan_scan_wqcap")) {
         if (value < 0 || value > d2d::NAN_WQCAP) return fail(D2D_ERR_INVALID, "nan_scan_wqcap must be in [0, %d], got %lld", d2d::NAN_WQCAP, (long long)value);
         c->nan_wqcap = value;
@@ -2235,8 +2200,6 @@ int d2d_set_option(d2d_ctx* c, const char* name, int64_t value) {
         if (value < 0 || value > d2d::NAN_RB) return fail(D2D_ERR_INVALID, "nan_scan_rb must be in [0, %d], got %lld", d2d::NAN_RB, (long long)value);
         c->nan_rb = value;
     }
-    else if (!strcmp(name, "nan_scan_prio")) c->nan_scan_prio = value != 0 ? 1 : 0;
-    else if (!strcmp(name, "prep_fused")) c->prep_fused = value != 0;
     else if (!strcmp(name, "opt_parallel")) c->opt_parallel = value != 0;
     else if (!strcmp(name, "opt_grad_mode")) {
         if (value != 0 && value != 1) return fail(D2D_ERR_INVALID, "opt_grad_mode must be 0 (reverse mode) or 1 (forward tangents), got %lld", (long long)value);

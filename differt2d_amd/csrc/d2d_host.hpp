@@ -233,8 +233,8 @@ struct SweepThresholds {
     bool degenerate_invalid = false;
 };
 // The thresholds of the culling tests and shortcuts of an ImagePath sweep with parameters p (checked by check_params).
-// grad: a value+grad sweep; sig_narrow_filter: the "sig_narrow_filter" option.
-inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad, bool sig_narrow_filter) {
+// grad: a value+grad sweep.
+inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad) {
     SweepThresholds t;
     // Filter thresholds: the soft window is where some activation of t is not exactly saturated
     // to "outside": hard -> [-tol, 1+tol]; hard_sigmoid -> widened by 3/alpha; sigmoid -> by 89/alpha
@@ -249,7 +249,7 @@ inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad, bool sig
     // -- z < -17.33 -- leaves 1 - hit at exactly 1.0f, as no test at all would: the divide-free filter may drop what is
     // certainly below -17.5 instead of what is certainly below -89.  The value+grad build keeps the wide window: it records
     // which test carries the max.)
-    t.widen_flt = (t.mode == SWEEP_SIG && !grad && sig_narrow_filter) ? 17.5 / (double)p.alpha : t.widen;
+    t.widen_flt = (t.mode == SWEEP_SIG && !grad) ? 17.5 / (double)p.alpha : t.widen;
     const double lo = -((double)p.seg_tol + t.widen_flt);
     const double hi = 1.0 + (double)p.seg_tol + t.widen_flt;
     t.flt_lo = (float)(lo * (1.0 + 1e-5) - 1e-30);

@@ -12,7 +12,7 @@
 //     t = fl(a/d) outside the soft window by a 1e-5 relative margin.
 //
 //   * a candidate is never evaluated at all when conservative geometry proves that exact zero for a whole 8 x 8 patch:
-//     the tile culling (cull_candidate), the first-segment shadow masks (shadow_tx_kernel / shadow_fill_kernel), the
+//     the tile culling (cull_candidate), the first-segment shadow masks (shadow_fill_kernel), the
 //     wall-to-wall masks (pair_shadow_kernel) and the last-segment masks of the leaf regions (hidden_region_kernel), each
 //     with explicit rounding bounds.
 //
@@ -133,7 +133,7 @@ struct SweepArgs {
     float loss_skip;           // a loss certainly below this cannot change less(loss, tol) (see eval_candidate); < 0: never
     float sig_l2f;             // MODE_SIG: log2 of an upper bound of |fun| over the launch's orders, 1e30: none (sig_zc_of)
     int sig_mono;              // MODE_SIG: fun >= 0 throughout, so a cell's running sum never shrinks
-    // first-segment shadow culling (shadow_tx_kernel): bit b of shadow[w] = every point of wall w with parametric
+    // first-segment shadow culling (shadow_fill_kernel): bit b of shadow[w] = every point of wall w with parametric
     // coordinate in [b/64, (b+1)/64] (and within shadow_dperp of the wall's line) is certainly hidden from the fixed
     // end point by some other object
     const unsigned long long* __restrict__ shadow;  // [N] or null
@@ -212,30 +212,16 @@ __device__ __forceinline__ bool wave_any(bool p) { return __any(p); }
 // The same wave-uniform index, unknown to the optimiser: a table row loaded through it is loaded HERE, not kept in scalar
 // registers from an earlier load of the same row (the candidate's walls are read before the wall loop and again behind it,
 // where few candidates arrive: held across the loop they are 4 scalars per wall that the loop's own state then has to do without)
-#ifndef D2D_LATE_INDEX
-#define D2D_LATE_INDEX 1
-#endif
 __device__ __forceinline__ int late_index(int i) {
-#if D2D_LATE_INDEX
     asm volatile("" : "+s"(i));
-#endif
     return i;
 }
 
 // counter I += x in a vector register (see WaveStats)
-#ifndef D2D_WALL_PAIRS_MODES
-#define D2D_WALL_PAIRS_MODES 3  // bit m: validity mode m takes two walls per trip (A/B)
-#endif
-#ifndef D2D_WALL_PAIRS
-#define D2D_WALL_PAIRS 1  // A/B: 0 = the wall loop of eval_candidate takes one wall per trip (rounds 1 - 3)
-#endif
-#ifndef D2D_STAT_MASK  // (A/B: the counters an instrumented build keeps)
-#define D2D_STAT_MASK 0xffff
-#endif
 template <int I>
 __device__ __forceinline__ void stat_add(WaveStats& st, unsigned long long x) {
     const unsigned x32 = (unsigned)x;
-    if ((D2D_STAT_MASK >> I) & 1) asm volatile("v_add_u32 %0, %0, %1" : "+v"(st.c[I]) : "v"(x32));
+    asm volatile("v_add_u32 %0, %0, %1" : "+v"(st.c[I]) : "v"(x32));
 }
 
 // ---- correctly rounded fp32 division without the range scaling of the generic expansion --------------
@@ -699,11 +685,11 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
     // do not depend on the order of the tests, and neighbouring candidates tend to share their occluder.
     // (the next wall's data are fetched while this one is tested: a lone wave would otherwise sit out one scalar-load
     // latency per wall)
-    // (D2D_WALL_PAIRS_MODES: hard and hard_sigmoid.  hard_sigmoid LOST 3 % with two walls per trip -- 147 scalars parked in VGPR
+    // (hard and hard_sigmoid.  hard_sigmoid LOST 3 % with two walls per trip -- 147 scalars parked in VGPR
     // lanes instead of 62 -- until the loss stage reloaded its walls' rows (late_index): 0.132 -> 0.125 ms at cfg2 with both;
     // sigmoid gains nothing, 5.0 ms either way.  How far ahead the pair loop loads its walls -- both next walls before the
     // filters, one, none -- makes no difference: 0.077 - 0.078)
-    constexpr bool PAIRS = D2D_WALL_PAIRS && ((D2D_WALL_PAIRS_MODES >> MODE) & 1);
+    constexpr bool PAIRS = MODE != MODE_SIG;
     if constexpr (PAIRS) {
     // Two walls per trip: their filters are independent instruction streams (a lone wave issues a dependent chain at a
     // fraction of its rate), and the wave-level question "does any lane need an exact test" is asked once for both.  The
@@ -1947,9 +1933,6 @@ __device__ __forceinline__ void first_wall_range(const SweepArgs& a, int part, i
     hi = (part == parts - 1) ? Nc : boundary((int)(((long)A * (part + 1)) / parts));
 }
 
-#ifndef D2D_HIDDEN_PATCH
-#define D2D_HIDDEN_PATCH 1  // A/B: 0 = the last-segment masks are consulted for the regions' lists (and order 1) only
-#endif
 // One batch of a candidate list, lanes = candidates: decodes the lane's entry, builds its image chain and runs the full
 // tile-culling test against the box (bx, by).  Returns the ballot of the entries that cannot be dropped.
 // TXG (TX grids): the chain is the fixed end point's through the walls in REVERSE order (sweep_order_culled_txg), with the
@@ -2011,7 +1994,7 @@ __device__ __forceinline__ void sweep_order_listed(const SweepArgs& a, const flo
     const auto* pool = cmem(rlc->lp.pool);
     const auto* next = cmem(rlc->lp.next);
     // the region's last-segment masks once more, now with the bins this PATCH can reach (hidden_region_kernel)
-    const unsigned long long* hidden_row = (D2D_HIDDEN_PATCH && rlc->leaf.hidden) ? rlc->leaf.hidden + (size_t)region * a.N : nullptr;
+    const unsigned long long* hidden_row = rlc->leaf.hidden ? rlc->leaf.hidden + (size_t)region * a.N : nullptr;
     const float hidden_dperp = hidden_row ? rlc->leaf.hidden_dperp : 0.0f;
     int r_lo = 0, r_hi = 0x7fffffff;
     if (parts > 1) {
@@ -2118,41 +2101,27 @@ __device__ __forceinline__ long region_of(const SweepArgs& a, int tcol, int trow
     return (long)(trow / R) * cmem(a.rl)->leaf.regions_x + (tcol / R);
 }
 
-#ifndef D2D_HEAVY_PARTS
-#define D2D_HEAVY_PARTS 4
-#endif
 // Hand-over between the parts of a cut patch without cache maintenance (fwd_patch): relies on gfx9 encodings and on the
-// memory system of gfx942 / gfx950; every other target (and -DD2D_FENCE_FREE_HANDOVER=0) uses release / acquire.
-#ifndef D2D_FENCE_FREE_HANDOVER
+// memory system of gfx942 / gfx950; every other target uses release / acquire.
 #if defined(__gfx942__) || defined(__gfx950__)
 #define D2D_FENCE_FREE_HANDOVER 1
 #else
 #define D2D_FENCE_FREE_HANDOVER 0
 #endif
-#endif
 // NaN scan of the value+grad sweeps (d2d_nanscan.hpp): waves per workgroup = patches per region (NAN_R x NAN_R), entries of the
 // region's list in LDS, batches tested per round (so that the list cannot overflow)
-#ifndef D2D_NAN_W
-#define D2D_NAN_W 16  // A/B: 8 = regions of 4 x 2 patches (twice the registers per lane, two workgroups per CU)
-#endif
-constexpr int NAN_W = D2D_NAN_W;
+constexpr int NAN_W = 16;
 constexpr int NAN_R = 4;            // patches per region along x; NAN_W / NAN_R along y
 constexpr int NAN_RY = NAN_W / NAN_R;
-#ifndef D2D_NAN_LCAP
-#define D2D_NAN_LCAP 2048  // A/B: entries of a region's list per round (a round = LCAP / 64 batches between two barriers)
-#endif
-constexpr int NAN_LCAP = D2D_NAN_LCAP;
+constexpr int NAN_LCAP = 2048;      // entries of a region's list per round (a round = LCAP / 64 batches between two barriers)
 constexpr int NAN_RB = NAN_LCAP / 64;
 constexpr int NAN_WQCAP = 2048;     // (patch, candidate) items of a region waiting for their probe (d2d_nanscan.hpp; beyond it a wave probes its own)
-constexpr int HEAVY_PARTS = D2D_HEAVY_PARTS;  // the dearest patches of a launch are cut into this many parts (power_fwd_kernel)
+constexpr int HEAVY_PARTS = 4;      // the dearest patches of a launch are cut into this many parts (power_fwd_kernel)
 constexpr int TILE_W = 8;  // a wave covers an 8 x 8 patch of RX cells: neighbouring cells share skips
 constexpr int TILE_H = 8;
 
 // MAXK = highest order compiled into this instantiation (the host picks the smallest that covers max_order:
 // register allocation is the maximum over all compiled paths, and orders 3 / 4 need many more VGPRs).
-#ifndef D2D_FWD_WAVES
-#define D2D_FWD_WAVES 1  // minimum waves per SIMD asked of the register allocator (1 = unconstrained)
-#endif
 // GRADK: also run the hand-derived adjoint of every surviving candidate (value + gradient in one sweep).  Culled
 // candidates contribute exactly 0 to the value and to every adjoint; what culling cannot reproduce are the
 // reference's autodiff NaN artefacts of candidates it never evaluates (see DESIGN.md "NaN parity"): those are
@@ -2402,31 +2371,12 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
 
 // WPB: waves (= patches) per workgroup.  1: the register allocation that serves small scenes best; 4: the waves share
 // the staged tables, which is what keeps big scenes (a 13 KB table at 200 walls) from running out of LDS at 3 waves per SIMD.
-#ifdef D2D_NUM_SGPR  // A/B: cap the scalar registers (96 -> 7 waves per SIMD, 80 -> 8 by MI355X_MICROARCH.md's residency formula)
-#ifdef D2D_NUM_VGPR
-#define D2D_SGPR_ATTR __attribute__((amdgpu_num_sgpr(D2D_NUM_SGPR), amdgpu_num_vgpr(D2D_NUM_VGPR)))
-#else
-#define D2D_SGPR_ATTR __attribute__((amdgpu_num_sgpr(D2D_NUM_SGPR)))
-#endif
-#else
-#define D2D_SGPR_ATTR
-#endif
-// Minimum waves per SIMD asked of the register allocator, A/B only.  The order-2 sweep from the region lists -- the benchmark's
-// kernel -- fits 7 waves (71 VGPRs, no scratch, -DD2D_FWD_WAVES_L2=7) now that its cold arguments are read late (late_kernarg:
-// 82 -> 58 parked scalars); unconstrained the allocator stops at 73, one register past the 72 that 7 waves allow.  Measured on
-// the MI355X (round 3, scripts/ab_build.sh "w1:-DD2D_FWD_WAVES_L2=1" "w7:-DD2D_FWD_WAVES_L2=7", two runs each): sweep kernel
-// 0.098 ms at 6 waves, 0.099 - 0.100 ms at 7 (90 parked scalars), step 0.110 - 0.113 vs 0.119 ms: residency is not what
-// bounds the kernel (mean 4.9 waves per SIMD over the launch: it is never full for long).  Default: unconstrained.
-#ifndef D2D_FWD_WAVES_L2
-#define D2D_FWD_WAVES_L2 1
-#endif
-constexpr int fwd_min_waves(int mode, bool stats, int maxk, bool gradk, bool listed, int wpb) {
-    if (wpb != 1) return 1;
-    if (listed && maxk == 2 && !gradk && !stats && mode == MODE_HARD) return D2D_FWD_WAVES_L2;
-    return D2D_FWD_WAVES;
-}
+// The register allocator is left unconstrained.  The order-2 sweep from the region lists -- the benchmark's kernel -- fits
+// 7 waves per SIMD (71 VGPRs, no scratch) when asked; unconstrained it stops at 73, one register past the 72 that 7 waves
+// allow.  Measured on the MI355X (round 3, two runs each): sweep kernel 0.098 ms at 6 waves, 0.099 - 0.100 ms at 7 (90 parked
+// scalars), step 0.110 - 0.113 vs 0.119 ms: residency is not what bounds the kernel (mean 4.9 waves per SIMD over the launch).
 template <int MODE, bool STATS, int MAXK, bool GRADK = false, bool LISTED = false, int WPB = 1>
-__global__ void __launch_bounds__(64 * WPB, fwd_min_waves(MODE, STATS, MAXK, GRADK, LISTED, WPB)) D2D_SGPR_ATTR power_fwd_kernel(SweepArgs a) {
+__global__ void __launch_bounds__(64 * WPB) power_fwd_kernel(SweepArgs a) {
     const int lane = threadIdx.x & 63;
     // LDS copy of the per-wall tables for the lanes-as-candidates phase (lane-varying wall index), staged once per wave
     extern __shared__ float4 tab[];  // [2N] refl, [N] flt, then (GRADK) [N] float4 = the wave's scene-VJP partial sums
@@ -2672,7 +2622,7 @@ __device__ __forceinline__ void coop_order(const SweepArgs& a, const float4* tab
                         const bool have = off + lane < n;
                         const unsigned long long code = pool[(size_t)ch * RL_CHUNK + (off & (RL_CHUNK - 1)) + (have ? lane : 0)];
                         float Ix[K], Iy[K];
-                        const unsigned long long* hid = D2D_HIDDEN_PATCH ? rlc->leaf.hidden : nullptr;
+                        const unsigned long long* hid = rlc->leaf.hidden;
                         m = cull_batch<K, false>(a, tab, bx, by, code, have, Ix, Iy, on_lo, on_hi, hid ? hid + (size_t)region * a.N : nullptr,
                                                  hid ? rlc->leaf.hidden_dperp : 0.0f);
                     }
@@ -3065,7 +3015,7 @@ __device__ __forceinline__ void sweep_order_listed_txg(const SweepArgs& a, const
         const unsigned long long code = pool[(size_t)chunk * RL_CHUNK + (off & (RL_CHUNK - 1)) + (have ? lane : 0)];
         if ((off & (RL_CHUNK - 1)) == RL_CHUNK - 64 && off + 64 < n) chunk = next[chunk];
         float Ix[K], Iy[K];
-        const unsigned long long* hid = D2D_HIDDEN_PATCH ? rlc->leaf.hidden : nullptr;
+        const unsigned long long* hid = rlc->leaf.hidden;
         unsigned long long mask = cull_batch<K, GRAD, true>(a, tab, bx, by, code, have, Ix, Iy, a.on_lo, a.on_hi, hid ? hid + (size_t)region * a.N : nullptr,
                                                             hid ? rlc->leaf.hidden_dperp : 0.0f);
         D2D_WORK(5 * K);
@@ -3219,10 +3169,7 @@ __global__ void __launch_bounds__(64) power_fwd_txg_kernel(SweepArgs a) {
 // patch_cost_kernel: one wave per patch -> key in [0, 63] + histogram;  patch_order_kernel: counting sort, dearest
 // first.  Ties are placed in atomic order: the schedule may differ from run to run, the results cannot.
 constexpr int SCHED_KEYS = 256;  // = blockDim of the two sort passes
-#ifndef D2D_SCHED_PER_THREAD
-#define D2D_SCHED_PER_THREAD 4
-#endif
-constexpr int SCHED_PER_THREAD = D2D_SCHED_PER_THREAD;  // patches per thread in the two counting-sort passes (16: 4 % slower steps at 1024^2 -- too few blocks)
+constexpr int SCHED_PER_THREAD = 4;  // patches per thread in the two counting-sort passes (16: 4 % slower steps at 1024^2 -- too few blocks)
 #ifdef D2D_AUX_KERNELS  // non-template kernels: defined once, in d2d.hip
 __global__ void __launch_bounds__(256) patch_cost_kernel(SweepArgs a, unsigned char* __restrict__ key) {
     const int lane = threadIdx.x & 63;
@@ -3479,13 +3426,6 @@ __global__ void tl_end_kernel(unsigned long long* __restrict__ ring, int seq) { 
 // The lists' descriptor as the sweep kernels read it (a.rl), written in stream order from a by-value argument.
 __global__ void write_region_lists_kernel(RegionLists* __restrict__ dst, RegionLists v) { *dst = v; }
 
-// What a launch needs zeroed (shadow masks, sort counters, list bookkeeping): a kernel of its own rather than
-// hipMemsetAsync, which the runtime does not let run ahead on the side stream.
-__global__ void __launch_bounds__(256) zero_words_kernel(unsigned long long* __restrict__ p, long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = 0ull;
-}
-
 // Self-test of the bare division chain against the compiler's generic expansion (bit equality expected).
 __global__ void selftest_div_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ q_fast,
                                     float* __restrict__ q_ref, float* __restrict__ q_hostr, const float* __restrict__ ry, long n) {
@@ -3502,12 +3442,12 @@ __global__ void selftest_expf_kernel(const float* __restrict__ x, float* __restr
     if (i < n) y[i] = expf_libm(x[i]);
 }
 
-// Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one thread per
+// Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per
 // (wall w, blocker j) pair rasterises, into 64 bins of w's parametric range, where the segment e -> p is CERTAINLY
 // reported as intersecting j by the exact path (hard: hit; approx: the four activations exactly saturated), for every
 // p within `dperp` of the bin.  t_a, t_b are linear-fractional in p, so on a thin quad around a bin that does not meet
 // the pole (fd keeps its sign) their ranges are spanned by the 4 vertices.  Margins: 8 eps per product sum for the
-// rounding of either evaluation chain.  Only bins certified at all four vertices are set (atomicOr).
+// rounding of either evaluation chain.  Only bins certified at all four vertices are set.
 // (one (wall w, blocker j) pair, lane = bin b: is bin b of w certainly hidden from (ex, ey) by j?)
 __device__ __forceinline__ bool shadow_pair_bin(const float4* __restrict__ occl, const float4* __restrict__ refl,
                                                 const unsigned char* __restrict__ kind, int w, int j, int b, float ex, float ey, float win_lo,
@@ -3554,19 +3494,7 @@ __device__ __forceinline__ bool shadow_pair_bin(const float4* __restrict__ occl,
     return ok;
 }
 
-__global__ void shadow_tx_kernel(const float4* __restrict__ occl, const float4* __restrict__ refl,
-                                 const unsigned char* __restrict__ kind, int N, float ex, float ey, float win_lo, float win_hi,
-                                 float dperp, float dom_lo, float dom_w, unsigned long long* __restrict__ shadow) {
-    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = (int)(gid & 63);       // one lane per bin: a wave = one (w, j) pair, its ballot = the pair's 64 bits
-    const long idx = gid >> 6;
-    if (idx >= (long)N * N) return;
-    const int w = (int)(idx / N), j = (int)(idx % N);
-    const unsigned long long bits = __ballot(shadow_pair_bin(occl, refl, kind, w, j, b, ex, ey, win_lo, win_hi, dperp, dom_lo, dom_w));
-    if (bits && b == 0) atomicOr(&shadow[w], bits);
-}
-
-// The same masks by ONE kernel that needs nothing zeroed beforehand and zeroes what the rest of the launch's preparation
+// The masks by ONE kernel that needs nothing zeroed beforehand and zeroes what the rest of the launch's preparation
 // wants zeroed (sort counters of big launches, the lists' bookkeeping: `zero[0 .. n_zero)`): workgroup w < N owns wall w -- its
 // four waves take every fourth blocker each, OR their ballots in registers, combine through LDS and STORE the mask --, the
 // workgroups behind them clear 256 words each.  N + a few workgroups instead of N x N single-wave ones and a memset kernel in
@@ -3596,7 +3524,7 @@ __global__ void __launch_bounds__(256) shadow_fill_kernel(const float4* __restri
 // p -> q is CERTAINLY reported as intersecting j by the exact path for every p within dperp of we's bin and every q
 // within dperp of wl's bin: t_a, t_b and the denominator are (bi)linear-fractional in (p, q), monotone along straight
 // lines in either argument while fd keeps its sign, so their ranges over the two thin quads are spanned by the 4 x 4
-// vertex pairs.  Same margins as shadow_tx_kernel.
+// vertex pairs.  Same margins as shadow_pair_bin.
 __global__ void __launch_bounds__(256) pair_shadow_kernel(const float4* __restrict__ occl, const float4* __restrict__ refl,
                                                           const unsigned char* __restrict__ kind, int N, float win_lo, float win_hi,
                                                           float dperp, float dom_lo, float dom_w8, unsigned long long* __restrict__ pair) {

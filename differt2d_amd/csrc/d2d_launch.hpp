@@ -32,7 +32,7 @@ hipError_t launch_region_lists(int K, bool grad, bool txg, dim3 grid, size_t lds
 hipError_t launch_region_refine(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,
                                 const RegionLevel& parent, const ListPool& lp, int* flag);
 
-// nan_scan_kernel<APPROX, TXG, MAXK> (d2d_nanscan.hpp): the reference's autodiff NaN positions, behind a culled value+grad sweep
+// nan_scan_kernel<APPROX, TXG, MAXK> (d2d_nanscan.hpp): the reference's autodiff NaN positions, beside a culled value+grad sweep
 // regions: nan_scan_region_kernel (16 waves per region of 4 x 4 patches; grid = regions) instead of one wave per patch
 hipError_t launch_nan_scan(bool approx, bool txg, int max_order, bool regions, bool dbg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a,
                            unsigned long long* stats);

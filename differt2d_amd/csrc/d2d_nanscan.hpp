@@ -627,9 +627,6 @@ __device__ __forceinline__ void nan_region_order(const SweepArgs& a, const float
     for (long long r0 = 0; r0 < nb; r0 += rb, ++round) {  // (workgroup-uniform)
         int* const cnt_p = lcount + (round & 1);
         if (threadIdx.x == 0) *wqn = 0;  // (the previous round's queue was emptied before its last barrier)
-#ifdef D2D_NAN_QUEUE_R5
-        for (int i = threadIdx.x; i < NAN_WQCAP; i += 64 * NAN_W) wq[i] = ~0ull;  // (probe build: the sentinel; ordered by the barrier below)
-#endif
         // ---- region level: batches [r0, r0 + rb) of the order, batch r0 + t * NAN_W + wv to wave wv: at most 64 rb <= NAN_LCAP
         // survivors per round, the list cannot overflow
         const int nbr = (nb - r0 < (long long)rb) ? (int)(nb - r0) : rb;  // batches of this round
@@ -729,25 +726,6 @@ __device__ __forceinline__ void nan_region_order(const SweepArgs& a, const float
                     // cap belongs to exactly one lane whatever the interleaving, and the slots below min(counter, cap) have all been
                     // written once the barrier is passed.  (Round 5 reserved and rolled back when the queue was full: a successful
                     // reservation between another wave's add and its subtraction left the final count covering slots nobody wrote.)
-#ifdef D2D_NAN_QUEUE_R5
-                    // PROBE BUILD ONLY (scripts/nan_queue_race.py): round 5's reserve-and-roll-back, kept to SHOW its race -- the
-                    // queue is filled with a sentinel every round (below), and a drained sentinel is a slot the final count covers
-                    // but nobody wrote; the item check in probe_item refuses it and counts it in stats[4].
-                    int base = 0;
-                    if (lane == 0) {
-                        base = atomicAdd(wqn, cnt);
-                        if (base + cnt > wqcap) {
-                            atomicSub(wqn, cnt);
-                            base = -1;
-                        }
-                    }
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base >= 0) {
-                        if (alive) wq[base + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = code | ((unsigned long long)wv << 56);
-                        mask = 0ull;
-                    }
-                    if (dbg_counts != nullptr && lane == 0 && mask != 0ull) atomicAdd(&dbg_counts[0], (unsigned)__builtin_popcountll(mask));
-#else
                     int base = 0;
                     if (lane == 0) base = atomicAdd(wqn, cnt);
                     base = __builtin_amdgcn_readfirstlane(base);
@@ -756,7 +734,6 @@ __device__ __forceinline__ void nan_region_order(const SweepArgs& a, const float
                     if (queued) wq[slot] = code | ((unsigned long long)wv << 56);
                     mask = __ballot(alive && !queued);
                     if (dbg_counts != nullptr && lane == 0 && mask != 0ull) atomicAdd(&dbg_counts[0], (unsigned)__builtin_popcountll(mask));
-#endif
                 }
                 // ... unless it is full: then the wave probes its own
                 while (mask) {
@@ -785,11 +762,8 @@ __device__ __forceinline__ void nan_region_order(const SweepArgs& a, const float
     }
 }
 
-#ifndef D2D_NAN_MIN_WAVES
-#define D2D_NAN_MIN_WAVES 1  // A/B: waves per SIMD the region scan must leave room for (8: two of its workgroups per CU, <= 64 VGPRs)
-#endif
 template <bool APPROX, bool TXG, int MAXK, bool DBG = false>
-__global__ void __launch_bounds__(64 * NAN_W, D2D_NAN_MIN_WAVES) nan_scan_region_kernel(SweepArgs a, unsigned long long* __restrict__ stats) {
+__global__ void __launch_bounds__(64 * NAN_W) nan_scan_region_kernel(SweepArgs a, unsigned long long* __restrict__ stats) {
     extern __shared__ float4 tab[];  // [2N] refl, [N] flt, the region's list [NAN_LCAP], then [2 NAN_W + 1][ceil(N / 32)] flag bits
     __shared__ float pbox[NAN_W][4];
     __shared__ int lcount[2];

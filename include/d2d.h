@@ -289,8 +289,6 @@ int d2d_power_map_wave_cycles(d2d_ctx* ctx, const d2d_params* params, const floa
  *                  candidates whose last interaction point can only lie in hidden bins leave the region's list, and order-1
  *                  candidates the patch's culling (same results); "hidden_min_tiles": only launches of at least this many
  *                  patches use them (default 400: smaller ones are latency-bound and lose more to the extra load than they gain)
- *   "prep_fused": non-zero (default) = the per-launch preparation runs as 4 kernels (masks of both kinds in one, the
- *                  schedule's histogram + sort in one); zero = the 7 separate kernels of round 2 (same results)
  *   "sched_min_tiles": launches of at least this many patches start their dearest patches first (default 2048)
  *   "heavy_split": with a work history and max_order == 2, this many of the dearest patches of a launch that is too big to
  *                  share every patch are cut in four parts swept by separate workgroups (0 = none, at most a quarter of the
@@ -299,21 +297,18 @@ int d2d_power_map_wave_cycles(d2d_ctx* ctx, const d2d_params* params, const floa
  *   "cost_history": non-zero (default) = a launch that sweeps the same grid as the previous one orders its patches by the
  *                   work each took then (counted by the kernels); zero = always by the geometric proxy
  *   "pair_masks": zero = do not build / use the wall-to-wall occlusion masks (A/B and tests; same results)
- *   "nan_scan": the pass behind a culled value+grad sweep that finds the reference's autodiff NaN cells (d2d_params.strict_nan):
+ *   "nan_scan": the pass beside a culled value+grad sweep that finds the reference's autodiff NaN cells (d2d_params.strict_nan):
  *                  1 (default) = one workgroup of 16 waves per region of 4 x 4 patches, 2 = one wave per patch (same flags),
  *                  0 = off (round 3's behaviour: NaN only inside the candidates the sweep evaluates; A/B);
  *                  "nan_scan_stats": non-zero = count its work (d2d_debug_nan_scan; slows the scan down)
- *                  "nan_scan_async": non-zero (default) = the scan runs BESIDE the sweep on a stream of its own and leaves flags
- *                  that a small kernel applies once both are through; zero = behind the sweep on the sweep's stream (same results)
- *                  "nan_scan_prio": priority of that stream, 0 (default) = lowest, 1 = highest (A/B: the highest is slower)
+ *                  (it runs on a stream of its own at the lowest priority and leaves flags that a small kernel applies once
+ *                  both are through)
  *                  "nan_scan_wqcap" / "nan_scan_rb": entries of a region's probe queue / batches per round of its list that the
  *                  two-level scan USES (0 = default: all it has; tests set them small so that a full queue and a full list are the
  *                  rule instead of a rare event -- same flags whatever the values).  Any of these two, or "nan_scan_stats", selects the
  *                  region kernel's debug instance (run-time sizes, counters through LDS); the product instance has neither
  *   "comm_prio": priority of the stream the RCCL collectives run on beside the next sweep: -1 lowest, 0 (default) normal, 1 highest;
  *                  set it BEFORE the first collective (D2D_ERR_STATE afterwards)
- *   "sig_narrow_filter": sigmoid validity, forward sweeps: 1 (default) = the divide-free filter of the occlusion tests drops what is
- *                  certainly below z = -17.5 (1 - sigmoid(z) is exactly 1.0f there), 0 = what is certainly below -89 (same results)
  *   "opt_parallel": zero = MinPath / FermatPath sweeps walk the candidates one after the other in every lane (same results)
  *   "opt_grad_mode": gradients through the MinPath / FermatPath solvers: 0 (default) reverse mode over the stored trajectory,
  *                   1 forward tangents carried through the loop (same derivative; NaN only where a local partial derivative
@@ -331,8 +326,6 @@ int d2d_power_map_wave_cycles(d2d_ctx* ctx, const d2d_params* params, const floa
  *                   the allowed objects); "region_budget_mb": device memory of ALL list pools (default 24576: an upper bound; the pipeline keeps one pool per
  *                   rotating set, three in all, so a pool may grow to a third of it); a list
  *                   that does not fit is marked as not listed and the patches of its region enumerate (same results)
- *   "sched_key_mode": schedule keys from 0 (default) the work history if there is one, else the lengths of the region
- *                   lists, else the geometric proxy; 1 never the history; 2 never the lists
  *   "pipeline": non-zero (default) = everything a launch rebuilds (shadow masks, region lists, the schedule's sort) lives
  *                   in three rotating sets and is built on side streams beside the previous launches' sweeps; the work
  *                   history a schedule is sorted by is then three launches old instead of one; zero = on the
@@ -340,14 +333,13 @@ int d2d_power_map_wave_cycles(d2d_ctx* ctx, const d2d_params* params, const floa
  *   "unpiped_max_tiles": launches of orders <= 1 over at most this many 8 x 8 patches (default 256) prepare on the sweep's own
  *                   stream whatever "pipeline" says: a small call is launch latency, and the side stream's fork and join cost it
  *                   8 us of 45 (same results); 0 = never
- *   "side_stream": zero = the schedule's sort is never moved to a stream of its own; "fwd_waves": patches per workgroup
+ *   "fwd_waves": patches per workgroup
  *                   of the sweep with region lists (0 default: 4 when the per-wall LDS table is big, else 1)
  *   "region_budget_mb" also bounds the growth of the list pool: it starts at 256 MB and is quadrupled (up to the budget,
  *                   a third of it per pool) when a launch's lists did not fit (read back without waiting); when the device cannot
  *                   provide the pool, the launch enumerates instead (same results) and later launches ask for a quarter
  *   "time_kernel": non-zero = bracket the sweep kernel of every launch with HIP events (see d2d_last_kernel_ms)
- * Also read once at d2d_create from the environment: D2D_SPLIT_MAX_TILES, D2D_SCHED_MIN_TILES. No reference counterpart
- * (XLA picks its own launch shapes). Returns D2D_ERR_INVALID for an unknown name. */
+ * No reference counterpart (XLA picks its own launch shapes). Returns D2D_ERR_INVALID for an unknown name. */
 int d2d_set_option(d2d_ctx* ctx, const char* name, int64_t value);
 
 /* Diagnostics of the patch schedule (the order in which the culled kernels start their 8 x 8 patches; it changes

@@ -8,7 +8,7 @@ from bench import workload, moving_transmitters
 from differt2d_amd.engine import Context, make_params
 tx0, walls, X, Y = workload(grid=1024)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-settings = sys.argv[2:] or ["-"]  # e.g. sched_key_mode=1,heavy_split=0
+settings = sys.argv[2:] or ["-"]  # e.g. cost_history=0,heavy_split=0
 txs = moving_transmitters(tx0, n + 5)
 for approx, pipe, setting in [(a, q, s) for a in (False, True) for q in (1, 0) for s in settings]:
     if True:

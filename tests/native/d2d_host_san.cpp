@@ -59,8 +59,8 @@ void san_region_plan(int tiles_x, int tiles_y, long long Nc, int min_order, int 
 
 // d: widen, widen_in, widen_flt; f: flt_lo, flt_hi, on_lo, on_hi, loss_skip, h2, sig_l2f, fnum[0 .. D2D_MAX_ORDER];
 // i: mode, sig_mono, degenerate_invalid
-void san_sweep_thresholds(const d2d_params* p, int grad, int sig_narrow_filter, double* d3, float* f12, int* i3) {
-    const d2d_host::SweepThresholds t = d2d_host::sweep_thresholds(*p, grad != 0, sig_narrow_filter != 0);
+void san_sweep_thresholds(const d2d_params* p, int grad, double* d3, float* f12, int* i3) {
+    const d2d_host::SweepThresholds t = d2d_host::sweep_thresholds(*p, grad != 0);
     d3[0] = t.widen; d3[1] = t.widen_in; d3[2] = t.widen_flt;
     f12[0] = t.flt_lo; f12[1] = t.flt_hi; f12[2] = t.on_lo; f12[3] = t.on_hi; f12[4] = t.loss_skip; f12[5] = t.h2; f12[6] = t.sig_l2f;
     for (int k = 0; k <= D2D_MAX_ORDER; ++k) f12[7 + k] = t.fnum[k];

@@ -447,6 +447,21 @@ def test_schedule_diagnostics_roundtrip():
         assert np.array_equal(ctx.get_map(), ref)
 
 
+def test_set_option_refuses_retired_names():
+    """Options whose default became the only behaviour are gone: d2d_set_option refuses their names like any unknown name, so a
+    caller who still sets one gets an error instead of a silent no-op.  A kept name is still accepted."""
+    from differt2d_amd import _lib as L
+    from differt2d_amd.engine import Context
+
+    retired = ("prep_fused", "nan_scan_async", "nan_scan_prio", "side_stream", "sig_narrow_filter", "sched_key_mode")
+    with Context(0) as ctx:
+        for name in retired:
+            for value in (0, 1):
+                with pytest.raises(L.D2DError, match="D2D_ERR_INVALID.*unknown option"):
+                    ctx.set_option(name, value)
+        ctx.set_option("hidden_min_tiles", 400)
+
+
 def test_resident_results_are_invalidated_with_what_they_were_computed_for():
     """include/d2d.h promises D2D_ERR_STATE, not stale or out-of-bounds reads: the per-cell gradient map belongs to the
     grid it was swept on, the scene VJP to the scene; a rejected d2d_set_scene leaves the previous scene in place."""

@@ -217,11 +217,11 @@ def test_libd2d_host_logic_under_asan_and_ubsan(asan, tmp_path):
         L.san_region_plan(2**31 - 1, 2**31 - 1, 50, 0, 2, 1, 1, 0, 2**62, 128, o)
         assert o[0] == 0                                                            # 2^62 regions: refused
         # ---- scalar thresholds of a sweep (sweep_thresholds): edge inputs, then values recorded from the inline code it replaced
-        L.san_sweep_thresholds.argtypes = [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.san_sweep_thresholds.argtypes = [C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.san_sweep_thresholds.restype = None
-        def thresholds(p, grad, narrow):
+        def thresholds(p, grad):
             d, f, i = np.zeros(3, np.float64), np.zeros(12, np.float32), np.zeros(3, np.int32)   # EXACTLY as many as it writes
-            L.san_sweep_thresholds(C.byref(p), grad, narrow, d.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p))
+            L.san_sweep_thresholds(C.byref(p), grad, d.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p))
             return d, f, i
         n_thr = 0
         for approx, act in ((0, 0), (1, 0), (1, 1)):                      # hard, hard_sigmoid, sigmoid
@@ -230,48 +230,47 @@ def test_libd2d_host_logic_under_asan_and_ubsan(asan, tmp_path):
                     for r_coef, height in ((0.5, 0.1), (-0.5, 0.1), (-3.0, 0.0), (0.5, 0.0)):
                         for fun_id in range(5):
                             for grad in (0, 1):
-                                for narrow in (0, 1):
-                                    p = params(approx=approx, act=act, tol=tol, alpha=alpha, r_coef=r_coef, height=height, fun_id=fun_id)
-                                    d, f, i = thresholds(p, grad, narrow)
-                                    mode = 0 if not approx else (1 if act == 0 else 2)
-                                    assert i[0] == mode and f[7] == 1.0 and f[8] == np.float32(r_coef) and f[5] == np.float32(height) * np.float32(height)
-                                    assert (d[0] == 0.0) == (not approx) and d[1] <= d[0] * (1 + 1e-5)
-                                    assert d[2] == (17.5 / np.float64(np.float32(alpha)) if (mode == 2 and not grad and narrow) else d[0])
-                                    assert not (f[0] > f[1]) and not (f[2] > f[3])
-                                    assert (f[4] == -1.0) == (not np.float32(tol) > np.float32(1e-30))
-                                    assert fun_id != 4 or i[1] == 0
-                                    assert approx or i[2] == (np.float32(tol) <= 0.5)
-                                    n_thr += 1
-        assert n_thr == 3 * 4 * 5 * 4 * 5 * 2 * 2
+                                p = params(approx=approx, act=act, tol=tol, alpha=alpha, r_coef=r_coef, height=height, fun_id=fun_id)
+                                d, f, i = thresholds(p, grad)
+                                mode = 0 if not approx else (1 if act == 0 else 2)
+                                assert i[0] == mode and f[7] == 1.0 and f[8] == np.float32(r_coef) and f[5] == np.float32(height) * np.float32(height)
+                                assert (d[0] == 0.0) == (not approx) and d[1] <= d[0] * (1 + 1e-5)
+                                assert d[2] == (17.5 / np.float64(np.float32(alpha)) if (mode == 2 and not grad) else d[0])
+                                assert not (f[0] > f[1]) and not (f[2] > f[3])
+                                assert (f[4] == -1.0) == (not np.float32(tol) > np.float32(1e-30))
+                                assert fun_id != 4 or i[1] == 0
+                                assert approx or i[2] == (np.float32(tol) <= 0.5)
+                                n_thr += 1
+        assert n_thr == 3 * 4 * 5 * 4 * 5 * 2
         recorded = [
-            (dict(approx=0, act=0, alpha=100, tol=0.00999999978, seg_tol=0.00499999989, r_coef=0.5, height=0.100000001, fun_id=0, min_order=0, max_order=2), 0, 1,
+            (dict(approx=0, act=0, alpha=100, tol=0.00999999978, seg_tol=0.00499999989, r_coef=0.5, height=0.100000001, fun_id=0, min_order=0, max_order=2), 0,
              [0x0000000000000000, 0x0000000000000000, 0x0000000000000000],
              [0xbba3d775, 0x3f80a42b, 0x8da24260, 0x3f800054, 0x3c23ad19, 0x3c23d70b, 0x40d4a2a9, 0x3f800000, 0x3f000000, 0x3e800000, 0x3e000000, 0x3d800000],
              [0, 1, 1]),
-            (dict(approx=1, act=0, alpha=100, tol=0.5, seg_tol=0.00499999989, r_coef=-0.5, height=0.100000001, fun_id=0, min_order=0, max_order=2), 1, 1,
+            (dict(approx=1, act=0, alpha=100, tol=0.5, seg_tol=0.00499999989, r_coef=-0.5, height=0.100000001, fun_id=0, min_order=0, max_order=2), 1,
              [0x3f9eb851eb851eb8, 0x3f9eb8660d7b12c6, 0x3f9eb851eb851eb8],
              [0xbd0f5c87, 0x3f847b38, 0xbcf5c330, 0x3f83d761, 0x327ae148, 0x3c23d70b, 0x40d4a2a9, 0x3f800000, 0xbf000000, 0x3e800000, 0xbe000000, 0x3d800000],
              [1, 0, 1]),
-            (dict(approx=1, act=1, alpha=10, tol=0.5, seg_tol=0, r_coef=0.5, height=1, fun_id=0, min_order=0, max_order=3), 0, 1,
+            (dict(approx=1, act=1, alpha=10, tol=0.5, seg_tol=0, r_coef=0.5, height=1, fun_id=0, min_order=0, max_order=3), 0,
              [0x4021cccccccccccd, 0x3ffc0012599ed7c8, 0x3ffc000000000000],
              [0xbfe00093, 0x40300073, 0xc10e66c4, 0x411e66ce, 0x327ae148, 0x3f800000, 0x3a83126f, 0x3f800000, 0x3f000000, 0x3e800000, 0x3e000000, 0x3d800000],
              [2, 1, 0]),
-            (dict(approx=1, act=1, alpha=1000000, tol=1, seg_tol=0.00499999989, r_coef=0.5, height=0.100000001, fun_id=3, min_order=1, max_order=4), 0, 0,
-             [0x3f1754b05b7cfe58, 0x3ef259aade68eb21, 0x3f1754b05b7cfe58],
-             [0xbba6c20d, 0x3f80a716, 0xb8baa5fd, 0x3f80033e, 0x32fae148, 0x3c23d70b, 0x00000000, 0x3f800000, 0x3f000000, 0x3e800000, 0x3e000000, 0x3d800000],
+            (dict(approx=1, act=1, alpha=1000000, tol=1, seg_tol=0.00499999989, r_coef=0.5, height=0.100000001, fun_id=3, min_order=1, max_order=4), 0,
+             [0x3f1754b05b7cfe58, 0x3ef259aade68eb21, 0x3ef2599ed7c6fbd2],
+             [0xbba46a43, 0x3f80a4be, 0xb8baa5fd, 0x3f80033e, 0x32fae148, 0x3c23d70b, 0x00000000, 0x3f800000, 0x3f000000, 0x3e800000, 0x3e000000, 0x3d800000],
              [2, 1, 0]),
-            (dict(approx=1, act=1, alpha=9.99999997e-07, tol=0, seg_tol=0.00499999989, r_coef=-3, height=0, fun_id=1, min_order=0, max_order=2), 1, 1,
+            (dict(approx=1, act=1, alpha=9.99999997e-07, tol=0, seg_tol=0.00499999989, r_coef=-3, height=0, fun_id=1, min_order=0, max_order=2), 1,
              [0x4195382100e618a6, 0x4170b080f0b4f9f7, 0x4195382100e618a6],
              [0xcca9c177, 0x4ca9c177, 0xcca9c177, 0x4ca9c177, 0xbf800000, 0x00000000, 0x7149f2ca, 0x3f800000, 0xc0400000, 0x41100000, 0xc1d80000, 0x42a20000],
              [2, 1, 0]),
-            (dict(approx=0, act=1, alpha=100, tol=9.99999935e-39, seg_tol=0, r_coef=-0.5, height=0, fun_id=4, min_order=1, max_order=4), 1, 0,
+            (dict(approx=0, act=1, alpha=100, tol=9.99999935e-39, seg_tol=0, r_coef=-0.5, height=0, fun_id=4, min_order=1, max_order=4), 1,
              [0x0000000000000000, 0x0000000000000000, 0x0000000000000000],
              [0x8da24260, 0x3f800054, 0x8da24260, 0x3f800054, 0xbf800000, 0x00000000, 0x7149f2ca, 0x3f800000, 0xbf000000, 0x3e800000, 0xbe000000, 0x3d800000],
              [0, 0, 1]),
         ]
-        for kw, grad, narrow, want_d, want_f, want_i in recorded:
-            d, f, i = thresholds(params(**kw), grad, narrow)
-            assert d.view(np.uint64).tolist() == want_d and f.view(np.uint32).tolist() == want_f and i.tolist() == want_i, (kw, grad, narrow)
+        for kw, grad, want_d, want_f, want_i in recorded:
+            d, f, i = thresholds(params(**kw), grad)
+            assert d.view(np.uint64).tolist() == want_d and f.view(np.uint32).tolist() == want_f and i.tolist() == want_i, (kw, grad)
         # ---- cells per chunk of the reverse sweep's trajectory store (opt_chunk_cells): edge inputs, then recorded values
         L.san_opt_chunk_cells.argtypes = [C.c_longlong] * 3 + [C.c_int] + [C.c_longlong] * 2
         L.san_opt_chunk_cells.restype = C.c_longlong
