@@ -22,7 +22,7 @@ D2D_MAX_ORDER = 4
 D2D_NUM_STATS = 16
 D2D_COMM_ID_BYTES = 128
 D2D_OPT_ADAM, D2D_OPT_SGD, D2D_OPT_SGD_MOMENTUM = 0, 1, 2  # d2d_set_optimizer kinds
-D2D_ABI_VERSION = 10
+D2D_ABI_VERSION = 11
 
 D2D_WALL, D2D_RIS, D2D_VERTEX = 0, 1, 2
 SOLVER_IMAGE, SOLVER_MINPATH, SOLVER_FERMAT = 0, 1, 2
@@ -128,6 +128,10 @@ SYMBOLS = [
     ("d2d_trace_paths", C.c_int, [_ctx, C.POINTER(Params), _f32p, _f32p, C.c_int32, _i32p, _i32p, C.c_int32,
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    ("d2d_valid_paths", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.POINTER(C.c_int64)]),
+    ("d2d_get_valid_paths", C.c_int, [_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    ("d2d_debug_valid_paths_ms", C.c_int, [_ctx, np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")]),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),
@@ -213,3 +217,44 @@ def enumerate_candidates(num_nodes: int, min_order: int = 0, max_order: int = 1,
     check(lib.d2d_enumerate_candidates(int(num_nodes), ap, int(min_order), int(max_order),
                                        cand.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), n.value))
     return [cand[i, : order[i]].copy() for i in range(n.value)]
+
+
+def candidate_rank(cand, order, n_objects: int, allowed=None, min_order: int = 0, max_order: int = 1) -> np.ndarray:
+    """Position of each wall tuple in :func:`enumerate_candidates`' list (int64), vectorised: orders ``min_order..max_order``
+    ascending, lexicographic over the allowed objects, no equal neighbours -- the inverse of the enumeration.
+
+    ``cand``: (n, >= max order present) object indices, entries beyond ``order[i]`` ignored; ``order``: (n,).  Every tuple of
+    k walls has ``(A - 1) ** (k - j)`` completions after its first j walls (A = allowed objects), whatever those walls are,
+    so the rank inside an order is a mixed-radix number: the first wall's position among the allowed objects, then for each
+    later wall its position among the allowed objects other than its predecessor.  A tuple the enumeration does not hold (an
+    object that is not allowed, equal neighbours, an order outside the range) raises ``ValueError``."""
+    cand = np.asarray(cand, dtype=np.int64)
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    if order.size == 0:
+        return np.zeros(0, np.int64)
+    cand = cand.reshape(order.size, -1)
+    n_objects, min_order, max_order = int(n_objects), int(min_order), int(max_order)
+    ok = np.ones(n_objects, bool) if allowed is None else np.asarray(allowed).reshape(-1) != 0
+    if ok.size != n_objects:
+        raise ValueError("allowed must have one entry per object")
+    A = int(ok.sum())
+    pos = np.cumsum(ok) - 1  # position of an allowed object among the allowed ones
+    count = lambda k: 1 if k == 0 else A * (A - 1) ** (k - 1)
+    base = np.zeros(max(max_order, 0) + 2, np.int64)  # base[k] = candidates of the orders below k
+    for k in range(max(min_order, 0), max_order + 1):
+        base[k + 1] = base[k] + count(k)
+    if order.min() < max(min_order, 0) or order.max() > max_order or order.max() > cand.shape[1]:
+        raise ValueError("an order lies outside min_order..max_order (or beyond the columns of cand)")
+    rank = base[order].copy()
+    prev = np.full(order.size, -1, np.int64)
+    for i in range(int(order.max())):
+        live = order > i
+        w = np.where(live, cand[:, min(i, cand.shape[1] - 1)], 0)
+        if ((w < 0) | (w >= n_objects)).any() or not ok[w[live]].all() or (live & (i > 0) & (w == prev)).any():
+            raise ValueError("a tuple names an object that is not allowed, or the same object twice in a row")
+        p = pos[w]
+        digit = p if i == 0 else p - (p > pos[np.where(live & (prev >= 0), prev, 0)])
+        weight = np.where(live, np.power(np.int64(max(A - 1, 0)), np.maximum(order - 1 - i, 0)), 0)
+        rank += np.where(live, digit * weight, 0)
+        prev = np.where(live, w, prev)
+    return rank

@@ -44,6 +44,9 @@ template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid
     template <> hipError_t launch_fwd_grad_listed_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);        \
     template <> hipError_t launch_fwd_split_listed_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&); \
     template <> hipError_t launch_fwd_coop_m<M>(int, int, dim3, size_t, hipStream_t, const SweepArgs&);
+template <int MODE> hipError_t launch_rec_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r);
+template <> hipError_t launch_rec_m<MODE_HARD>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
+template <> hipError_t launch_rec_m<MODE_HSIG>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
 D2D_DECLARE_MODE(MODE_HARD)
 D2D_DECLARE_MODE(MODE_HSIG)
 D2D_DECLARE_MODE(MODE_SIG)
@@ -79,6 +82,11 @@ hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid
 }
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     D2D_BY_MODE(launch_vg_m, txg, grad, grid, lds, s, a)
+}
+hipError_t launch_rec(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
+    if (mode == MODE_HARD) return launch_rec_m<MODE_HARD>(txg, max_order, grid, lds, s, a, r);
+    if (mode == MODE_HSIG) return launch_rec_m<MODE_HSIG>(txg, max_order, grid, lds, s, a, r);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace d2d
@@ -177,6 +185,19 @@ struct d2d_ctx {
     // trace scratch
     DevBuf<int> d_tcand, d_torder;
     DevBuf<float> d_ttx, d_trx, d_txys_in, d_tloss_in, d_txys, d_tloss, d_tvalid, d_ton, d_thit, d_tlen;
+    // record launch of the culled sweep (d2d_valid_paths): kept between calls, grown when needed, dropped with the grid
+    DevBuf<unsigned long long> d_rec_shadow;  // its own shadow masks: the sweeps' rotating sets are not touched
+    DevBuf<int> d_rec_counts, d_rec_offs, d_rec_flag, d_rec_cell, d_rec_cand, d_rec_order;
+    DevBuf<int4> d_rec;
+    DevBuf<float> d_rec_xys, d_rec_loss, d_rec_valid, d_rec_len;
+    long long rec_n = -1;  // records the buffers hold (-1: none)
+    hipEvent_t ev_rec[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // "time_kernel": around pass 1, pass 2 and the trace
+    bool have_rec_time = false;
+    void drop_records() {
+        d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
+        d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
+        rec_n = -1;
+    }
     // grid
     int m = 0, n = 0;
     bool have_grid = false;
@@ -681,6 +702,9 @@ void d2d_destroy(d2d_ctx* c) {
     c->d_pair.release();
     c->d_grad.release(); c->d_cot.release(); c->d_partial.release(); c->d_vjp.release();
     c->d_cust_f.release(); c->d_cust_pb.release();
+    c->drop_records(); c->d_rec_shadow.release(); c->d_rec_flag.release();
+    for (hipEvent_t e : c->ev_rec)
+        if (e) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
@@ -873,6 +897,8 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->have_grid = false;
         c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
         c->grid_version += 1;  // ... and the regions' bounding boxes another grid
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->drop_records();  // ... and the records' cells
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -1394,18 +1420,21 @@ static int prep_pair_masks(d2d_ctx* c, Sweep& s, const MaskWindow& w, float ext)
 }
 
 // first-segment shadow coverage (RX grids: the fixed end point is the transmitter) and the pair masks
-static int prep_masks(d2d_ctx* c, Sweep& s, Prep& pr) {
+// (`own`: a record launch's masks go to a buffer of its own -- nothing behind them to zero, no fork event -- so that the
+// rotating sets stay what the sweeps left)
+static int prep_masks(d2d_ctx* c, Sweep& s, Prep& pr, DevBuf<unsigned long long>* own = nullptr) {
     const d2d_params* p = s.p;
     d2d::SweepArgs& a = s.a;
     int rc;
     if (!((!s.txg || s.txg_culled) && c->N >= 2 && p->max_order >= 1)) return D2D_OK;
+    DevBuf<unsigned long long>& buf = own ? *own : c->cur.d_shadow;
     // [N] masks, then the {histogram, cursors} of the patch schedule's counting sort, then what the region lists need
     // zeroed per launch ({queue length, pool head}, one flag per leaf region): one memset for all of it
     const size_t rl_regions = (size_t)((s.tiles_x + c->region_size - 1) / c->region_size) * (size_t)((s.tiles_y + c->region_size - 1) / c->region_size);
     // (a multiple of 256 bytes: the runtime fills odd tails with a second kernel)
-    const size_t zero_words = ((size_t)c->N + d2d::SCHED_KEYS + (2 + rl_regions + 1) / 2 + 31) & ~(size_t)31;
-    if ((rc = c->cur.d_shadow.ensure(zero_words))) return rc;
-    pr.zeroed = true;
+    const size_t zero_words = own ? (size_t)c->N : ((size_t)c->N + d2d::SCHED_KEYS + (2 + rl_regions + 1) / 2 + 31) & ~(size_t)31;
+    if ((rc = buf.ensure(zero_words))) return rc;
+    pr.zeroed = !own;
     // window where a test is certainly "hit" (hard) / exactly saturated to 1 (approx): shrink [-tol, 1+tol] by widen
     MaskWindow& w = pr.win;
     w.in_lo = -(double)p->seg_tol + s.th.widen_in;
@@ -1421,11 +1450,11 @@ static int prep_masks(d2d_ctx* c, Sweep& s, Prep& pr) {
     const long n_zero = (long)zero_words - c->N;
     hipLaunchKernelGGL(d2d::shadow_fill_kernel, dim3((unsigned)(c->N + (n_zero + 255) / 256)), dim3(256), 0, s.ps, c->d_occl.p, c->d_refl.p,
                        c->d_kind.p, c->N, s.tx[0], s.tx[1], (float)(w.in_lo + 1e-4), (float)(w.in_hi - 1e-4), dperp, (float)w.dom_lo,
-                       (float)w.dom_w, w.ok ? 1 : 0, c->cur.d_shadow.p, c->cur.d_shadow.p + c->N, n_zero);
+                       (float)w.dom_w, w.ok ? 1 : 0, buf.p, buf.p + c->N, n_zero);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the sort of a big launch needs its counters zeroed: it may start here)
+    if (!own) HIP_TRY(hipEventRecord(c->ev_fork, s.ps));  // (the sort of a big launch needs its counters zeroed: it may start here)
     if (!w.ok) return D2D_OK;
-    a.shadow = c->cur.d_shadow.p;
+    a.shadow = buf.p;
     a.shadow_dperp = dperp;
     a.shadow_lo = (float)w.dom_lo;
     a.shadow_inv = (float)(1.0 / w.dom_w);
@@ -2016,9 +2045,182 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     return launch_rx_values(c, s, pr);
 }
 
+// Record launch of the culled forward sweep: pass 1 counts the (cell, candidate) pairs with valid != 0 per patch, the host scans
+// the counts, pass 2 writes the records, trace_rec_kernel solves their paths.  Everything runs on the main stream, behind whatever
+// the context has in flight, with masks of its own: the sweeps' rotating sets, work history, schedule and value map are not touched.
+static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int64_t* count) {
+    if (!c || !fixed || !count) return fail(D2D_ERR_INVALID, "NULL argument");
+    *count = 0;
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_valid_paths");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_valid_paths");
+    if (p_in->solver != D2D_SOLVER_IMAGE) return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths covers ImagePath only (solver %d)", p_in->solver);
+    if (p_in->approx && p_in->act != D2D_ACT_HARD_SIGMOID)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths covers hard and hard_sigmoid validity: the sigmoid sweeps skip candidates by the fused function's running sum");
+    d2d_params pp = *p_in;
+    pp.fun_id = D2D_FUN_ONE;  // a contribution is then the validity itself
+    pp.out_mode = D2D_OUT_OVERWRITE;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    if ((rc = check_image_sweep(c, p, nullptr))) return rc;
+    if (c->N > 4095) return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: %d objects exceed the records' 12-bit object indices", c->N);
+    if ((long long)c->m * c->n > 0x7fffffffLL) return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: the grid exceeds the records' 31-bit cell indices");
+    if ((rc = set_device(c))) return rc;
+    if ((rc = upload_occl(c, p->patch))) return rc;
+    c->rec_n = -1;
+    c->have_rec_time = false;
+
+    Sweep s;
+    s.p = p;
+    s.tx = fixed;
+    s.d_stats = nullptr;
+    s.grad_mode = 0;
+    s.tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
+    s.tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
+    s.tiles = (long long)s.tiles_x * s.tiles_y;
+    s.piped = false;
+    s.ps = c->stream;
+    Prep pr;
+    const long long fallbacks = c->txg_fallbacks;
+    if ((rc = sweep_args(c, s))) return rc;
+    c->txg_fallbacks = fallbacks;  // (sweep_args counts a sweep that falls back; this launch refuses instead)
+    if (s.txg && !s.txg_culled)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: a TX-grid sweep with these parameters is not culled (%s)",
+                    c->txg_exhaustive ? "the \"txg_exhaustive\" option is set" : "a degenerate path is not exactly invalid under tol / alpha");
+    if ((rc = prep_masks(c, s, pr, &c->d_rec_shadow))) return rc;
+    d2d::SweepArgs& a = s.a;
+    a.out = nullptr;  // never written by the record build
+    const size_t lds = d2d_host::tab_lds_bytes(c->N);  // tables + one culling queue
+    if (lds > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table (max ~2400)", c->N);
+    a.cullq_off = (int)((size_t)(4 * c->N + 1) * sizeof(float4));
+    const size_t tiles = (size_t)s.tiles;
+    if ((rc = c->d_rec_counts.ensure(tiles)) || (rc = c->d_rec_offs.ensure(tiles + 1)) || (rc = c->d_rec_flag.ensure(1))) return rc;
+    const bool timed = c->time_kernel;
+    if (timed)
+        for (hipEvent_t& e : c->ev_rec)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemsetAsync(c->d_rec_flag.p, 0, sizeof(int), c->stream));
+    d2d::RecArgs r;
+    r.counts = c->d_rec_counts.p;
+    r.offs = c->d_rec_offs.p;
+    r.rec = nullptr;
+    r.flag = c->d_rec_flag.p;
+    // pass 1: count
+    if (timed) HIP_TRY(hipEventRecord(c->ev_rec[0], c->stream));
+    HIP_TRY(d2d::launch_rec(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
+    if (timed) HIP_TRY(hipEventRecord(c->ev_rec[1], c->stream));
+    std::vector<int> offs(tiles + 1);
+    HIP_TRY(hipMemcpyAsync(offs.data() + 1, c->d_rec_counts.p, tiles * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // exclusive scan on the host (4 bytes per patch; the call is synchronous anyway)
+    long long total = 0;
+    offs[0] = 0;
+    for (size_t i = 1; i <= tiles; ++i) {
+        if (offs[i] < 0) return fail(D2D_ERR_STATE, "d2d_valid_paths: patch %zu counted %d records", i - 1, offs[i]);
+        total += offs[i];
+        offs[i] = (int)std::min<long long>(total, 0x7fffffffLL);
+    }
+    // what the records and their paths take: 16 B + cell, cand[4], order + xys[6][2], loss, valid, length
+    constexpr size_t NPTS = D2D_MAX_ORDER + 2;
+    const size_t per_record = sizeof(int4) + (2 + D2D_MAX_ORDER) * sizeof(int) + (NPTS * 2 + 3) * sizeof(float);
+    size_t mem_free = 0, mem_total = 0;
+    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+    // (half of what is free, plus what the buffers hold already; 2^30 records: positions are 32-bit)
+    const size_t held = c->d_rec.n * per_record;
+    *count = total;
+    if (total > (1ll << 30) || (size_t)total * per_record > (mem_free + held) / 2)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: %lld records (%zu bytes each) exceed half of the free device memory (%zu bytes free)",
+                    total, per_record, mem_free);
+    if (total == 0) {
+        c->rec_n = 0;
+        return D2D_OK;
+    }
+    const size_t n = (size_t)total;
+    if ((rc = c->d_rec.ensure(n)) || (rc = c->d_rec_cell.ensure(n)) || (rc = c->d_rec_cand.ensure(n * D2D_MAX_ORDER)) ||
+        (rc = c->d_rec_order.ensure(n)) || (rc = c->d_rec_xys.ensure(n * NPTS * 2)) || (rc = c->d_rec_loss.ensure(n)) ||
+        (rc = c->d_rec_valid.ensure(n)) || (rc = c->d_rec_len.ensure(n)))
+        return rc;
+    // (c->rec_n stays -1 until everything below is through)
+    HIP_TRY(hipMemcpyAsync(c->d_rec_offs.p, offs.data(), (tiles + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // a slot pass 2 does not write names no cell: trace_rec_kernel flags it instead of reading through it
+    HIP_TRY(hipMemsetAsync(c->d_rec.p, 0xff, n * sizeof(int4), c->stream));
+    // pass 2: the same sweep, writing
+    r.rec = c->d_rec.p;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_rec[2], c->stream));
+    HIP_TRY(d2d::launch_rec(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
+    if (timed) HIP_TRY(hipEventRecord(c->ev_rec[3], c->stream));
+    // stage 2: the paths of the records
+    d2d::TraceArgs t;
+    memset(&t, 0, sizeof t);
+    t.T = obj_tables(c);
+    t.solver = D2D_SOLVER_IMAGE;
+    t.xys = c->d_rec_xys.p;
+    t.loss = c->d_rec_loss.p;
+    t.valid = c->d_rec_valid.p;
+    t.length = c->d_rec_len.p;
+    set_validity(t, p);
+    d2d::RecTraceArgs q;
+    q.rec = c->d_rec.p;
+    q.n = (long)n;
+    q.X = c->d_X.p;
+    q.Y = c->d_Y.p;
+    q.cells = (long)c->m * c->n;
+    q.fx = fixed[0];
+    q.fy = fixed[1];
+    q.txg = s.txg ? 1 : 0;
+    q.cell = c->d_rec_cell.p;
+    q.cand = c->d_rec_cand.p;
+    q.order = c->d_rec_order.p;
+    q.flag = c->d_rec_flag.p;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_rec[4], c->stream));
+    hipLaunchKernelGGL(d2d::trace_rec_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, t, q);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(c->ev_rec[5], c->stream));
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, c->d_rec_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flag) return fail(D2D_ERR_STATE, "d2d_valid_paths: the two passes of the record launch disagree (%lld records counted)", total);
+    c->rec_n = total;
+    c->have_rec_time = timed;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_valid_paths(d2d_ctx* c, const d2d_params* p, const float* fixed, int64_t* count) { return valid_paths(c, p, fixed, count); }
+
+int d2d_get_valid_paths(d2d_ctx* c, int64_t capacity, int32_t* cell, int32_t* cand, int32_t* order, float* xys, float* loss, float* valid,
+                        float* length) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (c->rec_n < 0) return fail(D2D_ERR_STATE, "d2d_valid_paths must come first (its records go with the grid)");
+    if (capacity < c->rec_n) return fail(D2D_ERR_INVALID, "capacity %lld is less than the %lld records held", (long long)capacity, c->rec_n);
+    const size_t n = (size_t)c->rec_n;
+    if (n == 0) return D2D_OK;
+    int rc = set_device(c);
+    if (rc) return rc;
+    constexpr size_t NPTS = D2D_MAX_ORDER + 2;
+    if (cell) HIP_TRY(hipMemcpyAsync(cell, c->d_rec_cell.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (cand) HIP_TRY(hipMemcpyAsync(cand, c->d_rec_cand.p, n * D2D_MAX_ORDER * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (order) HIP_TRY(hipMemcpyAsync(order, c->d_rec_order.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (xys) HIP_TRY(hipMemcpyAsync(xys, c->d_rec_xys.p, n * NPTS * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (loss) HIP_TRY(hipMemcpyAsync(loss, c->d_rec_loss.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (valid) HIP_TRY(hipMemcpyAsync(valid, c->d_rec_valid.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (length) HIP_TRY(hipMemcpyAsync(length, c->d_rec_len.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
+
+int d2d_debug_valid_paths_ms(d2d_ctx* c, float* ms) {
+    if (!c || !ms) return fail(D2D_ERR_INVALID, "NULL argument");
+    if (!c->have_rec_time) return fail(D2D_ERR_STATE, "no timed d2d_valid_paths yet (set the \"time_kernel\" option; a call without records has no pass 2)");
+    HIP_TRY(hipEventElapsedTime(&ms[0], c->ev_rec[0], c->ev_rec[1]));
+    HIP_TRY(hipEventElapsedTime(&ms[1], c->ev_rec[2], c->ev_rec[3]));
+    HIP_TRY(hipEventElapsedTime(&ms[2], c->ev_rec[4], c->ev_rec[5]));
+    return D2D_OK;
+}
 
 int d2d_power_map_launch(d2d_ctx* c, const d2d_params* p, const float* tx) { return sweep_launch(c, p, tx, nullptr); }
 

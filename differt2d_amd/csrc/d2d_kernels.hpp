@@ -1580,6 +1580,30 @@ struct ListSink {
     }
 };
 
+// Record build (power_rec_kernel): every (cell, candidate) whose contribution is not exactly zero is handed out as a record
+// instead of being added.  Two passes of the same deterministic sweep: with rec == null the wave only counts (cnt is
+// wave-uniform: the popcount of the ballot of pushing lanes); else every pushing lane stores its record at
+// base + count so far + the pushing lanes below it -- never at or past `limit`, the next patch's offset: a position outside
+// [base, limit) raises the sticky flag instead.  A record: {cell (row-major), code bits 0..31, code bits 32..47 | order << 24,
+// the contribution's bits}; code = 12 bits per wall index, first wall lowest.
+struct RecSink {
+    int4* rec;
+    int base, limit;
+    int cnt;
+    int cell;  // this lane's cell; < 0: a clamped duplicate of a lane outside the grid, which never pushes
+    int* flag;
+    __device__ __forceinline__ void put(float t, unsigned long long code, int k) {
+        const bool p = cell >= 0 && !(t == 0.0f);
+        const unsigned long long m = __ballot(p);
+        if (rec != nullptr && p) {
+            const int pos = base + cnt + __builtin_popcountll(m & ((1ull << (threadIdx.x & 63)) - 1ull));
+            if (pos >= base && pos < limit) rec[pos] = make_int4(cell, (int)(unsigned)(code & 0xffffffffull), (int)(unsigned)(code >> 32) | (k << 24), __float_as_int(t));
+            else *flag = 1;
+        }
+        cnt += __builtin_popcountll(m);
+    }
+};
+
 // Survivors of a region's culling, in candidate order (region_list_kernel / region_refine_kernel): wave-uniform state
 // of the list being written.
 struct EmitSink {
@@ -1624,12 +1648,14 @@ __device__ __forceinline__ void emit_batch(EmitSink& e, unsigned long long code,
 // acc: acc is never -0.0), so that another wave can add them later in the reference's order.
 // EMIT (K >= 2): nothing is evaluated; the survivors of the full culling test are appended to `emit` instead (the box is
 // then a region's, not a patch's).
-template <int K, int MODE, bool STATS, bool GRAD = false, bool LIST = false, bool EMIT = false>
+// RECORD: like LIST, but the contribution goes to `rsink` with the candidate's code (all lanes take part: RecSink::put).
+template <int K, int MODE, bool STATS, bool GRAD = false, bool LIST = false, bool EMIT = false, bool RECORD = false>
 __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const float4* tab, const float (&bx)[4],
                                                    const float (&by)[4], float rxx, float rxy, bool lane_bad, float& acc,
                                                    WaveStats& st, GradCtx* g = nullptr, int p_lo = 0,
                                                    int p_hi = 0x7fffffff, ListSink* sink = nullptr, EmitSink* emit = nullptr,
-                                                   const unsigned long long* hidden_row = nullptr, float hidden_dperp = 0.0f) {
+                                                   const unsigned long long* hidden_row = nullptr, float hidden_dperp = 0.0f,
+                                                   RecSink* rsink = nullptr) {
     static_assert(!EMIT || K >= 2, "lists exist for orders >= 2");
     const int lane = threadIdx.x & 63;
     int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
@@ -1726,7 +1752,11 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 ce[d] = (int)((cu >> (12 * d)) & 0xfffull);
                 image_of(ldc4(a.refl, 2 * ce[d]), d == 0 ? a.txx : ex[d > 0 ? d - 1 : 0], d == 0 ? a.txy : ey[d > 0 ? d - 1 : 0], ex[d], ey[d]);
             }
-            if (LIST) {
+            if constexpr (RECORD) {
+                float t = 0.0f;
+                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
+                rsink->put(t, cu, K);
+            } else if (LIST) {
                 float t = 0.0f;
                 eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
                 if (!(t == 0.0f)) sink->push(t);  // non-zero or NaN
@@ -1861,7 +1891,14 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 mask &= mask - 1;
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), pIx, pIy, imgx[K - 1], imgy[K - 1]);
-                if (LIST) {
+                if constexpr (RECORD) {
+                    float t = 0.0f;
+                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
+                    unsigned long long cu = 0ull;
+#pragma unroll
+                    for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
+                    rsink->put(t, cu, K);
+                } else if (LIST) {
                     float t = 0.0f;
                     eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
                     if (!(t == 0.0f)) sink->push(t);  // non-zero or NaN
@@ -2907,12 +2944,13 @@ __global__ void __launch_bounds__(64) region_refine_kernel(SweepArgs a, RegionLe
 // Prefix = (w_0 .. w_{K-2}) wave-uniform, lanes = last wall, survivors in ascending order: the reference's order.
 // EMIT (K >= 2; region_list_kernel): first-wall positions [p_lo, p_hi) only, the box is a region's, and the survivors are
 // appended to `emit` (in candidate order: prefix-major, last walls ascending) instead of being evaluated.
-template <int K, int MODE, bool GRAD = false, bool EMIT = false>
+// RECORD: the contributions go to `rsink` with the candidate's code instead of acc (power_rec_kernel).
+template <int K, int MODE, bool GRAD = false, bool EMIT = false, bool RECORD = false>
 __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const float4* tab, const float (&bx)[4],
                                                        const float (&by)[4], float cx, float cy, bool lane_bad, float& acc,
                                                        WaveStats& st, GradCtx* g = nullptr, int p_lo = 0, int p_hi = 0x7fffffff,
                                                        EmitSink* emit = nullptr, const unsigned long long* hidden_row = nullptr,
-                                                       float hidden_dperp = 0.0f) {
+                                                       float hidden_dperp = 0.0f, RecSink* rsink = nullptr) {
     static_assert(!EMIT || K >= 2, "lists exist for orders >= 2");
     const int lane = threadIdx.x & 63;
     int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
@@ -2973,7 +3011,16 @@ __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const
                 mask &= mask - 1;
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), K == 1 ? cx : imgx[K >= 2 ? K - 2 : 0], K == 1 ? cy : imgy[K >= 2 ? K - 2 : 0], imgx[K - 1], imgy[K - 1]);
-                eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, acc, st, g);
+                if constexpr (RECORD) {
+                    float t = 0.0f;
+                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g);
+                    unsigned long long cu = 0ull;
+#pragma unroll
+                    for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
+                    rsink->put(t, cu, K);
+                } else {
+                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, acc, st, g);
+                }
             }
         }
         if (K == 1) break;
@@ -3160,6 +3207,79 @@ __global__ void __launch_bounds__(64) power_fwd_txg_kernel(SweepArgs a) {
     for (int i = lane; i < a.N; i += 64) tab[2 * a.N + i] = ldc4(a.flt, i);
     __syncthreads();
     txg_patch<MODE, MAXK, GRADK, LISTED>(a, tab, wl, (long)blockIdx.x, false);
+}
+
+// Record build of the culled forward sweep (d2d_valid_paths): one wave per 8 x 8 patch in row-major patch order, no schedule, no
+// cut patches, no region lists; the host sets fun_id = D2D_FUN_ONE, so a candidate's contribution is its validity itself (never
+// NaN: nan_to_num).  It touches neither the value map nor the work history.  Pass 1 (r.rec == null) writes the patch's number of
+// records to r.counts; pass 2 writes the records at r.offs[patch] .. r.offs[patch + 1] (see RecSink).
+struct RecArgs {
+    int* counts;      // [patches]
+    const int* offs;  // [patches + 1] exclusive scan of counts
+    int4* rec;        // [offs[patches]] or null
+    int* flag;        // != 0 afterwards: pass 2 met a position outside its patch's range (the passes disagree: an internal error)
+};
+template <int MODE, int MAXK, bool TXG>
+__global__ void __launch_bounds__(64) power_rec_kernel(SweepArgs a, RecArgs r) {
+    const int lane = threadIdx.x & 63;
+    extern __shared__ float4 tab[];  // [2N] refl, [N] flt, then (a.cullq_off) the culling queue
+    for (int i = lane; i < 2 * a.N; i += 64) tab[i] = ldc4(a.refl, i);
+    for (int i = lane; i < a.N; i += 64) tab[2 * a.N + i] = ldc4(a.flt, i);
+    __syncthreads();
+    const int tiles_x = (a.n + TILE_W - 1) / TILE_W;
+    const long tile = (long)blockIdx.x;
+    const int tcol = (int)(tile % tiles_x), trow = (int)(tile / tiles_x);
+    const int col = tcol * TILE_W + (lane & (TILE_W - 1));
+    const int row = trow * TILE_H + (lane / TILE_W);
+    const bool in_range = (col < a.n) && (row < a.m);
+    const int ccol = col < a.n ? col : a.n - 1;
+    const int crow = row < a.m ? row : a.m - 1;
+    const long idx = (long)crow * a.n + ccol;
+    const float cx = a.X[idx], cy = a.Y[idx];
+    const bool lane_bad = !(fabsf(cx) < 1e18f) || !(fabsf(cy) < 1e18f) || !(fabsf(a.txx) < 1e18f) || !(fabsf(a.txy) < 1e18f);
+    WaveStats st;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) st.c[i] = 0;
+    st.shadow = -1;
+    st.work = 0;
+    // bounding box of the wave's cells (NaN / inf coordinates make every comparison fail: nothing is culled)
+    float x0 = cx, x1 = cx, y0 = cy, y1 = cy;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        x0 = fminf(x0, __shfl_xor(x0, off, 64));
+        x1 = fmaxf(x1, __shfl_xor(x1, off, 64));
+        y0 = fminf(y0, __shfl_xor(y0, off, 64));
+        y1 = fmaxf(y1, __shfl_xor(y1, off, 64));
+    }
+    const bool box_ok = !wave_any(lane_bad);
+    const float qn = __builtin_nanf("");
+    const float bx[4] = {box_ok ? x0 : qn, x1, x1, x0};
+    const float by[4] = {y0, y0, y1, y1};
+    RecSink sink;
+    sink.rec = r.rec;
+    sink.base = r.rec ? r.offs[tile] : 0;
+    sink.limit = r.rec ? r.offs[tile + 1] : 0;
+    sink.cnt = 0;
+    sink.cell = in_range ? (int)idx : -1;
+    sink.flag = r.flag;
+    float dummy = 0.0f;
+    if (a.min_order <= 0 && a.max_order >= 0) {
+        float t = 0.0f;
+        if constexpr (TXG) sweep_order<0, MODE, false, false, true>(a, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr);
+        else sweep_order<0, MODE, false, false>(a, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr);
+        sink.put(t, 0ull, 0);
+    }
+    static_for<1, MAXK + 1>([&](auto KK) {
+        constexpr int K = decltype(KK)::value;
+        if (a.min_order <= K && a.max_order >= K) {
+            if constexpr (TXG)
+                sweep_order_culled_txg<K, MODE, false, false, true>(a, tab, bx, by, cx, cy, lane_bad, dummy, st, nullptr, 0, 0x7fffffff, nullptr, nullptr, 0.0f, &sink);
+            else
+                sweep_order_culled<K, MODE, false, false, false, false, true>(a, tab, bx, by, cx, cy, lane_bad, dummy, st, nullptr, 0, 0x7fffffff, nullptr, nullptr,
+                                                                              nullptr, 0.0f, &sink);
+        }
+    });
+    if (r.rec == nullptr && lane == 0) r.counts[tile] = sink.cnt;
 }
 
 // Patch schedule.  The hardware starts workgroups in blockIdx order, and a dear patch that starts late is the tail of the
@@ -4230,17 +4350,12 @@ struct TraceArgs {
 // One thread per (tx/rx pair, candidate).  Serves Scene.all_paths / all_valid_paths / accumulate_over_paths
 // (scene.py:1156-1334), {Image,Min,Fermat}Path.from_tx_objects_rx and Path.is_valid / on_objects /
 // intersects_with_objects (geometry.py:821-963) of the host mirror.
+// Row `tid` of a trace: candidate c = the walls cd[0 .. k) between (txx, txy) and (rxx, rxy) -- solved (or taken from xys_in),
+// evaluated against the scene and written out.  Shared by trace_kernel and trace_rec_kernel.
 template <bool SGD>
-__global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long)a.P * a.C) return;
-    const int p = (int)(tid / a.C), c = (int)(tid % a.C);
-    const int k = a.order[c];
-    int cd[D2D_MAX_ORDER];
-#pragma unroll
-    for (int i = 0; i < D2D_MAX_ORDER; ++i) cd[i] = a.cand[c * D2D_MAX_ORDER + i];
+__device__ __forceinline__ void trace_one(const TraceArgs& a, long tid, int c, int k, const int (&cd)[D2D_MAX_ORDER], float txx, float txy,
+                                          float rxx, float rxy) {
     float px[NP], py[NP];
-    const float txx = a.tx[2 * p], txy = a.tx[2 * p + 1], rxx = a.rx[2 * p], rxy = a.rx[2 * p + 1];
     const Truth L{a.mode, a.alpha};
     float loss = 0.0f;
     if (a.xys_in) {
@@ -4271,6 +4386,61 @@ __global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
     if (a.on) a.on[tid] = on;
     if (a.hit) a.hit[tid] = hit;
     if (a.length) a.length[tid] = r;
+}
+
+template <bool SGD>
+__global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= (long)a.P * a.C) return;
+    const int p = (int)(tid / a.C), c = (int)(tid % a.C);
+    const int k = a.order[c];
+    int cd[D2D_MAX_ORDER];
+#pragma unroll
+    for (int i = 0; i < D2D_MAX_ORDER; ++i) cd[i] = a.cand[c * D2D_MAX_ORDER + i];
+    trace_one<SGD>(a, tid, c, k, cd, a.tx[2 * p], a.tx[2 * p + 1], a.rx[2 * p], a.rx[2 * p + 1]);
+}
+
+// The paths of a record launch (power_rec_kernel): one thread per record, the ImagePath branch of trace_one with the cell's
+// coordinates from the resident grid and the candidate from the record; also unpacks the record into cell / cand / order.
+// A record that names no cell of the grid or no object of the scene (pass 2 left a slot unwritten: an internal error) raises
+// the flag and is not traced.
+struct RecTraceArgs {
+    const int4* __restrict__ rec;
+    long n;
+    const float* __restrict__ X;
+    const float* __restrict__ Y;
+    long cells;
+    float fx, fy;  // the fixed end point
+    int txg;       // the cells are the transmitters
+    int* __restrict__ cell;   // [n]
+    int* __restrict__ cand;   // [n][D2D_MAX_ORDER], -1 padded
+    int* __restrict__ order;  // [n]
+    int* flag;
+};
+__global__ void __launch_bounds__(64) trace_rec_kernel(TraceArgs a, RecTraceArgs r) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= r.n) return;
+    const int4 q = r.rec[tid];
+    const int k = (q.z >> 24) & 0xff;
+    const unsigned long long code = ((unsigned long long)(unsigned)(q.z & 0xffff) << 32) | (unsigned)q.y;
+    int cd[D2D_MAX_ORDER];
+    bool ok = q.x >= 0 && (long)q.x < r.cells && k <= D2D_MAX_ORDER;
+#pragma unroll
+    for (int i = 0; i < D2D_MAX_ORDER; ++i) {
+        cd[i] = i < k ? (int)((code >> (12 * i)) & 0xfffull) : -1;
+        ok = ok && cd[i] < a.T.N;
+    }
+    if (!ok) {
+        *r.flag = 1;
+        return;
+    }
+    r.cell[tid] = q.x;
+    r.order[tid] = k;
+#pragma unroll
+    for (int i = 0; i < D2D_MAX_ORDER; ++i) r.cand[tid * D2D_MAX_ORDER + i] = cd[i];
+    const float cx = r.X[q.x], cy = r.Y[q.x];
+    if (r.txg) trace_one<false>(a, tid, 0, k, cd, cx, cy, r.fx, r.fy);
+    else trace_one<false>(a, tid, 0, k, cd, r.fx, r.fy, cx, cy);
 }
 
 // the configured optimiser's instance (A zeroed, for an ImagePath trace: the Adam instance, which never runs the solver)

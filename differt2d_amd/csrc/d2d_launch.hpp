@@ -24,6 +24,8 @@ hipError_t launch_fwd_coop(int mode, int max_order, int W, dim3 grid, size_t lds
 hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
 // power_vg_kernel<MODE, TXG, GRADK>: exhaustive sweeps (strict_nan value+grad; "txg_exhaustive" values)
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
+// power_rec_kernel<MODE, MAXK, TXG>: the record build of the culled sweep (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
+hipError_t launch_rec(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RecArgs& r);
 
 // region_list_kernel<K, GRAD>: candidate lists of order K (2..4) of level `lv` by enumeration; grid = regions x slices
 hipError_t launch_region_lists(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,

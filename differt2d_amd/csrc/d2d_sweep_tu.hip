@@ -1,7 +1,8 @@
 // One translation unit per (kernel family, validity mode): instantiates the sweep kernels of that pair and defines the
 // per-mode launcher that d2d_launch.cpp's dispatchers call.  Compiled several times by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 5 region lists (mode 0 only), 9 fwd_coop,
-//   6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2 taken from the region lists (LISTED), 10 NaN scan (mode 0 only)}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}
+//   6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2 taken from the region lists (LISTED), 10 NaN scan (mode 0 only),
+//   11 record build (modes 0 and 1 only)}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}
 #include <type_traits>
 
 #include "d2d_launch.hpp"
@@ -163,6 +164,17 @@ hipError_t launch_nan_scan(bool approx, bool txg, int max_order, bool regions, b
 hipError_t launch_nan_apply(hipStream_t s, const SweepArgs& a, long tiles) {
     hipLaunchKernelGGL(nan_apply_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a.grad, a.partial, a.nan_cell_bits, a.nan_row_bits,
                        a.nan_row_words, a.N, a.m, a.n, tiles);
+    return hipGetLastError();
+}
+#elif D2D_TU_FAMILY == 11
+// power_rec_kernel<MODE, MAXK, TXG>: hard and hard_sigmoid only (the sigmoid sweeps' skips depend on the fused function's sum)
+template <int MODE> hipError_t launch_rec_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r);
+template <>
+hipError_t launch_rec_m<TU_MODE>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
+    static_assert(TU_MODE == MODE_HARD || TU_MODE == MODE_HSIG, "the record build has no sigmoid instance");
+    const dim3 block(64);
+    if (txg) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_rec_kernel<TU_MODE, decltype(K)::value, true>), grid, block, lds, s, a, r); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_rec_kernel<TU_MODE, decltype(K)::value, false>), grid, block, lds, s, a, r); });
     return hipGetLastError();
 }
 #else

@@ -435,6 +435,38 @@ class Context:
         out["order"] = order[:Cn]
         return out
 
+    def valid_paths(self, params: L.Params, fixed) -> dict:
+        """Every (cell of the resident grid, candidate of the current scene and mask) whose validity is not exactly zero, with
+        its solved path: the record launch of the culled sweep (include/d2d.h: d2d_valid_paths; ImagePath, hard or
+        hard_sigmoid validity).  ``params.grid_role`` says which end of the paths the cells are, ``fixed`` is the other end.
+
+        Returns a dict of arrays with leading length n (record order unspecified): ``cell`` (row-major index into the grid),
+        ``cand`` (n, D2D_MAX_ORDER; -1 padded), ``order``, ``xys`` (n, D2D_MAX_ORDER+2, 2; unused rows NaN), ``loss``,
+        ``valid``, ``length`` -- the entries :meth:`trace_paths` returns for the same (pair, candidate), bit for bit."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        n = C.c_int64(0)
+        L.check(self._lib.d2d_valid_paths(self._ctx, C.byref(params), fixed, C.byref(n)))
+        n = int(n.value)
+        out = {
+            "cell": np.empty(n, np.int32),
+            "cand": np.empty((n, L.D2D_MAX_ORDER), np.int32),
+            "order": np.empty(n, np.int32),
+            "xys": np.empty((n, L.D2D_MAX_ORDER + 2, 2), np.float32),
+            "loss": np.empty(n, np.float32),
+            "valid": np.empty(n, np.float32),
+            "length": np.empty(n, np.float32),
+        }
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        L.check(self._lib.d2d_get_valid_paths(self._ctx, n, vp(out["cell"]), vp(out["cand"]), vp(out["order"]), vp(out["xys"]),
+                                              vp(out["loss"]), vp(out["valid"]), vp(out["length"])))
+        return out
+
+    def valid_paths_ms(self) -> dict:
+        """Diagnostic: kernel times of the last :meth:`valid_paths` that found records (needs ``set_option("time_kernel", 1)``)."""
+        ms = np.zeros(3, np.float32)
+        L.check(self._lib.d2d_debug_valid_paths_ms(self._ctx, ms))
+        return {"count_ms": float(ms[0]), "write_ms": float(ms[1]), "trace_ms": float(ms[2])}
+
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -10,7 +10,9 @@ What runs where
 * ``accumulate_on_receivers_grid_over_paths`` with a natively fused ``fun`` (``utils.received_power``,
   ``utils.path_length_squared`` ...) is ONE fused kernel launch per transmitter (``d2d_power_map_launch``);
 * ``all_paths`` / ``all_valid_paths`` / ``accumulate_over_paths`` and grid sweeps with an arbitrary Python
-  ``fun`` trace every (pair, candidate) on the GPU (``d2d_trace_paths``) and call ``fun`` on the host.
+  ``fun`` trace every (pair, candidate) on the GPU (``d2d_trace_paths``) and call ``fun`` on the host;
+* grid sweeps with an arbitrary Python ``fun`` over more than ``EMIT_LIMIT`` (cell, candidate) pairs take the sparse
+  route: the GPU returns only the pairs whose validity is not exactly zero (``d2d_valid_paths``), ``fun`` runs on those.
 
 No CPU implementation of the path solve / validity exists in this package.
 """
@@ -44,6 +46,50 @@ PathFun = Callable[..., Any]
 
 #: grid cells x candidates above which a non-native ``fun`` is refused (host memory / time)
 EMIT_LIMIT = 8_000_000
+
+
+def _accumulate_dense(shape, grid, fixed, grid_is_rx, point_cls, path_cls, candidates, interacting, xys, loss, valid, fun,
+                      fun_args=(), fun_kwargs=None):
+    """The dense route's sum: ``xys`` [cells, C, D2D_MAX_ORDER+2, 2], ``loss`` / ``valid`` [cells, C] of every (cell,
+    candidate); ``fun`` once per candidate on grid-shaped batches, added in candidate order (fp32, reference
+    scene.py:1893-1916).  ``interacting(cand)`` -> the candidate's objects."""
+    acc = np.zeros(shape, F)
+    for c, cand in enumerate(candidates):
+        k = len(cand)
+        path = path_cls(xys=xys[:, c, : k + 2].reshape(*shape, k + 2, 2), loss=loss[:, c].reshape(shape))
+        moving = point_cls(xy=grid.reshape(*shape, 2))
+        a, b = (fixed, moving) if grid_is_rx else (moving, fixed)
+        val = np.asarray(fun(a, b, path, interacting(cand), *fun_args, **(fun_kwargs or {})), dtype=F)
+        acc = (acc + valid[:, c].reshape(shape) * val).astype(F)
+    return acc
+
+
+def _accumulate_sparse(shape, grid, fixed, grid_is_rx, point_cls, path_cls, records, rank, interacting, fun, fun_args=(),
+                       fun_kwargs=None):
+    """The sparse route's sum, a pure function of its arguments: ``records`` (``Context.valid_paths``: ``cell``, ``cand``,
+    ``order``, ``xys``, ``loss``, ``valid``, any order) hold the (cell, candidate) pairs whose validity is not exactly zero,
+    ``rank`` each record's position in the reference's enumeration (``_lib.candidate_rank``).  For every candidate that has
+    records, in ascending rank, ``fun`` is called ONCE on 1-D batches -- ``path.xys`` (n_c, k+2, 2), ``path.loss`` (n_c,),
+    the moving point's ``xy`` (n_c, 2) -- and ``valid * fun`` is added to the records' cells: every cell's fp32 sum runs in
+    the reference's candidate order (scene.py:1893-1916), and the pairs left out would have added ``0 * fun``."""
+    acc = np.zeros(int(np.prod(shape)), F)
+    rank = np.asarray(rank, np.int64)
+    if rank.size:
+        by = np.lexsort((records["cell"], rank))
+        rank_s, cell_s = rank[by], records["cell"][by].astype(np.int64)
+        xys_s, loss_s, valid_s = records["xys"][by], records["loss"][by], records["valid"][by]
+        starts = np.flatnonzero(np.concatenate(([True], rank_s[1:] != rank_s[:-1])))
+        ends = np.append(starts[1:], rank_s.size)
+        for lo, hi in zip(starts, ends):
+            k = int(records["order"][by[lo]])
+            cand = records["cand"][by[lo], :k]
+            cells = cell_s[lo:hi]  # (a cell occurs at most once per candidate: plain fancy indexing is right)
+            path = path_cls(xys=xys_s[lo:hi, : k + 2], loss=loss_s[lo:hi])
+            moving = point_cls(xy=grid[cells])
+            a, b = (fixed, moving) if grid_is_rx else (moving, fixed)
+            val = np.asarray(fun(a, b, path, interacting(cand), *fun_args, **(fun_kwargs or {})), dtype=F)
+            acc[cells] = (acc[cells] + valid_s[lo:hi] * val).astype(F)
+    return acc.reshape(shape)
 
 
 class PyTreeDict(Mapping):
@@ -680,14 +726,17 @@ class Scene(Plottable):
 
     def _emit_grid(self, X, Y, fixed: Point, grid_is_rx: bool, point_cls, fun, fun_args, fun_kwargs, common,
                    filter_objects, path_cls, path_cls_kwargs=None, key=None):
-        """Arbitrary Python ``fun`` on a grid: trace all (cell, candidate) on the GPU, call ``fun`` once per
-        candidate on the batched paths, accumulate in candidate order (fp32)."""
+        """Arbitrary Python ``fun`` on a grid.  Up to ``EMIT_LIMIT`` (cell, candidate) pairs, dense: trace all of them on the
+        GPU, call ``fun`` once per candidate on the grid-shaped batch of paths, accumulate in candidate order (fp32).  Above it,
+        sparse (``_emit_sparse``): ImagePath with hard or hard_sigmoid validity only."""
+        lo, hi = (common["order"],) * 2 if common.get("order") is not None else (common["min_order"], common["max_order"])
+        cells = X.size
+        count = L.count_candidates(len(self.objects), lo, hi, self._allowed_mask(filter_objects))
+        if cells * max(count, 1) > EMIT_LIMIT:
+            return self._emit_sparse(X, Y, fixed, grid_is_rx, point_cls, fun, fun_args, fun_kwargs, common, filter_objects, path_cls,
+                                     path_cls_kwargs, count)
         candidates = self.all_path_candidates(common["min_order"], common["max_order"], order=common.get("order"),
                                               filter_objects=filter_objects)
-        cells = X.size
-        if cells * max(len(candidates), 1) > EMIT_LIMIT:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively and {cells} cells x {len(candidates)} candidates "
-                                       f"exceed the emit limit; use a function from differt2d_amd.utils")
         grid = np.stack([X.reshape(-1), Y.reshape(-1)], axis=-1).astype(F)
         other = np.broadcast_to(fixed.xy, grid.shape)
         txs, rxs = (other, grid) if grid_is_rx else (grid, other)
@@ -698,16 +747,35 @@ class Scene(Plottable):
         p["min_order"], p["max_order"] = 0, L.D2D_MAX_ORDER
         extra, theta0 = self._solver_setup(path_cls, path_cls_kwargs, candidates, key)
         out = ctx.trace_paths(make_params(**extra, **p), txs, rxs, candidates, theta0=theta0)
-        acc = np.zeros(X.shape, F)
-        for c, cand in enumerate(candidates):
-            k = len(cand)
-            path = path_cls(xys=out["xys"][:, c, : k + 2].reshape(*X.shape, k + 2, 2), loss=out["loss"][:, c].reshape(X.shape))
-            inter = self.get_interacting_objects(cand)
-            moving = point_cls(xy=grid.reshape(*X.shape, 2))
-            a, b = (fixed, moving) if grid_is_rx else (moving, fixed)
-            val = np.asarray(fun(a, b, path, inter, *fun_args, **(fun_kwargs or {})), dtype=F)
-            acc = (acc + out["valid"][:, c].reshape(X.shape) * val).astype(F)
-        return acc
+        return _accumulate_dense(X.shape, grid, fixed, grid_is_rx, point_cls, path_cls, candidates, self.get_interacting_objects,
+                                 out["xys"], out["loss"], out["valid"], fun, fun_args, fun_kwargs)
+
+    def _emit_sparse(self, X, Y, fixed: Point, grid_is_rx: bool, point_cls, fun, fun_args, fun_kwargs, common, filter_objects,
+                     path_cls, path_cls_kwargs, count):
+        """Arbitrary Python ``fun`` on a grid too big for the dense route: the GPU's record launch of the culled sweep returns
+        only the (cell, candidate) pairs whose validity is not exactly zero, with their solved paths
+        (``Context.valid_paths``); ``fun`` is evaluated on those and accumulated in the reference's candidate order
+        (``_accumulate_sparse``).  What the sweep's culling cannot hand out this way is refused, and says which it was."""
+        why = None
+        if self._solver_of(path_cls) != "image":
+            why = f"path_cls={path_cls.__name__} (the sparse route covers ImagePath only)"
+        elif common.get("approx") and common.get("function") == "sigmoid":
+            why = "sigmoid validity (it is zero for no pair; hard and hard_sigmoid validity are covered)"
+        if why is not None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively, {X.size} cells x {count} candidates exceed the emit "
+                                       f"limit and the sparse route does not cover {why}; use a function from differt2d_amd.utils")
+        if path_cls_kwargs:
+            raise TypeError(f"ImagePath takes no path_cls_kwargs, got {sorted(path_cls_kwargs)}")
+        ctx = self._ctx()
+        self._upload(ctx, filter_objects)
+        ctx.set_grid(X, Y)
+        params = make_params(fun="one", solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **common)
+        rec = ctx.valid_paths(params, fixed.xy)
+        lo, hi = (common["order"],) * 2 if common.get("order") is not None else (common["min_order"], common["max_order"])
+        rank = L.candidate_rank(rec["cand"], rec["order"], len(self.objects), self._allowed_mask(filter_objects), lo, hi)
+        grid = np.stack([X.reshape(-1), Y.reshape(-1)], axis=-1).astype(F)
+        return _accumulate_sparse(X.shape, grid, fixed, grid_is_rx, point_cls, path_cls, rec, rank, self.get_interacting_objects,
+                                  fun, fun_args, fun_kwargs)
 
     def _emit_grid_grad(self, X, Y, fixed: Point, grid_is_rx: bool, point_cls, fun, fun_args, fun_kwargs, common,
                         filter_objects, path_cls, path_cls_kwargs=None, key=None):
@@ -725,7 +793,8 @@ class Scene(Plottable):
         cells = X.size
         if cells * max(len(candidates), 1) > EMIT_LIMIT:
             raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively and {cells} cells x {len(candidates)} candidates "
-                                       f"exceed the emit limit; use a function from differt2d_amd.utils")
+                                       f"exceed the emit limit: grad / value_and_grad need every pair's derivative (the sparse "
+                                       f"route above the limit returns values only); use a function from differt2d_amd.utils")
         if not candidates or not cells:
             return np.zeros(X.shape, F), np.zeros(X.shape + (2,), F)
         grid = np.stack([X.reshape(-1), Y.reshape(-1)], axis=-1).astype(F)
@@ -841,7 +910,15 @@ class Scene(Plottable):
         """Power-map sweep: for every transmitter, ``Z[i, j] = sum_candidates valid * fun`` with the receiver at
         ``(X[i, j], Y[i, j])`` (reference scene.py:1803-1953). Returns an iterator of ``(tx name, Z)``, or their
         sum if ``reduce_all``; ``grad`` / ``value_and_grad`` add the per-cell gradient w.r.t. the receiver position
-        (last axis ``(d/dx, d/dy)``). One fused kernel launch per transmitter when ``fun`` is native."""
+        (last axis ``(d/dx, d/dy)``). One fused kernel launch per transmitter when ``fun`` is native.
+
+        Any other callable is evaluated on the host.  Up to ``EMIT_LIMIT`` (cell, candidate) pairs every pair is traced and
+        ``fun`` receives grid-shaped batches, as in the reference.  Above it (``ImagePath``, hard or ``hard_sigmoid`` validity,
+        values only) the sparse route takes over: the GPU returns only the pairs whose validity is not exactly zero, ``fun``
+        is called once per candidate on 1-D batches of those, and ``0 * fun = 0`` is taken for the rest WITHOUT calling
+        ``fun`` on them.  That equals the reference wherever ``fun`` is finite on invalid paths; a ``fun`` that returns
+        inf / NaN on an invalid path makes the reference's (and the dense route's) cell NaN, which the sparse route does not
+        see."""
         return self._grid_sweep(X, Y, list(self.transmitters.items()), True, receiver_cls, fun, fun_args, fun_kwargs,
                                 reduce_all, grad, value_and_grad, path_cls, path_cls_kwargs, min_order, max_order, order,
                                 filter_objects, key, kwargs)
@@ -888,7 +965,13 @@ class Scene(Plottable):
         order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, key=None, **kwargs,
     ):
         """Transmitter-grid twin (reference scene.py:1489-1648): one map per receiver, the transmitter sits at
-        ``(X[i, j], Y[i, j])``; gradients are w.r.t. the transmitter position (scene.py:1617-1620)."""
+        ``(X[i, j], Y[i, j])``; gradients are w.r.t. the transmitter position (scene.py:1617-1620).
+
+        A ``fun`` that is not natively fused follows the same two host routes as the receiver grid's sweep: dense up to
+        ``EMIT_LIMIT`` (cell, candidate) pairs; above it the sparse route (``ImagePath``, hard or ``hard_sigmoid`` validity,
+        values only, and only where the TX-grid sweep is culled), which calls ``fun`` on 1-D batches of the pairs whose
+        validity is not exactly zero and takes ``0 * fun = 0`` for the others without calling ``fun`` on them -- equal to the
+        reference wherever ``fun`` is finite on invalid paths."""
         return self._grid_sweep(X, Y, list(self.receivers.items()), False, transmitter_cls, fun, fun_args, fun_kwargs,
                                 reduce_all, grad, value_and_grad, path_cls, path_cls_kwargs, min_order, max_order, order,
                                 filter_objects, key, kwargs)

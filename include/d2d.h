@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
-#define D2D_ABI_VERSION 10
+#define D2D_ABI_VERSION 11
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -400,6 +400,31 @@ int d2d_trace_paths(d2d_ctx* ctx, const d2d_params* params, const float* tx, con
                     const int32_t* cand, const int32_t* order, int32_t C, const float* theta0, int64_t theta0_rows,
                     const float* xys_in, const float* loss_in, float* xys, float* loss, float* valid, float* on, float* hit,
                     float* length);
+
+/* ---- valid paths of a whole grid, sparse (the plug-in point for an arbitrary host `fun` on grids too big to trace densely:
+ *      differt2d/scene.py:1892-1918 adds valid * fun(...), and valid is exactly 0 for nearly every (cell, candidate)) ---- */
+
+/* Record launch of the culled forward sweep (ImagePath; hard or hard_sigmoid validity; the current scene, candidate mask and
+ * grid; params->grid_role says which end the cells are, `fixed` is the other end; params->fun_id and out_mode are ignored):
+ * finds every (cell, candidate of orders min_order..max_order) whose validity is not exactly zero and solves its path.
+ * Two passes of the same sweep -- count per 8 x 8 patch, host scan, write -- then one thread per record for the path: no
+ * global atomics.  Synchronous.  *count = how many there are; the library keeps them (grown when needed, dropped by a
+ * d2d_set_grid of another grid) until the next call.  The resident value / gradient maps, the work history and the
+ * schedule of the fused sweeps are not touched.
+ * D2D_ERR_UNSUPPORTED: sigmoid validity (its sweeps skip candidates by the fused function's running sum), MinPath / FermatPath,
+ * a TX grid whose sweep would not be culled (d2d_params.grid_role), more than 4 095 objects, or a total that would take more
+ * than half of the free device memory (100 bytes per record; the message holds the count) -- decided before the second pass.
+ * D2D_ERR_STATE: the second pass disagreed with the first (an internal error; nothing is stored out of bounds). */
+int d2d_valid_paths(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, int64_t* count);
+/* Copies the records of the last d2d_valid_paths out: cell[n] (row-major index into the grid), cand[n][D2D_MAX_ORDER]
+ * (-1 padded), order[n], xys[n][D2D_MAX_ORDER+2][2] (unused rows NaN), loss[n], valid[n], length[n] -- what d2d_trace_paths
+ * returns for the same (pair, candidate), bit for bit.  Any pointer may be NULL; capacity (in records) must be at least the
+ * count; the order of the records is unspecified. */
+int d2d_get_valid_paths(d2d_ctx* ctx, int64_t capacity, int32_t* cell, int32_t* cand, int32_t* order, float* xys, float* loss,
+                        float* valid, float* length);
+/* Diagnostic ("time_kernel" option): kernel times of the last d2d_valid_paths that found records -- ms[0] pass 1 (count),
+ * ms[1] pass 2 (write), ms[2] the paths of the records. */
+int d2d_debug_valid_paths_ms(d2d_ctx* ctx, float* ms /* [3] */);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
