@@ -17,40 +17,13 @@
 #define D2D_AUX_KERNELS 1  // the non-template kernels are defined in this translation unit
 #include "d2d_launch.hpp"
 #include "d2d_host.hpp"
+#include "d2d_own.hpp"
 #include "d2d_optgrad.hpp"
 #include "d2d_optrev.hpp"
 
-// ---- mode dispatch of the sweep-kernel launchers (d2d_launch.hpp); the per-mode launchers live in the
+// ---- mode dispatch of the sweep-kernel launchers; the per-mode launchers (declared in d2d_launch.hpp too) live in the
 // d2d_sweep_tu objects, one per (kernel family, validity mode) ----
 namespace d2d {
-
-template <int MODE> hipError_t launch_fwd_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_fwd_grad_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_fwd_split_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_txg_m(bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_vg_m(bool txg, bool grad, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_fwd_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_fwd_grad_listed_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_fwd_split_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-
-#define D2D_DECLARE_MODE(M)                                                                                   \
-    template <> hipError_t launch_fwd_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);           \
-    template <> hipError_t launch_fwd_grad_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);            \
-    template <> hipError_t launch_fwd_split_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);     \
-    template <> hipError_t launch_txg_m<M>(bool, bool, int, dim3, size_t, hipStream_t, const SweepArgs&);           \
-    template <> hipError_t launch_vg_m<M>(bool, bool, dim3, size_t, hipStream_t, const SweepArgs&);              \
-    template <> hipError_t launch_fwd_listed_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);       \
-    template <> hipError_t launch_fwd_grad_listed_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);        \
-    template <> hipError_t launch_fwd_split_listed_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&); \
-    template <> hipError_t launch_fwd_coop_m<M>(int, int, dim3, size_t, hipStream_t, const SweepArgs&);
-template <int MODE> hipError_t launch_rec_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r);
-template <> hipError_t launch_rec_m<MODE_HARD>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
-template <> hipError_t launch_rec_m<MODE_HSIG>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
-D2D_DECLARE_MODE(MODE_HARD)
-D2D_DECLARE_MODE(MODE_HSIG)
-D2D_DECLARE_MODE(MODE_SIG)
-#undef D2D_DECLARE_MODE
 
 #define D2D_BY_MODE(fn, ...)                                   \
     switch (mode) {                                            \
@@ -111,36 +84,33 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(D2D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n && p) return D2D_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        if (count == 0) count = 1;
-        HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-        n = count;
-        return D2D_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
+using d2d_own::DevBuf;
+using Event = d2d_own::Unique<hipEvent_t, d2d_own::event_destroy>;
+using Stream = d2d_own::Unique<hipStream_t, d2d_own::stream_destroy>;
+template <typename T> using Pinned = d2d_own::Unique<T*, d2d_own::pinned_free>;
 
 using d2d_host::integer_pow;
 
 }  // namespace
 
+// the runtime calls behind d2d_own.hpp's owning types: the only places that free or destroy anything
+int d2d_own::dev_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    return e == hipSuccess ? D2D_OK : fail(D2D_ERR_HIP, "hipMalloc((void**)&p, count * sizeof(T)) failed: %s", hipGetErrorString(e));
+}
+void d2d_own::dev_free(void* p) { (void)hipFree(p); }
+void d2d_own::pinned_free(void* p) { (void)hipHostFree(p); }
+void d2d_own::event_destroy(void* h) { (void)hipEventDestroy((hipEvent_t)h); }
+void d2d_own::stream_destroy(void* h) { (void)hipStreamDestroy((hipStream_t)h); }
+
+// Every device buffer, event, stream and the pinned h_meta is an owning member (d2d_own.hpp): ~d2d_ctx drains the streams
+// and the members free themselves, in reverse order of declaration.  Invariant: `stream` is declared first, so it dies
+// last, after every buffer and event that work on it may still reference; the other streams are declared where they
+// belong and are idle by then (the destructor's body has synchronised each of them; d2d_create's failure paths end there too).
 struct d2d_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t evk0 = nullptr, evk1 = nullptr;  // around the dominant kernel of the last sweep ("time_kernel" option)
+    Stream stream;
+    Event ev0, ev1, evk0, evk1;  // evk*: around the dominant kernel of the last sweep ("time_kernel" option)
     bool time_kernel = false, have_kernel_time = false;
     // scene (host copies)
     int N = 0;
@@ -191,7 +161,7 @@ struct d2d_ctx {
     DevBuf<int4> d_rec;
     DevBuf<float> d_rec_xys, d_rec_loss, d_rec_valid, d_rec_len;
     long long rec_n = -1;  // records the buffers hold (-1: none)
-    hipEvent_t ev_rec[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // "time_kernel": around pass 1, pass 2 and the trace
+    Event ev_rec[6];  // "time_kernel": around pass 1, pass 2 and the trace
     bool have_rec_time = false;
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -243,8 +213,8 @@ struct d2d_ctx {
     DevBuf<unsigned long long> d_nan_stats;
     size_t lds_max = d2d_host::LDS_MAX;  // dynamic LDS a launch without a choice may take (gfx950: the CU's 160 KB less 4 KB of static LDS, d2d_host.hpp; d2d_create lowers it to what the device reports)
     long long nan_wqcap = 0, nan_rb = 0;  // "nan_scan_wqcap" / "nan_scan_rb": the region scan's queue entries / batches per round in use (0: all; tests)
-    hipStream_t scan_stream = nullptr;  // created at the first use, at the lowest priority
-    hipEvent_t ev_scan_fork = nullptr, ev_scan_done = nullptr;
+    Stream scan_stream;  // created at the first use, at the lowest priority
+    Event ev_scan_fork, ev_scan_done;
     DevBuf<unsigned long long> d_nan_cells;  // [patches]
     DevBuf<unsigned> d_nan_rows;             // [patches][1 + ceil(N / 32)]
     bool want_wave_cycles = false;
@@ -264,11 +234,11 @@ struct d2d_ctx {
     long long region_budget_mb = 24576; // device memory all list pools together may grow to (one pool per rotating set)
     long long rl_pool_mb = 256;        // its current size: quadrupled (up to the budget) after a launch whose lists did not fit
     bool rl_pool_by_option = false;    // "region_budget_mb" was set by the caller: no automatic first size
-    hipStream_t aux_stream = nullptr;  // the patch schedule's sort runs here, beside the shadow masks and the region lists
-    hipStream_t sort_stream = nullptr; // .. and here when aux_stream carries the whole preparation (pipeline)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int* h_meta = nullptr;             // pinned: {patches left to the enumerating kernel, pool chunks handed out} of the last launch with lists
-    hipEvent_t ev_meta = nullptr;
+    Stream aux_stream;  // the patch schedule's sort runs here, beside the shadow masks and the region lists
+    Stream sort_stream; // .. and here when aux_stream carries the whole preparation (pipeline)
+    Event ev_fork, ev_join;
+    Pinned<int> h_meta;                // pinned: {patches left to the enumerating kernel, pool chunks handed out} of the last launch with lists
+    Event ev_meta;
     bool meta_pending = false;
     long long rl_meta_static = 0, rl_meta_chunks = 0;  // n_static / max_chunks of the last launch that built lists
     long long pend_static = 0, pend_chunks = 0;        // ... of the launch the pending h_meta read-back describes
@@ -285,6 +255,7 @@ struct d2d_ctx {
     // start of every pipelined sweep launch).  The preparation of launch k+1 runs on aux_stream into its own set while the
     // sweep kernel of launch k still reads another one on the main stream: back-to-back launches (many transmitters, the
     // benchmark) hide it completely.  The work history a schedule is sorted by is then a few launches old instead of one.
+    // (a PrepSet moves through its members: the rotation's std::swap hands buffers, event and flags over together)
     struct PrepSet {
         DevBuf<unsigned long long> d_shadow;  // shadow masks, then the schedule sort's histogram and cursors, then the lists' meta
         DevBuf<int> d_sched;                  // patch schedule
@@ -299,7 +270,7 @@ struct d2d_ctx {
         DevBuf<d2d::RegionLists> d_rl;        // the descriptor the sweep kernels read
         d2d::RegionLists rl_host;             // what d_rl holds
         bool rl_host_valid = false;
-        hipEvent_t ev_swept = nullptr;        // recorded on the main stream behind the sweep that read this set
+        Event ev_swept;                       // recorded on the main stream behind the sweep that read this set
         bool swept_pending = false;
     };
     PrepSet cur;
@@ -312,7 +283,7 @@ struct d2d_ctx {
         f(cur);
         for (PrepSet& sp : spare_sets) f(sp);
     }
-    hipEvent_t ev_prep = nullptr;       // recorded on aux_stream behind a launch's preparation
+    Event ev_prep;                      // recorded on aux_stream behind a launch's preparation
     bool pipeline = true;
     long long unpiped_max_tiles = 256; // "unpiped_max_tiles": launches of orders <= 1 over at most this many patches prepare on the sweep's own stream (latency of a small call)
     bool last_small = false;           // ... what the previous launch was (a change of kind drains both streams first)
@@ -321,14 +292,15 @@ struct d2d_ctx {
     int rank = 0, world = 1;
     DevBuf<float> d_gather[2], d_send[2];  // [0] value map, [1] gradient map: gathered shards / staging copy of the local shard
     // the all-gather of step k runs on its own stream, overlapped with the sweep of step k+1
-    hipStream_t comm_stream = nullptr;
+    Stream comm_stream;
     long long comm_prio = 0;  // "comm_prio" option: priority of comm_stream when it is created
     // every collective runs on comm_stream behind a "ready" event of the main stream; [0] value-map gather, [1] gradient-map
     // gather, [2] scene-VJP all-reduce; the main stream waits for ev_done[i] only where it reuses what collective i touches
-    hipEvent_t ev_ready = nullptr, ev_done[3] = {nullptr, nullptr, nullptr};
+    Event ev_ready, ev_done[3];
     bool inflight[3] = {false, false, false};
     DevBuf<double> d_hostred;
     size_t gathered[2] = {0, 0};  // floats per rank in d_gather[what] (0: nothing gathered on this rank)
+    ~d2d_ctx();
 };
 
 namespace {
@@ -565,9 +537,9 @@ int ensure_comm_stream(d2d_ctx* c) {
     // to measure (bench.py --comm-prio).
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    HIP_TRY(hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, c->comm_prio > 0 ? prio_hi : (c->comm_prio < 0 ? prio_lo : 0)));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming));
-    for (int w = 0; w < 3; ++w) HIP_TRY(hipEventCreateWithFlags(&c->ev_done[w], hipEventDisableTiming));
+    HIP_TRY(hipStreamCreateWithPriority(c->comm_stream.put(), hipStreamNonBlocking, c->comm_prio > 0 ? prio_hi : (c->comm_prio < 0 ? prio_lo : 0)));
+    HIP_TRY(hipEventCreateWithFlags(c->ev_ready.put(), hipEventDisableTiming));
+    for (int w = 0; w < 3; ++w) HIP_TRY(hipEventCreateWithFlags(c->ev_done[w].put(), hipEventDisableTiming));
     return D2D_OK;
 }
 // main stream -> communication stream hand-over: everything enqueued on the main stream so far happens before what is
@@ -579,6 +551,13 @@ int comm_after_main(d2d_ctx* c) {
 }
 
 }  // namespace
+
+d2d_ctx::~d2d_ctx() {
+    (void)hipSetDevice(device);
+    for (hipStream_t st : {(hipStream_t)aux_stream, (hipStream_t)sort_stream, (hipStream_t)stream, (hipStream_t)comm_stream, (hipStream_t)scan_stream})
+        if (st) (void)hipStreamSynchronize(st);
+    if (comm && rccl().ok) rccl().CommDestroy(comm);
+}
 
 extern "C" {
 
@@ -640,26 +619,23 @@ int d2d_create(int device, d2d_ctx** out) {
             (void)hipGetLastError();
         }
     }
-    if (e1 == hipSuccess) e1 = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = hipEventCreate(&c->ev0);
-    if (e1 == hipSuccess) e1 = hipEventCreate(&c->ev1);
-    if (e1 == hipSuccess) e1 = hipEventCreate(&c->evk0);
-    if (e1 == hipSuccess) e1 = hipEventCreate(&c->evk1);
-    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_meta, hipEventDisableTiming);
+    if (e1 == hipSuccess) e1 = hipStreamCreateWithFlags(c->stream.put(), hipStreamNonBlocking);
+    for (Event* e : {&c->ev0, &c->ev1, &c->evk0, &c->evk1})
+        if (e1 == hipSuccess) e1 = hipEventCreate(e->put());
+    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(c->ev_meta.put(), hipEventDisableTiming);
     if (e1 == hipSuccess) {
         // the side stream carries short dependent chains that run beside a sweep kernel which fills the chip: highest priority
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        e1 = hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, prio_hi);
-        if (e1 == hipSuccess) e1 = hipStreamCreateWithPriority(&c->sort_stream, hipStreamNonBlocking, prio_hi);
+        e1 = hipStreamCreateWithPriority(c->aux_stream.put(), hipStreamNonBlocking, prio_hi);
+        if (e1 == hipSuccess) e1 = hipStreamCreateWithPriority(c->sort_stream.put(), hipStreamNonBlocking, prio_hi);
     }
-    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming | hipEventDisableSystemFence);
+    for (Event* e : {&c->ev_fork, &c->ev_join, &c->ev_prep})
+        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(e->put(), hipEventDisableTiming | hipEventDisableSystemFence);
     c->for_each_set([&](d2d_ctx::PrepSet& sp) {
-        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(&sp.ev_swept, hipEventDisableTiming | hipEventDisableSystemFence);
+        if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(sp.ev_swept.put(), hipEventDisableTiming | hipEventDisableSystemFence);
     });
-    if (e1 == hipSuccess) e1 = hipHostMalloc(reinterpret_cast<void**>(&c->h_meta), 2 * sizeof(int), hipHostMallocDefault);
+    if (e1 == hipSuccess) e1 = hipHostMalloc(reinterpret_cast<void**>(c->h_meta.put()), 2 * sizeof(int), hipHostMallocDefault);
     if (e1 != hipSuccess) {
         delete c;
         return fail(D2D_ERR_HIP, "context creation failed: %s", hipGetErrorString(e1));
@@ -669,69 +645,7 @@ int d2d_create(int device, d2d_ctx** out) {
 }
 
 void d2d_destroy(d2d_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
-    if (c->sort_stream) (void)hipStreamSynchronize(c->sort_stream);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
-    if (c->comm && rccl().ok) rccl().CommDestroy(c->comm);
-    for (int w = 0; w < 2; ++w) {
-        c->d_gather[w].release();
-        c->d_send[w].release();
-    }
-    c->d_hostred.release();
-    c->d_occl.release();
-    c->d_refl.release();
-    c->d_flt.release();
-    c->d_cw.release();
-    c->d_kind.release();
-    c->d_sincos.release();
-    c->d_xys.release(); c->d_gcontrib.release(); c->d_traj.release(); c->d_traj_off.release();
-    c->d_bc1.release(); c->d_bc2.release(); c->d_theta0.release(); c->d_contrib.release(); c->d_scand.release(); c->d_sorder.release();
-    c->d_tcand.release(); c->d_torder.release(); c->d_ttx.release(); c->d_trx.release();
-    c->d_txys_in.release(); c->d_tloss_in.release(); c->d_txys.release(); c->d_tloss.release();
-    c->d_tvalid.release(); c->d_ton.release(); c->d_thit.release(); c->d_tlen.release();
-    c->d_X.release();
-    c->d_Y.release();
-    c->d_out.release();
-    c->d_stats.release();
-    c->d_hidden.release(); c->d_rl_box.release();
-    c->d_sched_override.release();
-    c->d_heavy_list.release(); c->d_heavy_cnt.release(); c->d_heavy_done.release();
-    c->d_pair.release();
-    c->d_grad.release(); c->d_cot.release(); c->d_partial.release(); c->d_vjp.release();
-    c->d_cust_f.release(); c->d_cust_pb.release();
-    c->drop_records(); c->d_rec_shadow.release(); c->d_rec_flag.release();
-    for (hipEvent_t e : c->ev_rec)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
-    if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
-    for (int w = 0; w < 3; ++w)
-        if (c->ev_done[w]) (void)hipEventDestroy(c->ev_done[w]);
-    if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    if (c->evk0) (void)hipEventDestroy(c->evk0);
-    if (c->evk1) (void)hipEventDestroy(c->evk1);
-    if (c->ev_meta) (void)hipEventDestroy(c->ev_meta);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-    c->for_each_set([](d2d_ctx::PrepSet& sp) {
-        if (sp.ev_swept) (void)hipEventDestroy(sp.ev_swept);
-        sp.d_shadow.release(); sp.d_rl_pool.release(); sp.d_sched.release(); sp.d_rl_next.release();
-        sp.d_rl_idx.release(); sp.d_rl_meta.release(); sp.d_sched_key.release(); sp.d_cost.release();
-        sp.d_rl.release();
-    });
-    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-    if (c->sort_stream) (void)hipStreamDestroy(c->sort_stream);
-    if (c->scan_stream) { (void)hipStreamSynchronize(c->scan_stream); (void)hipStreamDestroy(c->scan_stream); }
-    if (c->ev_scan_fork) (void)hipEventDestroy(c->ev_scan_fork);
-    if (c->ev_scan_done) (void)hipEventDestroy(c->ev_scan_done);
-    if (c->h_meta) (void)hipHostFree(c->h_meta);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c) delete c;
 }
 
 int d2d_synchronize(d2d_ctx* c) {
@@ -1600,8 +1514,8 @@ static int prep_region_lists(d2d_ctx* c, Sweep& s, Prep& pr) {
     al.fb_n = nullptr;
     al.cullq_off = (int)((size_t)(3 * c->N + 1) * sizeof(float4));
     for (int k = rp.k_lo; k <= p->max_order; ++k) {
-        HIP_TRY(d2d::launch_region_lists(k, false, s.txg, dim3((unsigned)rp.top.slots), lds_l, s.ps, al, top, rl.lp));
-        HIP_TRY(d2d::launch_region_refine(k, false, s.txg, dim3((unsigned)rp.leaf.regions), lds_r, s.ps, al, rl.leaf, top, rl.lp, rl.flag));
+        HIP_TRY(d2d::launch_region_lists(k, s.txg, dim3((unsigned)rp.top.slots), lds_l, s.ps, al, top, rl.lp));
+        HIP_TRY(d2d::launch_region_refine(k, s.txg, dim3((unsigned)rp.leaf.regions), lds_r, s.ps, al, rl.leaf, top, rl.lp, rl.flag));
     }
     a.rl = cur.d_rl.p;
     c->rl_plan = rp;
@@ -1839,10 +1753,10 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         if (c->scan_stream == nullptr) {
             int prio_lo = 0, prio_hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            HIP_TRY(hipStreamCreateWithPriority(&c->scan_stream, hipStreamNonBlocking, prio_lo));
+            HIP_TRY(hipStreamCreateWithPriority(c->scan_stream.put(), hipStreamNonBlocking, prio_lo));
         }
-        if (!c->ev_scan_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_fork, hipEventDisableTiming | hipEventDisableSystemFence));
-        if (!c->ev_scan_done) HIP_TRY(hipEventCreateWithFlags(&c->ev_scan_done, hipEventDisableTiming | hipEventDisableSystemFence));
+        if (!c->ev_scan_fork) HIP_TRY(hipEventCreateWithFlags(c->ev_scan_fork.put(), hipEventDisableTiming | hipEventDisableSystemFence));
+        if (!c->ev_scan_done) HIP_TRY(hipEventCreateWithFlags(c->ev_scan_done.put(), hipEventDisableTiming | hipEventDisableSystemFence));
         if ((rc = c->d_nan_cells.ensure((size_t)s.tiles))) return rc;
         if (grad_mode == 2 && (rc = c->d_nan_rows.ensure((size_t)s.tiles * rw))) return rc;
         d2d::SweepArgs as = a;
@@ -2098,8 +2012,8 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     if ((rc = c->d_rec_counts.ensure(tiles)) || (rc = c->d_rec_offs.ensure(tiles + 1)) || (rc = c->d_rec_flag.ensure(1))) return rc;
     const bool timed = c->time_kernel;
     if (timed)
-        for (hipEvent_t& e : c->ev_rec)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+        for (Event& e : c->ev_rec)
+            if (!e) HIP_TRY(hipEventCreate(e.put()));
     HIP_TRY(hipMemsetAsync(c->d_rec_flag.p, 0, sizeof(int), c->stream));
     d2d::RecArgs r;
     r.counts = c->d_rec_counts.p;
@@ -2321,7 +2235,6 @@ int d2d_selftest_div(d2d_ctx* c, const float* x, const float* y, int64_t n, floa
     HIP_TRY(hipMemcpy(q_fast, d1.p, n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(q_ref, d2.p, n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(q_hostr, d3.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    dx.release(); dy.release(); dr.release(); d1.release(); d2.release(); d3.release();
     return D2D_OK;
 }
 
@@ -2336,8 +2249,6 @@ int d2d_selftest_expf(d2d_ctx* c, const float* x, int64_t n, float* y) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(y, dy.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    dx.release();
-    dy.release();
     return D2D_OK;
 }
 

@@ -1,7 +1,8 @@
 // Host-side launch entry points of the sweep kernels.  The kernels are templates (d2d_kernels.hpp); every
 // (kernel family, validity mode) pair is instantiated in its own translation unit (d2d_sweep_tu.hip compiled with
 // -DD2D_TU_FAMILY / -DD2D_TU_MODE, see the Makefile) so that the library builds in parallel; d2d.hip only sees these
-// declarations.  `mode` is a d2d::Mode; every function returns the hipGetLastError() of its launch.
+// declarations, and nothing else declares them: the per-mode launchers (each defined as a `template <>` by the d2d_sweep_tu
+// object of its family and mode), then d2d.hip's by-mode dispatchers.  `mode` is a d2d::Mode; every function returns the hipGetLastError() of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,35 @@
 
 namespace d2d {
 
+// ---- per-mode launchers: the primary templates, then their explicit specialisations for the modes that exist ----
+template <int MODE> hipError_t launch_fwd_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_fwd_grad_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_fwd_split_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_txg_m(bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_vg_m(bool txg, bool grad, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_fwd_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_fwd_grad_listed_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_fwd_split_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
+template <int MODE> hipError_t launch_rec_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r);
+#define D2D_DECLARE_MODE(M)                                                                                      \
+    template <> hipError_t launch_fwd_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);              \
+    template <> hipError_t launch_fwd_grad_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);               \
+    template <> hipError_t launch_fwd_split_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);        \
+    template <> hipError_t launch_txg_m<M>(bool, bool, int, dim3, size_t, hipStream_t, const SweepArgs&);        \
+    template <> hipError_t launch_vg_m<M>(bool, bool, dim3, size_t, hipStream_t, const SweepArgs&);              \
+    template <> hipError_t launch_fwd_listed_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);       \
+    template <> hipError_t launch_fwd_grad_listed_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);        \
+    template <> hipError_t launch_fwd_split_listed_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&); \
+    template <> hipError_t launch_fwd_coop_m<M>(int, int, dim3, size_t, hipStream_t, const SweepArgs&);
+D2D_DECLARE_MODE(MODE_HARD)
+D2D_DECLARE_MODE(MODE_HSIG)
+D2D_DECLARE_MODE(MODE_SIG)
+#undef D2D_DECLARE_MODE  // (the record build has no sigmoid instance: launch_rec answers hipErrorInvalidValue)
+template <> hipError_t launch_rec_m<MODE_HARD>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
+template <> hipError_t launch_rec_m<MODE_HSIG>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
+
+// ---- by-mode dispatchers ----
 // `listed`: the LISTED build (orders >= 2 from the region candidate lists, a.rl); otherwise the enumerating build, which
 // walks the queue of left-over patches when a.fb_n is set.
 // power_fwd_kernel<MODE, STATS, MAXK, false>: one wave per 8 x 8 patch (big launches)
@@ -27,11 +57,11 @@ hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipSt
 // power_rec_kernel<MODE, MAXK, TXG>: the record build of the culled sweep (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
 hipError_t launch_rec(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RecArgs& r);
 
-// region_list_kernel<K, GRAD>: candidate lists of order K (2..4) of level `lv` by enumeration; grid = regions x slices
-hipError_t launch_region_lists(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,
+// region_list_kernel<K, false, TXG>: candidate lists of order K (2..4) of level `lv` by enumeration; grid = regions x slices
+hipError_t launch_region_lists(int K, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,
                                const ListPool& lp);
-// region_refine_kernel<K, GRAD>: the lists of level `lv` (one per region) from those of `parent`; grid = regions of `lv`
-hipError_t launch_region_refine(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,
+// region_refine_kernel<K, false, TXG>: the lists of level `lv` (one per region) from those of `parent`; grid = regions of `lv`
+hipError_t launch_region_refine(int K, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,
                                 const RegionLevel& parent, const ListPool& lp, int* flag);
 
 // nan_scan_kernel<APPROX, TXG, MAXK> (d2d_nanscan.hpp): the reference's autodiff NaN positions, beside a culled value+grad sweep

@@ -1,8 +1,8 @@
 // One translation unit per (kernel family, validity mode): instantiates the sweep kernels of that pair and defines the
-// per-mode launcher that d2d_launch.cpp's dispatchers call.  Compiled several times by the Makefile with
-//   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 5 region lists (mode 0 only), 9 fwd_coop,
-//   6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2 taken from the region lists (LISTED), 10 NaN scan (mode 0 only),
-//   11 record build (modes 0 and 1 only)}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}
+// per-mode launcher (declared in d2d_launch.hpp) that d2d.hip's dispatchers call.  Compiled by the Makefile with
+//   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2
+//   taken from the region lists (LISTED), 9 fwd_coop}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}: all 27 pairs;
+//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 record build for modes 0 and 1 (no sigmoid instance)
 #include <type_traits>
 
 #include "d2d_launch.hpp"
@@ -11,7 +11,7 @@
 #endif
 
 #ifndef D2D_TU_FAMILY
-#error "compile with -DD2D_TU_FAMILY=<0..4> -DD2D_TU_MODE=<0..2>"
+#error "compile with -DD2D_TU_FAMILY=<0..11> -DD2D_TU_MODE=<0..2> (see the Makefile for the pairs that exist)"
 #endif
 
 namespace d2d {
@@ -27,7 +27,6 @@ static void by_maxk(int max_order, F f) {
 }
 
 #if D2D_TU_FAMILY == 0
-template <int MODE> hipError_t launch_fwd_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
@@ -36,7 +35,6 @@ hipError_t launch_fwd_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t ld
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 1
-template <int MODE> hipError_t launch_fwd_grad_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_grad_m<TU_MODE>(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
@@ -44,7 +42,6 @@ hipError_t launch_fwd_grad_m<TU_MODE>(int max_order, dim3 grid, size_t lds, hipS
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 2
-template <int MODE> hipError_t launch_fwd_split_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_split_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64 * SPLIT_W);
@@ -53,7 +50,6 @@ hipError_t launch_fwd_split_m<TU_MODE>(bool stats, int max_order, dim3 grid, siz
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 3
-template <int MODE> hipError_t launch_txg_m(bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_txg_m<TU_MODE>(bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
@@ -64,7 +60,6 @@ hipError_t launch_txg_m<TU_MODE>(bool listed, bool grad, int max_order, dim3 gri
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 4
-template <int MODE> hipError_t launch_vg_m(bool txg, bool grad, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_vg_m<TU_MODE>(bool txg, bool grad, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
@@ -74,7 +69,6 @@ hipError_t launch_vg_m<TU_MODE>(bool txg, bool grad, dim3 grid, size_t lds, hipS
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 6
-template <int MODE> hipError_t launch_fwd_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_listed_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const bool wide = grid.y == 4;  // (grid.y carries the waves per workgroup: 1 or 4)
@@ -86,7 +80,6 @@ hipError_t launch_fwd_listed_m<TU_MODE>(bool stats, int max_order, dim3 grid, si
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 7
-template <int MODE> hipError_t launch_fwd_grad_listed_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_grad_listed_m<TU_MODE>(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64);
@@ -94,7 +87,6 @@ hipError_t launch_fwd_grad_listed_m<TU_MODE>(int max_order, dim3 grid, size_t ld
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 8
-template <int MODE> hipError_t launch_fwd_split_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <>
 hipError_t launch_fwd_split_listed_m<TU_MODE>(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64 * SPLIT_W);
@@ -103,7 +95,6 @@ hipError_t launch_fwd_split_listed_m<TU_MODE>(bool stats, int max_order, dim3 gr
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 9
-template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <int W>
 static void launch_fwd_coop_w(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     const dim3 block(64 * W);
@@ -118,15 +109,15 @@ hipError_t launch_fwd_coop_m<TU_MODE>(int max_order, int W, dim3 grid, size_t ld
 }
 #elif D2D_TU_FAMILY == 5
 // region_list_kernel / region_refine_kernel <K, GRAD>: independent of the validity mode (compiled once, -DD2D_TU_MODE=0)
-// (`grad` is unused: the value+grad sweeps read the forward sweeps' lists, their NaN positions come from d2d_nanscan.hpp)
-hipError_t launch_region_lists(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RegionLevel& lv,
+// (GRAD = false always: the value+grad sweeps read the forward sweeps' lists, their NaN positions come from d2d_nanscan.hpp)
+hipError_t launch_region_lists(int K, bool txg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RegionLevel& lv,
                                const ListPool& lp) {
     const dim3 block(64);
     if (txg) by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_list_kernel<decltype(KK)::value, false, true>), grid, block, lds, s, a, lv, lp); });
     else by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_list_kernel<decltype(KK)::value, false, false>), grid, block, lds, s, a, lv, lp); });
     return hipGetLastError();
 }
-hipError_t launch_region_refine(int K, bool grad, bool txg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RegionLevel& lv,
+hipError_t launch_region_refine(int K, bool txg, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RegionLevel& lv,
                                 const RegionLevel& parent, const ListPool& lp, int* flag) {
     const dim3 block(64);
     if (txg) by_maxk(K, [&](auto KK) { hipLaunchKernelGGL((region_refine_kernel<decltype(KK)::value, false, true>), grid, block, lds, s, a, lv, parent, lp, flag); });
@@ -168,7 +159,6 @@ hipError_t launch_nan_apply(hipStream_t s, const SweepArgs& a, long tiles) {
 }
 #elif D2D_TU_FAMILY == 11
 // power_rec_kernel<MODE, MAXK, TXG>: hard and hard_sigmoid only (the sigmoid sweeps' skips depend on the fused function's sum)
-template <int MODE> hipError_t launch_rec_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r);
 template <>
 hipError_t launch_rec_m<TU_MODE>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
     static_assert(TU_MODE == MODE_HARD || TU_MODE == MODE_HSIG, "the record build has no sigmoid instance");

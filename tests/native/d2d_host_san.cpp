@@ -2,9 +2,82 @@
 // parameter validation, sweep thresholds, launch buffer sizes, the reverse sweep's trajectory chunks) -- for the CPU sanitizer build:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared -fPIC
 // (tests/test_host_sanitizers.py).  The product compiles the very same header into libd2d.so with hipcc.
+// The same for differt2d_amd/csrc/d2d_own.hpp, the owning types of the context's GPU resources, over a counting stand-in
+// for the five runtime functions it calls (d2d.hip defines those with the HIP calls).
 #include "../../differt2d_amd/csrc/d2d_host.hpp"
+#include "../../differt2d_amd/csrc/d2d_own.hpp"
 
+#include <cstdlib>
 #include <cstring>
+#include <map>
+
+// ---- the stand-in runtime: every allocation is a malloc of EXACTLY the bytes asked for (an overrun is an ASan report), kept
+// in a ledger; a free or destroy of something the ledger does not hold (a second free, a moved-from copy) is counted, not done
+namespace {
+struct Ledger {
+    std::map<void*, size_t> live;
+    long long allocs = 0, frees = 0, bad_frees = 0;
+    bool fail_next = false;
+    void* take(size_t bytes) {
+        void* q = std::malloc(bytes);
+        live[q] = bytes;
+        ++allocs;
+        return q;
+    }
+    void give(void* q) {
+        auto it = live.find(q);
+        if (it == live.end()) {
+            ++bad_frees;
+            return;
+        }
+        live.erase(it);
+        std::free(q);
+        ++frees;
+    }
+} g_led;
+}  // namespace
+
+int d2d_own::dev_alloc(void** p, size_t bytes) {
+    if (g_led.fail_next) {
+        g_led.fail_next = false;
+        return D2D_ERR_HIP;
+    }
+    *p = g_led.take(bytes);
+    return 0;
+}
+void d2d_own::dev_free(void* p) { g_led.give(p); }
+void d2d_own::pinned_free(void* p) { g_led.give(p); }
+void d2d_own::event_destroy(void* h) { g_led.give(h); }
+void d2d_own::stream_destroy(void* h) { g_led.give(h); }
+
+namespace {
+using d2d_own::DevBuf;
+struct FakeEvent;
+struct FakeStream;
+using Event = d2d_own::Unique<FakeEvent*, d2d_own::event_destroy>;
+using Stream = d2d_own::Unique<FakeStream*, d2d_own::stream_destroy>;
+using Pinned = d2d_own::Unique<int*, d2d_own::pinned_free>;
+template <class H> void create(H* h) { *h = static_cast<H>(g_led.take(1)); }
+
+// the shape of d2d_ctx::PrepSet: buffers, a pointer into one of them, plain flags and an event
+struct Set {
+    DevBuf<unsigned long long> d_shadow;
+    DevBuf<int> d_sched;
+    long long cost_tiles = 0;
+    int* rl_meta_ptr = nullptr;
+    bool swept_pending = false;
+    Event ev_swept;
+};
+// ... and of d2d_ctx: the main stream first, owners in between, three rotating sets
+struct Ctx {
+    Stream stream;
+    Event ev0;
+    DevBuf<float> d_a, d_b, d_c;
+    Pinned h_meta;
+    Set cur, spare[2];
+    Stream aux;
+};
+}  // namespace
 
 extern "C" {
 
@@ -70,6 +143,86 @@ void san_sweep_thresholds(const d2d_params* p, int grad, double* d3, float* f12,
 long long san_opt_chunk_cells(long long cells, long long floats_per_cell, long long traj_mb, int mem_known, long long free_bytes,
                               long long resident_bytes) {
     return d2d_host::opt_chunk_cells(cells, floats_per_cell, traj_mb, mem_known != 0, free_bytes, resident_bytes);
+}
+
+// ---- d2d_own.hpp ----
+void san_own_counts(long long* out4) {
+    out4[0] = g_led.allocs; out4[1] = g_led.frees; out4[2] = g_led.bad_frees; out4[3] = (long long)g_led.live.size();
+}
+void* san_buf_new() { return new DevBuf<float>(); }
+void san_buf_delete(void* b) { delete static_cast<DevBuf<float>*>(b); }
+int san_buf_ensure(void* b, uint64_t count, int fail) {
+    g_led.fail_next = fail != 0;
+    const int rc = static_cast<DevBuf<float>*>(b)->ensure((size_t)count);
+    g_led.fail_next = false;
+    return rc;
+}
+void san_buf_release(void* b) { static_cast<DevBuf<float>*>(b)->release(); }
+// n, whether p is set, and the bytes the stand-in was asked for when it handed p out (-1: p is not a live allocation)
+void san_buf_query(void* b, long long* out3) {
+    const DevBuf<float>* d = static_cast<DevBuf<float>*>(b);
+    out3[0] = (long long)d->n;
+    out3[1] = d->p != nullptr;
+    auto it = g_led.live.find(d->p);
+    out3[2] = it == g_led.live.end() ? -1 : (long long)it->second;
+    if (d->p) std::memset(d->p, 0x5a, d->n * sizeof(float));  // all of it is writable
+}
+void* san_buf_move_construct(void* b) { return new DevBuf<float>(std::move(*static_cast<DevBuf<float>*>(b))); }
+void san_buf_move_assign(void* dst, void* src) {
+    DevBuf<float>& d = *static_cast<DevBuf<float>*>(dst);
+    DevBuf<float>& s = *static_cast<DevBuf<float>*>(src);  // (through references: dst == src is the self-assignment case)
+    d = std::move(s);
+}
+
+// A context-like aggregate.  built: how many of its steps succeed (the next allocation fails and the rest is never created),
+// as a d2d_create that fails half way; 9 or more: all of it.  Sets are tagged 100, 101, 102 (cur, spare[0], spare[1]).
+void* san_ctx_new(int built) {
+    Ctx* c = new Ctx();
+    int step = 0;
+    auto more = [&] { return step++ < built; };
+    if (more()) create(c->stream.put());
+    if (more()) create(c->ev0.put());
+    if (more()) c->d_a.ensure(10);
+    if (more()) c->d_b.ensure(0);
+    if (more()) create(c->h_meta.put());
+    Set* sets[3] = {&c->cur, &c->spare[0], &c->spare[1]};
+    for (int i = 0; i < 3; ++i) {
+        if (!more()) break;
+        create(sets[i]->ev_swept.put());
+        sets[i]->d_shadow.ensure(16 + (size_t)i);
+        sets[i]->rl_meta_ptr = reinterpret_cast<int*>(sets[i]->d_shadow.p + 4);
+        sets[i]->cost_tiles = 100 + i;
+        sets[i]->swept_pending = i == 1;
+    }
+    if (more()) create(c->aux.put());
+    if (built >= 9) return c;
+    g_led.fail_next = true;
+    (void)c->d_c.ensure(5);  // the failure itself: nothing allocated, nothing to free
+    return c;
+}
+void san_ctx_delete(void* c) { delete static_cast<Ctx*>(c); }
+// take_prep_set's rotation, `times` times: the oldest set becomes the current one, the current one the newest spare
+void san_ctx_rotate(void* cv, int times) {
+    Ctx* c = static_cast<Ctx*>(cv);
+    for (int t = 0; t < times; ++t) {
+        std::swap(c->cur, c->spare[0]);
+        for (int i = 0; i + 1 < 2; ++i) std::swap(c->spare[i], c->spare[i + 1]);
+        if (c->cur.d_sched.ensure(8 + (size_t)(t % 5) * 8)) return;  // (the sets also grow while they rotate)
+    }
+}
+// per set (cur, spare[0], spare[1]): tag, d_shadow.n, whether rl_meta_ptr still points into its own d_shadow, swept_pending,
+// whether the event is a live handle
+void san_ctx_sets(void* cv, long long* out15) {
+    Ctx* c = static_cast<Ctx*>(cv);
+    const Set* sets[3] = {&c->cur, &c->spare[0], &c->spare[1]};
+    for (int i = 0; i < 3; ++i) {
+        const Set& s = *sets[i];
+        out15[5 * i + 0] = s.cost_tiles;
+        out15[5 * i + 1] = (long long)s.d_shadow.n;
+        out15[5 * i + 2] = s.rl_meta_ptr == reinterpret_cast<const int*>(s.d_shadow.p + 4);
+        out15[5 * i + 3] = s.swept_pending;
+        out15[5 * i + 4] = g_led.live.count((FakeEvent*)s.ev_swept) == 1;
+    }
 }
 
 }  // extern "C"

@@ -842,3 +842,63 @@ def test_custom_fun_values_are_checked_by_the_library():
     ctx.set_grid(X, Y + F(0.01))  # a new grid drops the rows
     with pytest.raises(L.D2DError):
         ctx.launch_vg(p, tx)
+
+
+# ---- a context owns its GPU resources: created and closed over and over in one process ----------------------------------
+
+
+def test_contexts_created_and_closed_in_a_row_compute_the_same_bits():
+    """Every buffer, event and stream of a context is freed by the context's own members when it is closed.  A buffer freed
+    twice, or one used after the rotation of the preparation sets moved it, shows as a HIP error, a crash or other bits: a
+    handful of contexts, one after the other in this process, each run the sweeps that allocate the most kinds of resources
+    -- a forward sweep with region lists (the rotating sets), a culled value+grad sweep with the scene VJP (the NaN scan's
+    stream, events and flag buffers; once on its counting instance), the record launch, a MinPath sweep on another grid
+    (which drops the records), single paths and the two self-tests (local buffers) -- and must return what the first did,
+    bit for bit.  (Free device memory is not looked at: that figure belongs to everything else that runs on the device.)"""
+    from differt2d_amd.engine import Context, make_params
+    from conftest import random_scene
+
+    tx, walls = random_scene(30, seed=3)
+    x = np.linspace(0.0, 1.0, 96).astype(F)
+    X, Y = np.meshgrid(x, x)
+    xs = np.linspace(0.05, 0.95, 24).astype(F)
+    Xs, Ys = np.meshgrid(xs, xs)
+    rng = np.random.default_rng(5)
+    dx, dy = rng.standard_normal(1000).astype(F), (rng.standard_normal(1000).astype(F) + F(3.0))
+    cands = [np.array([0], np.int32), np.array([1], np.int32), np.array([2], np.int32)]
+
+    def cycle(stats):
+        out = {}
+        with Context(0) as ctx:
+            if stats:
+                ctx.set_option("nan_scan_stats", 1)
+            ctx.set_scene(walls)
+            for rep in range(4):  # (back-to-back launches: the three preparation sets rotate)
+                out[f"fwd{rep}"] = ctx.power_map(tx, X, Y, min_order=0, max_order=2)
+            for k, v in ctx.value_and_grads(tx, X, Y, min_order=0, max_order=2, approx=True).items():
+                out["vg_" + k] = v
+            if stats:
+                assert ctx.debug_nan_scan()["bad_items"] == 0 and ctx.debug_nan_scan()["probes"] > 0
+            rec = ctx.valid_paths(make_params(min_order=0, max_order=2), tx)
+            assert len(rec["cell"]) > 0
+            order = np.lexsort((*rec["cand"].T[::-1], rec["order"], rec["cell"]))  # (record order is unspecified)
+            for k, v in rec.items():
+                out["rec_" + k] = v[order]
+            ctx.set_theta0([np.array([0.5], F)] * ctx.num_candidates(1, 1))
+            out["min"] = ctx.power_map(tx, Xs, Ys, min_order=1, max_order=1, approx=True, solver="min", steps=20)
+            tr = ctx.trace_paths(make_params(order=1, solver="min", steps=10), [[0.2, 0.2]], [[0.8, 0.6]], cands, theta0=[[0.5]] * 3)
+            for k, v in tr.items():
+                out["trace_" + k] = v
+            for i, q in enumerate(ctx.selftest_div(dx, dy)):
+                out[f"div{i}"] = q
+            out["expf"] = ctx.selftest_expf(dx)
+        return out
+
+    first = cycle(False)
+    assert np.isfinite(first["fwd0"]).any() and np.isfinite(first["vg_walls_bar"]).any() and np.isfinite(first["min"]).any()
+    for n in range(1, 5):
+        again = cycle(stats=(n == 2))
+        assert again.keys() == first.keys()
+        for k in first:
+            a, b = np.ascontiguousarray(again[k]), np.ascontiguousarray(first[k])
+            assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), f"context {n}: {k} differs from the first context's"

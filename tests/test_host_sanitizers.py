@@ -3,7 +3,9 @@
 * the C oracle's sanitizer build (`make -C oracle asan`: -fsanitize=address,undefined) sweeps small and degenerate inputs;
 * the host-only logic of libd2d.so -- differt2d_amd/csrc/d2d_host.hpp: candidate enumeration, parameter validation, the
   sweep thresholds, the LDS / heavy-list size arithmetic with its 4 GiB guard, the reverse sweep's trajectory chunks -- compiled with g++ -fsanitize=address,undefined
-  (tests/native/d2d_host_san.cpp) and driven through ctypes with edge cases.
+  (tests/native/d2d_host_san.cpp) and driven through ctypes with edge cases;
+* the owning types of the context's GPU resources -- differt2d_amd/csrc/d2d_own.hpp -- in the same library, over a counting
+  stand-in for the runtime: every allocation freed exactly once through growth, moves, rotation and partial construction.
 
 Both run in a child process with libasan preloaded (an instrumented library cannot be loaded into a plain python
 otherwise); any sanitizer report makes the child exit non-zero.
@@ -77,10 +79,15 @@ def test_oracle_under_asan_and_ubsan(asan):
     assert out.returncode == 0 and "ORACLE-SAN-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
 
 
-def test_libd2d_host_logic_under_asan_and_ubsan(asan, tmp_path):
+def _build_host_san(tmp_path):
     so = str(tmp_path / "libd2d_host_san.so")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-shared", "-fPIC", "-Wall", "-Wextra", "-o", so, os.path.join(ROOT, "tests", "native", "d2d_host_san.cpp")])
+    return so
+
+
+def test_libd2d_host_logic_under_asan_and_ubsan(asan, tmp_path):
+    so = _build_host_san(tmp_path)
     code = f"""
         import ctypes as C, itertools, sys
         import numpy as np
@@ -302,3 +309,94 @@ def test_libd2d_host_logic_under_asan_and_ubsan(asan, tmp_path):
     """
     out = _run_child(code, asan)
     assert out.returncode == 0 and "HOST-SAN-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+def test_libd2d_ownership_under_asan_and_ubsan(asan, tmp_path):
+    so = _build_host_san(tmp_path)
+    code = f"""
+        import ctypes as C
+        L = C.CDLL({so!r})
+        vp, ll = C.c_void_p, C.c_longlong
+        for name, res, args in (("san_own_counts", None, [C.POINTER(ll)]), ("san_buf_new", vp, []), ("san_buf_delete", None, [vp]),
+                                ("san_buf_ensure", C.c_int, [vp, C.c_uint64, C.c_int]), ("san_buf_release", None, [vp]),
+                                ("san_buf_query", None, [vp, C.POINTER(ll)]), ("san_buf_move_construct", vp, [vp]),
+                                ("san_buf_move_assign", None, [vp, vp]), ("san_ctx_new", vp, [C.c_int]), ("san_ctx_delete", None, [vp]),
+                                ("san_ctx_rotate", None, [vp, C.c_int]), ("san_ctx_sets", None, [vp, C.POINTER(ll)])):
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+
+        def counts():
+            o = (ll * 4)()
+            L.san_own_counts(o)
+            return dict(allocs=o[0], frees=o[1], bad=o[2], live=o[3])
+
+        def query(b):    # (n, p set, bytes the stand-in was asked for)
+            o = (ll * 3)()
+            L.san_buf_query(b, o)
+            return o[0], o[1], o[2]
+
+        def balanced(live=0):
+            c = counts()
+            assert c["bad"] == 0 and c["allocs"] - c["frees"] == c["live"] == live, c
+            return c
+
+        # ---- ensure: grow / no-grow / zero; release, then ensure again
+        b = L.san_buf_new()
+        assert query(b) == (0, 0, -1) and balanced()["allocs"] == 0
+        assert L.san_buf_ensure(b, 0, 0) == 0 and query(b) == (1, 1, 4)            # a count of 0 allocates 1
+        assert L.san_buf_ensure(b, 1, 0) == 0 and balanced(1)["allocs"] == 1       # big enough: nothing happens
+        assert L.san_buf_ensure(b, 100, 0) == 0 and query(b) == (100, 1, 400)      # grows by free-then-allocate
+        assert balanced(1)["allocs"] == 2
+        for count in (100, 7, 0):
+            assert L.san_buf_ensure(b, count, 0) == 0 and query(b) == (100, 1, 400) and balanced(1)["allocs"] == 2
+        assert L.san_buf_ensure(b, 101, 0) == 0 and query(b) == (101, 1, 404) and balanced(1)["allocs"] == 3
+        L.san_buf_release(b)
+        assert query(b) == (0, 0, -1) and balanced()["frees"] == 3
+        L.san_buf_release(b)                                                       # twice: still one free per allocation
+        assert balanced()["frees"] == 3
+        assert L.san_buf_ensure(b, 5, 0) == 0 and query(b) == (5, 1, 20) and balanced(1)["allocs"] == 4
+        # a failed growth reports the error, frees the old buffer and leaves the buffer empty and usable
+        assert L.san_buf_ensure(b, 50, 1) == -2 and query(b) == (0, 0, -1) and balanced()["allocs"] == 4
+        assert L.san_buf_ensure(b, 50, 0) == 0 and query(b) == (50, 1, 200) and balanced(1)
+        # ---- move construction and move assignment, self-assignment included
+        m = L.san_buf_move_construct(b)
+        assert query(b) == (0, 0, -1) and query(m) == (50, 1, 200) and balanced(1)["allocs"] == 5
+        L.san_buf_move_assign(m, m)                                                # self: untouched
+        assert query(m) == (50, 1, 200) and balanced(1)
+        assert L.san_buf_ensure(b, 3, 0) == 0 and balanced(2)
+        L.san_buf_move_assign(b, m)                                                # the target's own buffer is freed
+        assert query(b) == (50, 1, 200) and query(m) == (0, 0, -1) and balanced(1)
+        L.san_buf_move_assign(b, m)                                                # from an empty one
+        assert query(b) == (0, 0, -1) and query(m) == (0, 0, -1) and balanced()
+        L.san_buf_move_assign(b, b)                                                # self, empty
+        assert L.san_buf_ensure(m, 9, 0) == 0
+        L.san_buf_delete(m)                                                        # the destructor frees
+        L.san_buf_delete(b)
+        assert balanced()["allocs"] == 7
+        # ---- three PrepSet-like sets rotated the way take_prep_set rotates them: buffers, pointer, flags and event travel together
+        base = counts()["allocs"]
+        c = L.san_ctx_new(9)
+        assert balanced(12)["allocs"] == base + 12    # 2 streams, 4 events, the pinned block, 2 + 3 buffers
+        def sets():
+            o = (ll * 15)()
+            L.san_ctx_sets(c, o)
+            return [tuple(o[5 * i: 5 * i + 5]) for i in range(3)]
+        start = sets()
+        assert start == [(100, 16, 1, 0, 1), (101, 17, 1, 1, 1), (102, 18, 1, 0, 1)]
+        done = 0
+        for times in (1, 1, 1, 2, 5, 300, 1001):
+            L.san_ctx_rotate(c, times)
+            done += times
+            k = done % 3
+            assert sets() == start[k:] + start[:k], (done, sets())   # cur <- spare[0] <- spare[1] <- cur
+            assert counts()["bad"] == 0
+        L.san_ctx_delete(c)
+        balanced()
+        # ---- destruction of a partly built aggregate (a d2d_create that fails at any step)
+        for built in range(0, 10):
+            c = L.san_ctx_new(built)
+            L.san_ctx_delete(c)
+            balanced()
+        print("OWN-SAN-OK", counts())
+    """
+    out = _run_child(code, asan)
+    assert out.returncode == 0 and "OWN-SAN-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
