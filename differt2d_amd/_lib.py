@@ -22,12 +22,12 @@ D2D_MAX_ORDER = 4
 D2D_NUM_STATS = 16
 D2D_COMM_ID_BYTES = 128
 D2D_OPT_ADAM, D2D_OPT_SGD, D2D_OPT_SGD_MOMENTUM = 0, 1, 2  # d2d_set_optimizer kinds
-D2D_ABI_VERSION = 11
+D2D_ABI_VERSION = 12
 
 D2D_WALL, D2D_RIS, D2D_VERTEX = 0, 1, 2
 SOLVER_IMAGE, SOLVER_MINPATH, SOLVER_FERMAT = 0, 1, 2
 ACT_HARD_SIGMOID, ACT_SIGMOID = 0, 1
-FUN_RECEIVED_POWER, FUN_LENGTH_SQUARED, FUN_LENGTH, FUN_ONE, FUN_CUSTOM = 0, 1, 2, 3, 4
+FUN_RECEIVED_POWER, FUN_LENGTH_SQUARED, FUN_LENGTH, FUN_ONE, FUN_CUSTOM, FUN_RECEIVED_POWER_PER_OBJECT = 0, 1, 2, 3, 4, 5
 OUT_OVERWRITE, OUT_ADD = 0, 1
 GRID_RX, GRID_TX = 0, 1
 
@@ -93,6 +93,8 @@ SYMBOLS = [
     ("d2d_synchronize", C.c_int, [_ctx]),
     ("d2d_set_scene", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     ("d2d_set_candidate_mask", C.c_int, [_ctx, C.c_void_p]),
+    ("d2d_set_reflection_coefs", C.c_int, [_ctx, C.c_void_p, C.c_int32]),
+    ("d2d_get_reflection_coefs_vjp", C.c_int, [_ctx, _f32p]),
     ("d2d_count_candidates", C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     ("d2d_enumerate_candidates", C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     ("d2d_num_candidates", C.c_int, [_ctx, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),

@@ -200,7 +200,12 @@ struct d2d_ctx {
     DevBuf<float> d_grad, d_cot, d_partial;
     DevBuf<float> d_cust_f, d_cust_pb;  // d2d_set_path_fun_values: a host-evaluated path function, [C][cells] and [C][cells][NP][2]
     long long cust_C = -1;              // candidates they hold (-1: none); reset by d2d_set_grid
-    DevBuf<double> d_vjp;
+    DevBuf<double> d_vjp;  // [4N] end points, [2] fixed point, [N] phi, [N] reflection coefficients
+    // d2d_set_reflection_coefs (D2D_FUN_RECEIVED_POWER_PER_OBJECT): one coefficient per object of the resident scene
+    std::vector<float> coef;   // host copy (empty: none set)
+    DevBuf<float> d_coef;      // [N], beside refl / occl
+    DevBuf<float> d_coef_partial;  // [patches][N] per-patch sums of the coefficient adjoint
+    bool vjp_has_coef = false;  // d_vjp[5N+2 .. 6N+2) holds d/d coef (else: identically 0)
     bool have_cot = false;
     bool have_vjp = false;   // d_vjp holds the scene VJP of a sweep of the CURRENT scene (4 N + 2 values)
     bool vjp_has_phi = false;  // d_vjp[4N+2 .. 5N+2) holds d/d phi (optimiser-based sweeps); image sweeps: identically 0
@@ -699,6 +704,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     }
     // from here on the old scene is gone: a failed upload leaves the context without a scene, never with half of one
     c->have_scene = false;
+    c->coef.clear();              // (the reflection coefficients belong to the objects of the previous scene)
     c->cust_C = -1;               // (a host-evaluated path function's rows belong to the paths of the previous scene)
     c->have_vjp = false;          // d_vjp was sized for (and computed from) the previous scene
     c->have_kernel_time = false;
@@ -721,6 +727,44 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     rc = upload_mask(c);
     if (rc) return rc;
     c->have_scene = true;
+    return D2D_OK;
+}
+
+int d2d_set_reflection_coefs(d2d_ctx* c, const float* coef, int32_t n) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come first");
+    if (!coef || n == 0) {
+        if (coef || n != 0) return fail(D2D_ERR_INVALID, "d2d_set_reflection_coefs: NULL with n = 0 drops the coefficients; got %s with n = %d", coef ? "an array" : "NULL", n);
+        c->coef.clear();
+        return D2D_OK;
+    }
+    if (n != c->N) return fail(D2D_ERR_INVALID, "d2d_set_reflection_coefs: %d coefficients for a scene of %d objects", n, c->N);
+    for (int j = 0; j < n; ++j)
+        if (!std::isfinite(coef[j])) return fail(D2D_ERR_INVALID, "reflection coefficient %d is not finite", j);
+    if ((int)c->coef.size() == n && c->d_coef.p && std::memcmp(c->coef.data(), coef, (size_t)n * sizeof(float)) == 0) return D2D_OK;  // resident already
+    int rc = set_device(c);
+    if (rc) return rc;
+    c->coef.clear();  // (a failed upload leaves the context without coefficients, never with stale ones)
+    if ((rc = c->d_coef.ensure((size_t)n + 1))) return rc;
+    // (stream order: the sweeps that read the previous values are in front of this copy)
+    HIP_TRY(hipMemcpyAsync(c->d_coef.p, coef, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->coef.assign(coef, coef + n);
+    return D2D_OK;
+}
+
+int d2d_get_reflection_coefs_vjp(d2d_ctx* c, float* coef_bar) {
+    if (!c || !coef_bar) return fail(D2D_ERR_INVALID, "NULL argument");
+    if (!c->have_vjp) return fail(D2D_ERR_STATE, "no scene-VJP sweep has run");
+    for (int j = 0; j < c->N; ++j) coef_bar[j] = 0.0f;
+    if (!c->vjp_has_coef || c->N == 0) return D2D_OK;  // none of the sweeps used D2D_FUN_RECEIVED_POWER_PER_OBJECT
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = join_comm(c, 2))) return rc;  // an all-reduce of the VJP in flight lands first
+    std::vector<double> h((size_t)c->N);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->d_vjp.p + 5 * (size_t)c->N + 2, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < c->N; ++j) coef_bar[j] = (float)h[(size_t)j];
     return D2D_OK;
 }
 
@@ -989,6 +1033,7 @@ static int opt_grad_zero(d2d_ctx* c, const OptSweep& s) {
         if (!(p->out_mode == D2D_OUT_ADD && c->have_vjp)) {
             HIP_TRY(hipMemsetAsync(c->d_vjp.p, 0, (size_t)s.n_elem * sizeof(double), c->stream));
             c->vjp_has_phi = true;
+            c->vjp_has_coef = false;
             c->vjp_reduced = false;
         }
         c->have_vjp = true;
@@ -1103,6 +1148,7 @@ static int opt_vjp_reduce(d2d_ctx* c, const OptSweep& s) {
     HIP_TRY(hipGetLastError());
     c->have_vjp = true;
     c->vjp_has_phi = true;
+    c->vjp_has_coef = false;  // (the optimiser-based sweeps refuse the per-object function)
     return D2D_OK;
 }
 
@@ -1261,7 +1307,9 @@ static int sweep_args(d2d_ctx* c, Sweep& s) {
     a.tol = p->tol;
     a.seg_lo = -p->seg_tol;
     a.seg_hi = 1.0f + p->seg_tol;
-    s.th = d2d_host::sweep_thresholds(*p, s.grad_mode != 0);
+    const bool per_object = p->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT;
+    s.th = d2d_host::sweep_thresholds(*p, s.grad_mode != 0, per_object ? c->coef.data() : nullptr, c->allowed.data(), c->N);
+    a.coef = per_object ? c->d_coef.p : nullptr;
     a.flt_lo = s.th.flt_lo;
     a.flt_hi = s.th.flt_hi;
     a.on_lo = s.th.on_lo;
@@ -1722,8 +1770,15 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
     const int n_elem = 4 * c->N + 2;
     if (grad_mode == 2) {
         if ((rc = c->d_partial.ensure((size_t)s.tiles * n_elem))) return rc;
-        if ((rc = c->d_vjp.ensure((size_t)n_elem + (size_t)c->N))) return rc;  // [4N] end points, [2] fixed point, [N] phi
+        if ((rc = c->d_vjp.ensure((size_t)n_elem + 2 * (size_t)c->N))) return rc;  // [4N] end points, [2] fixed point, [N] phi, [N] coef
         a.partial = c->d_partial.p;
+    }
+    // the coefficient adjoint of the per-object function: N more floats of LDS per wave behind everything else, one row per patch
+    const bool coef_vjp = grad_mode == 2 && p->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT && c->N > 0;
+    const size_t lds_coef = coef_vjp ? (size_t)c->N * sizeof(float) : 0;
+    if (coef_vjp) {
+        if ((rc = c->d_coef_partial.ensure((size_t)s.tiles * (size_t)c->N))) return rc;
+        a.coef_partial = c->d_coef_partial.p;
     }
     if (p->out_mode == D2D_OUT_OVERWRITE) c->have_vjp = false;
     // (hard validity with fun = 1: nothing is differentiated through the path; order 0 alone: only path_length's own trap)
@@ -1739,7 +1794,10 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
     const bool culled_rx = !txg && !p->strict_nan;
     const size_t lds_tab = (size_t)(4 * c->N + 1) * sizeof(float4);  // tables, adjoint table
     const size_t lds_culled = culled_rx ? lds_tab + 512 : lds_tab;    // (+ the culling queue)
-    if ((culled_rx || s.txg_culled) && lds_culled > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
+    if ((culled_rx || s.txg_culled) && lds_culled + lds_coef > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
+    const size_t lds_vg = (size_t)(4 * c->N + 4) * sizeof(float);  // the exhaustive kernel's wall adjoints
+    if (coef_vjp && !culled_rx && !s.txg_culled && lds_vg + lds_coef > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table", c->N);
+    if (coef_vjp) a.coef_lds_off = (int)((culled_rx || s.txg_culled) ? lds_culled : lds_vg);
     // ... and should a launch fail behind the fork all the same (a HIP error), the scan is waited for before the error is returned
     struct ScanJoin {
         d2d_ctx* c;
@@ -1774,16 +1832,15 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         // culled value+grad sweep (default)
         a.cullq_off = (int)lds_tab;
         rc = sweep_and_walk(c, s, pr, a, s.grid_patches, [&](const d2d::SweepArgs& x, dim3 g) {
-            return d2d::launch_fwd_grad(mode, x.rl != nullptr, p->max_order, g, lds_culled, c->stream, x);
+            return d2d::launch_fwd_grad(mode, x.rl != nullptr, p->max_order, g, lds_culled + lds_coef, c->stream, x);
         });
     } else if (s.txg_culled) {
         // TX grid, culled value+grad sweep
         rc = sweep_and_walk(c, s, pr, a, s.grid_patches, [&](const d2d::SweepArgs& x, dim3 g) {
-            return d2d::launch_txg(mode, x.rl != nullptr, true, p->max_order, g, lds_culled, c->stream, x);
+            return d2d::launch_txg(mode, x.rl != nullptr, true, p->max_order, g, lds_culled + lds_coef, c->stream, x);
         });
     } else {
-        const size_t lds = (size_t)(4 * c->N + 4) * sizeof(float);
-        HIP_TRY(d2d::launch_vg(mode, txg, true, s.grid_patches, lds, c->stream, a));
+        HIP_TRY(d2d::launch_vg(mode, txg, true, s.grid_patches, lds_vg + lds_coef, c->stream, a));
     }
     if (rc) return rc;
     if (scan) {
@@ -1805,6 +1862,17 @@ static int launch_value_grad(d2d_ctx* c, Sweep& s, const Prep& pr) {
         hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)n_elem), dim3(256), 0, c->stream, c->d_partial.p,
                            rows, n_elem, c->d_vjp.p, accumulate);
         HIP_TRY(hipGetLastError());
+        if (!accumulate) c->vjp_has_coef = false;  // a new sum
+        if (coef_vjp) {
+            // the fourth block, behind a phi block that an ImagePath sweep leaves at zero (d2d_comm_allreduce_vjp covers both by length)
+            double* const phi_block = c->d_vjp.p + n_elem;
+            const int acc_coef = (accumulate && c->vjp_has_coef) ? 1 : 0;
+            if (!acc_coef) HIP_TRY(hipMemsetAsync(phi_block, 0, (size_t)c->N * sizeof(double), c->stream));
+            hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->d_coef_partial.p, rows, c->N,
+                               phi_block + c->N, acc_coef);
+            HIP_TRY(hipGetLastError());
+            c->vjp_has_coef = true;
+        }
         c->have_vjp = true;
     }
     return D2D_OK;
@@ -1928,6 +1996,13 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before a sweep");
     c->have_kernel_time = false;  // whatever this launch turns out to be, the previous launch's kernel time is stale
     if (p->fun_id == D2D_FUN_CUSTOM && !grad_mode) return fail(D2D_ERR_UNSUPPORTED, "fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only");
+    if (p->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT) {
+        if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT)
+            return fail(D2D_ERR_UNSUPPORTED, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT (received_power_per_object) is fused for ImagePath sweeps only, not for the MinPath / FermatPath solvers");
+        if (d_stats) return fail(D2D_ERR_UNSUPPORTED, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT (received_power_per_object) has no instrumented build");
+        if ((int)c->coef.size() != c->N || (c->N > 0 && !c->d_coef.p))
+            return fail(D2D_ERR_STATE, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT needs d2d_set_reflection_coefs for the resident scene");
+    }
     if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT) {
         if (d_stats) return fail(D2D_ERR_UNSUPPORTED, "the optimiser-based solvers have no instrumented build");
         return opt_sweep_launch(c, p, tx, grad_mode);
@@ -2741,7 +2816,7 @@ int d2d_comm_allreduce_vjp(d2d_ctx* c) {
     // on the communication stream like the gathers (collectives of one communicator execute in issue order), behind the
     // reduction kernel that produced d_vjp; d2d_get_scene_vjp and the next sweep's reduction wait for it
     if ((rc = comm_after_main(c))) return rc;
-    const size_t n = (size_t)(4 * c->N + 2) + (c->vjp_has_phi ? (size_t)c->N : 0);
+    const size_t n = (size_t)(4 * c->N + 2) + (c->vjp_has_coef ? 2 * (size_t)c->N : (c->vjp_has_phi ? (size_t)c->N : 0));
     RCCL_TRY(rccl().AllReduce(c->d_vjp.p, c->d_vjp.p, n, ncclFloat64, ncclSum, c->comm, c->comm_stream));
     HIP_TRY(hipEventRecord(c->ev_done[2], c->comm_stream));
     c->inflight[2] = true;

@@ -153,7 +153,7 @@ inline int check_params(const d2d_params* p, std::string& err) {
     if (p->approx && !(p->alpha > 0.0f)) return err = "alpha must be > 0 in approx mode", D2D_ERR_INVALID;
     if (p->approx && p->act != D2D_ACT_HARD_SIGMOID && p->act != D2D_ACT_SIGMOID)
         return err = "activation " + std::to_string(p->act) + " is not one of the native activations", D2D_ERR_UNSUPPORTED;
-    if (p->fun_id < 0 || p->fun_id > D2D_FUN_CUSTOM) return err = "fun_id " + std::to_string(p->fun_id) + " is not a native path function", D2D_ERR_UNSUPPORTED;
+    if (p->fun_id < 0 || p->fun_id > D2D_FUN_RECEIVED_POWER_PER_OBJECT) return err = "fun_id " + std::to_string(p->fun_id) + " is not a native path function", D2D_ERR_UNSUPPORTED;
     if (p->out_mode != D2D_OUT_OVERWRITE && p->out_mode != D2D_OUT_ADD) return err = "bad out_mode " + std::to_string(p->out_mode), D2D_ERR_INVALID;
     if (p->grid_role != D2D_GRID_RX && p->grid_role != D2D_GRID_TX) return err = "bad grid_role " + std::to_string(p->grid_role), D2D_ERR_INVALID;
     if (!(p->seg_tol >= 0.0f)) return err = "seg_tol must be >= 0", D2D_ERR_INVALID;
@@ -233,8 +233,10 @@ struct SweepThresholds {
     bool degenerate_invalid = false;
 };
 // The thresholds of the culling tests and shortcuts of an ImagePath sweep with parameters p (checked by check_params).
-// grad: a value+grad sweep.
-inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad) {
+// grad: a value+grad sweep.  coef / allowed / n_objects: the reflection coefficients of D2D_FUN_RECEIVED_POWER_PER_OBJECT and the
+// candidate mask (null: all objects) -- without coefficients that function gets no bound (correct, and nothing is skipped).
+inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad, const float* coef = nullptr, const uint8_t* allowed = nullptr,
+                                        int n_objects = 0) {
     SweepThresholds t;
     // Filter thresholds: the soft window is where some activation of t is not exactly saturated
     // to "outside": hard -> [-tol, 1+tol]; hard_sigmoid -> widened by 3/alpha; sigmoid -> by 89/alpha
@@ -280,6 +282,28 @@ inline SweepThresholds sweep_thresholds(const d2d_params& p, bool grad) {
         else if (ok) t.sig_l2f = -1e30f;  // fun == 0 throughout
     }
     if (p.fun_id == D2D_FUN_CUSTOM) t.sig_mono = 0;  // (values of any sign)
+    if (p.fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT) {
+        // |fun| = prod_i |coef[cand_i]| / (h^2 + r^2) <= cmax^k / h^2 with cmax over the objects a candidate may hold; fun >= 0
+        // throughout only when none of those coefficients is negative
+        t.sig_mono = 0;
+        if (coef) {
+            float cmax = 0.0f;
+            bool nonneg = true;
+            for (int j = 0; j < n_objects; ++j) {
+                if (allowed && !allowed[j]) continue;
+                cmax = std::fmax(cmax, std::fabs(coef[j]));
+                nonneg = nonneg && coef[j] >= 0.0f;
+            }
+            t.sig_mono = (nonneg || p.max_order < 1) ? 1 : 0;
+            if (t.h2 > 0.0f && std::isfinite(t.h2)) {
+                double fm = 0.0;
+                for (int k = p.min_order; k <= p.max_order; ++k) fm = std::fmax(fm, std::pow((double)cmax, k) / (double)t.h2);
+                // (1e-3 in log2 units is 7e-4 relative: far above the k roundings of the kernels' fp32 fold)
+                if (std::isfinite(fm) && fm > 0.0) t.sig_l2f = (float)std::log2(fm) + 1e-3f;
+                else if (std::isfinite(fm)) t.sig_l2f = -1e30f;  // fun == 0 throughout
+            }
+        }
+    }
     // A step of the backward scan with un == 0 (the line to the image parallel to the wall, geometry.py:1105) leaves a
     // zero-length segment, loss >= 1 (0.999 with roundings): is such a path exactly invalid under this tol / activation?
     const double x_deg = (double)p.tol - 0.999;  // tol - loss at best

@@ -160,6 +160,11 @@ struct SweepArgs {
     const float* __restrict__ cust_f;   // [C][m * n]
     const float* __restrict__ cust_pb;  // [C][m * n][D2D_MAX_ORDER + 2][2]
     long cust_cells;                    // m * n
+    // fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT: one reflection coefficient per object (d2d_set_reflection_coefs).  Read with
+    // D2D_LATE_ARG where a surviving candidate needs them: they never sit in scalar registers through the candidate loop.
+    const float* __restrict__ coef;     // [N] wave-uniform index -> scalar loads
+    float* __restrict__ coef_partial;   // value+grad kernels with the scene VJP: [n_patches][N] per-patch sums of cot * d Z / d coef, or null
+    int coef_lds_off;                   // ... and the byte offset, from the start of dynamic LDS, of the wave's [N] sums (behind all else)
 
     // patch schedule (patch_cost_kernel / patch_order_kernel): workgroup b takes patch sched[b]; null = identity
     const int* __restrict__ sched;
@@ -360,6 +365,7 @@ struct GradCtx {
     float cot;       // cotangent of this cell's accumulated value
     float* wl;       // LDS [4 N] of this wave: sum over lanes/candidates of cot * (d/d origin.xy, d/d dest.xy)
     bool scene;      // accumulate tbx/tby/wl ?
+    float* cb;       // LDS [N] of this wave, or null: sum over lanes/candidates of cot * d/d coef (D2D_FUN_RECEIVED_POWER_PER_OBJECT)
     int ci;          // D2D_FUN_CUSTOM: ordinal of the next candidate in the sweep's order (wave-uniform)
     long cell;       // D2D_FUN_CUSTOM: this lane's cell
 };
@@ -368,6 +374,25 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// The wave's sums of the coefficient adjoint (SweepArgs::coef_partial): N floats of dynamic LDS behind everything else the
+// kernel keeps there, zeroed with the wall adjoints `wl` and written as the patch's row once the patch is through.  Rows are
+// reduced in patch order (vjp_reduce_kernel), and the NaN scan never touches them: the reference's autodiff NaN traps lie
+// between the path points and the geometry, the coefficients are not on that way.
+__device__ __forceinline__ float* coef_acc_ptr(void* lds_base) {
+    const int off = D2D_LATE_ARG(int, coef_lds_off);
+    return off ? reinterpret_cast<float*>(reinterpret_cast<char*>(lds_base) + off) : nullptr;
+}
+__device__ __forceinline__ void coef_acc_zero(float* cb, int N) {
+    if (cb)
+        for (int i = threadIdx.x & 63; i < N; i += 64) cb[i] = 0.0f;
+}
+__device__ __forceinline__ void coef_acc_store(const float* cb, int N, long tile) {
+    if (cb) {
+        float* dst = D2D_LATE_ARG(float*, coef_partial) + tile * N;
+        for (int i = threadIdx.x & 63; i < N; i += 64) dst[i] = cb[i];
+    }
 }
 
 // d activation(x) / d x as JAX differentiates it: hard_sigmoid = relu6(alpha x + 3) / 6 -> alpha/6 strictly inside
@@ -1006,8 +1031,19 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
         r = r + sqrtf(vx * vx + vy * vy);
     }
     float f;
+    float cf[K > 0 ? K : 1];  // D2D_FUN_RECEIVED_POWER_PER_OBJECT: the candidate's coefficients (wave-uniform)
     if (a.fun_id == D2D_FUN_RECEIVED_POWER) f = a.fnum[K] / (a.h2 + r * r);
-    else if (a.fun_id == D2D_FUN_LENGTH_SQUARED) f = r * r;
+    else if (a.fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT) {
+        // one coefficient per interacting object, folded from the left in candidate order (include/d2d.h)
+        const float* const coef = D2D_LATE_ARG(const float*, coef);
+        float num = 1.0f;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            cf[i] = cmem(coef)[cand[i]];
+            num = num * cf[i];
+        }
+        f = num / (a.h2 + r * r);
+    } else if (a.fun_id == D2D_FUN_LENGTH_SQUARED) f = r * r;
     else if (a.fun_id == D2D_FUN_LENGTH) f = r;
     else if (GRAD && a.fun_id == D2D_FUN_CUSTOM) f = a.cust_f[cust];
     else f = 1.0f;
@@ -1019,9 +1055,25 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
         const float fbar = valid;
         const float vbar = (MODE == MODE_HARD || nanflag) ? 0.0f : f;
         float rbar;
-        if (a.fun_id == D2D_FUN_RECEIVED_POWER) {
+        if (a.fun_id == D2D_FUN_RECEIVED_POWER || a.fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT) {
             float Dn = a.h2 + r * r;
             rbar = -(fbar * (f / Dn)) * (2.0f * r);
+            if (K > 0 && a.fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT && g->scene && g->cb != nullptr) {
+                // d f / d coef[cand_i] = (prod_{q != i} coef[cand_q]) / Dn: the product of the OTHER coefficients is wave-uniform
+                // and formed explicitly (a coefficient may be zero: nothing is divided by one); an object that occurs twice in
+                // the candidate receives both terms.  One writer per wave, candidates in order: the same bits run to run.
+                const float s = wave_sum(g->cot * (fbar / Dn));
+                if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                    for (int i = 0; i < K; ++i) {
+                        float others = 1.0f;
+#pragma unroll
+                        for (int q = 0; q < K; ++q)
+                            if (q != i) others = others * cf[q];
+                        g->cb[cand[i]] += s * others;
+                    }
+                }
+            }
         } else if (a.fun_id == D2D_FUN_LENGTH_SQUARED) rbar = fbar * (2.0f * r);
         else if (a.fun_id == D2D_FUN_LENGTH) rbar = fbar;
         else rbar = 0.0f;
@@ -2205,8 +2257,10 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
     const int crow = row < a.m ? row : a.m - 1;
     const long idx = (long)crow * a.n + ccol;
     const float rxx = a.X[idx], rxy = a.Y[idx];
+    float* const cb = scene ? coef_acc_ptr(tab) : nullptr;
     if (scene) {
         for (int i = lane; i < 4 * a.N; i += 64) wl[i] = 0.0f;
+        coef_acc_zero(cb, a.N);
         __syncthreads();
     }
     if (!exists) return;
@@ -2224,6 +2278,7 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
     g.grx = g.gry = g.tbx = g.tby = 0.0f;
     g.cot = in_range ? (a.cot ? a.cot[idx] : 1.0f) : 0.0f;
     g.wl = wl;
+    g.cb = cb;
     g.scene = scene;
     g.ci = 0;
     g.cell = 0;
@@ -2394,6 +2449,7 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
             dst[4 * a.N] = tbx_sum;
             dst[4 * a.N + 1] = tby_sum;
         }
+        coef_acc_store(cb, a.N, tile);
     }
     if (STATS && a.stats) {
 #pragma unroll
@@ -3095,8 +3151,10 @@ __device__ __forceinline__ void txg_patch(const SweepArgs& a, const float4* tab,
     const int lane = threadIdx.x & 63;
     const int tiles_x = (a.n + TILE_W - 1) / TILE_W;
     const bool scene = GRADK && a.partial != nullptr;
+    float* const cb = scene ? coef_acc_ptr(const_cast<float4*>(tab)) : nullptr;
     if (scene) {
         for (int i = lane; i < 4 * a.N; i += 64) wl[i] = 0.0f;
+        coef_acc_zero(cb, a.N);
         __syncthreads();
     }
     WaveStats st;
@@ -3127,6 +3185,7 @@ __device__ __forceinline__ void txg_patch(const SweepArgs& a, const float4* tab,
     g.grx = g.gry = g.tbx = g.tby = 0.0f;
     g.cot = in_range ? (a.cot ? a.cot[idx] : 1.0f) : 0.0f;  // clamped duplicate lanes contribute nothing
     g.wl = wl;
+    g.cb = cb;
     g.scene = scene;
     g.ci = 0;
     g.cell = 0;
@@ -3182,6 +3241,7 @@ __device__ __forceinline__ void txg_patch(const SweepArgs& a, const float4* tab,
             dst[4 * a.N] = sx;
             dst[4 * a.N + 1] = sy;
         }
+        coef_acc_store(cb, a.N, tile);
     }
 }
 
@@ -3787,14 +3847,17 @@ __global__ void __launch_bounds__(64) power_vg_kernel(SweepArgs a) {
     const bool lane_bad = !(fabsf(gx_) < 1e18f) || !(fabsf(gy_) < 1e18f) || !(fabsf(a.txx) < 1e18f) ||
                           !(fabsf(a.txy) < 1e18f);
     const bool scene = GRADK && a.partial != nullptr;
+    float* const cb = scene ? coef_acc_ptr(wl) : nullptr;
     if (scene) {
         for (int i = lane; i < 4 * a.N; i += 64) wl[i] = 0.0f;
+        coef_acc_zero(cb, a.N);
         __syncthreads();
     }
     GradCtx g;
     g.grx = g.gry = g.tbx = g.tby = 0.0f;
     g.cot = in_range ? (a.cot ? a.cot[idx] : 1.0f) : 0.0f;  // clamped duplicate lanes contribute nothing
     g.wl = wl;
+    g.cb = cb;
     g.scene = scene;
     g.ci = 0;
     g.cell = idx;
@@ -3831,6 +3894,7 @@ __global__ void __launch_bounds__(64) power_vg_kernel(SweepArgs a) {
             dst[4 * a.N] = sx;
             dst[4 * a.N + 1] = sy;
         }
+        coef_acc_store(cb, a.N, (long)blockIdx.x);
     }
 }
 

@@ -20,6 +20,7 @@ FUN_IDS = {
     "length_squared": L.FUN_LENGTH_SQUARED,
     "length": L.FUN_LENGTH,
     "one": L.FUN_ONE,
+    "received_power_per_object": L.FUN_RECEIVED_POWER_PER_OBJECT,  # one coefficient per object: Context.set_reflection_coefs
     "custom": L.FUN_CUSTOM,  # values and derivatives from the host: Context.set_path_fun_values (value+grad launches only)
 }
 ACT_IDS = {"hard_sigmoid": L.ACT_HARD_SIGMOID, "sigmoid": L.ACT_SIGMOID}
@@ -141,6 +142,22 @@ class Context:
         if a.shape != (self.n_objects,):
             raise ValueError("mask must have one entry per object")
         L.check(self._lib.d2d_set_candidate_mask(self._ctx, a.ctypes.data_as(C.c_void_p)))
+
+    def set_reflection_coefs(self, coefs=None):
+        """One reflection coefficient per object of the resident scene, for ``fun="received_power_per_object"`` (include/d2d.h:
+        d2d_set_reflection_coefs).  They stay with the scene: another scene drops them; ``None`` drops them too."""
+        if coefs is None:
+            L.check(self._lib.d2d_set_reflection_coefs(self._ctx, None, 0))
+            return
+        c = np.ascontiguousarray(coefs, dtype=np.float32).reshape(-1)
+        L.check(self._lib.d2d_set_reflection_coefs(self._ctx, c.ctypes.data_as(C.c_void_p), c.size))
+
+    def get_reflection_coefs_vjp(self) -> np.ndarray:
+        """``<cotangent, d Z / d coefficients>`` [N] of the last scene-VJP sweep(s); zeros unless they ran
+        ``fun="received_power_per_object"`` (include/d2d.h: d2d_get_reflection_coefs_vjp)."""
+        out = np.zeros(max(self.n_objects, 1), np.float32)
+        L.check(self._lib.d2d_get_reflection_coefs_vjp(self._ctx, out))
+        return out[: self.n_objects]
 
     def num_candidates(self, min_order=0, max_order=1) -> int:
         n = C.c_int64(0)

@@ -32,6 +32,7 @@ import numpy as np
 from . import _lib as L
 from . import logic
 from .abc import Object, Plottable, random_uniform
+from .defaults import DEFAULT_R_COEF
 from .engine import Context, default_context, make_params
 from .geometry import (
     FermatPath, ImagePath, MinPath, Path, Point, RIS, Vertex, Wall, _opt_kwargs, _validity_kwargs, closest_point,
@@ -276,7 +277,7 @@ def _native_fun(fun, fun_args, fun_kwargs):
     if fun_args:
         return None
     extra = dict(fun_kwargs or {})
-    if name != "received_power" and extra:
+    if name not in ("received_power", "received_power_per_object") and extra:
         return None
     if set(extra) - {"r_coef", "height"}:
         return None
@@ -489,6 +490,20 @@ class Scene(Plottable):
         if mask is not None:
             ctx.set_candidate_mask(mask)
 
+    def _upload_for(self, ctx: Context, native, filter_objects=None):
+        """``_upload`` in front of a fused launch of the native function ``native`` = (name, kwargs): the per-object function also
+        gets its coefficients, ``coef[j] = getattr(objects[j], "r_coef", r_coef)``."""
+        self._upload(ctx, filter_objects)
+        name, extra = native
+        if name == "received_power_per_object":
+            default = extra.get("r_coef", DEFAULT_R_COEF)
+            ctx.set_reflection_coefs(np.array([getattr(o, "r_coef", default) for o in self.objects], F))
+
+    def _refuse_per_object_solver(self, native, path_cls):
+        if native is not None and native[0] == "received_power_per_object" and self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"received_power_per_object is fused for ImagePath only, not for path_cls={path_cls.__name__} "
+                                       "(the MinPath / FermatPath sweeps have no per-object coefficients)")
+
     @staticmethod
     def _solver_of(path_cls) -> str:
         solver = getattr(path_cls, "solver", None)
@@ -589,6 +604,7 @@ class Scene(Plottable):
         if native is None or not self.receivers or not self.transmitters:
             return None
         name, extra = native
+        self._refuse_per_object_solver(native, path_cls)
         solver = self._solver_of(path_cls)
         if solver == "image":
             # (ImagePath draws nothing per candidate: only WHETHER there are candidates matters here -- counted in the library
@@ -622,7 +638,7 @@ class Scene(Plottable):
             sextra, theta0 = self._solver_setup(path_cls, path_cls_kwargs, cands if solver != "image" else [], key)
             X, Y = np.ascontiguousarray(rx[None, :, 0]), np.ascontiguousarray(rx[None, :, 1])
             launches = [(tx_key, tx, rx_keys, X, Y, theta0) for tx_key, tx in self.transmitters.items()]
-        return dict(params={"fun": name, **extra, **sextra, **common}, filter_objects=filter_objects, launches=launches)
+        return dict(params={"fun": name, **extra, **sextra, **common}, filter_objects=filter_objects, launches=launches, native=native)
 
     def accumulate_over_paths(self, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *,
                               reduce_all: bool = False, **kwargs):
@@ -636,7 +652,7 @@ class Scene(Plottable):
             ctx = self._ctx()
             params = make_params(**fused["params"])
             for tx_key, tx, rx_keys, X, Y, theta0 in fused["launches"]:
-                self._upload(ctx, fused["filter_objects"])
+                self._upload_for(ctx, fused["native"], fused["filter_objects"])
                 ctx.set_grid(X, Y)
                 if theta0 is not None:
                     ctx.set_theta0(theta0)
@@ -687,7 +703,7 @@ class Scene(Plottable):
         values = {}
         if callable(cotangent) or cotangent is None:
             for tx_key, tx, keys, X, Y, theta0 in fused["launches"]:
-                self._upload(ctx, fused["filter_objects"])
+                self._upload_for(ctx, fused["native"], fused["filter_objects"])
                 ctx.set_grid(X, Y)
                 if theta0 is not None:
                     ctx.set_theta0(theta0)
@@ -698,9 +714,12 @@ class Scene(Plottable):
         n = len(self.objects)
         vjp = {"transmitters": {k: np.zeros(2, F) for k in self.transmitters}, "receivers": {k: np.zeros(2, F) for k in rx_keys},
                "objects": np.zeros((n, 2, 2), F), "phi": np.zeros(n, F)}
+        per_object = fused["native"][0] == "received_power_per_object"
+        if per_object:
+            vjp["r_coefs"] = np.zeros(n, F)  # d objective / d coefficient of every object (this function only)
         for tx_key, tx, keys, X, Y, theta0 in fused["launches"]:
             w = np.ones((1, len(keys)), F) if cot is None else np.array([[cot.get((tx_key, k), 0.0) for k in keys]], F)
-            self._upload(ctx, fused["filter_objects"])
+            self._upload_for(ctx, fused["native"], fused["filter_objects"])
             ctx.set_grid(X, Y)
             ctx.set_cotangent(w)
             if theta0 is not None:
@@ -714,6 +733,8 @@ class Scene(Plottable):
                 vjp["receivers"][k] = (vjp["receivers"][k] + w[0, j] * g[j]).astype(F)
             vjp["objects"] = (vjp["objects"] + objects_bar).astype(F)
             vjp["phi"] = (vjp["phi"] + phi_bar).astype(F)
+            if per_object:
+                vjp["r_coefs"] = (vjp["r_coefs"] + ctx.get_reflection_coefs_vjp()).astype(F)
         return values, vjp
 
     # ------------------------------------------------------------------------ grid sweeps
@@ -859,6 +880,7 @@ class Scene(Plottable):
             return gen
 
         name, extra = native
+        self._refuse_per_object_solver(native, path_cls)
         ctx = self._ctx()
         cands = None
         if self._solver_of(path_cls) != "image":
@@ -886,7 +908,7 @@ class Scene(Plottable):
         if reduce_all:
             if not fixed_items:
                 return (F(0.0), F(0.0)) if value_and_grad else F(0.0)
-            self._upload(ctx, filter_objects)
+            self._upload_for(ctx, native, filter_objects)
             ctx.set_grid(X, Y)
             for i, (_, pt) in enumerate(fixed_items):
                 launch(pt, L.OUT_ADD if i else L.OUT_OVERWRITE)
@@ -894,7 +916,7 @@ class Scene(Plottable):
 
         def results():
             for pt_name, pt in fixed_items:
-                self._upload(ctx, filter_objects)
+                self._upload_for(ctx, native, filter_objects)
                 ctx.set_grid(X, Y)
                 launch(pt, L.OUT_OVERWRITE)
                 yield pt_name, fetch()
@@ -941,6 +963,7 @@ class Scene(Plottable):
         if native is None:
             raise L.D2DUnsupported(-4, "the scene VJP needs a natively fused fun (differt2d_amd.utils)")
         name, extra = native
+        self._refuse_per_object_solver(native, path_cls)
         ctx = self._ctx()
         cands = None
         if self._solver_of(path_cls) != "image":
@@ -948,15 +971,18 @@ class Scene(Plottable):
         sextra, theta0 = self._solver_setup(path_cls, path_cls_kwargs, cands or [], key)
         extra = {**extra, **sextra}
         for tx_name, tx in self.transmitters.items():
-            self._upload(ctx, filter_objects)
+            self._upload_for(ctx, native, filter_objects)
             ctx.set_grid(X, Y)
             ctx.set_cotangent(cotangent)
             if theta0 is not None:
                 ctx.set_theta0(theta0)
             ctx.launch_vg(make_params(fun=name, **extra, **common), tx.xy, scene_vjp=True)
             tx_bar, objects_bar, phi_bar = ctx.get_scene_vjp(with_phi=True)
-            yield tx_name, {"value": ctx.get_map(), "grad_rx": ctx.get_grad_rx(), "tx_bar": tx_bar, "objects_bar": objects_bar,
-                            "phi_bar": phi_bar}
+            out = {"value": ctx.get_map(), "grad_rx": ctx.get_grad_rx(), "tx_bar": tx_bar, "objects_bar": objects_bar,
+                   "phi_bar": phi_bar}
+            if name == "received_power_per_object":
+                out["r_coef_bar"] = ctx.get_reflection_coefs_vjp()  # <cot, dZ/d coefficient of every object> [N]
+            yield tx_name, out
 
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,

@@ -41,6 +41,20 @@ def received_power(transmitter, receiver, path: Path, interacting_objects, r_coe
     return (_integer_pow(r_coef, n) / (h * h + r * r)).astype(F)
 
 
+def received_power_per_object(transmitter, receiver, path: Path, interacting_objects, r_coef: float = DEFAULT_R_COEF,
+                              height: float = DEFAULT_HEIGHT):
+    """``prod_o coef(o) / (height**2 + length**2)`` over the interacting objects, ``coef(o) = getattr(o, "r_coef", r_coef)``: a
+    reflection coefficient per wall -- a ``Wall`` subclass with an ``r_coef`` field or class attribute is all a user writes
+    (the reference hands ``interacting_objects`` to every path function for this, scene.py:51, 1136-1154).  The product is
+    folded from the left in fp32, in the candidate's order; with equal coefficients it is :func:`received_power`."""
+    r = path.length()
+    h = F(height)
+    num = F(1.0)
+    for o in interacting_objects:
+        num = F(num * F(getattr(o, "r_coef", r_coef)))
+    return (num / (h * h + r * r)).astype(F)
+
+
 def path_length_squared(transmitter, receiver, path: Path, interacting_objects):
     """``path.length() ** 2`` -- the function the reference's accumulate tests use (tests/test_scene.py:444)."""
     r = path.length()
@@ -58,6 +72,7 @@ def one(transmitter, receiver, path: Path, interacting_objects):
 
 
 received_power._d2d_native = "received_power"
+received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"
 path_length_fun._d2d_native = "length"
 one._d2d_native = "one"

@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
-#define D2D_ABI_VERSION 11
+#define D2D_ABI_VERSION 12
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -52,13 +52,21 @@ enum { D2D_ACT_HARD_SIGMOID = 0, D2D_ACT_SIGMOID = 1 };
  *   RECEIVED_POWER  differt2d/utils.py:17-54        r_coef**n / (height^2 + length^2)
  *   LENGTH_SQUARED  tests/test_scene.py:444-445     path.length() ** 2
  *   LENGTH          differt2d/geometry.py:811-819   path.length()
- *   ONE             1.0 (the map then counts valid paths -- "intersection counts") */
+ *   ONE             1.0 (the map then counts valid paths -- "intersection counts")
+ *   RECEIVED_POWER_PER_OBJECT   the `interacting_objects` argument of PathFun put to use (differt2d/scene.py:51, 1136-1154): one
+ *                   reflection coefficient per object (d2d_set_reflection_coefs) instead of one for all,
+ *                       num = 1;  for o in interacting_objects (candidate order):  num = num * coef[o]     (fp32, left fold)
+ *                       f   = num / (height^2 + length^2)
+ *                   Order 0 has num = 1.  With every coefficient equal to c this is RECEIVED_POWER(r_coef = c) bit for bit for the
+ *                   orders 0..3 (lax.integer_pow's square-and-multiply and the left fold coincide there); at order 4 the two may
+ *                   differ by an ulp, and the left fold is the definition.  d2d_params.r_coef is ignored. */
 enum {
     D2D_FUN_RECEIVED_POWER = 0,
     D2D_FUN_LENGTH_SQUARED = 1,
     D2D_FUN_LENGTH = 2,
     D2D_FUN_ONE = 3,
-    D2D_FUN_CUSTOM = 4 /* values and derivatives supplied per (candidate, cell): d2d_set_path_fun_values; value+grad launches only */
+    D2D_FUN_CUSTOM = 4, /* values and derivatives supplied per (candidate, cell): d2d_set_path_fun_values; value+grad launches only */
+    D2D_FUN_RECEIVED_POWER_PER_OBJECT = 5 /* ImagePath sweeps only; needs d2d_set_reflection_coefs */
 };
 
 /* Which end of the paths the grid cells are. */
@@ -139,6 +147,17 @@ int d2d_set_scene(d2d_ctx* ctx, const float* xys, const uint8_t* kind, const flo
 /* filter_objects of Scene.all_path_candidates (differt2d/scene.py:1089-1134): allowed[i] != 0
  * means object i may appear in a path candidate; NULL = all. Filtered objects still occlude. */
 int d2d_set_candidate_mask(d2d_ctx* ctx, const uint8_t* allowed);
+
+/* Reflection coefficient of every object for D2D_FUN_RECEIVED_POWER_PER_OBJECT: coef[n], n = the scene's number of objects
+ * (D2D_ERR_INVALID otherwise, and for a value that is not finite; negative values and zero are allowed).  A host array, copied
+ * before the call returns.  The values belong to the resident scene: a d2d_set_scene that uploads another scene drops them,
+ * one that recognises the resident scene keeps them.  Setting the values that are set already uploads nothing; NULL / 0 drops
+ * them.  A sweep with fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT returns D2D_ERR_STATE without coefficients and
+ * D2D_ERR_UNSUPPORTED (naming the function) with the MinPath / FermatPath solvers or through the instrumented build
+ * (d2d_power_map_stats, d2d_power_map_wave_cycles); d2d_power_map_launch and d2d_power_map_vg_launch run it in both grid roles,
+ * all three validity modes, orders 0..D2D_MAX_ORDER, with D2D_OUT_ADD, the candidate mask, cotangents and either strict_nan.
+ * d2d_valid_paths / d2d_trace_paths ignore fun_id as ever. */
+int d2d_set_reflection_coefs(d2d_ctx* ctx, const float* coef, int32_t n);
 
 /* Context-free candidate enumeration (pure host integer code, replaces the Rust
  * differt_core.rt.CompleteGraph / DiGraph.all_paths calls at differt2d/scene.py:153-175): for each order
@@ -256,6 +275,18 @@ int d2d_get_grad_rx(d2d_ctx* ctx, float* out);
  * may be NULL) and phi_bar[N] (RIS angles, differt2d/geometry.py:683-721; may be NULL; identically 0 after an ImagePath
  * sweep, whose candidates hold Wall objects only). */
 int d2d_get_scene_vjp(d2d_ctx* ctx, float* tx_bar, float* xys_bar, float* phi_bar);
+
+/* Synchronises and copies <cot, d Z / d coef> [N] of the last scene-VJP sweep(s) (d2d_power_map_vg_launch with
+ * want_scene_vjp != 0): the derivative of the objective w.r.t. the reflection coefficients of
+ * D2D_FUN_RECEIVED_POWER_PER_OBJECT,  coef_bar[o] = sum over cells and candidates, once per occurrence i of o in the candidate, of
+ * cot * valid * (prod_{q != i} coef[cand_q]) / (height^2 + length^2)  -- the product of the OTHER coefficients is formed explicitly,
+ * nothing is divided by a coefficient (zero is a legal value).  It accumulates over D2D_OUT_ADD launches exactly as tx_bar /
+ * xys_bar do, is all zeros when none of the accumulated sweeps used that function, and D2D_ERR_STATE without a scene-VJP sweep.
+ * The reference's reverse-mode NaN traps sit on the way from the path points back to the geometry, and the coefficients are not
+ * on that way: cells whose grad_rx is NaN (d2d_params.strict_nan) poison tx_bar / xys_bar, never coef_bar.
+ * Stored as a fourth block of the resident VJP ([4N] end points, [2] fixed point, [N] phi, [N] coef), which
+ * d2d_comm_allreduce_vjp then covers by length -- that path has NEVER run on more than one rank. */
+int d2d_get_reflection_coefs_vjp(d2d_ctx* ctx, float* coef_bar /* [N] */);
 
 /* Same sweep through the instrumented build of the kernel (same results, not for timing): fills
  * stats[D2D_NUM_STATS] with executed-work counters summed over waves (one count = one 64-lane wave):
@@ -452,7 +483,7 @@ int d2d_comm_gather_map(d2d_ctx* ctx, int32_t what, int32_t root);
 /* Synchronises and copies the gathered map (what = 0 / 1 as above; the two are kept in separate buffers, so a step may
  * gather both) to out[world * per_rank]; capacity (in floats) must be exactly that. */
 int d2d_comm_get_gathered(d2d_ctx* ctx, int32_t what, float* out, int64_t capacity);
-/* Collective, asynchronous: sums the resident scene VJP (fp64, 4N+2 values, + N for phi) over ranks in place, on the
+/* Collective, asynchronous: sums the resident scene VJP (fp64, 4N+2 values, + N for phi, + N for the reflection coefficients) over ranks in place, on the
  * communication stream behind the reduction that produced it; d2d_get_scene_vjp waits for it. */
 int d2d_comm_allreduce_vjp(d2d_ctx* ctx);
 
