@@ -134,6 +134,8 @@ SYMBOLS = [
     ("d2d_get_valid_paths", C.c_int, [_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     ("d2d_debug_valid_paths_ms", C.c_int, [_ctx, np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")]),
+    ("d2d_power_profile_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_float, C.c_float, C.c_int32]),
+    ("d2d_get_power_profile", C.c_int, [_ctx, _f32p]),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),

@@ -61,6 +61,11 @@ hipError_t launch_rec(int mode, bool txg, int max_order, dim3 grid, size_t lds, 
     if (mode == MODE_HSIG) return launch_rec_m<MODE_HSIG>(txg, max_order, grid, lds, s, a, r);
     return hipErrorInvalidValue;
 }
+hipError_t launch_bin(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const BinArgs& b) {
+    if (mode == MODE_HARD) return launch_bin_m<MODE_HARD>(txg, max_order, grid, lds, s, a, b);
+    if (mode == MODE_HSIG) return launch_bin_m<MODE_HSIG>(txg, max_order, grid, lds, s, a, b);
+    return hipErrorInvalidValue;
+}
 
 }  // namespace d2d
 
@@ -163,6 +168,13 @@ struct d2d_ctx {
     long long rec_n = -1;  // records the buffers hold (-1: none)
     Event ev_rec[6];  // "time_kernel": around pass 1, pass 2 and the trace
     bool have_rec_time = false;
+    // per-cell power-delay profile (d2d_power_profile_launch): [prof_nbins][m][n], kept until the next launch, dropped with the grid
+    DevBuf<float> d_profile;
+    int prof_nbins = 0;  // bins the buffer holds a profile of (0: none)
+    void drop_profile() {
+        d_profile.release();
+        prof_nbins = 0;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -857,6 +869,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->grid_version += 1;  // ... and the regions' bounding boxes another grid
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->drop_records();  // ... and the records' cells
+        c->drop_profile();  // ... and the profile's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -2175,9 +2188,109 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     return D2D_OK;
 }
 
+// Bin launch of the culled forward sweep: the record launch's preparation (masks of its own, main stream, nothing of the fused
+// sweeps touched) with the caller's path function, then ONE pass of power_bin_kernel into the zeroed profile.  Asynchronous.
+// Every check comes before anything is enqueued.
+static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float r_min, float r_max, int32_t nbins) {
+    if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_power_profile_launch");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_power_profile_launch");
+    c->prof_nbins = 0;  // whatever this launch turns out to be, the previous profile is gone
+    if (p_in->solver == D2D_SOLVER_MINPATH || p_in->solver == D2D_SOLVER_FERMAT)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch covers ImagePath only, not the MinPath / FermatPath solvers (solver %d)", p_in->solver);
+    if (p_in->approx && p_in->act != D2D_ACT_HARD_SIGMOID)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch covers hard and hard_sigmoid validity: the sigmoid sweeps skip candidates by the fused function's running sum");
+    if (p_in->fun_id == D2D_FUN_CUSTOM)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only (a host function's profile: bin the records of d2d_valid_paths)");
+    if (p_in->out_mode == D2D_OUT_ADD) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: D2D_OUT_ADD is not supported, a profile is always overwritten");
+    if (p_in->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT && ((int)c->coef.size() != c->N || (c->N > 0 && !c->d_coef.p)))
+        return fail(D2D_ERR_STATE, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT needs d2d_set_reflection_coefs for the resident scene");
+    d2d_host::ProfileBins bins;
+    {
+        std::string err;
+        if ((rc = d2d_host::profile_bins(r_min, r_max, nbins, bins, err))) return fail(rc, "%s", err.c_str());
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    if ((rc = check_image_sweep(c, p, nullptr))) return rc;
+    if (c->N > 4095) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: %d objects exceed the culling queue's 12-bit object indices", c->N);
+    if ((long long)c->m * c->n > 0x7fffffffLL) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: the grid exceeds 31-bit cell indices");
+    const size_t lds = d2d_host::tab_lds_bytes(c->N);  // tables + one culling queue
+    if (lds > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table (max ~2400)", c->N);
+    if (p->grid_role == D2D_GRID_TX) {
+        // the record route's rule: a TX grid is swept by the culled kernels only (sweep_args), and a refusal is not a fall-back
+        const bool degenerate_invalid = d2d_host::sweep_thresholds(*p, false).degenerate_invalid;
+        if (c->txg_exhaustive || !degenerate_invalid)
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: a TX-grid sweep with these parameters is not culled (%s)",
+                        c->txg_exhaustive ? "the \"txg_exhaustive\" option is set" : "a degenerate path is not exactly invalid under tol / alpha");
+    }
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        // (half of what is free, plus what the buffer holds already)
+        const size_t held = c->d_profile.n * sizeof(float);
+        const size_t budget = (mem_free + held) / 2;
+        if (cells > 0 && (size_t)nbins > budget / sizeof(float) / cells)
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: %d bins of %zu cells (4 bytes each) exceed half of the free device memory (%zu bytes free)",
+                        nbins, cells, mem_free);
+    }
+    if ((rc = c->d_profile.ensure((size_t)nbins * cells))) return rc;
+    if ((rc = upload_occl(c, p->patch))) return rc;
+
+    Sweep s;
+    s.p = p;
+    s.tx = fixed;
+    s.d_stats = nullptr;
+    s.grad_mode = 0;
+    s.tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
+    s.tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
+    s.tiles = (long long)s.tiles_x * s.tiles_y;
+    s.piped = false;
+    s.ps = c->stream;
+    Prep pr;
+    const long long fallbacks = c->txg_fallbacks;
+    if ((rc = sweep_args(c, s))) return rc;
+    c->txg_fallbacks = fallbacks;  // (refused above instead)
+    if (s.txg && !s.txg_culled) return fail(D2D_ERR_STATE, "d2d_power_profile_launch: the TX-grid sweep is not culled after all (an internal error)");
+    if ((rc = prep_masks(c, s, pr, &c->d_rec_shadow))) return rc;
+    d2d::SweepArgs& a = s.a;
+    a.out = nullptr;  // never written by the bin build
+    a.cullq_off = (int)((size_t)(4 * c->N + 1) * sizeof(float4));
+    d2d::BinArgs b;
+    b.out = c->d_profile.p;
+    b.cells = (long)cells;
+    b.r_min = bins.r_min;
+    b.inv = bins.inv;
+    b.nbins = bins.nbins;
+    HIP_TRY(hipMemsetAsync(c->d_profile.p, 0, (size_t)nbins * cells * sizeof(float), c->stream));
+    if (s.tiles > 0) HIP_TRY(d2d::launch_bin(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, b));
+    c->prof_nbins = nbins;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_power_profile_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float r_min, float r_max, int32_t nbins) {
+    return power_profile_launch(c, p, fixed, r_min, r_max, nbins);
+}
+
+int d2d_get_power_profile(d2d_ctx* c, float* out) {
+    if (!c || !out) return fail(D2D_ERR_INVALID, "NULL argument");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (c->prof_nbins < 1 || !c->d_profile.p) return fail(D2D_ERR_STATE, "d2d_power_profile_launch must come first (its profile goes with the grid)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_profile.p, (size_t)c->prof_nbins * (size_t)c->m * c->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_valid_paths(d2d_ctx* c, const d2d_params* p, const float* fixed, int64_t* count) { return valid_paths(c, p, fixed, count); }
 

@@ -1,6 +1,6 @@
 // Host-only logic of libd2d.so that needs neither a device nor the HIP headers: candidate enumeration (the stand-in for
 // differt-core's Rust graph iterator, differt2d/scene.py:153-175), parameter validation, lax.integer_pow, the
-// scalar thresholds of a sweep, and the buffer-size arithmetic of the sweep launches (LDS tables, the contribution lists
+// scalar thresholds of a sweep, the bins of the power-delay profile, and the buffer-size arithmetic of the sweep launches (LDS tables, the contribution lists
 // of the patches cut in four and their 4 GiB guard).  d2d.hip uses these functions as they are; tests/native/d2d_host_san.cpp compiles the same header with
 // g++ -fsanitize=address,undefined and tests/test_host_sanitizers.py drives it (sanitizers run on the CPU build only).
 #pragma once
@@ -217,6 +217,28 @@ inline HeavyPlan heavy_plan(long long tiles, long long Nc, long long heavy_split
     hp.list_floats = H * parts * cap * 64;
     hp.cnt_ints = H * parts * 64 + H * parts;
     return hp;
+}
+
+// ---- bins of the per-cell power-delay profile (d2d_power_profile_launch, d2d::BinSink) ------------------------------
+// nbins half-open bins of equal width over [r_min, r_max): a path of length r falls into bin floorf((r - r_min) * inv) with
+//     inv = (float)nbins / (r_max - r_min)      fp32: one subtraction, one division
+// -- the one place the range is checked and inv is formed (tests/native/power_profile_host.cpp holds it to NumPy's fp32).
+// D2D_ERR_INVALID: nbins < 1, a bound that is not finite, r_max <= r_min.
+struct ProfileBins {
+    float r_min = 0.0f, inv = 0.0f;
+    int32_t nbins = 0;
+};
+inline int profile_bins(float r_min, float r_max, int32_t nbins, ProfileBins& b, std::string& err) {
+    if (nbins < 1) return err = "the power profile needs nbins >= 1, got " + std::to_string(nbins), D2D_ERR_INVALID;
+    if (!std::isfinite(r_min) || !std::isfinite(r_max)) return err = "the power profile's length range must be finite", D2D_ERR_INVALID;
+    if (!(r_max > r_min))
+        return err = "the power profile's length range needs r_max > r_min, got [" + std::to_string(r_min) + ", " + std::to_string(r_max) + ")", D2D_ERR_INVALID;
+    const volatile float width = r_max - r_min;  // (volatile: rounded to fp32 here, whatever the host compiler's excess precision)
+    const volatile float inv = (float)nbins / width;
+    b.r_min = r_min;
+    b.inv = inv;
+    b.nbins = nbins;
+    return D2D_OK;
 }
 
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------

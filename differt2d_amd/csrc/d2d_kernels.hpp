@@ -22,8 +22,9 @@
 // power_fwd_kernel (one wave per patch; dearest patches cut in four) / power_fwd_split_kernel (small launches: every
 // patch shared by 4 waves prefix by prefix) / power_fwd_coop_kernel (the smallest: 4 / 8 / 16 waves, candidate by candidate) /
 // sweep_order_culled_txg + power_fwd_txg_kernel (TX grids) / patch_* (dearest-first schedule) / shadow_fill_kernel,
-// pair_shadow_kernel, hidden_region_kernel (occlusion masks) / power_vg_kernel (exhaustive value+grad) / trace_kernel and
-// the literal object code (any mix of Wall / RIS / Vertex) / power_opt_*_kernel (MinPath / FermatPath sweeps).
+// pair_shadow_kernel, hidden_region_kernel (occlusion masks) / power_rec_kernel, power_bin_kernel (record and bin builds) /
+// power_vg_kernel (exhaustive value+grad) / trace_kernel and the literal object code (any mix of Wall / RIS / Vertex) /
+// power_opt_*_kernel (MinPath / FermatPath sweeps).
 //
 // Reference lines followed (DiffeRT2d v0.4.0): see include/d2d.h and oracle/ref.py.
 #pragma once
@@ -426,7 +427,10 @@ template <int K, int MODE, bool STATS, bool GRAD = false, bool PREF = true, bool
 __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&cand)[D2D_MAX_ORDER],
                                                const float (&imgx)[D2D_MAX_ORDER], const float (&imgy)[D2D_MAX_ORDER],
                                                float txx, float txy, float rxx, float rxy, bool lane_bad, float& acc,
-                                               WaveStats& st, GradCtx* g = nullptr, float acc_floor = -1.0f) {
+                                               WaveStats& st, GradCtx* g = nullptr, float acc_floor = -1.0f, float* r_out = nullptr) {
+    // r_out (power_bin_kernel): receives the path length the path function is evaluated with -- written only where the
+    // contribution is (a candidate that leaves early leaves both alone).  Null everywhere else, a constant of the inlined call:
+    // it costs those instances no instruction.
     // acc_floor >= 0 (MODE_SIG, fun >= 0): the caller adds this candidate to a sum it does not hold -- `acc` is a scratch
     // that receives the contribution alone -- but knows that sum to be at least acc_floor when the addition happens
     const float zc_acc = (acc_floor >= 0.0f) ? acc_floor : acc;
@@ -1030,6 +1034,7 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
         float vy = (py[i + 1] - py[i]) + D2D_EPS;
         r = r + sqrtf(vx * vx + vy * vy);
     }
+    if (r_out != nullptr) *r_out = r;
     float f;
     float cf[K > 0 ? K : 1];  // D2D_FUN_RECEIVED_POWER_PER_OBJECT: the candidate's coefficients (wave-uniform)
     if (a.fun_id == D2D_FUN_RECEIVED_POWER) f = a.fnum[K] / (a.h2 + r * r);
@@ -1639,12 +1644,13 @@ struct ListSink {
 // [base, limit) raises the sticky flag instead.  A record: {cell (row-major), code bits 0..31, code bits 32..47 | order << 24,
 // the contribution's bits}; code = 12 bits per wall index, first wall lowest.
 struct RecSink {
+    static constexpr bool WANTS_R = false;  // (the path length is not asked of eval_candidate)
     int4* rec;
     int base, limit;
     int cnt;
     int cell;  // this lane's cell; < 0: a clamped duplicate of a lane outside the grid, which never pushes
     int* flag;
-    __device__ __forceinline__ void put(float t, unsigned long long code, int k) {
+    __device__ __forceinline__ void put(float t, unsigned long long code, int k, float /*r*/ = 0.0f) {
         const bool p = cell >= 0 && !(t == 0.0f);
         const unsigned long long m = __ballot(p);
         if (rec != nullptr && p) {
@@ -1653,6 +1659,34 @@ struct RecSink {
             else *flag = 1;
         }
         cnt += __builtin_popcountll(m);
+    }
+};
+
+// Bin build (power_bin_kernel): every contribution that is not exactly zero is added to the bin of its path length instead of
+// to acc -- the power-delay profile out[nbins][cells] (include/d2d.h: d2d_power_profile_launch):
+//     u = (r - r_min) * inv ;  b = (int)floorf(u) ;  if (u >= 0 && b < nbins) out[b][cell] = out[b][cell] + t
+// in fp32 without contraction, candidates in the sweep's order.  A lane is the only writer of its cell's column and reads back
+// what it stored itself: plain loads and stores, the same bits run to run.  A NaN length fails u >= 0 and names no bin; lanes
+// outside the grid (cell < 0) never write.  (u < 2^31 in front of the conversion: beyond it the conversion is undefined, and
+// the bin is past any nbins anyway.)
+struct BinSink {
+    static constexpr bool WANTS_R = true;
+    float* out;  // [nbins][cells]
+    long cells;
+    int cell;    // this lane's cell; < 0: a clamped duplicate of a lane outside the grid
+    float r_min, inv;
+    int nbins;
+    __device__ __forceinline__ void put(float t, unsigned long long /*code*/, int /*k*/, float r) {
+        if (cell < 0 || t == 0.0f) return;
+        const float d = r - r_min;
+        const float u = d * inv;
+        if (u >= 0.0f && u < 2147483648.0f) {
+            const int b = (int)floorf(u);
+            if (b < nbins) {
+                float* p = out + (size_t)b * (size_t)cells + (size_t)cell;
+                *p = *p + t;
+            }
+        }
     }
 };
 
@@ -1700,14 +1734,15 @@ __device__ __forceinline__ void emit_batch(EmitSink& e, unsigned long long code,
 // acc: acc is never -0.0), so that another wave can add them later in the reference's order.
 // EMIT (K >= 2): nothing is evaluated; the survivors of the full culling test are appended to `emit` instead (the box is
 // then a region's, not a patch's).
-// RECORD: like LIST, but the contribution goes to `rsink` with the candidate's code (all lanes take part: RecSink::put).
-template <int K, int MODE, bool STATS, bool GRAD = false, bool LIST = false, bool EMIT = false, bool RECORD = false>
+// RECORD: like LIST, but the contribution goes to `rsink` with the candidate's code (all lanes take part: RecSink::put) -- or,
+// RS = BinSink, with the candidate's path length.
+template <int K, int MODE, bool STATS, bool GRAD = false, bool LIST = false, bool EMIT = false, bool RECORD = false, class RS = RecSink>
 __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const float4* tab, const float (&bx)[4],
                                                    const float (&by)[4], float rxx, float rxy, bool lane_bad, float& acc,
                                                    WaveStats& st, GradCtx* g = nullptr, int p_lo = 0,
                                                    int p_hi = 0x7fffffff, ListSink* sink = nullptr, EmitSink* emit = nullptr,
                                                    const unsigned long long* hidden_row = nullptr, float hidden_dperp = 0.0f,
-                                                   RecSink* rsink = nullptr) {
+                                                   RS* rsink = nullptr) {
     static_assert(!EMIT || K >= 2, "lists exist for orders >= 2");
     const int lane = threadIdx.x & 63;
     int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
@@ -1805,9 +1840,9 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 image_of(ldc4(a.refl, 2 * ce[d]), d == 0 ? a.txx : ex[d > 0 ? d - 1 : 0], d == 0 ? a.txy : ey[d > 0 ? d - 1 : 0], ex[d], ey[d]);
             }
             if constexpr (RECORD) {
-                float t = 0.0f;
-                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
-                rsink->put(t, cu, K);
+                float t = 0.0f, rl = 0.0f;
+                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr);
+                rsink->put(t, cu, K, rl);
             } else if (LIST) {
                 float t = 0.0f;
                 eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
@@ -1944,12 +1979,12 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), pIx, pIy, imgx[K - 1], imgy[K - 1]);
                 if constexpr (RECORD) {
-                    float t = 0.0f;
-                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
+                    float t = 0.0f, rl = 0.0f;
+                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr);
                     unsigned long long cu = 0ull;
 #pragma unroll
                     for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
-                    rsink->put(t, cu, K);
+                    rsink->put(t, cu, K, rl);
                 } else if (LIST) {
                     float t = 0.0f;
                     eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
@@ -3000,13 +3035,14 @@ __global__ void __launch_bounds__(64) region_refine_kernel(SweepArgs a, RegionLe
 // Prefix = (w_0 .. w_{K-2}) wave-uniform, lanes = last wall, survivors in ascending order: the reference's order.
 // EMIT (K >= 2; region_list_kernel): first-wall positions [p_lo, p_hi) only, the box is a region's, and the survivors are
 // appended to `emit` (in candidate order: prefix-major, last walls ascending) instead of being evaluated.
-// RECORD: the contributions go to `rsink` with the candidate's code instead of acc (power_rec_kernel).
-template <int K, int MODE, bool GRAD = false, bool EMIT = false, bool RECORD = false>
+// RECORD: the contributions go to `rsink` with the candidate's code instead of acc (power_rec_kernel), or with the candidate's path
+// length (RS = BinSink, power_bin_kernel).
+template <int K, int MODE, bool GRAD = false, bool EMIT = false, bool RECORD = false, class RS = RecSink>
 __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const float4* tab, const float (&bx)[4],
                                                        const float (&by)[4], float cx, float cy, bool lane_bad, float& acc,
                                                        WaveStats& st, GradCtx* g = nullptr, int p_lo = 0, int p_hi = 0x7fffffff,
                                                        EmitSink* emit = nullptr, const unsigned long long* hidden_row = nullptr,
-                                                       float hidden_dperp = 0.0f, RecSink* rsink = nullptr) {
+                                                       float hidden_dperp = 0.0f, RS* rsink = nullptr) {
     static_assert(!EMIT || K >= 2, "lists exist for orders >= 2");
     const int lane = threadIdx.x & 63;
     int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
@@ -3068,12 +3104,12 @@ __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), K == 1 ? cx : imgx[K >= 2 ? K - 2 : 0], K == 1 ? cy : imgy[K >= 2 ? K - 2 : 0], imgx[K - 1], imgy[K - 1]);
                 if constexpr (RECORD) {
-                    float t = 0.0f;
-                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g);
+                    float t = 0.0f, rl = 0.0f;
+                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr);
                     unsigned long long cu = 0ull;
 #pragma unroll
                     for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
-                    rsink->put(t, cu, K);
+                    rsink->put(t, cu, K, rl);
                 } else {
                     eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, acc, st, g);
                 }
@@ -3340,6 +3376,81 @@ __global__ void __launch_bounds__(64) power_rec_kernel(SweepArgs a, RecArgs r) {
         }
     });
     if (r.rec == nullptr && lane == 0) r.counts[tile] = sink.cnt;
+}
+
+// Bin build of the culled forward sweep (d2d_power_profile_launch): power_rec_kernel's launch shape and enumeration -- one wave per
+// 8 x 8 patch in row-major patch order, no schedule, no cut patches, no region lists -- with the CALLER's fused path function and a
+// BinSink in the records' place: one pass, the per-cell power-delay profile b.out[nbins][m * n] (zeroed on the stream in front of the
+// launch).  It touches neither the value map nor the work history.
+struct BinArgs {
+    float* out;       // [nbins][cells]
+    long cells;       // m * n
+    float r_min, inv; // the bins: floorf((r - r_min) * inv), d2d_host::profile_bins
+    int nbins;
+};
+template <int MODE, int MAXK, bool TXG>
+__global__ void __launch_bounds__(64) power_bin_kernel(SweepArgs a, BinArgs b) {
+    const int lane = threadIdx.x & 63;
+    extern __shared__ float4 tab[];  // [2N] refl, [N] flt, then (a.cullq_off) the culling queue
+    for (int i = lane; i < 2 * a.N; i += 64) tab[i] = ldc4(a.refl, i);
+    for (int i = lane; i < a.N; i += 64) tab[2 * a.N + i] = ldc4(a.flt, i);
+    __syncthreads();
+    const int tiles_x = (a.n + TILE_W - 1) / TILE_W;
+    const long tile = (long)blockIdx.x;
+    const int tcol = (int)(tile % tiles_x), trow = (int)(tile / tiles_x);
+    const int col = tcol * TILE_W + (lane & (TILE_W - 1));
+    const int row = trow * TILE_H + (lane / TILE_W);
+    const bool in_range = (col < a.n) && (row < a.m);
+    const int ccol = col < a.n ? col : a.n - 1;
+    const int crow = row < a.m ? row : a.m - 1;
+    const long idx = (long)crow * a.n + ccol;
+    const float cx = a.X[idx], cy = a.Y[idx];
+    const bool lane_bad = !(fabsf(cx) < 1e18f) || !(fabsf(cy) < 1e18f) || !(fabsf(a.txx) < 1e18f) || !(fabsf(a.txy) < 1e18f);
+    WaveStats st;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) st.c[i] = 0;
+    st.shadow = -1;
+    st.work = 0;
+    // bounding box of the wave's cells (NaN / inf coordinates make every comparison fail: nothing is culled)
+    float x0 = cx, x1 = cx, y0 = cy, y1 = cy;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        x0 = fminf(x0, __shfl_xor(x0, off, 64));
+        x1 = fmaxf(x1, __shfl_xor(x1, off, 64));
+        y0 = fminf(y0, __shfl_xor(y0, off, 64));
+        y1 = fmaxf(y1, __shfl_xor(y1, off, 64));
+    }
+    const bool box_ok = !wave_any(lane_bad);
+    const float qn = __builtin_nanf("");
+    const float bx[4] = {box_ok ? x0 : qn, x1, x1, x0};
+    const float by[4] = {y0, y0, y1, y1};
+    BinSink sink;
+    sink.out = b.out;
+    sink.cells = b.cells;
+    sink.cell = in_range ? (int)idx : -1;
+    sink.r_min = b.r_min;
+    sink.inv = b.inv;
+    sink.nbins = b.nbins;
+    float dummy = 0.0f;
+    if (a.min_order <= 0 && a.max_order >= 0) {
+        // (sweep_order<0>'s one candidate, with the length handed out)
+        const int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
+        const float imgx[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f}, imgy[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float t = 0.0f, rl = 0.0f;
+        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, &rl);
+        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, &rl);
+        sink.put(t, 0ull, 0, rl);
+    }
+    static_for<1, MAXK + 1>([&](auto KK) {
+        constexpr int K = decltype(KK)::value;
+        if (a.min_order <= K && a.max_order >= K) {
+            if constexpr (TXG)
+                sweep_order_culled_txg<K, MODE, false, false, true>(a, tab, bx, by, cx, cy, lane_bad, dummy, st, nullptr, 0, 0x7fffffff, nullptr, nullptr, 0.0f, &sink);
+            else
+                sweep_order_culled<K, MODE, false, false, false, false, true>(a, tab, bx, by, cx, cy, lane_bad, dummy, st, nullptr, 0, 0x7fffffff, nullptr, nullptr,
+                                                                              nullptr, 0.0f, &sink);
+        }
+    });
 }
 
 // Patch schedule.  The hardware starts workgroups in blockIdx order, and a dear patch that starts late is the tail of the

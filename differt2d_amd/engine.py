@@ -484,6 +484,26 @@ class Context:
         L.check(self._lib.d2d_debug_valid_paths_ms(self._ctx, ms))
         return {"count_ms": float(ms[0]), "write_ms": float(ms[1]), "trace_ms": float(ms[2])}
 
+    def power_profile(self, params: L.Params, fixed, r_min: float, r_max: float, nbins: int) -> np.ndarray:
+        """Per-cell power-delay profile of the resident grid: the fused sweep's contributions ``valid * fun`` binned by path
+        length into ``nbins`` half-open bins of equal width over ``[r_min, r_max)`` -- one launch of the bin build of the culled
+        sweep (include/d2d.h: d2d_power_profile_launch holds the definition; ImagePath, hard or hard_sigmoid validity, every fused
+        function).  ``params.grid_role`` says which end of the paths the cells are, ``fixed`` is the other end.  The resident value
+        map is not touched.  Returns an fp32 array ``[nbins, m, n]``; :func:`differt2d_amd.utils.delay_statistics` reduces it."""
+        self.launch_profile(params, fixed, r_min, r_max, nbins)
+        return self.get_profile(nbins)
+
+    def launch_profile(self, params: L.Params, fixed, r_min: float, r_max: float, nbins: int):
+        """The launch of :meth:`power_profile` alone (asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        L.check(self._lib.d2d_power_profile_launch(self._ctx, C.byref(params), fixed, float(r_min), float(r_max), int(nbins)))
+
+    def get_profile(self, nbins: int) -> np.ndarray:
+        """Synchronises and returns the profile of the last :meth:`launch_profile`, which was launched with ``nbins`` bins."""
+        out = np.empty((int(nbins),) + tuple(self.shape), np.float32)
+        L.check(self._lib.d2d_get_power_profile(self._ctx, out))
+        return out
+
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id() -> bytes:

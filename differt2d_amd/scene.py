@@ -984,6 +984,59 @@ class Scene(Plottable):
                 out["r_coef_bar"] = ctx.get_reflection_coefs_vjp()  # <cot, dZ/d coefficient of every object> [N]
             yield tx_name, out
 
+    def _grid_profile(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, length_range, nbins, path_cls, min_order, max_order,
+                      order, filter_objects, kwargs):
+        """Shared driver of the two power-delay profiles: one launch of the bin build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the power-delay profile is a fused sweep (a function "
+                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+                                       "(Context.valid_paths: every valid path with its length) and bin fun's values on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the power-delay profile covers ImagePath only, not path_cls={path_cls.__name__}")
+        r_min, r_max = length_range
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.power_profile(params, pt.xy, r_min, r_max, nbins)
+
+        return results()
+
+    def power_delay_profile_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, length_range, nbins: int, path_cls: type = ImagePath,
+        min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Per-cell power-delay profile: for every transmitter, ``P[b, i, j]`` = the sum of ``valid * fun`` over the candidates
+        whose path length falls into bin ``b`` of ``nbins`` half-open bins of equal width over ``length_range = (r_min, r_max)``,
+        the receiver at ``(X[i, j], Y[i, j])`` -- what :meth:`accumulate_on_receivers_grid_over_paths` adds up per cell, spread
+        over path length (delay = length / c).  Yields ``(tx name, P)`` with ``P`` an fp32 array ``[nbins, m, n]``; one fused
+        kernel launch per transmitter (include/d2d.h: d2d_power_profile_launch holds the exact definition).
+        :func:`differt2d_amd.utils.delay_statistics` gives total power, mean length and RMS spread per cell.
+
+        ``fun`` must be natively fused (:mod:`differt2d_amd.utils`), the path class ``ImagePath``, the validity hard
+        (``approx=False``) or ``hard_sigmoid``; anything else raises :class:`D2DUnsupported`.  For another callable the sparse
+        valid-path records (:meth:`Context.valid_paths`) hold every valid path's length for binning on the host."""
+        return self._grid_profile(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, length_range, nbins, path_cls,
+                                  min_order, max_order, order, filter_objects, kwargs)
+
+    def power_delay_profile_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, length_range, nbins: int, path_cls: type = ImagePath,
+        min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`power_delay_profile_on_receivers_grid`: one profile per receiver, the transmitter sits
+        at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_profile(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, length_range, nbins, path_cls,
+                                  min_order, max_order, order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

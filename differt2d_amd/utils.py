@@ -71,6 +71,31 @@ def one(transmitter, receiver, path: Path, interacting_objects):
     return np.ones(path.xys.shape[:-2], F)
 
 
+def delay_statistics(profile, length_range):
+    """Total power, mean path length and RMS length spread per cell of a power-delay profile ``[nbins, ...]``
+    (``Scene.power_delay_profile_on_receivers_grid``, ``Context.power_profile``) whose bins are ``nbins`` equal parts of
+    ``length_range = (r_min, r_max)``.  On the host, in float64, every bin taken at its centre ``c_b``:
+
+        total = sum_b P_b        mean_length = sum_b P_b c_b / total        rms_spread = sqrt(sum_b P_b (c_b - mean_length)^2 / total)
+
+    Returns ``(total, mean_length, rms_spread)``, each of the profile's shape without its first axis; ``mean_length`` and
+    ``rms_spread`` are NaN where ``total == 0`` (no path in range).  Divide lengths by the wave speed for the mean delay and the
+    RMS delay spread; subtract the first occupied bin's centre for the mean EXCESS delay."""
+    P = np.asarray(profile, dtype=np.float64)
+    if P.ndim < 1 or P.shape[0] < 1:
+        raise ValueError("profile must have the bins on its first axis")
+    r_min, r_max = float(length_range[0]), float(length_range[1])
+    nbins = P.shape[0]
+    width = (r_max - r_min) / nbins
+    centres = (r_min + (np.arange(nbins, dtype=np.float64) + 0.5) * width).reshape((nbins,) + (1,) * (P.ndim - 1))
+    total = P.sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(total == 0.0, np.nan, (P * centres).sum(axis=0) / total)
+        var = (P * (centres - mean) ** 2).sum(axis=0) / total
+        rms = np.where(total == 0.0, np.nan, np.sqrt(var))
+    return total, mean, rms
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
-#define D2D_ABI_VERSION 12
+#define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile are additive: no struct, enum or existing entry point
+                              changed with them, so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -456,6 +457,40 @@ int d2d_get_valid_paths(d2d_ctx* ctx, int64_t capacity, int32_t* cell, int32_t* 
 /* Diagnostic ("time_kernel" option): kernel times of the last d2d_valid_paths that found records -- ms[0] pass 1 (count),
  * ms[1] pass 2 (write), ms[2] the paths of the records. */
 int d2d_debug_valid_paths_ms(d2d_ctx* ctx, float* ms /* [3] */);
+
+/* ---- per-cell power-delay profile: the fused sweep binned by path length (no reference counterpart: the reference reduces every
+ *      cell to one number, differt2d/scene.py:1892-1918; mean excess delay and RMS delay spread follow from the profile) ---- */
+
+/* Launches the bin build of the culled forward sweep for the fixed end point `fixed` on the ctx stream (asynchronous): the
+ * profile out[nbins][m][n], fp32, of the current scene, candidate mask and grid.  `params` as for d2d_power_map_launch
+ * (params->grid_role says which end the cells are), r_min, r_max fp32 and finite with r_max > r_min, nbins >= 1.  Definition:
+ *
+ *     inv = (float)nbins / (r_max - r_min)          // host, fp32: one subtraction, one division
+ *     for candidates in the sweep's enumeration order:
+ *         t = valid * fun                             // exactly the fused sweep's contribution (nan_to_num rules included)
+ *         r = path_length(points)                     // the fp32 value the path function is evaluated with
+ *         u = (r - r_min) * inv ;  b = (int)floorf(u) // fp32, no contraction
+ *         if (u >= 0 && b < nbins) out[b][cell] = out[b][cell] + t    // NaN r / u: no bin
+ *
+ *   - Contributions that are exactly zero may be skipped; the sums are never -0.0.
+ *   - Bins are half-open.  Anything outside [r_min, r_max) is dropped.
+ *   - With nbins == 1 and a range that covers every path, out[0] equals the fused map bit for bit.
+ *   - For any nbins over a covering range, the bins of a cell sum to the fused value up to fp32 summation order.
+ *
+ * One pass of one kernel (one wave per 8 x 8 patch, every lane the only writer of its cell: no atomics, the same bits run to
+ * run) behind a zeroing of the profile on the same stream.  The resident value / gradient maps, the work history and the
+ * schedule of the fused sweeps are not touched.  Every fused function but D2D_FUN_CUSTOM; D2D_FUN_RECEIVED_POWER_PER_OBJECT
+ * with the coefficients of d2d_set_reflection_coefs, D2D_ERR_STATE without them.
+ * D2D_ERR_INVALID: nbins < 1, r_max <= r_min, a bound that is not finite.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): sigmoid validity (its sweeps skip candidates by the fused function's
+ * running sum), MinPath / FermatPath, D2D_FUN_CUSTOM, D2D_OUT_ADD, a TX grid whose sweep would not be culled
+ * (d2d_params.grid_role; not counted by d2d_debug_txg_fallbacks), more than 4 095 objects, or nbins * m * n * 4 bytes above
+ * half of the free device memory -- all decided before anything is enqueued. */
+int d2d_power_profile_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, float r_min, float r_max,
+                             int32_t nbins);
+/* Synchronises and copies the profile of the last d2d_power_profile_launch to out[nbins][m][n].  D2D_ERR_STATE before a launch,
+ * after a launch that was refused, and after a d2d_set_grid of another grid (the profile goes with the grid). */
+int d2d_get_power_profile(d2d_ctx* ctx, float* out /* [nbins][m][n] */);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
