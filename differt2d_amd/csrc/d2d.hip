@@ -371,7 +371,10 @@ int upload_refl(d2d_ctx* c) {
 // Patched end points, geometry.py:632-636: P1 = origin - patch*t, P2 = dest + patch*t, A = P2 - P1.
 int upload_occl(d2d_ctx* c, float patch) {
     if (c->occl_patch == patch && c->d_occl.p) return D2D_OK;
-    std::vector<float4> occl((size_t)c->N + 1);
+    // (N rounded up to an even number of rows, and one more pair: the occlusion loop reads the table two adjacent walls at a
+    // time, one pair ahead, without clamping an index -- the wall beside the last one of an odd table and the pair behind the
+    // last one must exist in memory.  Rows from N on are zero; they are loaded and take no part in any test)
+    std::vector<float4> occl((((size_t)c->N + 1) & ~(size_t)1) + 2, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (int j = 0; j < c->N; ++j) {
         const float* w = &c->xys[4 * (size_t)j];
         float ox = w[0], oy = w[1], dx = w[2], dy = w[3];
@@ -1312,6 +1315,7 @@ static int sweep_args(d2d_ctx* c, Sweep& s) {
     a.out = c->d_out.p;
     a.m = c->m;
     a.n = c->n;
+    a.tiles_x_div = d2d::make_div((uint32_t)s.tiles_x);
     a.txx = s.tx[0];
     a.txy = s.tx[1];
     a.min_order = p->min_order;
@@ -1535,6 +1539,7 @@ static int prep_region_lists(d2d_ctx* c, Sweep& s, Prep& pr) {
     auto fill = [](d2d::RegionLevel& l, const d2d_host::RegionLevelPlan& lp_) {
         l.S = lp_.S;
         l.R = lp_.R;
+        l.R_div = d2d::make_div((uint32_t)lp_.R);
         l.regions_x = lp_.regions_x;
         l.regions_y = lp_.regions_y;
     };

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "../../include/d2d.h"
+#include "d2d_div.hpp"
 
 namespace d2d {
 
@@ -50,6 +51,17 @@ __device__ __forceinline__ float4 ldc4(const float4* p, long i) {
     const v4f v = ((const __attribute__((address_space(4))) v4f*)(unsigned long long)p)[i];
     return make_float4(v.x, v.y, v.z, v.w);
 }
+// Two adjacent rows with one load of 32 bytes (s_load_dwordx8), at a 32-bit byte offset that is a multiple of 32 from a base
+// the allocator aligns to 256 bytes (the occlusion loop of eval_candidate: rows 2 t and 2 t + 1 of the wall table)
+__device__ __forceinline__ void ldc4x2(const float4* p, unsigned byte_off, float4& r0, float4& r1) {
+    typedef float v8f __attribute__((ext_vector_type(8)));
+    const v8f v = *(const __attribute__((address_space(4))) v8f*)((unsigned long long)p + byte_off);
+    r0 = make_float4(v.s0, v.s1, v.s2, v.s3);
+    r1 = make_float4(v.s4, v.s5, v.s6, v.s7);
+}
+// (compile-time flags handed to a generic lambda)
+struct FlagOn { static constexpr bool value = true; };
+struct FlagOff { static constexpr bool value = false; };
 __device__ __forceinline__ int4 ldc4i(const int4* p, long i) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     const v4i v = ((const __attribute__((address_space(4))) v4i*)(unsigned long long)p)[i];
@@ -94,6 +106,7 @@ struct RegionLevel {
     int S;                          // lists per region: slices of first-wall positions (first_wall_range(s, S)); 1 at the leaf level
     int R;                          // a region is R x R patches
     int regions_x, regions_y;
+    DivU32 R_div;                   // division by R (region_of)
     const float4* box;              // [regions] bounding boxes of the regions' cells (region_box_kernel)
     // [regions][N] last-segment masks (hidden_region_kernel; leaf level only, null: none): bit b of word [r][w] = the segment
     // from any point within hidden_dperp of bin b of wall w to ANY point of region r's box is certainly reported as
@@ -124,6 +137,7 @@ struct SweepArgs {
     const float* __restrict__ Y;
     float* __restrict__ out;
     int m, n;
+    DivU32 tiles_x_div;  // division by the patches per grid row, (n + TILE_W - 1) / TILE_W (the host fills it in: sweep_args)
     // per-sweep scalars
     float txx, txy;
     int min_order, max_order;
@@ -724,13 +738,16 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
     // fraction of its rate), and the wave-level question "does any lane need an exact test" is asked once for both.  The
     // exact tests recompute the three bilinear forms (the same expressions on the same operands: the same bits) instead of
     // keeping them in registers for the one wall in ten that needs them.
-    auto filt = [&](const float4& ww, int jj) -> unsigned {
+    // (own_c = FlagOff: the caller knows that wall jj is none of the candidate's own, or clears the bits of the segments that
+    // end on it himself)
+    auto filt = [&](const float4& ww, int jj, auto own_c) -> unsigned {
+        constexpr bool OWN = decltype(own_c)::value;
         unsigned wbits = 0u;  // bit i: this lane needs the exact test of segment i
 #pragma unroll
         for (int i = 0; i <= K; ++i) {
             const int ig0 = (i == 0) ? -1 : cand[i - 1];
             const int ig1 = (i == K) ? -1 : cand[i];
-            const bool skip = (jj == ig0 || jj == ig1);  // wave-uniform: a segment ignores the walls it joins
+            const bool skip = OWN && (jj == ig0 || jj == ig1);  // wave-uniform: a segment ignores the walls it joins
             float Cx = ww.x - px[i], Cy = ww.y - py[i];
             float fa = by[i] * Cx - bx[i] * Cy;   // geometry.py:157
             float fb = ww.z * Cy - ww.w * Cx;     // geometry.py:158
@@ -799,7 +816,7 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
     {
         bool done = a.N <= 0;
         if (!done && sh >= 0) {  // the cached occluder, on its own: it usually ends the loop
-            const unsigned b0 = filt(w, sh);
+            const unsigned b0 = filt(w, sh, FlagOn());
             D2D_WORK(K + 1);
             if (wave_any(b0 != 0u)) {
                 exact(w, sh, b0);
@@ -809,6 +826,71 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                 }
             }
         }
+        if constexpr (!GRAD) {
+        // Then the plain sequence 0, 1, 2, ..., two adjacent walls per trip: one load of 32 bytes at a running offset, no
+        // index selects.  It meets wall sh a second time (or / max are idempotent: nothing changes; one redundant wall per
+        // full-length loop, against a compare-and-select per index of every trip).  The table ends with spare rows
+        // (upload_occl), so neither the wall beside the last one of an odd N nor the pair loaded ahead needs a clamp; a wall
+        // that does not exist is loaded and never tested.
+        // The candidate's own walls -- at most K of N -- are not looked for segment by segment: own_nxt is the first wall of
+        // the next trip that holds one, and only that trip clears the bits of the segments that end on a wall of its pair
+        // (computed and masked, as before).  Every other trip carries no skip logic.
+        if (!done) {
+            int own_nxt = 0x7fffffff;
+#pragma unroll
+            for (int d = 0; d < K; ++d) own_nxt = min(own_nxt, cand[d] & ~1);
+            int jA = 0;
+            float4 wA, wB;
+            ldc4x2(a.occl, 0u, wA, wB);
+            while (true) {
+                float4 wnA, wnB;  // (the next trip's walls: their load flies while this trip computes)
+                ldc4x2(a.occl, (unsigned)(jA + 2) << 4, wnA, wnB);
+                const int jB = jA + 1;
+                const bool hasB = jB < a.N;
+                unsigned ba = filt(wA, jA, FlagOff());
+                unsigned bb = hasB ? filt(wB, jB, FlagOff()) : 0u;
+                D2D_WORK(hasB ? 2 * (K + 1) : (K + 1));
+                unsigned own_tests = 0u;  // (STATS: segment tests of this trip that were computed and masked)
+                if (K > 0 && jA == own_nxt) {  // wave-uniform, at most K trips of a loop
+                    unsigned ma = 0u, mb = 0u;  // bit i: segment i ends on wall jA / jB
+                    int nxt = 0x7fffffff;
+#pragma unroll
+                    for (int d = 0; d < K; ++d) {
+                        ma |= (cand[d] == jA) ? (3u << d) : 0u;
+                        mb |= (cand[d] == jB) ? (3u << d) : 0u;
+                        const int o = cand[d] & ~1;
+                        nxt = min(nxt, o > jA ? o : 0x7fffffff);
+                    }
+                    own_nxt = nxt;
+                    ba &= ~ma;
+                    bb &= ~mb;
+                    own_tests = (unsigned)(__builtin_popcount(ma) + (hasB ? __builtin_popcount(mb) : 0));
+                }
+                if (STATS) stat_add<4>(st, 0ull - own_tests);  // (outside the branch on purpose: see the single-wall loop below)
+                if (wave_any((ba | bb) != 0u)) {
+                    if (wave_any(ba != 0u)) {
+                        exact(wA, jA, ba);
+                        if (!wave_any(active)) {
+                            st.shadow = jA;
+                            break;
+                        }
+                    }
+                    if (wave_any(bb != 0u)) {
+                        exact(wB, jB, bb);
+                        if (!wave_any(active)) {
+                            st.shadow = jB;
+                            break;
+                        }
+                    }
+                }
+                jA += 2;
+                if (!(jA < a.N)) break;
+                wA = wnA;
+                wB = wnB;
+            }
+        }
+        } else {
+        // (the value+grad builds: the arg-max of the adjoint depends on the order of the tests -- wall sh is stepped over)
         auto next_idx = [&](int x) -> int {
             ++x;
             return x == sh ? x + 1 : x;
@@ -823,8 +905,8 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                 const int nA = next_idx(jB), nB = next_idx(nA);
                 // (the next trip's walls: their loads fly while this trip computes)
                 const float4 wnA = ldc4(a.occl, nA < a.N ? nA : jA), wnB = ldc4(a.occl, nB < a.N ? nB : jA);
-                const unsigned ba = filt(wA, jA);
-                const unsigned bb = hasB ? filt(wB, jB) : 0u;
+                const unsigned ba = filt(wA, jA, FlagOn());
+                const unsigned bb = hasB ? filt(wB, jB, FlagOn()) : 0u;
                 D2D_WORK(hasB ? 2 * (K + 1) : (K + 1));
                 if (wave_any((ba | bb) != 0u)) {
                     if (wave_any(ba != 0u)) {
@@ -848,6 +930,7 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                 wA = wnA;
                 wB = wnB;
             }
+        }
         }
     }
     } else {
@@ -2220,9 +2303,10 @@ __device__ __forceinline__ void sweep_order_any(const SweepArgs& a, const float4
 }
 
 // The region (R x R patches) of patch (tcol, trow)
-__device__ __forceinline__ long region_of(const SweepArgs& a, int tcol, int trow) {
-    const int R = cmem(a.rl)->leaf.R;
-    return (long)(trow / R) * cmem(a.rl)->leaf.regions_x + (tcol / R);
+__device__ __forceinline__ int region_of(const SweepArgs& a, int tcol, int trow) {
+    const auto* rd = &cmem(a.rl)->leaf.R_div;  // (a class type cannot be copied out of another address space: field by field)
+    const DivU32 R = {rd->d, rd->mul, rd->shift};
+    return (int)(div_by(R, (unsigned)trow) * (unsigned)cmem(a.rl)->leaf.regions_x + div_by(R, (unsigned)tcol));
 }
 
 // Hand-over between the parts of a cut patch without cache maintenance (fwd_patch): relies on gfx9 encodings and on the
@@ -2253,9 +2337,11 @@ constexpr int TILE_H = 8;
 // LISTED: the orders >= 2 come from the region candidate lists (a.rl); a patch that cannot use them is queued for the
 // enumerating build of the same kernel (LISTED = false), which is launched right behind with a.fb_n set.
 template <int MODE, bool STATS, int MAXK, bool GRADK, bool LISTED, bool SPARE = false>
-__device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float* wl, const long b0_in, const bool from_queue) {
+__device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float* wl, const unsigned b0_in, const bool from_queue) {
     const int lane = threadIdx.x & 63;
-    const int tiles_x = (a.n + TILE_W - 1) / TILE_W;
+    // (patch, item and region indices are 32-bit: the host refuses a grid of 2^31 patches or more, and at most a quarter of a
+    // launch's patches are cut, so the items fit an unsigned; they are widened where a byte offset is formed)
+    const DivU32 tiles_x = a.tiles_x_div;
     const bool scene = GRADK && a.partial != nullptr;
     float tbx_sum = 0.0f, tby_sum = 0.0f;  // scene VJP w.r.t. the fixed end point (wave sum)
     WaveStats st;
@@ -2271,20 +2357,24 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
     // four quarters of first walls, swept by four single-wave workgroups that leave their non-zero contributions as
     // ordered lists in global memory; the quarter that finishes last adds them up in candidate order (bit for bit the
     // reference's sum) and writes the cell.  A list cannot overflow: it holds as many entries as the quarter has candidates.
-    const long n_items = (long)tiles_x * ((a.m + TILE_H - 1) / TILE_H) + (long)(HEAVY_PARTS - 1) * a.n_heavy;
+    const unsigned n_items = tiles_x.d * ((unsigned)(a.m + TILE_H - 1) / TILE_H) + (unsigned)(HEAVY_PARTS - 1) * (unsigned)a.n_heavy;
     const bool exists = !SPARE || b0_in < n_items;  // (the last workgroup of a launch of several waves per workgroup may have spare waves)
-    const long b0 = exists ? b0_in : 0;
-    const bool quarter = !STATS && !GRADK && MAXK == 2 && !from_queue && (b0 < (long)HEAVY_PARTS * a.n_heavy);  // wave-uniform
-    const long tile0 = quarter ? (b0 / HEAVY_PARTS) : (b0 - (long)(HEAVY_PARTS - 1) * a.n_heavy);
+    // (the wave's own item: wave-uniform also where the compiler cannot see it -- a wave of a wider workgroup, a queue entry)
+    const unsigned b0 = exists ? (unsigned)__builtin_amdgcn_readfirstlane((int)b0_in) : 0u;
+    const bool quarter = !STATS && !GRADK && MAXK == 2 && !from_queue && (b0 < (unsigned)HEAVY_PARTS * (unsigned)a.n_heavy);  // wave-uniform
+    const int tile0 = (int)(quarter ? (b0 / HEAVY_PARTS) : (b0 - (unsigned)(HEAVY_PARTS - 1) * (unsigned)a.n_heavy));
     const int part = quarter ? (int)(b0 % HEAVY_PARTS) : 0;
-    const long tile = from_queue ? b0 : (a.sched ? (long)a.sched[tile0] : tile0);
+    // (read through a plain load, the schedule's entry sits in a vector register: the scalar index arithmetic below wants it scalar)
+    const int tile = __builtin_amdgcn_readfirstlane(from_queue ? (int)b0 : (a.sched ? a.sched[tile0] : tile0));
 #ifdef D2D_AB_TIMELINE
     const unsigned long long t_line0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, common to all XCDs
     if (a.tl_ring && lane == 0 && !from_queue && b0_in == 0) a.tl_ring[2 * (a.tl_seq & 255)] = t_line0;  // (workgroup 0 starts first, or nearly so)
 #endif
     const unsigned long long t_start = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
-    const int tcol = (int)(tile % tiles_x), trow = (int)(tile / tiles_x);
-    const long region = LISTED ? region_of(a, tcol, trow) : 0;
+    unsigned tcol_u, trow_u;
+    divmod(tiles_x, (unsigned)tile, trow_u, tcol_u);
+    const int tcol = (int)tcol_u, trow = (int)trow_u;
+    const int region = LISTED ? region_of(a, tcol, trow) : 0;
     const int col = tcol * TILE_W + (lane & (TILE_W - 1));
     const int row = trow * TILE_H + (lane / TILE_W);
     const bool in_range = (col < a.n) && (row < a.m);
@@ -2304,7 +2394,7 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
     if (LISTED) {
         // not this kernel's patch: leave it (once) to the enumerating kernel
         if (cmem(cmem(a.rl)->flag)[region] != 0 || wave_any(lane_bad)) {
-            if (part == 0 && lane == 0) a.fb_list[atomicAdd(a.fb_n, 1)] = (int)tile;
+            if (part == 0 && lane == 0) a.fb_list[atomicAdd(a.fb_n, 1)] = tile;
             return;
         }
     }
@@ -2337,9 +2427,9 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
     unsigned t_lineC = t_lineB;
 #endif
     if (quarter) {
-        const long hq = tile0 * HEAVY_PARTS + part;
+        const int hq = tile0 * HEAVY_PARTS + part;
         ListSink sink;
-        sink.col = a.heavy_list + hq * (long)a.heavy_cap * 64 + lane;
+        sink.col = a.heavy_list + (long)hq * (long)a.heavy_cap * 64 + lane;
         sink.cnt = 0;
         sink.over = false;
         sink.cap = a.heavy_cap;
@@ -2372,7 +2462,7 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
         int* const heavy_cnt = D2D_LATE_ARG(int*, heavy_cnt);
         int* const heavy_done = D2D_LATE_ARG(int*, heavy_done);
         const int n_heavy_l = D2D_LATE_ARG(int, n_heavy), heavy_cap_l = D2D_LATE_ARG(int, heavy_cap);
-        __hip_atomic_store(&heavy_cnt[hq * 64 + lane], sink.over ? -1 : sink.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&heavy_cnt[(long)hq * 64 + lane], sink.over ? -1 : sink.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane == 0) __hip_atomic_store(&heavy_cnt[(long)n_heavy_l * HEAVY_PARTS * 64 + hq], (int)st.work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int old = 0;
 #if D2D_FENCE_FREE_HANDOVER
@@ -2397,7 +2487,7 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
 #endif
         unsigned work = 0;
         for (int q = 0; q < HEAVY_PARTS; ++q) {
-            const long hq2 = tile0 * HEAVY_PARTS + q;
+            const long hq2 = (long)tile0 * HEAVY_PARTS + q;
             int n = __hip_atomic_load(&heavy_cnt[hq2 * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const bool bad = n < 0 || n > heavy_cap_l;  // cannot happen (heavy_cap covers every candidate); never silently wrong
             n = bad ? 0 : n;
@@ -2478,7 +2568,7 @@ __device__ __forceinline__ void fwd_patch(const SweepArgs& a, float4* tab, float
     if (scene) {
         __syncthreads();
         // one row per patch: the row order of the fp64 reduction must not depend on the schedule
-        float* dst = a.partial + tile * (4 * a.N + 2);
+        float* dst = a.partial + (long)tile * (4 * a.N + 2);
         for (int i = lane; i < 4 * a.N; i += 64) dst[i] = wl[i];
         if (lane == 0) {
             dst[4 * a.N] = tbx_sum;
@@ -2518,7 +2608,7 @@ __global__ void __launch_bounds__(64 * WPB) power_fwd_kernel(SweepArgs a) {
             __syncthreads();
         }
         for (int i = blockIdx.x; i < n; i += gridDim.x) {
-            fwd_patch<MODE, STATS, MAXK, GRADK, false>(a, tab, wl, (long)a.fb_list[i], true);
+            fwd_patch<MODE, STATS, MAXK, GRADK, false>(a, tab, wl, (unsigned)a.fb_list[i], true);
             __syncthreads();
         }
         return;
@@ -2527,7 +2617,7 @@ __global__ void __launch_bounds__(64 * WPB) power_fwd_kernel(SweepArgs a) {
     for (int i = threadIdx.x; i < 2 * a.N; i += 64 * WPB) tab[i] = ldc4(a.refl, i);
     for (int i = threadIdx.x; i < a.N; i += 64 * WPB) tab[2 * a.N + i] = ldc4(a.flt, i);
     __syncthreads();
-    fwd_patch<MODE, STATS, MAXK, GRADK, LISTED, (WPB > 1)>(a, tab, wl, WPB == 1 ? (long)blockIdx.x : (long)blockIdx.x * WPB + (threadIdx.x >> 6), false);
+    fwd_patch<MODE, STATS, MAXK, GRADK, LISTED, (WPB > 1)>(a, tab, wl, WPB == 1 ? blockIdx.x : blockIdx.x * WPB + (threadIdx.x >> 6), false);
 }
 
 // Forward sweep with every 8 x 8 patch shared by W waves (one workgroup).  Patches differ a lot in cost and the dearest
@@ -3271,7 +3361,7 @@ __device__ __forceinline__ void txg_patch(const SweepArgs& a, const float4* tab,
     if (scene) {
         const float sx = wave_sum(g.tbx), sy = wave_sum(g.tby);
         __syncthreads();
-        float* dst = a.partial + tile * (4 * a.N + 2);  // one row per patch, whatever the schedule
+        float* dst = a.partial + (long)tile * (4 * a.N + 2);  // one row per patch, whatever the schedule
         for (int i = lane; i < 4 * a.N; i += 64) dst[i] = wl[i];
         if (lane == 0) {
             dst[4 * a.N] = sx;
