@@ -56,14 +56,10 @@ hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
     D2D_BY_MODE(launch_vg_m, txg, grad, grid, lds, s, a)
 }
-hipError_t launch_rec(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
-    if (mode == MODE_HARD) return launch_rec_m<MODE_HARD>(txg, max_order, grid, lds, s, a, r);
-    if (mode == MODE_HSIG) return launch_rec_m<MODE_HSIG>(txg, max_order, grid, lds, s, a, r);
-    return hipErrorInvalidValue;
-}
-hipError_t launch_bin(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const BinArgs& b) {
-    if (mode == MODE_HARD) return launch_bin_m<MODE_HARD>(txg, max_order, grid, lds, s, a, b);
-    if (mode == MODE_HSIG) return launch_bin_m<MODE_HSIG>(txg, max_order, grid, lds, s, a, b);
+template <class Sink>
+hipError_t launch_sink(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const typename Sink::Args& x) {
+    if (mode == MODE_HARD) return launch_sink_m<MODE_HARD, Sink>(txg, max_order, grid, lds, s, a, x);
+    if (mode == MODE_HSIG) return launch_sink_m<MODE_HSIG, Sink>(txg, max_order, grid, lds, s, a, x);
     return hipErrorInvalidValue;
 }
 
@@ -1204,7 +1200,7 @@ static int opt_sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, in
 }
 
 // ---- ImagePath sweeps: sweep_launch and its steps ------------------------------------------------------------------
-// What the steps of one launch share.  sweep_launch sets the inputs; take_prep_set and sweep_args the rest.
+// What the steps of one launch share.  The constructor sets the inputs; take_prep_set (or prep_sink_sweep) and sweep_args the rest.
 struct Sweep {
     const d2d_params* p;
     const float* tx;
@@ -1212,11 +1208,15 @@ struct Sweep {
     int grad_mode;                // 0 values, 1 value+grad, 2 ... and the scene VJP
     int tiles_x, tiles_y;
     long long tiles;
+    Sweep(const d2d_ctx* c, const d2d_params* p, const float* tx, unsigned long long* d_stats = nullptr, int grad_mode = 0)
+        : p(p), tx(tx), d_stats(d_stats), grad_mode(grad_mode), tiles_x((c->n + d2d::TILE_W - 1) / d2d::TILE_W),
+          tiles_y((c->m + d2d::TILE_H - 1) / d2d::TILE_H), tiles((long long)tiles_x * tiles_y) {}
     bool piped = false;           // the preparation runs on aux_stream into a rotated set
     bool set_was_swept = false;   // the set this launch takes was read by a sweep that may still be running (its ev_swept says when)
     hipStream_t ps = nullptr;     // where this launch's preparation runs
     d2d_host::SweepThresholds th;
     bool txg = false, txg_culled = false;
+    bool txg_fallback = false;    // a TX-grid sweep that would be culled if a degenerate path could not count: whoever runs it exhaustively counts it
     dim3 grid_patches;            // one single-wave workgroup per 8 x 8 patch
     d2d::SweepArgs a;
 };
@@ -1354,7 +1354,7 @@ static int sweep_args(d2d_ctx* c, Sweep& s) {
     // a zero-length segment still leaves sigmoid(-5) -- walls on a lattice); tests/test_gpu_forward.py keeps the case.
     const bool txg_cullable = s.txg && !c->txg_exhaustive && !(s.grad_mode && p->strict_nan);
     s.txg_culled = txg_cullable && s.th.degenerate_invalid;
-    if (txg_cullable && !s.th.degenerate_invalid) ++c->txg_fallbacks;
+    s.txg_fallback = txg_cullable && !s.th.degenerate_invalid;
     return D2D_OK;
 }
 
@@ -2034,16 +2034,10 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     if ((rc = set_device(c))) return rc;
     if ((rc = upload_occl(c, p->patch))) return rc;
 
-    Sweep s;
-    s.p = p;
-    s.tx = tx;
-    s.d_stats = d_stats;
-    s.grad_mode = grad_mode;
-    s.tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
-    s.tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
-    s.tiles = (long long)s.tiles_x * s.tiles_y;
+    Sweep s(c, p, tx, d_stats, grad_mode);
     Prep pr;
     if ((rc = take_prep_set(c, s)) || (rc = sweep_args(c, s))) return rc;
+    if (s.txg_fallback) ++c->txg_fallbacks;
     if ((rc = prep_masks(c, s, pr)) || (rc = prep_region_lists(c, s, pr))) return rc;
     if (!s.a.rl) c->rl_plan.on = false;
     if ((rc = prep_schedule(c, s, pr)) || (rc = sweep_begin(c, s))) return rc;
@@ -2052,9 +2046,37 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     return launch_rx_values(c, s, pr);
 }
 
-// Record launch of the culled forward sweep: pass 1 counts the (cell, candidate) pairs with valid != 0 per patch, the host scans
-// the counts, pass 2 writes the records, trace_rec_kernel solves their paths.  Everything runs on the main stream, behind whatever
+// What the two sink launches (d2d_valid_paths, d2d_power_profile_launch: `who` in the messages) share, from the validity mode on.
+// Every refusal that the arguments and the context decide comes first, before anything is uploaded or enqueued; a TX grid is swept
+// by the culled kernels only, and refusing one is not a fall-back.  Then the launch is prepared on the main stream, behind whatever
 // the context has in flight, with masks of its own: the sweeps' rotating sets, work history, schedule and value map are not touched.
+static int prep_sink_sweep(d2d_ctx* c, Sweep& s, const char* who, size_t& lds) {
+    const d2d_params* p = s.p;
+    int rc;
+    if (p->approx && p->act != D2D_ACT_HARD_SIGMOID)
+        return fail(D2D_ERR_UNSUPPORTED, "%s covers hard and hard_sigmoid validity: the sigmoid sweeps skip candidates by the fused function's running sum", who);
+    if ((rc = check_image_sweep(c, p, nullptr))) return rc;
+    if (c->N > 4095) return fail(D2D_ERR_UNSUPPORTED, "%s: %d objects exceed the 12-bit object indices of the culling queue and the records", who, c->N);
+    if ((long long)c->m * c->n > 0x7fffffffLL) return fail(D2D_ERR_UNSUPPORTED, "%s: the grid exceeds 31-bit cell indices", who);
+    lds = d2d_host::tab_lds_bytes(c->N);  // tables + one culling queue
+    if (lds > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%s: %d objects exceed the kernel's LDS table (max ~2400)", who, c->N);
+    if (p->grid_role == D2D_GRID_TX && (c->txg_exhaustive || !d2d_host::sweep_thresholds(*p, false).degenerate_invalid))
+        return fail(D2D_ERR_UNSUPPORTED, "%s: a TX-grid sweep with these parameters is not culled (%s)", who,
+                    c->txg_exhaustive ? "the \"txg_exhaustive\" option is set" : "a degenerate path is not exactly invalid under tol / alpha");
+    if ((rc = set_device(c))) return rc;
+    if ((rc = upload_occl(c, p->patch))) return rc;
+    s.ps = c->stream;
+    if ((rc = sweep_args(c, s))) return rc;
+    if (s.txg && !s.txg_culled) return fail(D2D_ERR_STATE, "%s: the TX-grid sweep is not culled after all (an internal error)", who);
+    Prep pr;
+    if ((rc = prep_masks(c, s, pr, &c->d_rec_shadow))) return rc;
+    s.a.out = nullptr;  // never written by a sink
+    s.a.cullq_off = (int)((size_t)(4 * c->N + 1) * sizeof(float4));
+    return D2D_OK;
+}
+
+// Record launch of the culled forward sweep: pass 1 counts the (cell, candidate) pairs with valid != 0 per patch, the host scans
+// the counts, pass 2 writes the records, trace_rec_kernel solves their paths.
 static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int64_t* count) {
     if (!c || !fixed || !count) return fail(D2D_ERR_INVALID, "NULL argument");
     *count = 0;
@@ -2063,44 +2085,17 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_valid_paths");
     if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_valid_paths");
     if (p_in->solver != D2D_SOLVER_IMAGE) return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths covers ImagePath only (solver %d)", p_in->solver);
-    if (p_in->approx && p_in->act != D2D_ACT_HARD_SIGMOID)
-        return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths covers hard and hard_sigmoid validity: the sigmoid sweeps skip candidates by the fused function's running sum");
+    c->rec_n = -1;  // whatever this call turns out to be, the previous records are gone
+    c->have_rec_time = false;
     d2d_params pp = *p_in;
     pp.fun_id = D2D_FUN_ONE;  // a contribution is then the validity itself
     pp.out_mode = D2D_OUT_OVERWRITE;
     pp.strict_nan = 0;
     const d2d_params* p = &pp;
-    if ((rc = check_image_sweep(c, p, nullptr))) return rc;
-    if (c->N > 4095) return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: %d objects exceed the records' 12-bit object indices", c->N);
-    if ((long long)c->m * c->n > 0x7fffffffLL) return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: the grid exceeds the records' 31-bit cell indices");
-    if ((rc = set_device(c))) return rc;
-    if ((rc = upload_occl(c, p->patch))) return rc;
-    c->rec_n = -1;
-    c->have_rec_time = false;
-
-    Sweep s;
-    s.p = p;
-    s.tx = fixed;
-    s.d_stats = nullptr;
-    s.grad_mode = 0;
-    s.tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
-    s.tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
-    s.tiles = (long long)s.tiles_x * s.tiles_y;
-    s.piped = false;
-    s.ps = c->stream;
-    Prep pr;
-    const long long fallbacks = c->txg_fallbacks;
-    if ((rc = sweep_args(c, s))) return rc;
-    c->txg_fallbacks = fallbacks;  // (sweep_args counts a sweep that falls back; this launch refuses instead)
-    if (s.txg && !s.txg_culled)
-        return fail(D2D_ERR_UNSUPPORTED, "d2d_valid_paths: a TX-grid sweep with these parameters is not culled (%s)",
-                    c->txg_exhaustive ? "the \"txg_exhaustive\" option is set" : "a degenerate path is not exactly invalid under tol / alpha");
-    if ((rc = prep_masks(c, s, pr, &c->d_rec_shadow))) return rc;
-    d2d::SweepArgs& a = s.a;
-    a.out = nullptr;  // never written by the record build
-    const size_t lds = d2d_host::tab_lds_bytes(c->N);  // tables + one culling queue
-    if (lds > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table (max ~2400)", c->N);
-    a.cullq_off = (int)((size_t)(4 * c->N + 1) * sizeof(float4));
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_valid_paths", lds))) return rc;
+    const d2d::SweepArgs& a = s.a;
     const size_t tiles = (size_t)s.tiles;
     if ((rc = c->d_rec_counts.ensure(tiles)) || (rc = c->d_rec_offs.ensure(tiles + 1)) || (rc = c->d_rec_flag.ensure(1))) return rc;
     const bool timed = c->time_kernel;
@@ -2115,7 +2110,7 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     r.flag = c->d_rec_flag.p;
     // pass 1: count
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[0], c->stream));
-    HIP_TRY(d2d::launch_rec(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
+    HIP_TRY(d2d::launch_sink<d2d::RecSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[1], c->stream));
     std::vector<int> offs(tiles + 1);
     HIP_TRY(hipMemcpyAsync(offs.data() + 1, c->d_rec_counts.p, tiles * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2155,7 +2150,7 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     // pass 2: the same sweep, writing
     r.rec = c->d_rec.p;
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[2], c->stream));
-    HIP_TRY(d2d::launch_rec(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
+    HIP_TRY(d2d::launch_sink<d2d::RecSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[3], c->stream));
     // stage 2: the paths of the records
     d2d::TraceArgs t;
@@ -2193,9 +2188,8 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     return D2D_OK;
 }
 
-// Bin launch of the culled forward sweep: the record launch's preparation (masks of its own, main stream, nothing of the fused
-// sweeps touched) with the caller's path function, then ONE pass of power_bin_kernel into the zeroed profile.  Asynchronous.
-// Every check comes before anything is enqueued.
+// Bin launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed profile.
+// Asynchronous.  Every check comes before anything is enqueued.
 static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float r_min, float r_max, int32_t nbins) {
     if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
     int rc = check_params(p_in);
@@ -2205,8 +2199,6 @@ static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float*
     c->prof_nbins = 0;  // whatever this launch turns out to be, the previous profile is gone
     if (p_in->solver == D2D_SOLVER_MINPATH || p_in->solver == D2D_SOLVER_FERMAT)
         return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch covers ImagePath only, not the MinPath / FermatPath solvers (solver %d)", p_in->solver);
-    if (p_in->approx && p_in->act != D2D_ACT_HARD_SIGMOID)
-        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch covers hard and hard_sigmoid validity: the sigmoid sweeps skip candidates by the fused function's running sum");
     if (p_in->fun_id == D2D_FUN_CUSTOM)
         return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only (a host function's profile: bin the records of d2d_valid_paths)");
     if (p_in->out_mode == D2D_OUT_ADD) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: D2D_OUT_ADD is not supported, a profile is always overwritten");
@@ -2216,21 +2208,6 @@ static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float*
     {
         std::string err;
         if ((rc = d2d_host::profile_bins(r_min, r_max, nbins, bins, err))) return fail(rc, "%s", err.c_str());
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    if ((rc = check_image_sweep(c, p, nullptr))) return rc;
-    if (c->N > 4095) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: %d objects exceed the culling queue's 12-bit object indices", c->N);
-    if ((long long)c->m * c->n > 0x7fffffffLL) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: the grid exceeds 31-bit cell indices");
-    const size_t lds = d2d_host::tab_lds_bytes(c->N);  // tables + one culling queue
-    if (lds > c->lds_max) return fail(D2D_ERR_UNSUPPORTED, "%d objects exceed the kernel's LDS table (max ~2400)", c->N);
-    if (p->grid_role == D2D_GRID_TX) {
-        // the record route's rule: a TX grid is swept by the culled kernels only (sweep_args), and a refusal is not a fall-back
-        const bool degenerate_invalid = d2d_host::sweep_thresholds(*p, false).degenerate_invalid;
-        if (c->txg_exhaustive || !degenerate_invalid)
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: a TX-grid sweep with these parameters is not culled (%s)",
-                        c->txg_exhaustive ? "the \"txg_exhaustive\" option is set" : "a degenerate path is not exactly invalid under tol / alpha");
     }
     if ((rc = set_device(c))) return rc;
     const size_t cells = (size_t)c->m * (size_t)c->n;
@@ -2244,28 +2221,13 @@ static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float*
             return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: %d bins of %zu cells (4 bytes each) exceed half of the free device memory (%zu bytes free)",
                         nbins, cells, mem_free);
     }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_power_profile_launch", lds))) return rc;
     if ((rc = c->d_profile.ensure((size_t)nbins * cells))) return rc;
-    if ((rc = upload_occl(c, p->patch))) return rc;
-
-    Sweep s;
-    s.p = p;
-    s.tx = fixed;
-    s.d_stats = nullptr;
-    s.grad_mode = 0;
-    s.tiles_x = (c->n + d2d::TILE_W - 1) / d2d::TILE_W;
-    s.tiles_y = (c->m + d2d::TILE_H - 1) / d2d::TILE_H;
-    s.tiles = (long long)s.tiles_x * s.tiles_y;
-    s.piped = false;
-    s.ps = c->stream;
-    Prep pr;
-    const long long fallbacks = c->txg_fallbacks;
-    if ((rc = sweep_args(c, s))) return rc;
-    c->txg_fallbacks = fallbacks;  // (refused above instead)
-    if (s.txg && !s.txg_culled) return fail(D2D_ERR_STATE, "d2d_power_profile_launch: the TX-grid sweep is not culled after all (an internal error)");
-    if ((rc = prep_masks(c, s, pr, &c->d_rec_shadow))) return rc;
-    d2d::SweepArgs& a = s.a;
-    a.out = nullptr;  // never written by the bin build
-    a.cullq_off = (int)((size_t)(4 * c->N + 1) * sizeof(float4));
     d2d::BinArgs b;
     b.out = c->d_profile.p;
     b.cells = (long)cells;
@@ -2273,7 +2235,7 @@ static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float*
     b.inv = bins.inv;
     b.nbins = bins.nbins;
     HIP_TRY(hipMemsetAsync(c->d_profile.p, 0, (size_t)nbins * cells * sizeof(float), c->stream));
-    if (s.tiles > 0) HIP_TRY(d2d::launch_bin(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, b));
+    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::BinSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, b));
     c->prof_nbins = nbins;
     return D2D_OK;
 }

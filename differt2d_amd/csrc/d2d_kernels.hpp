@@ -22,7 +22,7 @@
 // power_fwd_kernel (one wave per patch; dearest patches cut in four) / power_fwd_split_kernel (small launches: every
 // patch shared by 4 waves prefix by prefix) / power_fwd_coop_kernel (the smallest: 4 / 8 / 16 waves, candidate by candidate) /
 // sweep_order_culled_txg + power_fwd_txg_kernel (TX grids) / patch_* (dearest-first schedule) / shadow_fill_kernel,
-// pair_shadow_kernel, hidden_region_kernel (occlusion masks) / power_rec_kernel, power_bin_kernel (record and bin builds) /
+// pair_shadow_kernel, hidden_region_kernel (occlusion masks) / power_sink_kernel (record and bin builds) /
 // power_vg_kernel (exhaustive value+grad) / trace_kernel and the literal object code (any mix of Wall / RIS / Vertex) /
 // power_opt_*_kernel (MinPath / FermatPath sweeps).
 //
@@ -442,7 +442,7 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                                                const float (&imgx)[D2D_MAX_ORDER], const float (&imgy)[D2D_MAX_ORDER],
                                                float txx, float txy, float rxx, float rxy, bool lane_bad, float& acc,
                                                WaveStats& st, GradCtx* g = nullptr, float acc_floor = -1.0f, float* r_out = nullptr) {
-    // r_out (power_bin_kernel): receives the path length the path function is evaluated with -- written only where the
+    // r_out (power_sink_kernel, BinSink): receives the path length the path function is evaluated with -- written only where the
     // contribution is (a candidate that leaves early leaves both alone).  Null everywhere else, a constant of the inlined call:
     // it costs those instances no instruction.
     // acc_floor >= 0 (MODE_SIG, fun >= 0): the caller adds this candidate to a sum it does not hold -- `acc` is a scratch
@@ -1720,19 +1720,42 @@ struct ListSink {
     }
 };
 
-// Record build (power_rec_kernel): every (cell, candidate) whose contribution is not exactly zero is handed out as a record
+// A sink of power_sink_kernel: what takes the contributions of the culled forward sweep in acc's place.  The contract:
+//     Args                   the sink's kernel argument (by value, behind SweepArgs)
+//     begin(args, tile, cell)  fills the lane's sink for patch `tile`; cell = the lane's row-major cell, < 0 for a clamped
+//                              duplicate of a lane outside the grid, which never contributes
+//     put(t, code, k, r)     one candidate's contribution t (every lane of the wave calls it, zeros included), the candidate's
+//                              code (12 bits per wall index, first wall lowest) and order, and -- WANTS_R -- its path length
+//     end(args, tile, lane)  after the last order
+//
+// RecSink (d2d_valid_paths): every (cell, candidate) whose contribution is not exactly zero is handed out as a record
 // instead of being added.  Two passes of the same deterministic sweep: with rec == null the wave only counts (cnt is
-// wave-uniform: the popcount of the ballot of pushing lanes); else every pushing lane stores its record at
-// base + count so far + the pushing lanes below it -- never at or past `limit`, the next patch's offset: a position outside
-// [base, limit) raises the sticky flag instead.  A record: {cell (row-major), code bits 0..31, code bits 32..47 | order << 24,
-// the contribution's bits}; code = 12 bits per wall index, first wall lowest.
+// wave-uniform: the popcount of the ballot of pushing lanes) and end() writes the patch's number of records to counts; else
+// every pushing lane stores its record at base + count so far + the pushing lanes below it, in offs[patch] .. offs[patch + 1] --
+// never at or past `limit`, the next patch's offset: a position outside [base, limit) raises the sticky flag instead.  A
+// record: {cell (row-major), code bits 0..31, code bits 32..47 | order << 24, the contribution's bits}.
+struct RecArgs {
+    int* counts;      // [patches]
+    const int* offs;  // [patches + 1] exclusive scan of counts
+    int4* rec;        // [offs[patches]] or null
+    int* flag;        // != 0 afterwards: pass 2 met a position outside its patch's range (the passes disagree: an internal error)
+};
 struct RecSink {
+    using Args = RecArgs;
     static constexpr bool WANTS_R = false;  // (the path length is not asked of eval_candidate)
     int4* rec;
     int base, limit;
     int cnt;
-    int cell;  // this lane's cell; < 0: a clamped duplicate of a lane outside the grid, which never pushes
+    int cell;
     int* flag;
+    __device__ __forceinline__ void begin(const RecArgs& r, long tile, int lane_cell) {
+        rec = r.rec;
+        base = r.rec ? r.offs[tile] : 0;
+        limit = r.rec ? r.offs[tile + 1] : 0;
+        cnt = 0;
+        cell = lane_cell;
+        flag = r.flag;
+    }
     __device__ __forceinline__ void put(float t, unsigned long long code, int k, float /*r*/ = 0.0f) {
         const bool p = cell >= 0 && !(t == 0.0f);
         const unsigned long long m = __ballot(p);
@@ -1743,22 +1766,40 @@ struct RecSink {
         }
         cnt += __builtin_popcountll(m);
     }
+    __device__ __forceinline__ void end(const RecArgs& r, long tile, int lane) const {
+        if (r.rec == nullptr && lane == 0) r.counts[tile] = cnt;
+    }
 };
 
-// Bin build (power_bin_kernel): every contribution that is not exactly zero is added to the bin of its path length instead of
-// to acc -- the power-delay profile out[nbins][cells] (include/d2d.h: d2d_power_profile_launch):
+// BinSink (d2d_power_profile_launch): every contribution that is not exactly zero is added to the bin of its path length instead
+// of to acc -- the power-delay profile out[nbins][cells] (include/d2d.h), zeroed on the stream in front of the launch:
 //     u = (r - r_min) * inv ;  b = (int)floorf(u) ;  if (u >= 0 && b < nbins) out[b][cell] = out[b][cell] + t
 // in fp32 without contraction, candidates in the sweep's order.  A lane is the only writer of its cell's column and reads back
 // what it stored itself: plain loads and stores, the same bits run to run.  A NaN length fails u >= 0 and names no bin; lanes
 // outside the grid (cell < 0) never write.  (u < 2^31 in front of the conversion: beyond it the conversion is undefined, and
 // the bin is past any nbins anyway.)
+struct BinArgs {
+    float* out;       // [nbins][cells]
+    long cells;       // m * n
+    float r_min, inv; // the bins: floorf((r - r_min) * inv), d2d_host::profile_bins
+    int nbins;
+};
 struct BinSink {
+    using Args = BinArgs;
     static constexpr bool WANTS_R = true;
     float* out;  // [nbins][cells]
     long cells;
-    int cell;    // this lane's cell; < 0: a clamped duplicate of a lane outside the grid
+    int cell;
     float r_min, inv;
     int nbins;
+    __device__ __forceinline__ void begin(const BinArgs& b, long /*tile*/, int lane_cell) {
+        out = b.out;
+        cells = b.cells;
+        cell = lane_cell;
+        r_min = b.r_min;
+        inv = b.inv;
+        nbins = b.nbins;
+    }
     __device__ __forceinline__ void put(float t, unsigned long long /*code*/, int /*k*/, float r) {
         if (cell < 0 || t == 0.0f) return;
         const float d = r - r_min;
@@ -1771,6 +1812,7 @@ struct BinSink {
             }
         }
     }
+    __device__ __forceinline__ void end(const BinArgs&, long, int) const {}
 };
 
 // Survivors of a region's culling, in candidate order (region_list_kernel / region_refine_kernel): wave-uniform state
@@ -3125,8 +3167,8 @@ __global__ void __launch_bounds__(64) region_refine_kernel(SweepArgs a, RegionLe
 // Prefix = (w_0 .. w_{K-2}) wave-uniform, lanes = last wall, survivors in ascending order: the reference's order.
 // EMIT (K >= 2; region_list_kernel): first-wall positions [p_lo, p_hi) only, the box is a region's, and the survivors are
 // appended to `emit` (in candidate order: prefix-major, last walls ascending) instead of being evaluated.
-// RECORD: the contributions go to `rsink` with the candidate's code instead of acc (power_rec_kernel), or with the candidate's path
-// length (RS = BinSink, power_bin_kernel).
+// RECORD: the contributions go to `rsink` with the candidate's code instead of acc (power_sink_kernel), or with the candidate's path
+// length (RS = BinSink).
 template <int K, int MODE, bool GRAD = false, bool EMIT = false, bool RECORD = false, class RS = RecSink>
 __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const float4* tab, const float (&bx)[4],
                                                        const float (&by)[4], float cx, float cy, bool lane_bad, float& acc,
@@ -3395,25 +3437,11 @@ __global__ void __launch_bounds__(64) power_fwd_txg_kernel(SweepArgs a) {
     txg_patch<MODE, MAXK, GRADK, LISTED>(a, tab, wl, (long)blockIdx.x, false);
 }
 
-// Record build of the culled forward sweep (d2d_valid_paths): one wave per 8 x 8 patch in row-major patch order, no schedule, no
-// cut patches, no region lists; the host sets fun_id = D2D_FUN_ONE, so a candidate's contribution is its validity itself (never
-// NaN: nan_to_num).  It touches neither the value map nor the work history.  Pass 1 (r.rec == null) writes the patch's number of
-// records to r.counts; pass 2 writes the records at r.offs[patch] .. r.offs[patch + 1] (see RecSink).
-struct RecArgs {
-    int* counts;      // [patches]
-    const int* offs;  // [patches + 1] exclusive scan of counts
-    int4* rec;        // [offs[patches]] or null
-    int* flag;        // != 0 afterwards: pass 2 met a position outside its patch's range (the passes disagree: an internal error)
-};
-template <int MODE, int MAXK, bool TXG>
-__global__ void __launch_bounds__(64) power_rec_kernel(SweepArgs a, RecArgs r) {
-    const int lane = threadIdx.x & 63;
-    extern __shared__ float4 tab[];  // [2N] refl, [N] flt, then (a.cullq_off) the culling queue
-    for (int i = lane; i < 2 * a.N; i += 64) tab[i] = ldc4(a.refl, i);
-    for (int i = lane; i < a.N; i += 64) tab[2 * a.N + i] = ldc4(a.flt, i);
-    __syncthreads();
+// What a wave that owns patch `tile` starts from: its lane's cell (a lane outside the grid takes the nearest cell inside and gets
+// cell < 0), lane_bad, zeroed statistics and the bounding box of the wave's cells for the culling.
+__device__ __forceinline__ void wave_prologue(const SweepArgs& a, long tile, int lane, float& cx, float& cy, int& cell, bool& lane_bad,
+                                              WaveStats& st, float (&bx)[4], float (&by)[4]) {
     const int tiles_x = (a.n + TILE_W - 1) / TILE_W;
-    const long tile = (long)blockIdx.x;
     const int tcol = (int)(tile % tiles_x), trow = (int)(tile / tiles_x);
     const int col = tcol * TILE_W + (lane & (TILE_W - 1));
     const int row = trow * TILE_H + (lane / TILE_W);
@@ -3421,9 +3449,10 @@ __global__ void __launch_bounds__(64) power_rec_kernel(SweepArgs a, RecArgs r) {
     const int ccol = col < a.n ? col : a.n - 1;
     const int crow = row < a.m ? row : a.m - 1;
     const long idx = (long)crow * a.n + ccol;
-    const float cx = a.X[idx], cy = a.Y[idx];
-    const bool lane_bad = !(fabsf(cx) < 1e18f) || !(fabsf(cy) < 1e18f) || !(fabsf(a.txx) < 1e18f) || !(fabsf(a.txy) < 1e18f);
-    WaveStats st;
+    cx = a.X[idx];
+    cy = a.Y[idx];
+    cell = in_range ? (int)idx : -1;
+    lane_bad = !(fabsf(cx) < 1e18f) || !(fabsf(cy) < 1e18f) || !(fabsf(a.txx) < 1e18f) || !(fabsf(a.txy) < 1e18f);
 #pragma unroll
     for (int i = 0; i < 16; ++i) st.c[i] = 0;
     st.shadow = -1;
@@ -3438,97 +3467,41 @@ __global__ void __launch_bounds__(64) power_rec_kernel(SweepArgs a, RecArgs r) {
         y1 = fmaxf(y1, __shfl_xor(y1, off, 64));
     }
     const bool box_ok = !wave_any(lane_bad);
-    const float qn = __builtin_nanf("");
-    const float bx[4] = {box_ok ? x0 : qn, x1, x1, x0};
-    const float by[4] = {y0, y0, y1, y1};
-    RecSink sink;
-    sink.rec = r.rec;
-    sink.base = r.rec ? r.offs[tile] : 0;
-    sink.limit = r.rec ? r.offs[tile + 1] : 0;
-    sink.cnt = 0;
-    sink.cell = in_range ? (int)idx : -1;
-    sink.flag = r.flag;
-    float dummy = 0.0f;
-    if (a.min_order <= 0 && a.max_order >= 0) {
-        float t = 0.0f;
-        if constexpr (TXG) sweep_order<0, MODE, false, false, true>(a, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr);
-        else sweep_order<0, MODE, false, false>(a, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr);
-        sink.put(t, 0ull, 0);
-    }
-    static_for<1, MAXK + 1>([&](auto KK) {
-        constexpr int K = decltype(KK)::value;
-        if (a.min_order <= K && a.max_order >= K) {
-            if constexpr (TXG)
-                sweep_order_culled_txg<K, MODE, false, false, true>(a, tab, bx, by, cx, cy, lane_bad, dummy, st, nullptr, 0, 0x7fffffff, nullptr, nullptr, 0.0f, &sink);
-            else
-                sweep_order_culled<K, MODE, false, false, false, false, true>(a, tab, bx, by, cx, cy, lane_bad, dummy, st, nullptr, 0, 0x7fffffff, nullptr, nullptr,
-                                                                              nullptr, 0.0f, &sink);
-        }
-    });
-    if (r.rec == nullptr && lane == 0) r.counts[tile] = sink.cnt;
+    bx[0] = box_ok ? x0 : __builtin_nanf("");
+    bx[1] = bx[2] = x1;
+    bx[3] = x0;
+    by[0] = by[1] = y0;
+    by[2] = by[3] = y1;
 }
 
-// Bin build of the culled forward sweep (d2d_power_profile_launch): power_rec_kernel's launch shape and enumeration -- one wave per
-// 8 x 8 patch in row-major patch order, no schedule, no cut patches, no region lists -- with the CALLER's fused path function and a
-// BinSink in the records' place: one pass, the per-cell power-delay profile b.out[nbins][m * n] (zeroed on the stream in front of the
-// launch).  It touches neither the value map nor the work history.
-struct BinArgs {
-    float* out;       // [nbins][cells]
-    long cells;       // m * n
-    float r_min, inv; // the bins: floorf((r - r_min) * inv), d2d_host::profile_bins
-    int nbins;
-};
-template <int MODE, int MAXK, bool TXG>
-__global__ void __launch_bounds__(64) power_bin_kernel(SweepArgs a, BinArgs b) {
+// The culled forward sweep with a sink in acc's place (RecSink: d2d_valid_paths, where the host sets fun_id = D2D_FUN_ONE, so a
+// contribution is the validity itself; BinSink: d2d_power_profile_launch with the caller's fused path function): one wave per
+// 8 x 8 patch in row-major patch order, no schedule, no cut patches, no region lists.  It touches neither the value map nor the
+// work history.  Hard and hard_sigmoid only (the sigmoid sweeps' skips depend on the fused function's sum).
+template <int MODE, int MAXK, bool TXG, class Sink>
+__global__ void __launch_bounds__(64) power_sink_kernel(SweepArgs a, typename Sink::Args x) {
     const int lane = threadIdx.x & 63;
     extern __shared__ float4 tab[];  // [2N] refl, [N] flt, then (a.cullq_off) the culling queue
     for (int i = lane; i < 2 * a.N; i += 64) tab[i] = ldc4(a.refl, i);
     for (int i = lane; i < a.N; i += 64) tab[2 * a.N + i] = ldc4(a.flt, i);
     __syncthreads();
-    const int tiles_x = (a.n + TILE_W - 1) / TILE_W;
     const long tile = (long)blockIdx.x;
-    const int tcol = (int)(tile % tiles_x), trow = (int)(tile / tiles_x);
-    const int col = tcol * TILE_W + (lane & (TILE_W - 1));
-    const int row = trow * TILE_H + (lane / TILE_W);
-    const bool in_range = (col < a.n) && (row < a.m);
-    const int ccol = col < a.n ? col : a.n - 1;
-    const int crow = row < a.m ? row : a.m - 1;
-    const long idx = (long)crow * a.n + ccol;
-    const float cx = a.X[idx], cy = a.Y[idx];
-    const bool lane_bad = !(fabsf(cx) < 1e18f) || !(fabsf(cy) < 1e18f) || !(fabsf(a.txx) < 1e18f) || !(fabsf(a.txy) < 1e18f);
+    float cx, cy, bx[4], by[4];
+    int cell;
+    bool lane_bad;
     WaveStats st;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st.c[i] = 0;
-    st.shadow = -1;
-    st.work = 0;
-    // bounding box of the wave's cells (NaN / inf coordinates make every comparison fail: nothing is culled)
-    float x0 = cx, x1 = cx, y0 = cy, y1 = cy;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        x0 = fminf(x0, __shfl_xor(x0, off, 64));
-        x1 = fmaxf(x1, __shfl_xor(x1, off, 64));
-        y0 = fminf(y0, __shfl_xor(y0, off, 64));
-        y1 = fmaxf(y1, __shfl_xor(y1, off, 64));
-    }
-    const bool box_ok = !wave_any(lane_bad);
-    const float qn = __builtin_nanf("");
-    const float bx[4] = {box_ok ? x0 : qn, x1, x1, x0};
-    const float by[4] = {y0, y0, y1, y1};
-    BinSink sink;
-    sink.out = b.out;
-    sink.cells = b.cells;
-    sink.cell = in_range ? (int)idx : -1;
-    sink.r_min = b.r_min;
-    sink.inv = b.inv;
-    sink.nbins = b.nbins;
+    wave_prologue(a, tile, lane, cx, cy, cell, lane_bad, st, bx, by);
+    Sink sink;
+    sink.begin(x, tile, cell);
     float dummy = 0.0f;
     if (a.min_order <= 0 && a.max_order >= 0) {
-        // (sweep_order<0>'s one candidate, with the length handed out)
+        // (sweep_order<0>'s one candidate, with the length handed out where the sink wants it)
         const int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
         const float imgx[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f}, imgy[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f};
         float t = 0.0f, rl = 0.0f;
-        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, &rl);
-        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, &rl);
+        float* const r_out = Sink::WANTS_R ? &rl : nullptr;
+        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, r_out);
+        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, r_out);
         sink.put(t, 0ull, 0, rl);
     }
     static_for<1, MAXK + 1>([&](auto KK) {
@@ -3541,6 +3514,7 @@ __global__ void __launch_bounds__(64) power_bin_kernel(SweepArgs a, BinArgs b) {
                                                                               nullptr, 0.0f, &sink);
         }
     });
+    sink.end(x, tile, lane);
 }
 
 // Patch schedule.  The hardware starts workgroups in blockIdx order, and a dear patch that starts late is the tail of the
@@ -4665,7 +4639,7 @@ __global__ void __launch_bounds__(64) trace_kernel(TraceArgs a) {
     trace_one<SGD>(a, tid, c, k, cd, a.tx[2 * p], a.tx[2 * p + 1], a.rx[2 * p], a.rx[2 * p + 1]);
 }
 
-// The paths of a record launch (power_rec_kernel): one thread per record, the ImagePath branch of trace_one with the cell's
+// The paths of a record launch (power_sink_kernel, RecSink): one thread per record, the ImagePath branch of trace_one with the cell's
 // coordinates from the resident grid and the candidate from the record; also unpacks the record into cell / cand / order.
 // A record that names no cell of the grid or no object of the scene (pass 2 left a slot unwritten: an internal error) raises
 // the flag and is not traced.

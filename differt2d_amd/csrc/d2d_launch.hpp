@@ -20,8 +20,8 @@ template <int MODE> hipError_t launch_fwd_listed_m(bool stats, int max_order, di
 template <int MODE> hipError_t launch_fwd_grad_listed_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <int MODE> hipError_t launch_fwd_split_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE> hipError_t launch_rec_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r);
-template <int MODE> hipError_t launch_bin_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const BinArgs& b);
+template <int MODE, class Sink>
+hipError_t launch_sink_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const typename Sink::Args& x);
 #define D2D_DECLARE_MODE(M)                                                                                      \
     template <> hipError_t launch_fwd_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);              \
     template <> hipError_t launch_fwd_grad_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);               \
@@ -35,11 +35,11 @@ template <int MODE> hipError_t launch_bin_m(bool txg, int max_order, dim3 grid, 
 D2D_DECLARE_MODE(MODE_HARD)
 D2D_DECLARE_MODE(MODE_HSIG)
 D2D_DECLARE_MODE(MODE_SIG)
-#undef D2D_DECLARE_MODE  // (the record and bin builds have no sigmoid instance: launch_rec / launch_bin answer hipErrorInvalidValue)
-template <> hipError_t launch_rec_m<MODE_HARD>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
-template <> hipError_t launch_rec_m<MODE_HSIG>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
-template <> hipError_t launch_bin_m<MODE_HARD>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const BinArgs&);
-template <> hipError_t launch_bin_m<MODE_HSIG>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const BinArgs&);
+#undef D2D_DECLARE_MODE  // (the sink kernel has no sigmoid instance: launch_sink answers hipErrorInvalidValue)
+template <> hipError_t launch_sink_m<MODE_HARD, RecSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
+template <> hipError_t launch_sink_m<MODE_HSIG, RecSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
+template <> hipError_t launch_sink_m<MODE_HARD, BinSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const BinArgs&);
+template <> hipError_t launch_sink_m<MODE_HSIG, BinSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const BinArgs&);
 
 // ---- by-mode dispatchers ----
 // `listed`: the LISTED build (orders >= 2 from the region candidate lists, a.rl); otherwise the enumerating build, which
@@ -57,10 +57,10 @@ hipError_t launch_fwd_coop(int mode, int max_order, int W, dim3 grid, size_t lds
 hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
 // power_vg_kernel<MODE, TXG, GRADK>: exhaustive sweeps (strict_nan value+grad; "txg_exhaustive" values)
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
-// power_rec_kernel<MODE, MAXK, TXG>: the record build of the culled sweep (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
-hipError_t launch_rec(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RecArgs& r);
-// power_bin_kernel<MODE, MAXK, TXG>: the bin build of the culled sweep, the per-cell power-delay profile (hard / hard_sigmoid likewise)
-hipError_t launch_bin(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const BinArgs& b);
+// power_sink_kernel<MODE, MAXK, TXG, Sink>: the culled sweep into a sink -- RecSink the record build, BinSink the per-cell
+// power-delay profile (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
+template <class Sink>
+hipError_t launch_sink(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const typename Sink::Args& x);
 
 // region_list_kernel<K, false, TXG>: candidate lists of order K (2..4) of level `lv` by enumeration; grid = regions x slices
 hipError_t launch_region_lists(int K, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,

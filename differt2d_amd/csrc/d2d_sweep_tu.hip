@@ -2,7 +2,7 @@
 // per-mode launcher (declared in d2d_launch.hpp) that d2d.hip's dispatchers call.  Compiled by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2
 //   taken from the region lists (LISTED), 9 fwd_coop}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}: all 27 pairs;
-//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 record build and bin build for modes 0 and 1 (no sigmoid instance)
+//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (record and bin builds) for modes 0 and 1 (no sigmoid instance)
 #include <type_traits>
 
 #include "d2d_launch.hpp"
@@ -158,22 +158,22 @@ hipError_t launch_nan_apply(hipStream_t s, const SweepArgs& a, long tiles) {
     return hipGetLastError();
 }
 #elif D2D_TU_FAMILY == 11
-// power_rec_kernel<MODE, MAXK, TXG>: hard and hard_sigmoid only (the sigmoid sweeps' skips depend on the fused function's sum)
-template <>
-hipError_t launch_rec_m<TU_MODE>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
-    static_assert(TU_MODE == MODE_HARD || TU_MODE == MODE_HSIG, "the record build has no sigmoid instance");
+// power_sink_kernel<MODE, MAXK, TXG, Sink>: hard and hard_sigmoid only (the sigmoid sweeps' skips depend on the fused function's sum)
+template <class Sink>
+static hipError_t launch_sink_tu(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const typename Sink::Args& x) {
+    static_assert(TU_MODE == MODE_HARD || TU_MODE == MODE_HSIG, "the sink kernel has no sigmoid instance");
     const dim3 block(64);
-    if (txg) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_rec_kernel<TU_MODE, decltype(K)::value, true>), grid, block, lds, s, a, r); });
-    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_rec_kernel<TU_MODE, decltype(K)::value, false>), grid, block, lds, s, a, r); });
+    if (txg) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_sink_kernel<TU_MODE, decltype(K)::value, true, Sink>), grid, block, lds, s, a, x); });
+    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_sink_kernel<TU_MODE, decltype(K)::value, false, Sink>), grid, block, lds, s, a, x); });
     return hipGetLastError();
 }
-// power_bin_kernel<MODE, MAXK, TXG>: the same sweep with a bin sink (d2d_power_profile_launch)
 template <>
-hipError_t launch_bin_m<TU_MODE>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const BinArgs& b) {
-    const dim3 block(64);
-    if (txg) by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_bin_kernel<TU_MODE, decltype(K)::value, true>), grid, block, lds, s, a, b); });
-    else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_bin_kernel<TU_MODE, decltype(K)::value, false>), grid, block, lds, s, a, b); });
-    return hipGetLastError();
+hipError_t launch_sink_m<TU_MODE, RecSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
+    return launch_sink_tu<RecSink>(txg, max_order, grid, lds, s, a, r);
+}
+template <>
+hipError_t launch_sink_m<TU_MODE, BinSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const BinArgs& b) {
+    return launch_sink_tu<BinSink>(txg, max_order, grid, lds, s, a, b);
 }
 #else
 #error "unknown D2D_TU_FAMILY"

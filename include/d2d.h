@@ -444,8 +444,9 @@ int d2d_trace_paths(d2d_ctx* ctx, const d2d_params* params, const float* tx, con
  * d2d_set_grid of another grid) until the next call.  The resident value / gradient maps, the work history and the
  * schedule of the fused sweeps are not touched.
  * D2D_ERR_UNSUPPORTED: sigmoid validity (its sweeps skip candidates by the fused function's running sum), MinPath / FermatPath,
- * a TX grid whose sweep would not be culled (d2d_params.grid_role), more than 4 095 objects, or a total that would take more
- * than half of the free device memory (100 bytes per record; the message holds the count) -- decided before the second pass.
+ * a TX grid whose sweep would not be culled (d2d_params.grid_role), more than 4 095 objects -- all decided before anything is
+ * enqueued -- or a total that would take more than half of the free device memory (100 bytes per record; the message holds the
+ * count) -- decided before the second pass.
  * D2D_ERR_STATE: the second pass disagreed with the first (an internal error; nothing is stored out of bounds). */
 int d2d_valid_paths(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, int64_t* count);
 /* Copies the records of the last d2d_valid_paths out: cell[n] (row-major index into the grid), cand[n][D2D_MAX_ORDER]

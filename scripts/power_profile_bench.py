@@ -1,6 +1,6 @@
 """What does the per-cell power-delay profile cost?  BASELINE.json configs[1] (50 walls, seed 1234, 1024 x 1024 cells, orders 0..2),
 32 bins over [0, 4), hard and hard_sigmoid validity, both grid roles.  Per leg, on ONE context in ONE process: the profile launch
-(d2d_power_profile_launch: the zeroing of the profile and power_bin_kernel) beside the fused sweep of the same parameters,
+(d2d_power_profile_launch: the zeroing of the profile and power_sink_kernel with a BinSink) beside the fused sweep of the same parameters,
 interleaved in blocks so that clock drift hits both alike -- HIP events around a block of back-to-back launches, median over the
 blocks of the per-launch time -- and beside ONE record pass of d2d_valid_paths (pass 1, the library's own events: the same
 enumeration in the same launch shape with a record sink).  Every leg is a child process of its own under its own time limit; the

@@ -1,4 +1,4 @@
-"""The per-cell power-delay profile (include/d2d.h: d2d_power_profile_launch; power_bin_kernel): the fused sweep's contributions
+"""The per-cell power-delay profile (include/d2d.h: d2d_power_profile_launch; power_sink_kernel, BinSink): the fused sweep's contributions
 binned by path length.  Held bit for bit to the oracle recipe of ``tests/power_profile_oracle.py`` (which
 ``tests/test_power_profile_cpu.py`` pins to ``R.power_map``), to the consequences of the definition against the fused sweep itself,
 and to its state rules and refusals."""

@@ -283,3 +283,46 @@ def test_the_library_refuses_what_the_record_launch_does_not_cover(ctx):
     with pytest.raises(L.D2DUnsupported):
         ctx.valid_paths(make_params(max_order=1, tol=0.75, grid_role=L.GRID_TX), tx)
     assert ctx.txg_fallbacks() == before
+
+
+def test_a_refused_record_launch_comes_before_anything_is_enqueued(ctx):
+    """A record launch that is refused for a reason its arguments and the context decide -- a TX grid whose sweep is not culled,
+    more objects than the kernel's LDS table holds -- returns D2D_ERR_UNSUPPORTED without having built a mask, counted a
+    fall-back or touched the resident map.  Both refusals drop the previous records (they always did: the call that replaces
+    the records starts by giving them up)."""
+    import ctypes as C
+
+    from differt2d_amd import _lib as L
+    from differt2d_amd.engine import make_params
+
+    tx, walls = random_scene(6, seed=33)
+    ctx.set_scene(walls)
+    ctx.set_grid(*unit_grid(16))
+    p = make_params(min_order=0, max_order=2)
+    ctx.launch(p, tx)
+    resident = ctx.get_map()
+    assert np.count_nonzero(resident) > 0
+    lib, handle, fixed, null = ctx._lib, ctx._ctx, np.ascontiguousarray(tx, F), [None] * 7
+
+    def refused(params, word):
+        assert lib.d2d_get_valid_paths(handle, 1 << 20, *null) == 0  # records to lose
+        before = (ctx.hidden_masks(), ctx.txg_fallbacks())
+        n = C.c_int64(-1)
+        assert lib.d2d_valid_paths(handle, C.byref(params), fixed, C.byref(n)) == -4 and n.value == 0
+        message = lib.d2d_last_error().decode()
+        assert word in message and "d2d_valid_paths" in message
+        assert (ctx.hidden_masks(), ctx.txg_fallbacks()) == before
+        assert np.array_equal(ctx.get_map(), resident)
+        assert lib.d2d_get_valid_paths(handle, 1 << 20, *null) == -5  # the previous records are gone
+
+    assert ctx.valid_paths(p, tx)["cell"].size > 0
+    ctx.set_option("txg_exhaustive", 1)
+    try:
+        refused(make_params(min_order=0, max_order=2, grid_role=L.GRID_TX), "txg_exhaustive")
+    finally:
+        ctx.set_option("txg_exhaustive", 0)
+    # 2600 walls: (4 * 2600 + 1) * 16 + 512 bytes of tables and queue, above the CU's 160 KB (the records of the small scene are
+    # still held when the call comes: they go with the grid, not with the scene)
+    assert ctx.valid_paths(p, tx)["cell"].size > 0
+    ctx.set_scene(random_scene(2600, seed=34)[1])
+    refused(make_params(min_order=0, max_order=1), "LDS")
