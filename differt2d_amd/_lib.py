@@ -19,6 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("D2D_LIB") or os.path.join(CSRC, "libd2d.so")
 
 D2D_MAX_ORDER = 4
+D2D_TOP_MAX = 8
 D2D_NUM_STATS = 16
 D2D_COMM_ID_BYTES = 128
 D2D_OPT_ADAM, D2D_OPT_SGD, D2D_OPT_SGD_MOMENTUM = 0, 1, 2  # d2d_set_optimizer kinds
@@ -136,6 +137,8 @@ SYMBOLS = [
     ("d2d_debug_valid_paths_ms", C.c_int, [_ctx, np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")]),
     ("d2d_power_profile_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_float, C.c_float, C.c_int32]),
     ("d2d_get_power_profile", C.c_int, [_ctx, _f32p]),
+    ("d2d_strongest_paths_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_int32]),
+    ("d2d_get_strongest_paths", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),

@@ -171,6 +171,15 @@ struct d2d_ctx {
         d_profile.release();
         prof_nbins = 0;
     }
+    // per-cell strongest paths (d2d_strongest_paths_launch): the first top_k slots of every cell, kept until the next launch,
+    // dropped with the grid
+    DevBuf<float> d_top_power, d_top_len, d_top_total;  // [top_k][m][n], [top_k][m][n], [m][n]
+    DevBuf<int> d_top_cand, d_top_order, d_top_count;   // [top_k][m][n][D2D_MAX_ORDER], [top_k][m][n], [m][n]
+    int top_k = 0;  // slots per cell the buffers hold a result of (0: none)
+    void drop_top() {
+        d_top_power.release(); d_top_len.release(); d_top_total.release(); d_top_cand.release(); d_top_order.release(); d_top_count.release();
+        top_k = 0;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -869,6 +878,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->drop_records();  // ... and the records' cells
         c->drop_profile();  // ... and the profile's
+        c->drop_top();      // ... and the strongest paths'
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -2188,6 +2198,19 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     return D2D_OK;
 }
 
+// What the fused sinks (d2d_power_profile_launch, d2d_strongest_paths_launch: `who`) refuse of the caller's parameters before
+// prep_sink_sweep's share; `custom_route` and `add_why` end the two messages that say what to do instead.
+static int check_fused_sink(d2d_ctx* c, const d2d_params* p, const char* who, const char* custom_route, const char* add_why) {
+    if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT)
+        return fail(D2D_ERR_UNSUPPORTED, "%s covers ImagePath only, not the MinPath / FermatPath solvers (solver %d)", who, p->solver);
+    if (p->fun_id == D2D_FUN_CUSTOM)
+        return fail(D2D_ERR_UNSUPPORTED, "%s: fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only (%s)", who, custom_route);
+    if (p->out_mode == D2D_OUT_ADD) return fail(D2D_ERR_UNSUPPORTED, "%s: D2D_OUT_ADD is not supported, %s", who, add_why);
+    if (p->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT && ((int)c->coef.size() != c->N || (c->N > 0 && !c->d_coef.p)))
+        return fail(D2D_ERR_STATE, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT needs d2d_set_reflection_coefs for the resident scene");
+    return D2D_OK;
+}
+
 // Bin launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed profile.
 // Asynchronous.  Every check comes before anything is enqueued.
 static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float r_min, float r_max, int32_t nbins) {
@@ -2197,13 +2220,9 @@ static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float*
     if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_power_profile_launch");
     if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_power_profile_launch");
     c->prof_nbins = 0;  // whatever this launch turns out to be, the previous profile is gone
-    if (p_in->solver == D2D_SOLVER_MINPATH || p_in->solver == D2D_SOLVER_FERMAT)
-        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch covers ImagePath only, not the MinPath / FermatPath solvers (solver %d)", p_in->solver);
-    if (p_in->fun_id == D2D_FUN_CUSTOM)
-        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only (a host function's profile: bin the records of d2d_valid_paths)");
-    if (p_in->out_mode == D2D_OUT_ADD) return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: D2D_OUT_ADD is not supported, a profile is always overwritten");
-    if (p_in->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT && ((int)c->coef.size() != c->N || (c->N > 0 && !c->d_coef.p)))
-        return fail(D2D_ERR_STATE, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT needs d2d_set_reflection_coefs for the resident scene");
+    if ((rc = check_fused_sink(c, p_in, "d2d_power_profile_launch", "a host function's profile: bin the records of d2d_valid_paths",
+                               "a profile is always overwritten")))
+        return rc;
     d2d_host::ProfileBins bins;
     {
         std::string err;
@@ -2240,9 +2259,75 @@ static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float*
     return D2D_OK;
 }
 
+// Top-k launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel, every lane writing the
+// whole of its cell (no zeroing in front).  Asynchronous.  Every check comes before anything is enqueued.
+static int strongest_paths_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int32_t k) {
+    if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_strongest_paths_launch");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_strongest_paths_launch");
+    c->top_k = 0;  // whatever this launch turns out to be, the previous result is gone
+    if ((rc = check_fused_sink(c, p_in, "d2d_strongest_paths_launch", "a host function's strongest paths: sort the records of d2d_valid_paths",
+                               "the slots are always overwritten")))
+        return rc;
+    if (k < 1 || k > D2D_TOP_MAX) return fail(D2D_ERR_INVALID, "d2d_strongest_paths_launch: k = %d is outside 1..D2D_TOP_MAX (%d)", k, D2D_TOP_MAX);
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_top_power.n + c->d_top_len.n + c->d_top_total.n + c->d_top_cand.n + c->d_top_order.n + c->d_top_count.n) * 4;
+        if (!d2d_host::top_fits(cells, k, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_strongest_paths_launch: %d slots of %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
+                        k, cells, d2d_host::top_bytes_per_cell(k), mem_free);
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_strongest_paths_launch", lds))) return rc;
+    const size_t kc = (size_t)k * cells;
+    if ((rc = c->d_top_power.ensure(kc)) || (rc = c->d_top_len.ensure(kc)) || (rc = c->d_top_cand.ensure(kc * D2D_MAX_ORDER)) ||
+        (rc = c->d_top_order.ensure(kc)) || (rc = c->d_top_total.ensure(cells)) || (rc = c->d_top_count.ensure(cells)))
+        return rc;
+    d2d::TopArgs t;
+    t.power = c->d_top_power.p;
+    t.length = c->d_top_len.p;
+    t.cand = c->d_top_cand.p;
+    t.order = c->d_top_order.p;
+    t.total = c->d_top_total.p;
+    t.count = c->d_top_count.p;
+    t.cells = (long)cells;
+    t.k = k;
+    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::TopSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, t));
+    c->top_k = k;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_strongest_paths_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t k) { return strongest_paths_launch(c, p, fixed, k); }
+
+int d2d_get_strongest_paths(d2d_ctx* c, float* power, float* length, int32_t* cand, int32_t* order, float* total, int32_t* count) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (c->top_k < 1 || !c->d_top_power.p) return fail(D2D_ERR_STATE, "d2d_strongest_paths_launch must come first (its result goes with the grid)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n, kc = (size_t)c->top_k * cells;
+    if (power) HIP_TRY(hipMemcpyAsync(power, c->d_top_power.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (length) HIP_TRY(hipMemcpyAsync(length, c->d_top_len.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (cand) HIP_TRY(hipMemcpyAsync(cand, c->d_top_cand.p, kc * D2D_MAX_ORDER * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (order) HIP_TRY(hipMemcpyAsync(order, c->d_top_order.p, kc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_top_total.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (count) HIP_TRY(hipMemcpyAsync(count, c->d_top_count.p, cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_power_profile_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float r_min, float r_max, int32_t nbins) {
     return power_profile_launch(c, p, fixed, r_min, r_max, nbins);

@@ -241,6 +241,16 @@ inline int profile_bins(float r_min, float r_max, int32_t nbins, ProfileBins& b,
     return D2D_OK;
 }
 
+// ---- outputs of the per-cell strongest paths (d2d_strongest_paths_launch, d2d::TopSink) ------------------------------
+// Per cell: k slots of power, length, order (4 bytes each) and D2D_MAX_ORDER wall indices, then total and count.  The launch is
+// refused when the outputs exceed half of the device memory that is free, counting what the buffers hold already as free
+// (tests/native/strongest_paths_host.cpp: a grid large enough to be refused does not fit a quick test).
+inline size_t top_bytes_per_cell(int32_t k) { return (size_t)k * (3 + D2D_MAX_ORDER) * 4 + 8; }
+inline bool top_fits(size_t cells, int32_t k, size_t mem_free, size_t held_bytes) {
+    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
+    return cells <= budget / top_bytes_per_cell(k);
+}
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

@@ -33,6 +33,7 @@
 
 #include "../../include/d2d.h"
 #include "d2d_div.hpp"
+#include "d2d_top.hpp"
 
 namespace d2d {
 
@@ -1813,6 +1814,71 @@ struct BinSink {
         }
     }
     __device__ __forceinline__ void end(const BinArgs&, long, int) const {}
+};
+
+// TopSink (d2d_strongest_paths_launch): the k strongest contributions of every cell instead of their sum alone (include/d2d.h
+// holds the definition).  Per lane, in registers: TOP_SLOTS slots of (t, r, code low, code high | order) kept sorted by
+// d2d_top.hpp's top_insert, the running fp32 sum of every contribution (the fused map, bit for bit) and the number of
+// contributions that are not exactly zero.  The whole insertion is skipped for a candidate that no lane of the wave has a
+// non-zero contribution from, the common case.  end() unpacks the codes and stores slots 0 .. k-1: every lane is the only writer
+// of its cell and writes all of it, so there are no atomics and no zeroing pass; lanes outside the grid (cell < 0) never write.
+struct TopArgs {
+    float* power;   // [k][cells]
+    float* length;  // [k][cells]
+    int* cand;      // [k][cells][D2D_MAX_ORDER]
+    int* order;     // [k][cells]
+    float* total;   // [cells]
+    int* count;     // [cells]
+    long cells;     // m * n
+    int k;          // 1 .. TOP_SLOTS
+};
+struct TopSink {
+    using Args = TopArgs;
+    static constexpr bool WANTS_R = true;
+    static_assert(D2D_MAX_ORDER == 4, "a slot's wall indices are stored as one int4");
+    static_assert(TOP_SLOTS == D2D_TOP_MAX, "d2d_top.hpp and include/d2d.h disagree");
+    TopSlots s;
+    float total;
+    int count;
+    int cell;
+    __device__ __forceinline__ void begin(const TopArgs&, long /*tile*/, int lane_cell) {
+        top_clear(s);
+        total = 0.0f;
+        count = 0;
+        cell = lane_cell;
+    }
+    __device__ __forceinline__ void put(float t, unsigned long long code, int k, float r) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        if (p) {
+            ++count;
+            top_insert(s, (uint32_t)__float_as_int(t), (uint32_t)__float_as_int(r), (uint32_t)(code & 0xffffffffull), (uint32_t)(code >> 32) | ((uint32_t)k << 24));
+        }
+    }
+    __device__ __forceinline__ void end(const TopArgs& x, long, int) const {
+        if (cell < 0) return;
+        x.total[cell] = total;
+        x.count[cell] = count;
+        static_for<0, TOP_SLOTS>([&](auto SS) {
+            constexpr int S = decltype(SS)::value;
+            if (S < x.k) {
+                const size_t at = (size_t)S * (size_t)x.cells + (size_t)cell;
+                const bool empty = top_key(s.tb[S]) == 0u;
+                const int ord = empty ? -1 : (int)(s.hi[S] >> 24);
+                const unsigned long long code = ((unsigned long long)(s.hi[S] & 0xffffu) << 32) | s.lo[S];
+                int4 w;
+                w.x = ord > 0 ? (int)(code & 0xfffull) : -1;
+                w.y = ord > 1 ? (int)((code >> 12) & 0xfffull) : -1;
+                w.z = ord > 2 ? (int)((code >> 24) & 0xfffull) : -1;
+                w.w = ord > 3 ? (int)((code >> 36) & 0xfffull) : -1;
+                x.power[at] = __int_as_float((int)s.tb[S]);
+                x.length[at] = empty ? __builtin_nanf("") : __int_as_float((int)s.rb[S]);
+                x.order[at] = ord;
+                reinterpret_cast<int4*>(x.cand)[at] = w;
+            }
+        });
+    }
 };
 
 // Survivors of a region's culling, in candidate order (region_list_kernel / region_refine_kernel): wave-uniform state

@@ -8,7 +8,7 @@ benchmarks and tests may use it directly.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -67,6 +67,17 @@ def make_params(
     return p
 
 
+class StrongestPaths(NamedTuple):
+    """Result of :meth:`Context.strongest_paths` (include/d2d.h: d2d_strongest_paths_launch): slots first, cell axes after."""
+
+    power: np.ndarray   # fp32 [k, m, n]: the slot's contribution valid * fun (+0.0: empty)
+    length: np.ndarray  # fp32 [k, m, n]: the slot's path length (NaN: empty)
+    cand: np.ndarray    # int32 [k, m, n, D2D_MAX_ORDER]: wall indices of the path, -1 padded
+    order: np.ndarray   # int32 [k, m, n]: order of the path (-1: empty)
+    total: np.ndarray   # fp32 [m, n]: the sum over all candidates, the fused map bit for bit
+    count: np.ndarray   # int32 [m, n]: non-zero contributions of the cell
+
+
 def _immutable(a: np.ndarray) -> bool:
     """Nobody can write to this array's memory through NumPy: it and every array it is a view of are read-only."""
     while isinstance(a, np.ndarray):
@@ -88,6 +99,7 @@ class Context:
         self.n_objects = 0
         self._grid_held = None
         self._grid_serial = 0
+        self._top_k = 0  # slots per cell of the last launch_strongest_paths that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -503,6 +515,45 @@ class Context:
         out = np.empty((int(nbins),) + tuple(self.shape), np.float32)
         L.check(self._lib.d2d_get_power_profile(self._ctx, out))
         return out
+
+    def strongest_paths(self, params: L.Params, fixed, k: int) -> "StrongestPaths":
+        """The ``k`` strongest multipath components of every cell of the resident grid (``1 <= k <= D2D_TOP_MAX``): the fused
+        sweep's contributions ``valid * fun`` with the largest magnitude, strongest first, ties in enumeration order -- one launch
+        of the top-k build of the culled sweep (include/d2d.h: d2d_strongest_paths_launch holds the definition; ImagePath, hard or
+        hard_sigmoid validity, every fused function).  ``params.grid_role`` says which end of the paths the cells are, ``fixed`` is
+        the other end.  The resident value map, the records of :meth:`valid_paths` and the profile are not touched.
+
+        Returns a :class:`StrongestPaths`: ``power`` and ``length`` fp32 ``[k, m, n]``, ``cand`` int32 ``[k, m, n, D2D_MAX_ORDER]``
+        (-1 padded), ``order`` int32 ``[k, m, n]``, ``total`` fp32 ``[m, n]`` (the fused map, bit for bit) and ``count`` int32
+        ``[m, n]`` (non-zero contributions; ``count > k``: something was cut).  An empty slot holds power +0.0, length NaN, order
+        -1.  :func:`differt2d_amd.utils.strongest_share` gives the kept slots' share of ``total``."""
+        self.launch_strongest_paths(params, fixed, k)
+        return self.get_strongest_paths()
+
+    def launch_strongest_paths(self, params: L.Params, fixed, k: int):
+        """The launch of :meth:`strongest_paths` alone (asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        self._top_k = 0
+        L.check(self._lib.d2d_strongest_paths_launch(self._ctx, C.byref(params), fixed, int(k)))
+        self._top_k = int(k)
+
+    def get_strongest_paths(self) -> "StrongestPaths":
+        """Synchronises and returns the result of the last :meth:`launch_strongest_paths`."""
+        k = self._top_k
+        if k < 1:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_strongest_paths(self._ctx, None, None, None, None, None, None))
+            raise L.D2DError(-5, "launch_strongest_paths must come first")
+        shape = tuple(self.shape)
+        sp = StrongestPaths(
+            power=np.empty((k,) + shape, np.float32),
+            length=np.empty((k,) + shape, np.float32),
+            cand=np.empty((k,) + shape + (L.D2D_MAX_ORDER,), np.int32),
+            order=np.empty((k,) + shape, np.int32),
+            total=np.empty(shape, np.float32),
+            count=np.empty(shape, np.int32),
+        )
+        L.check(self._lib.d2d_get_strongest_paths(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in sp)))
+        return sp
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

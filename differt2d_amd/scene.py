@@ -1037,6 +1037,60 @@ class Scene(Plottable):
         return self._grid_profile(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, length_range, nbins, path_cls,
                                   min_order, max_order, order, filter_objects, kwargs)
 
+    def _grid_strongest(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, k, path_cls, min_order, max_order, order,
+                        filter_objects, kwargs):
+        """Shared driver of the two strongest-path sweeps: one launch of the top-k build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the strongest paths come from a fused sweep (a function "
+                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+                                       "(Context.valid_paths: every valid path of every cell) and sort fun's values on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the strongest paths cover ImagePath only, not path_cls={path_cls.__name__}")
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.strongest_paths(params, pt.xy, k)
+
+        return results()
+
+    def strongest_paths_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, k: int, path_cls: type = ImagePath,
+        min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The ``k`` strongest multipath components of every cell (``1 <= k <= 8``): for every transmitter, the ``k`` candidates
+        with the largest ``|valid * fun|`` at the receiver ``(X[i, j], Y[i, j])``, strongest first and ties in enumeration order
+        -- the terms that :meth:`accumulate_on_receivers_grid_over_paths` adds up per cell, kept apart.  Yields
+        ``(tx name, StrongestPaths(power, length, cand, order, total, count))`` (:class:`differt2d_amd.engine.StrongestPaths`:
+        slots on the first axis; ``cand`` holds the indices into ``self.objects`` of the walls a path bounces off, -1 padded;
+        ``total`` is the fused map bit for bit, ``count`` the number of non-zero contributions); one fused kernel launch per
+        transmitter (include/d2d.h: d2d_strongest_paths_launch holds the exact definition).
+        :func:`differt2d_amd.utils.strongest_share` gives the share of a cell's power that the kept paths carry.
+
+        ``fun`` must be natively fused (:mod:`differt2d_amd.utils`), the path class ``ImagePath``, the validity hard
+        (``approx=False``) or ``hard_sigmoid``; anything else raises :class:`D2DUnsupported`.  For another callable the sparse
+        valid-path records (:meth:`Context.valid_paths`) hold every valid path for sorting on the host."""
+        return self._grid_strongest(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, k, path_cls, min_order, max_order,
+                                    order, filter_objects, kwargs)
+
+    def strongest_paths_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, k: int, path_cls: type = ImagePath,
+        min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`strongest_paths_on_receivers_grid`: one result per receiver, the transmitter sits at
+        ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_strongest(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, k, path_cls, min_order, max_order,
+                                    order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

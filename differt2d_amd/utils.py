@@ -96,6 +96,17 @@ def delay_statistics(profile, length_range):
     return total, mean, rms
 
 
+def strongest_share(sp):
+    """The share of every cell's sum that its kept strongest paths carry: the sum of the slots' ``power`` divided by ``total``,
+    for a ``StrongestPaths`` (``Scene.strongest_paths_on_receivers_grid``, ``Context.strongest_paths``) or any object with
+    ``power`` ``[k, ...]`` and ``total`` ``[...]``.  On the host, in float64 (empty slots hold +0.0 and add nothing); NaN where
+    ``total == 0``.  With a path function that is never negative the share lies in [0, 1], and 1 where nothing was cut."""
+    kept = np.asarray(sp.power, dtype=np.float64).sum(axis=0)
+    total = np.asarray(sp.total, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(total == 0.0, np.nan, kept / total)
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

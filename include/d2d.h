@@ -26,8 +26,9 @@ extern "C" {
 #endif
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
-#define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile are additive: no struct, enum or existing entry point
-                              changed with them, so the version did not) */
+#define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile and d2d_strongest_paths_launch /
+                              d2d_get_strongest_paths are additive: no struct, enum or existing entry point changed with them,
+                              so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -492,6 +493,57 @@ int d2d_power_profile_launch(d2d_ctx* ctx, const d2d_params* params, const float
 /* Synchronises and copies the profile of the last d2d_power_profile_launch to out[nbins][m][n].  D2D_ERR_STATE before a launch,
  * after a launch that was refused, and after a d2d_set_grid of another grid (the profile goes with the grid). */
 int d2d_get_power_profile(d2d_ctx* ctx, float* out /* [nbins][m][n] */);
+
+/* ---- per-cell strongest paths: the k largest contributions of the fused sweep, with their lengths and wall sequences (no
+ *      reference counterpart: the reference reduces every cell to one number; the dominant path, the share of the power that
+ *      the few strongest paths carry, and channel taps follow from the slots) ---- */
+
+#define D2D_TOP_MAX 8
+/* Launches the top-k build of the culled forward sweep for the fixed end point `fixed` on the ctx stream (asynchronous), for
+ * the current scene, candidate mask and grid.  `params` as for d2d_power_map_launch (params->grid_role says which end the
+ * cells are); k lies in 1..D2D_TOP_MAX.  Definition, per cell:
+ *
+ *     slots empty;  total = +0.0f;  count = 0
+ *     for candidates in the sweep's enumeration order:
+ *         t = valid * fun            // exactly the fused sweep's contribution (nan_to_num rules included)
+ *         r = path_length(points)    // the fp32 value the path function is evaluated with (what the profile bins by)
+ *         total = total + t          // fp32: hence the fused map bit for bit
+ *         if (t == 0) continue       // exact zeros of either sign take no slot
+ *         count += 1
+ *         key = bit pattern of fabsf(t), compared as uint32   // a total order; NaN ranks above inf
+ *         insert (t, r, candidate) in front of the first slot whose key is STRICTLY smaller; the (k+1)-th falls off
+ *
+ *   - Slots are therefore sorted by key, descending.  Among equal keys the earlier candidate in enumeration order comes first
+ *     and survives the cut.
+ *   - "Strongest" means largest |t|.  A negative per-object coefficient gives negative contributions, and those compete by
+ *     magnitude.
+ *
+ * Outputs, cell axes last:
+ *     power   fp32  [k][m][n]                  the slot's t
+ *     length  fp32  [k][m][n]                  the slot's r
+ *     cand    int32 [k][m][n][D2D_MAX_ORDER]   wall indices of the path, -1 padded
+ *     order   int32 [k][m][n]                  order of the path
+ *     total   fp32  [m][n]                     the running sum over all candidates
+ *     count   int32 [m][n]                     how many non-zero contributions the cell had
+ *
+ *   - count > k means something was cut.
+ *   - An empty slot holds power = +0.0, length = NaN, order = -1 and cand = -1.
+ *   - The top-k of the top-8 is the top-k under this rule: the kernel keeps D2D_TOP_MAX slots and stores the first k.
+ *
+ * One pass of one kernel (one wave per 8 x 8 patch, a lane's slots in registers, every lane the only writer of its cell and
+ * writing all of it: no atomics, no zeroing, the same bits run to run).  The resident value / gradient maps, the work history,
+ * the schedule of the fused sweeps, the records of d2d_valid_paths and the profile are not touched.  Every fused function but
+ * D2D_FUN_CUSTOM; D2D_FUN_RECEIVED_POWER_PER_OBJECT with the coefficients of d2d_set_reflection_coefs, D2D_ERR_STATE without
+ * them.  The interaction points of a kept path: d2d_trace_paths with its `cand`.
+ * D2D_ERR_INVALID: k outside 1..D2D_TOP_MAX.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): sigmoid validity, MinPath / FermatPath, D2D_FUN_CUSTOM, D2D_OUT_ADD, a TX
+ * grid whose sweep would not be culled (d2d_params.grid_role; not counted by d2d_debug_txg_fallbacks), more than 4 095 objects,
+ * or outputs above half of the free device memory -- all decided before anything is enqueued. */
+int d2d_strongest_paths_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, int32_t k);
+/* Synchronises and copies the result of the last d2d_strongest_paths_launch (its k) to the arrays that are not NULL.
+ * D2D_ERR_STATE before a launch, after a launch that was refused, and after a d2d_set_grid of another grid (the result goes with
+ * the grid). */
+int d2d_get_strongest_paths(d2d_ctx* ctx, float* power, float* length, int32_t* cand, int32_t* order, float* total, int32_t* count);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
