@@ -180,6 +180,14 @@ struct d2d_ctx {
         d_top_power.release(); d_top_len.release(); d_top_total.release(); d_top_cand.release(); d_top_order.release(); d_top_count.release();
         top_k = 0;
     }
+    // coherent field (d2d_coherent_field_launch): re, im and the incoherent total of every cell, kept until the next launch,
+    // dropped with the grid
+    DevBuf<float> d_field_re, d_field_im, d_field_total;  // [m][n] each
+    bool have_field = false;
+    void drop_field() {
+        d_field_re.release(); d_field_im.release(); d_field_total.release();
+        have_field = false;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -879,6 +887,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->drop_records();  // ... and the records' cells
         c->drop_profile();  // ... and the profile's
         c->drop_top();      // ... and the strongest paths'
+        c->drop_field();    // ... and the coherent field's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -2198,7 +2207,7 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     return D2D_OK;
 }
 
-// What the fused sinks (d2d_power_profile_launch, d2d_strongest_paths_launch: `who`) refuse of the caller's parameters before
+// What the fused sinks (d2d_power_profile_launch, d2d_strongest_paths_launch, d2d_coherent_field_launch: `who`) refuse of the caller's parameters before
 // prep_sink_sweep's share; `custom_route` and `add_why` end the two messages that say what to do instead.
 static int check_fused_sink(d2d_ctx* c, const d2d_params* p, const char* who, const char* custom_route, const char* add_why) {
     if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT)
@@ -2306,9 +2315,72 @@ static int strongest_paths_launch(d2d_ctx* c, const d2d_params* p_in, const floa
     return D2D_OK;
 }
 
+// Coherent-field launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel, every lane
+// writing the three values of its cell (no zeroing in front).  Asynchronous.  Every check comes before anything is enqueued.
+static int coherent_field_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float inv_wavelength, int32_t amplitude) {
+    if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_coherent_field_launch");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_coherent_field_launch");
+    c->have_field = false;  // whatever this launch turns out to be, the previous result is gone
+    if ((rc = check_fused_sink(c, p_in, "d2d_coherent_field_launch", "a host function's field: add the phasors of the records of d2d_valid_paths",
+                               "the field is always overwritten")))
+        return rc;
+    {
+        std::string err;
+        if ((rc = d2d_host::field_params(inv_wavelength, amplitude, err))) return fail(rc, "d2d_coherent_field_launch: %s", err.c_str());
+    }
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_field_re.n + c->d_field_im.n + c->d_field_total.n) * sizeof(float);
+        if (!d2d_host::field_fits(cells, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_coherent_field_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
+                        cells, d2d_host::FIELD_BYTES_PER_CELL, mem_free);
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_coherent_field_launch", lds))) return rc;
+    if ((rc = c->d_field_re.ensure(cells)) || (rc = c->d_field_im.ensure(cells)) || (rc = c->d_field_total.ensure(cells))) return rc;
+    d2d::FieldArgs f;
+    f.re = c->d_field_re.p;
+    f.im = c->d_field_im.p;
+    f.total = c->d_field_total.p;
+    f.cells = (long)cells;
+    f.inv_wavelength = inv_wavelength;
+    f.amplitude = amplitude;
+    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::FieldSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, f));
+    c->have_field = true;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_coherent_field_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude) {
+    return coherent_field_launch(c, p, fixed, inv_wavelength, amplitude);
+}
+
+int d2d_get_coherent_field(d2d_ctx* c, float* re, float* im, float* total) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (!c->have_field || !c->d_field_re.p) return fail(D2D_ERR_STATE, "d2d_coherent_field_launch must come first (its result goes with the grid)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_field_re.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_field_im.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_field_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_strongest_paths_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t k) { return strongest_paths_launch(c, p, fixed, k); }
 
@@ -2489,6 +2561,21 @@ int d2d_selftest_expf(d2d_ctx* c, const float* x, int64_t n, float* y) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(y, dy.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_phasor(d2d_ctx* c, const float* f, int64_t n, float* cs, float* sn) {
+    if (!c || !f || !cs || !sn || n <= 0) return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> df, dc, ds;
+    if ((rc = df.ensure((size_t)n)) || (rc = dc.ensure((size_t)n)) || (rc = ds.ensure((size_t)n))) return rc;
+    HIP_TRY(hipMemcpy(df.p, f, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_phasor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, df.p, dc.p, ds.p, (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(cs, dc.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sn, ds.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }
 

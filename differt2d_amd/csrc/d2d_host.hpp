@@ -251,6 +251,25 @@ inline bool top_fits(size_t cells, int32_t k, size_t mem_free, size_t held_bytes
     return cells <= budget / top_bytes_per_cell(k);
 }
 
+// ---- parameters and outputs of the coherent field (d2d_coherent_field_launch, d2d::FieldSink) -----------------------
+// D2D_ERR_INVALID: an inverse wavelength that is negative, NaN or infinite (0 is allowed: every phase is 0), an amplitude
+// mode that is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.
+inline int field_params(float inv_wavelength, int32_t amplitude, std::string& err) {
+    if (!std::isfinite(inv_wavelength) || inv_wavelength < 0.0f)
+        return err = "the coherent field needs a finite inv_wavelength >= 0, got " + std::to_string(inv_wavelength), D2D_ERR_INVALID;
+    if (amplitude != D2D_FIELD_AMP_SQRT && amplitude != D2D_FIELD_AMP_LINEAR)
+        return err = "the coherent field's amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
+               D2D_ERR_INVALID;
+    return D2D_OK;
+}
+// Per cell: re, im and total, 4 bytes each.  Refused like the strongest paths: outputs above half of the device memory that is
+// free, counting what the buffers hold already as free (tests/native/coherent_field_host.cpp).
+constexpr size_t FIELD_BYTES_PER_CELL = 12;
+inline bool field_fits(size_t cells, size_t mem_free, size_t held_bytes) {
+    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
+    return cells <= budget / FIELD_BYTES_PER_CELL;
+}
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

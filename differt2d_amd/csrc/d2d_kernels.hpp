@@ -34,6 +34,7 @@
 #include "../../include/d2d.h"
 #include "d2d_div.hpp"
 #include "d2d_top.hpp"
+#include "d2d_phasor.hpp"
 
 namespace d2d {
 
@@ -1878,6 +1879,60 @@ struct TopSink {
                 reinterpret_cast<int4*>(x.cand)[at] = w;
             }
         });
+    }
+};
+
+// FieldSink (d2d_coherent_field_launch): the coherent sum of every cell -- each contribution as a complex amplitude with the phase
+// of its path length -- beside the incoherent one (include/d2d.h holds the definition).  Per lane, in registers: re, im and the
+// running fp32 sum of every contribution (the fused map, bit for bit).  Per contribution that is not exactly zero:
+//     a = sqrt mode ? copysignf(sqrtf(fabsf(t)), t) : t ;  u = r * inv_wavelength ;  f = u - floorf(u)
+//     (c, s) = phasor(f) ;  re = re + a * c ;  im = im - a * s
+// in fp32 without contraction, candidates in the sweep's order; f is exact and in [0, 1) for every finite u >= 0, NaN otherwise.
+// phasor (d2d_phasor.hpp) is plain arithmetic: no sine or cosine of the device library or the hardware is involved.  The
+// phasor is skipped for a candidate that no lane of the wave has a non-zero contribution from, the common case.  end() stores the
+// three values: every lane is the only writer of its cell and writes all of it, so there are no atomics and no zeroing pass; lanes
+// outside the grid (cell < 0) never write.
+struct FieldArgs {
+    float* re;             // [cells]
+    float* im;             // [cells]
+    float* total;          // [cells]
+    long cells;            // m * n
+    float inv_wavelength;  // turns per unit length, finite and >= 0
+    int amplitude;         // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+};
+struct FieldSink {
+    using Args = FieldArgs;
+    static constexpr bool WANTS_R = true;
+    float re, im, total;
+    float inv;
+    bool root;
+    int cell;
+    __device__ __forceinline__ void begin(const FieldArgs& x, long /*tile*/, int lane_cell) {
+        re = im = total = 0.0f;
+        inv = x.inv_wavelength;
+        root = x.amplitude == D2D_FIELD_AMP_SQRT;
+        cell = lane_cell;
+    }
+    __device__ __forceinline__ void put(float t, unsigned long long /*code*/, int /*k*/, float r) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        if (p) {
+            const float a = root ? copysignf(sqrtf(fabsf(t)), t) : t;
+            const float u = r * inv;
+            const float f = u - floorf(u);
+            float c, s;
+            phasor(f, c, s);
+            const float ac = a * c, as = a * s;
+            re = re + ac;
+            im = im - as;
+        }
+    }
+    __device__ __forceinline__ void end(const FieldArgs& x, long, int) const {
+        if (cell < 0) return;
+        x.re[cell] = re;
+        x.im[cell] = im;
+        x.total[cell] = total;
     }
 };
 
@@ -3861,6 +3916,12 @@ __global__ void selftest_div_kernel(const float* __restrict__ x, const float* __
 __global__ void selftest_expf_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = expf_libm(x[i]);
+}
+
+// phasor (d2d_phasor.hpp) on the device, for comparison with its host build (tests/test_gpu_coherent_field.py)
+__global__ void selftest_phasor_kernel(const float* __restrict__ f, float* __restrict__ c, float* __restrict__ s, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) phasor(f[i], c[i], s[i]);
 }
 
 // Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per

@@ -78,6 +78,17 @@ class StrongestPaths(NamedTuple):
     count: np.ndarray   # int32 [m, n]: non-zero contributions of the cell
 
 
+class CoherentField(NamedTuple):
+    """Result of :meth:`Context.coherent_field` (include/d2d.h: d2d_coherent_field_launch)."""
+
+    re: np.ndarray     # fp32 [m, n]: real part of the sum of a * e^(-j 2 pi r / lambda)
+    im: np.ndarray     # fp32 [m, n]: imaginary part
+    total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
+
+
+FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
+
+
 def _immutable(a: np.ndarray) -> bool:
     """Nobody can write to this array's memory through NumPy: it and every array it is a view of are read-only."""
     while isinstance(a, np.ndarray):
@@ -100,6 +111,7 @@ class Context:
         self._grid_held = None
         self._grid_serial = 0
         self._top_k = 0  # slots per cell of the last launch_strongest_paths that was accepted
+        self._field = False  # a launch_coherent_field was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -370,6 +382,14 @@ class Context:
         L.check(self._lib.d2d_selftest_expf(self._ctx, x, x.size, y))
         return y
 
+    def selftest_phasor(self, f):
+        """``(cos(2 pi f), sin(2 pi f))`` as the coherent field's phasor computes them on the device (include/d2d.h: must equal the
+        host build of d2d_phasor.hpp bit for bit); ``f`` in turns, in [0, 1)."""
+        f = np.ascontiguousarray(f, dtype=np.float32).reshape(-1)
+        c, s = np.empty_like(f), np.empty_like(f)
+        L.check(self._lib.d2d_selftest_phasor(self._ctx, f, f.size, c, s))
+        return c, s
+
     def get_map(self) -> np.ndarray:
         out = np.empty(self.shape, np.float32)
         L.check(self._lib.d2d_get_map(self._ctx, out))
@@ -554,6 +574,43 @@ class Context:
         )
         L.check(self._lib.d2d_get_strongest_paths(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in sp)))
         return sp
+
+    def coherent_field(self, params: L.Params, fixed, inv_wavelength: float, amplitude="sqrt") -> "CoherentField":
+        """The coherent sum of every cell of the resident grid at one wavelength: the fused sweep's contributions ``valid * fun``
+        as complex amplitudes with the phase of their path length, ``sum a * e^(-j 2 pi r * inv_wavelength)`` -- one launch of the
+        coherent-field build of the culled sweep (include/d2d.h: d2d_coherent_field_launch holds the definition; ImagePath, hard or
+        hard_sigmoid validity, every fused function).  ``inv_wavelength`` is ``1 / lambda`` in turns per unit length, finite and
+        ``>= 0``; ``amplitude`` is ``"sqrt"`` (the fused function is a power: its amplitude is the square root, its sign a pi flip)
+        or ``"linear"`` (the fused function is the amplitude), or the library's constant.  ``params.grid_role`` says which end of
+        the paths the cells are, ``fixed`` is the other end.  The resident value map, the records of :meth:`valid_paths`, the
+        profile and the strongest paths are not touched.
+
+        Returns a :class:`CoherentField`: ``re``, ``im`` and ``total`` (the fused map, bit for bit), fp32 ``[m, n]`` each.
+        :func:`differt2d_amd.utils.field_power` and :func:`differt2d_amd.utils.fading_gain` turn it into a power and into the
+        gain of the coherent sum over the incoherent one."""
+        self.launch_coherent_field(params, fixed, inv_wavelength, amplitude)
+        return self.get_coherent_field()
+
+    def launch_coherent_field(self, params: L.Params, fixed, inv_wavelength: float, amplitude="sqrt"):
+        """The launch of :meth:`coherent_field` alone (asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        self._field = False
+        if isinstance(amplitude, str):
+            if amplitude not in FIELD_AMPLITUDES:
+                raise L.D2DError(-1, f"coherent_field: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
+            amplitude = FIELD_AMPLITUDES[amplitude]
+        L.check(self._lib.d2d_coherent_field_launch(self._ctx, C.byref(params), fixed, float(inv_wavelength), int(amplitude)))
+        self._field = True
+
+    def get_coherent_field(self) -> "CoherentField":
+        """Synchronises and returns the result of the last :meth:`launch_coherent_field`."""
+        if not self._field:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_coherent_field(self._ctx, None, None, None))
+            raise L.D2DError(-5, "launch_coherent_field must come first")
+        shape = tuple(self.shape)
+        cf = CoherentField(re=np.empty(shape, np.float32), im=np.empty(shape, np.float32), total=np.empty(shape, np.float32))
+        L.check(self._lib.d2d_get_coherent_field(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in cf)))
+        return cf
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

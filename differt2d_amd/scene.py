@@ -1091,6 +1091,66 @@ class Scene(Plottable):
         return self._grid_strongest(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, k, path_cls, min_order, max_order,
                                     order, filter_objects, kwargs)
 
+    def _grid_field(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelength, amplitude, path_cls, min_order, max_order,
+                    order, filter_objects, kwargs):
+        """Shared driver of the two coherent-field sweeps: one launch of the coherent-field build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the coherent field comes from a fused sweep (a function "
+                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+                                       "(Context.valid_paths: every valid path of every cell, with its length) and add fun's "
+                                       "phasors on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the coherent field covers ImagePath only, not path_cls={path_cls.__name__}")
+        with np.errstate(divide="ignore"):
+            inv = F(1) / F(wavelength)  # fp32: one division (an infinite wavelength gives 0: every phase is 0)
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.coherent_field(params, pt.xy, inv, amplitude)
+
+        return results()
+
+    def coherent_field_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelength: float, amplitude: str = "sqrt",
+        path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The coherent field of every cell at one ``wavelength``: for every transmitter, the sum over the candidates of
+        ``a * exp(-2j pi r / wavelength)`` at the receiver ``(X[i, j], Y[i, j])``, where ``r`` is the path's length and ``a`` the
+        amplitude of its contribution ``t = valid * fun`` -- ``sign(t) * sqrt(|t|)`` with ``amplitude="sqrt"`` (``fun`` is a
+        power), ``t`` itself with ``amplitude="linear"``.  Where :meth:`accumulate_on_receivers_grid_over_paths` adds powers, this
+        adds phasors: paths interfere.  Yields ``(tx name, CoherentField(re, im, total))``
+        (:class:`differt2d_amd.engine.CoherentField`: fp32 ``[m, n]`` each; ``total`` is the incoherent sum, the fused map bit for
+        bit); one fused kernel launch per transmitter (include/d2d.h: d2d_coherent_field_launch holds the exact definition, the
+        phasor's included).  :func:`differt2d_amd.utils.field_power` and :func:`differt2d_amd.utils.fading_gain` give the power of
+        the field and its gain over the incoherent sum.
+
+        The library takes ``float32(1) / float32(wavelength)``; the phase resolves ``ulp(r / wavelength)`` turns, so paths of
+        more than ``2**24`` wavelengths all get phase 0.  ``fun`` must be natively fused (:mod:`differt2d_amd.utils`), the path
+        class ``ImagePath``, the validity hard (``approx=False``) or ``hard_sigmoid``; anything else raises
+        :class:`D2DUnsupported`.  For another callable the sparse valid-path records (:meth:`Context.valid_paths`) hold every
+        valid path and its length for a sum on the host."""
+        return self._grid_field(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, wavelength, amplitude, path_cls,
+                                min_order, max_order, order, filter_objects, kwargs)
+
+    def coherent_field_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelength: float, amplitude: str = "sqrt",
+        path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`coherent_field_on_receivers_grid`: one result per receiver, the transmitter sits at
+        ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_field(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelength, amplitude, path_cls,
+                                min_order, max_order, order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

@@ -107,6 +107,25 @@ def strongest_share(sp):
         return np.where(total == 0.0, np.nan, kept / total)
 
 
+def field_power(cf):
+    """The power of a coherent field, ``re**2 + im**2`` per cell, for a ``CoherentField``
+    (``Scene.coherent_field_on_receivers_grid``, ``Context.coherent_field``) or any object with ``re`` and ``im``.  On the host, in
+    float64.  With ``amplitude="sqrt"`` it is a power in the units of the fused function, and equals ``|total|`` where a cell has
+    one path."""
+    re = np.asarray(cf.re, dtype=np.float64)
+    im = np.asarray(cf.im, dtype=np.float64)
+    return re * re + im * im
+
+
+def fading_gain(cf):
+    """The gain of the coherent sum over the incoherent one, ``field_power(cf) / total`` per cell: 1 where a cell has one path,
+    above 1 where its paths add in phase, towards 0 where they cancel (small-scale fading).  On the host, in float64; NaN where
+    ``total == 0``."""
+    total = np.asarray(cf.total, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(total == 0.0, np.nan, field_power(cf) / total)
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

@@ -26,9 +26,9 @@ extern "C" {
 #endif
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
-#define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile and d2d_strongest_paths_launch /
-                              d2d_get_strongest_paths are additive: no struct, enum or existing entry point changed with them,
-                              so the version did not) */
+#define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile, d2d_strongest_paths_launch /
+                              d2d_get_strongest_paths and d2d_coherent_field_launch / d2d_get_coherent_field are additive: no
+                              struct, enum or existing entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -409,6 +409,10 @@ int d2d_selftest_div(d2d_ctx* ctx, const float* x, const float* y, int64_t n, fl
  * d2d_kernels.hpp expf_libm) on x[n] -> y[n]; must equal the host C library's expf bit for bit. */
 int d2d_selftest_expf(d2d_ctx* ctx, const float* x, int64_t n, float* y);
 
+/* Diagnostic: the coherent field's phasor (differt2d_amd/csrc/d2d_phasor.hpp) on the device, f[n] (turns, in [0, 1)) -> c[n] =
+ * cos(2 pi f), s[n] = sin(2 pi f); must equal the header's host build bit for bit. */
+int d2d_selftest_phasor(d2d_ctx* ctx, const float* f, int64_t n, float* c, float* s);
+
 /* Synchronises and copies the resident value map to out[m*n]. */
 int d2d_get_map(d2d_ctx* ctx, float* out);
 
@@ -544,6 +548,55 @@ int d2d_strongest_paths_launch(d2d_ctx* ctx, const d2d_params* params, const flo
  * D2D_ERR_STATE before a launch, after a launch that was refused, and after a d2d_set_grid of another grid (the result goes with
  * the grid). */
 int d2d_get_strongest_paths(d2d_ctx* ctx, float* power, float* length, int32_t* cand, int32_t* order, float* total, int32_t* count);
+
+/* ---- coherent field: the per-cell sum of complex amplitudes at one wavelength (no reference counterpart: every grid product
+ *      of the reference adds powers; interference fringes, small-scale fading and coherent coverage follow from re and im) ---- */
+
+#define D2D_FIELD_AMP_SQRT 0   /* the fused function is a power: its amplitude is the square root, its sign a pi flip */
+#define D2D_FIELD_AMP_LINEAR 1 /* the fused function is the amplitude itself */
+/* Launches the coherent-field build of the culled forward sweep for the fixed end point `fixed` on the ctx stream
+ * (asynchronous), for the current scene, candidate mask and grid.  `params` as for d2d_power_map_launch (params->grid_role says
+ * which end the cells are).  inv_wavelength: fp32, finite and >= 0, in turns per unit length (1 / lambda); amplitude:
+ * D2D_FIELD_AMP_SQRT or D2D_FIELD_AMP_LINEAR.  Definition, per cell:
+ *
+ *     re = im = total = +0.0f
+ *     for candidates in the sweep's enumeration order:
+ *         t = valid * fun            // exactly the fused sweep's contribution (nan_to_num rules included)
+ *         r = path_length(points)    // the fp32 value the path function is evaluated with (what the profile bins by)
+ *         total = total + t          // fp32: hence the fused map bit for bit
+ *         if (t == 0) continue       // exact zeros of either sign add no phasor (culled candidates are such zeros)
+ *         a = amplitude == SQRT ? copysignf(sqrtf(fabsf(t)), t) : t       // IEEE sqrtf
+ *         u = r * inv_wavelength     // fp32, turns
+ *         f = u - floorf(u)          // exact; in [0, 1) for u >= 0; a NaN or infinite r gives NaN
+ *         (c, s) = phasor(f)         // cos(2 pi f), sin(2 pi f) as d2d::phasor of differt2d_amd/csrc/d2d_phasor.hpp computes
+ *                                    // them: fp32 multiplies, adds and compares, within 2 * 2^-24 of the true values
+ *         re = re + a * c ;  im = im - a * s                              // e^(-j 2 pi r / lambda); fp32, no contraction
+ *
+ * Outputs: re, im and total, each fp32 [m][n].
+ *
+ *   - SQRT treats the fused function as a power.  Its sign becomes a pi flip of the amplitude, which is what a negative
+ *     coefficient of D2D_FUN_RECEIVED_POWER_PER_OBJECT means here.  re^2 + im^2 is then a power again, and equals |t| where a
+ *     cell has one path.
+ *   - LINEAR takes the fused function as the amplitude itself.
+ *   - With inv_wavelength == 0 and LINEAR, re equals the fused map bit for bit and im is +0.0 wherever total is finite.
+ *   - The phase resolution is ulp(r / lambda) turns: 2 pi * 7.6e-6 rad at 64 wavelengths of path.  At r / lambda >= 2^24 every
+ *     phase is 0.  This is documented, not refused.
+ *
+ * One pass of one kernel (one wave per 8 x 8 patch, three registers per lane, every lane the only writer of its cell and writing
+ * all of it: no atomics, no zeroing, the same bits run to run).  The resident value / gradient maps, the work history, the
+ * schedule of the fused sweeps, the records of d2d_valid_paths, the profile and the strongest paths are not touched.  Every fused
+ * function but D2D_FUN_CUSTOM; D2D_FUN_RECEIVED_POWER_PER_OBJECT with the coefficients of d2d_set_reflection_coefs, D2D_ERR_STATE
+ * without them.
+ * D2D_ERR_INVALID: inv_wavelength negative, NaN or infinite; an unknown amplitude.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): sigmoid validity, MinPath / FermatPath, D2D_FUN_CUSTOM, D2D_OUT_ADD, a TX
+ * grid whose sweep would not be culled (d2d_params.grid_role; not counted by d2d_debug_txg_fallbacks), more than 4 095 objects,
+ * or outputs (12 bytes per cell) above half of the free device memory -- all decided before anything is enqueued. */
+int d2d_coherent_field_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, float inv_wavelength,
+                              int32_t amplitude);
+/* Synchronises and copies the result of the last d2d_coherent_field_launch to the arrays that are not NULL ([m][n] each).
+ * D2D_ERR_STATE before a launch, after a launch that was refused, and after a d2d_set_grid of another grid (the result goes with
+ * the grid). */
+int d2d_get_coherent_field(d2d_ctx* ctx, float* re, float* im, float* total);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
