@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("D2D_LIB") or os.path.join(CSRC, "libd2d.so")
 D2D_MAX_ORDER = 4
 D2D_TOP_MAX = 8
 D2D_FIELD_AMP_SQRT, D2D_FIELD_AMP_LINEAR = 0, 1  # d2d_coherent_field_launch amplitude modes
+D2D_FREQ_MAX = 1024  # most wavelengths of one d2d_frequency_response_launch
 D2D_NUM_STATS = 16
 D2D_COMM_ID_BYTES = 128
 D2D_OPT_ADAM, D2D_OPT_SGD, D2D_OPT_SGD_MOMENTUM = 0, 1, 2  # d2d_set_optimizer kinds
@@ -143,6 +144,8 @@ SYMBOLS = [
     ("d2d_get_strongest_paths", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_coherent_field_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_float, C.c_int32]),
     ("d2d_get_coherent_field", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("d2d_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32]),
+    ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),

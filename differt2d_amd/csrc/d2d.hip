@@ -188,6 +188,14 @@ struct d2d_ctx {
         d_field_re.release(); d_field_im.release(); d_field_total.release();
         have_field = false;
     }
+    // frequency response (d2d_frequency_response_launch): nf planes of re and im and the incoherent total of every cell, kept until
+    // the next launch, dropped with the grid
+    DevBuf<float> d_freq_re, d_freq_im, d_freq_total;  // [nf][m][n], [nf][m][n], [m][n]
+    int32_t freq_nf = 0;                               // planes of the last accepted launch; 0: no result
+    void drop_freq() {
+        d_freq_re.release(); d_freq_im.release(); d_freq_total.release();
+        freq_nf = 0;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -888,6 +896,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->drop_profile();  // ... and the profile's
         c->drop_top();      // ... and the strongest paths'
         c->drop_field();    // ... and the coherent field's
+        c->drop_freq();     // ... and the frequency response's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -2207,7 +2216,7 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     return D2D_OK;
 }
 
-// What the fused sinks (d2d_power_profile_launch, d2d_strongest_paths_launch, d2d_coherent_field_launch: `who`) refuse of the caller's parameters before
+// What the fused sinks (d2d_power_profile_launch, d2d_strongest_paths_launch, d2d_coherent_field_launch, d2d_frequency_response_launch: `who`) refuse of the caller's parameters before
 // prep_sink_sweep's share; `custom_route` and `add_why` end the two messages that say what to do instead.
 static int check_fused_sink(d2d_ctx* c, const d2d_params* p, const char* who, const char* custom_route, const char* add_why) {
     if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT)
@@ -2360,9 +2369,81 @@ static int coherent_field_launch(d2d_ctx* c, const d2d_params* p_in, const float
     return D2D_OK;
 }
 
+// Frequency-response launch of the culled forward sweep with the caller's path function: ONE preparation, then one pass of the sink
+// kernel per chunk of FREQ_CHUNK wavelengths over the same SweepArgs (as d2d_valid_paths launches its two passes: the sink kernel
+// writes nothing that a later pass reads), every lane writing its cell's planes of the chunk and, in the first pass, the total.
+// Asynchronous.  Every check comes before anything is enqueued.
+static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK, "d2d_host.hpp and d2d_kernels.hpp disagree");
+static int frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude) {
+    if (!c || !fixed || !inv_wavelength) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_frequency_response_launch");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_frequency_response_launch");
+    c->freq_nf = 0;  // whatever this launch turns out to be, the previous result is gone
+    if ((rc = check_fused_sink(c, p_in, "d2d_frequency_response_launch",
+                               "a host function's response: add the phasors of the records of d2d_valid_paths", "the response is always overwritten")))
+        return rc;
+    {
+        std::string err;
+        if ((rc = d2d_host::freq_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "d2d_frequency_response_launch: %s", err.c_str());
+    }
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_freq_re.n + c->d_freq_im.n + c->d_freq_total.n) * sizeof(float);
+        if (!d2d_host::freq_fits(cells, nf, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_frequency_response_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
+                        cells, d2d_host::freq_bytes_per_cell(nf), mem_free);
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_frequency_response_launch", lds))) return rc;
+    const size_t planes = (size_t)nf * cells;
+    if ((rc = c->d_freq_re.ensure(planes)) || (rc = c->d_freq_im.ensure(planes)) || (rc = c->d_freq_total.ensure(cells))) return rc;
+    if (s.tiles > 0)
+        for (int32_t i = 0; i < d2d_host::freq_chunks(nf); ++i) {
+            const d2d_host::FreqChunk ch = d2d_host::freq_chunk(nf, i);
+            d2d::FreqArgs f;
+            f.re = c->d_freq_re.p + (size_t)ch.first * cells;
+            f.im = c->d_freq_im.p + (size_t)ch.first * cells;
+            f.total = ch.with_total ? c->d_freq_total.p : nullptr;
+            f.cells = (long)cells;
+            for (int32_t j = 0; j < d2d::FREQ_CHUNK; ++j) f.inv[j] = j < ch.count ? inv_wavelength[ch.first + j] : 0.0f;
+            f.nf = ch.count;
+            f.amplitude = amplitude;
+            HIP_TRY(d2d::launch_sink<d2d::FreqSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, f));
+        }
+    c->freq_nf = nf;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude) {
+    return frequency_response_launch(c, p, fixed, inv_wavelength, nf, amplitude);
+}
+
+int d2d_get_frequency_response(d2d_ctx* c, float* re, float* im, float* total) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (c->freq_nf < 1 || !c->d_freq_re.p) return fail(D2D_ERR_STATE, "d2d_frequency_response_launch must come first (its result goes with the grid)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_freq_re.p, bytes * (size_t)c->freq_nf, hipMemcpyDeviceToHost, c->stream));
+    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_freq_im.p, bytes * (size_t)c->freq_nf, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_freq_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_coherent_field_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude) {
     return coherent_field_launch(c, p, fixed, inv_wavelength, amplitude);

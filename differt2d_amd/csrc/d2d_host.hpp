@@ -270,6 +270,46 @@ inline bool field_fits(size_t cells, size_t mem_free, size_t held_bytes) {
     return cells <= budget / FIELD_BYTES_PER_CELL;
 }
 
+// ---- parameters, outputs and launch plan of the frequency response (d2d_frequency_response_launch, d2d::FreqSink) ---
+// D2D_ERR_INVALID: nf outside 1 .. D2D_FREQ_MAX, an entry that is negative, NaN or infinite (the message names its index; 0 is
+// allowed), an amplitude mode that is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.  The list is not read unless nf is in range.
+inline int freq_params(const float* inv_wavelength, int32_t nf, int32_t amplitude, std::string& err) {
+    if (nf < 1 || nf > D2D_FREQ_MAX)
+        return err = "the frequency response needs nf in 1 .. " + std::to_string(D2D_FREQ_MAX) + ", got " + std::to_string(nf), D2D_ERR_INVALID;
+    for (int32_t j = 0; j < nf; ++j)
+        if (!std::isfinite(inv_wavelength[j]) || inv_wavelength[j] < 0.0f)
+            return err = "the frequency response needs every inv_wavelength finite and >= 0, got " + std::to_string(inv_wavelength[j]) +
+                         " at index " + std::to_string(j),
+                   D2D_ERR_INVALID;
+    if (amplitude != D2D_FIELD_AMP_SQRT && amplitude != D2D_FIELD_AMP_LINEAR)
+        return err = "the frequency response's amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
+               D2D_ERR_INVALID;
+    return D2D_OK;
+}
+// Per cell: nf planes of re and im and one total, 4 bytes each.  Refused like the coherent field: outputs above half of the device
+// memory that is free, counting what the buffers hold already as free (tests/native/frequency_response_host.cpp).  No product is
+// formed: cells is held against a quotient.
+inline size_t freq_bytes_per_cell(int32_t nf) { return 8 * (size_t)nf + 4; }
+inline bool freq_fits(size_t cells, int32_t nf, size_t mem_free, size_t held_bytes) {
+    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
+    return cells <= budget / freq_bytes_per_cell(nf);
+}
+// The launches of one call: ceil(nf / FREQ_CHUNK) passes of the sink kernel over the same prepared sweep.  Launch i takes the entries
+// first .. first + count - 1 of the list, stores their planes from plane `first` on, and the first launch alone stores total.
+constexpr int32_t FREQ_CHUNK = 8;  // = d2d::FREQ_CHUNK (d2d_kernels.hpp)
+struct FreqChunk {
+    int32_t first = 0, count = 0;
+    bool with_total = false;
+};
+inline int32_t freq_chunks(int32_t nf) { return (nf + FREQ_CHUNK - 1) / FREQ_CHUNK; }
+inline FreqChunk freq_chunk(int32_t nf, int32_t i) {
+    FreqChunk ch;
+    ch.first = i * FREQ_CHUNK;
+    ch.count = std::min<int32_t>(FREQ_CHUNK, nf - ch.first);
+    ch.with_total = i == 0;
+    return ch;
+}
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

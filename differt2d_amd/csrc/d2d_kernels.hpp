@@ -1936,6 +1936,79 @@ struct FieldSink {
     }
 };
 
+// FreqSink (d2d_frequency_response_launch): the coherent sum of every cell at up to FREQ_CHUNK wavelengths of one sweep -- plane j
+// is, bit for bit, FieldSink's (re, im) at inv[j] (include/d2d.h holds the definition).  Per lane, in registers: re[C], im[C] and the
+// running fp32 sum of every contribution.  Per contribution that is not exactly zero, a is formed once and then, for every j < nf,
+//     u = r * inv[j] ;  f = u - floorf(u) ;  (c, s) = phasor(f) ;  re[j] = re[j] + a * c ;  im[j] = im[j] - a * s
+// in fp32 without contraction.  j is a compile-time index (static_for) behind the wave-uniform guard j < nf: a register array indexed
+// at run time goes to scratch.  inv[] and nf come by value in the kernel argument: scalar loads.  All of it is
+// skipped for a candidate that no lane of the wave has a non-zero contribution from, the common case.  end() stores planes 0 .. nf-1
+// at re / im + j * cells (the host hands every launch the planes of its chunk) and total where its pointer is not null (the first
+// chunk's launch): every lane is the only writer of its cell, no atomics, no zeroing pass; lanes outside the grid (cell < 0) never
+// write.
+constexpr int FREQ_CHUNK = 8;  // wavelengths per launch: internal, not in the ABI (d2d_host::FREQ_CHUNK is the host's copy)
+struct FreqArgs {
+    float* re;              // [nf][cells]: this chunk's planes
+    float* im;              // [nf][cells]
+    float* total;           // [cells] or null
+    long cells;             // m * n
+    float inv[FREQ_CHUNK];  // turns per unit length, finite and >= 0; entries at and past nf are not read
+    int nf;                 // 1 .. FREQ_CHUNK
+    int amplitude;          // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+};
+struct FreqSink {
+    using Args = FreqArgs;
+    static constexpr bool WANTS_R = true;
+    float re[FREQ_CHUNK], im[FREQ_CHUNK], total;
+    float inv[FREQ_CHUNK];
+    int nf;
+    bool root;
+    int cell;
+    __device__ __forceinline__ void begin(const FreqArgs& x, long /*tile*/, int lane_cell) {
+        static_for<0, FREQ_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            re[J] = im[J] = 0.0f;
+            inv[J] = x.inv[J];
+        });
+        total = 0.0f;
+        nf = x.nf;
+        root = x.amplitude == D2D_FIELD_AMP_SQRT;
+        cell = lane_cell;
+    }
+    __device__ __forceinline__ void put(float t, unsigned long long /*code*/, int /*k*/, float r) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        if (p) {
+            const float a = root ? copysignf(sqrtf(fabsf(t)), t) : t;
+            static_for<0, FREQ_CHUNK>([&](auto JJ) {
+                constexpr int J = decltype(JJ)::value;
+                if (J < nf) {
+                    const float u = r * inv[J];
+                    const float f = u - floorf(u);
+                    float c, s;
+                    phasor(f, c, s);
+                    const float ac = a * c, as = a * s;
+                    re[J] = re[J] + ac;
+                    im[J] = im[J] - as;
+                }
+            });
+        }
+    }
+    __device__ __forceinline__ void end(const FreqArgs& x, long, int) const {
+        if (cell < 0) return;
+        if (x.total != nullptr) x.total[cell] = total;
+        static_for<0, FREQ_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            if (J < x.nf) {
+                const size_t at = (size_t)J * (size_t)x.cells + (size_t)cell;
+                x.re[at] = re[J];
+                x.im[at] = im[J];
+            }
+        });
+    }
+};
+
 // Survivors of a region's culling, in candidate order (region_list_kernel / region_refine_kernel): wave-uniform state
 // of the list being written.
 struct EmitSink {

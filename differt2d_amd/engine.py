@@ -86,6 +86,14 @@ class CoherentField(NamedTuple):
     total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
 
 
+class FrequencyResponse(NamedTuple):
+    """Result of :meth:`Context.frequency_response` (include/d2d.h: d2d_frequency_response_launch)."""
+
+    re: np.ndarray     # fp32 [nf, m, n]: real part of the sum of a * e^(-j 2 pi r * inv_wavelength[j])
+    im: np.ndarray     # fp32 [nf, m, n]: imaginary part
+    total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
+
+
 FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
 
 
@@ -112,6 +120,7 @@ class Context:
         self._grid_serial = 0
         self._top_k = 0  # slots per cell of the last launch_strongest_paths that was accepted
         self._field = False  # a launch_coherent_field was accepted
+        self._freq_nf = 0  # planes of the last launch_frequency_response that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -611,6 +620,47 @@ class Context:
         cf = CoherentField(re=np.empty(shape, np.float32), im=np.empty(shape, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_coherent_field(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in cf)))
         return cf
+
+    def frequency_response(self, params: L.Params, fixed, inv_wavelengths, amplitude="sqrt") -> "FrequencyResponse":
+        """The channel frequency response of every cell of the resident grid: the coherent sum of :meth:`coherent_field` at every
+        entry of ``inv_wavelengths`` (``1 / lambda_j`` in turns per unit length: fp32, finite and ``>= 0``, 1 to
+        ``D2D_FREQ_MAX`` = 1024 entries) from ONE preparation of the culled sweep and one kernel pass per 8 entries, where a
+        :meth:`coherent_field` call per entry repeats the whole sweep (include/d2d.h: d2d_frequency_response_launch holds the
+        definition).  Plane ``j`` equals ``coherent_field(params, fixed, inv_wavelengths[j], amplitude)`` bit for bit, whatever
+        else the list holds.  ``amplitude``, ``params`` and ``fixed`` as for :meth:`coherent_field`.  The resident value map, the
+        records of :meth:`valid_paths`, the profile, the strongest paths and the coherent field are not touched.
+
+        Returns a :class:`FrequencyResponse`: ``re`` and ``im``, fp32 ``[nf, m, n]``, and ``total`` (the fused map, bit for bit),
+        fp32 ``[m, n]``.  :func:`differt2d_amd.utils.frequency_response`, :func:`differt2d_amd.utils.wideband_power` and
+        :func:`differt2d_amd.utils.impulse_response` turn it into complex ``H``, the frequency-averaged power and the taps of the
+        coherent impulse response."""
+        self.launch_frequency_response(params, fixed, inv_wavelengths, amplitude)
+        return self.get_frequency_response()
+
+    def launch_frequency_response(self, params: L.Params, fixed, inv_wavelengths, amplitude="sqrt"):
+        """The launch of :meth:`frequency_response` alone (asynchronous, like :meth:`launch`; the list is copied by the call)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        self._freq_nf = 0
+        if isinstance(amplitude, str):
+            if amplitude not in FIELD_AMPLITUDES:
+                raise L.D2DError(-1, f"frequency_response: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
+            amplitude = FIELD_AMPLITUDES[amplitude]
+        keep = inv if inv.size else np.zeros(1, np.float32)  # (an empty list still hands the library a pointer: it refuses nf = 0)
+        L.check(self._lib.d2d_frequency_response_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
+                                                        int(amplitude)))
+        self._freq_nf = int(inv.size)
+
+    def get_frequency_response(self) -> "FrequencyResponse":
+        """Synchronises and returns the result of the last :meth:`launch_frequency_response`."""
+        if not self._freq_nf:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_frequency_response(self._ctx, None, None, None))
+            raise L.D2DError(-5, "launch_frequency_response must come first")
+        shape = tuple(self.shape)
+        planes = (self._freq_nf,) + shape
+        fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
+        L.check(self._lib.d2d_get_frequency_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
+        return fr
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

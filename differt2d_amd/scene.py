@@ -1151,6 +1151,70 @@ class Scene(Plottable):
         return self._grid_field(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelength, amplitude, path_cls,
                                 min_order, max_order, order, filter_objects, kwargs)
 
+    def _grid_response(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelengths, inv_wavelengths, amplitude, path_cls,
+                       min_order, max_order, order, filter_objects, kwargs):
+        """Shared driver of the two frequency-response sweeps: one launch of the frequency-response build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        if (wavelengths is None) == (inv_wavelengths is None):
+            raise ValueError("the frequency response takes exactly one of wavelengths= and inv_wavelengths=")
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the frequency response comes from a fused sweep (a "
+                                       "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+                                       "records (Context.valid_paths: every valid path of every cell, with its length) and add "
+                                       "fun's phasors on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the frequency response covers ImagePath only, not path_cls={path_cls.__name__}")
+        if wavelengths is not None:
+            with np.errstate(divide="ignore"):
+                inv = F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the coherent field does
+        else:
+            inv = np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.frequency_response(params, pt.xy, inv, amplitude)
+
+        return results()
+
+    def frequency_response_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The channel frequency response of every cell: the coherent field of :meth:`coherent_field_on_receivers_grid` at many
+        wavelengths from one sweep per 8 of them instead of one sweep each.  Exactly one of ``wavelengths`` (each becomes
+        ``float32(1) / float32(w)``, as the coherent field does) and ``inv_wavelengths`` (``1 / lambda`` in turns per unit length,
+        passed as fp32 unchanged: what a uniform frequency grid needs) must be given: 1 to 1024 entries, each inverse finite and
+        ``>= 0``.  Yields ``(tx name, FrequencyResponse(re, im, total))`` (:class:`differt2d_amd.engine.FrequencyResponse`: ``re``
+        and ``im`` fp32 ``[nf, m, n]``, ``total`` fp32 ``[m, n]``, the fused map bit for bit).  Plane ``j`` equals the coherent
+        field at entry ``j`` bit for bit, whatever else the list holds (include/d2d.h: d2d_frequency_response_launch).
+        :func:`differt2d_amd.utils.frequency_response`, :func:`differt2d_amd.utils.wideband_power` and
+        :func:`differt2d_amd.utils.impulse_response` give complex ``H``, the frequency-averaged power and the taps of the coherent
+        impulse response.
+
+        ``fun``, ``amplitude``, the path class and the validity as for :meth:`coherent_field_on_receivers_grid`; anything else raises
+        :class:`D2DUnsupported`.  For another callable the sparse valid-path records (:meth:`Context.valid_paths`) hold every
+        valid path and its length for a sum on the host."""
+        return self._grid_response(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                   amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def frequency_response_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`frequency_response_on_receivers_grid`: one result per receiver, the transmitter sits at
+        ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_response(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                   amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

@@ -126,6 +126,42 @@ def fading_gain(cf):
         return np.where(total == 0.0, np.nan, field_power(cf) / total)
 
 
+def frequency_response(fr):
+    """The complex channel frequency response ``H = re + 1j * im``, complex64 ``[nf, m, n]``, of a ``FrequencyResponse``
+    (``Scene.frequency_response_on_receivers_grid``, ``Context.frequency_response``) or any object with ``re`` and ``im``."""
+    re = np.asarray(fr.re, dtype=np.float32)
+    im = np.asarray(fr.im, dtype=np.float32)
+    h = np.empty(re.shape, np.complex64)
+    h.real = re
+    h.imag = im
+    return h
+
+
+def wideband_power(fr):
+    """The frequency-averaged coverage of a ``FrequencyResponse``: the mean over the wavelengths ``j`` of ``re[j]**2 + im[j]**2`` per
+    cell, ``[m, n]``.  On the host, in float64.  The cross terms of two paths average out once the band spans many turns of their
+    length difference, so with ``amplitude="sqrt"`` it tends to ``total`` as the band widens."""
+    re = np.asarray(fr.re, dtype=np.float64)
+    im = np.asarray(fr.im, dtype=np.float64)
+    return (re * re + im * im).mean(axis=0)
+
+
+def impulse_response(fr, inv_wavelength_step):
+    """The coherent impulse response of a ``FrequencyResponse`` taken on a UNIFORM grid ``inv_wavelength[j] = inv_0 + j * step``:
+    ``numpy.fft.ifft`` of ``H`` along the frequency axis.  Returns ``(taps, spacing)``: ``taps`` complex ``[nf, m, n]`` and the tap
+    spacing in path length, ``1 / (nf * step)``.  A path of length ``r`` (``H[j] = a * exp(-2j pi r * inv_wavelength[j])``) peaks at
+    tap ``round(r * nf * step) mod nf``: path lengths alias with period ``1 / step``.  ``inv_wavelength_step`` is the caller's grid
+    spacing (it is not recovered from the result); ``nf < 2`` is refused."""
+    h = frequency_response(fr)
+    nf = h.shape[0]
+    if nf < 2:
+        raise ValueError(f"impulse_response needs at least 2 frequencies, got nf={nf}")
+    step = float(inv_wavelength_step)
+    if not (np.isfinite(step) and step > 0.0):
+        raise ValueError(f"impulse_response needs a finite inv_wavelength_step > 0, got {inv_wavelength_step!r}")
+    return np.fft.ifft(h, axis=0), 1.0 / (nf * step)
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

@@ -27,8 +27,9 @@ extern "C" {
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
 #define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile, d2d_strongest_paths_launch /
-                              d2d_get_strongest_paths and d2d_coherent_field_launch / d2d_get_coherent_field are additive: no
-                              struct, enum or existing entry point changed with them, so the version did not) */
+                              d2d_get_strongest_paths, d2d_coherent_field_launch / d2d_get_coherent_field and
+                              d2d_frequency_response_launch / d2d_get_frequency_response are additive: no struct, enum or existing
+                              entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -597,6 +598,44 @@ int d2d_coherent_field_launch(d2d_ctx* ctx, const d2d_params* params, const floa
  * D2D_ERR_STATE before a launch, after a launch that was refused, and after a d2d_set_grid of another grid (the result goes with
  * the grid). */
 int d2d_get_coherent_field(d2d_ctx* ctx, float* re, float* im, float* total);
+
+/* ---- channel frequency response: the coherent field at many wavelengths per sweep (no reference counterpart: H(f_j) per cell;
+ *      frequency-selective fading, subcarrier gains, frequency-averaged coverage and, through an inverse FFT, a coherent impulse
+ *      response follow from it) ---- */
+
+#define D2D_FREQ_MAX 1024 /* most wavelengths of one d2d_frequency_response_launch (128 kernel launches) */
+/* Launches the frequency-response build of the culled forward sweep for the fixed end point `fixed` on the ctx stream
+ * (asynchronous), for the current scene, candidate mask and grid.  Definition:
+ *
+ * `params`, `fixed`, the grid role and `amplitude` are as for `d2d_coherent_field_launch`. The wavelengths are
+ * `inv_wavelength[nf]`: fp32, each finite and `>= 0`, with `nf` in `1..D2D_FREQ_MAX`. Per cell and for every `j < nf`, the pair
+ * `(re[j], im[j])` is the `(re, im)` of the coherent-field definition evaluated with `inv_wavelength[j]`. It uses the same loop,
+ * the same skip of exact zeros, the same `a`, `u = r * inv_wavelength[j]`, `f = u − floorf(u)` and `phasor(f)`, and the same fp32
+ * adds without contraction. `total` is the coherent field's `total`, which is the fused map bit for bit.
+ *
+ * The outputs are `re` and `im`, fp32 `[nf][m][n]`, and `total`, fp32 `[m][n]`.
+ *
+ *   - Planes do not depend on the order, the number or the duplication of the other entries of the list.
+ *   - An entry `0` with `LINEAR` gives the fused map in `re[j]` and `+0.0` in `im[j]`.
+ *   - Plane j is therefore, bit for bit, what d2d_coherent_field_launch gives for inv_wavelength[j]: one call of this function
+ *     replaces nf of those, and the culled sweep (occlusion masks, culling, every candidate's evaluation, the path length) runs
+ *     once per 8 entries instead of once per entry.
+ *
+ * One preparation and ceil(nf / 8) passes of one kernel over it (one wave per 8 x 8 patch; per lane up to 8 (re, im) pairs and the
+ * total in registers; every lane the only writer of its cell and writing all of it: no atomics, no zeroing, the same bits run to
+ * run; the 8 is internal).  The list is copied during the call.  The resident value / gradient maps, the work history, the
+ * schedule of the fused sweeps, the records of d2d_valid_paths, the profile, the strongest paths and the coherent field of
+ * d2d_coherent_field_launch are not touched.  Fused functions as for d2d_coherent_field_launch.
+ * D2D_ERR_INVALID: nf outside 1 .. D2D_FREQ_MAX; an entry that is negative, NaN or infinite (the message names its index); an
+ * unknown amplitude.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): what d2d_coherent_field_launch refuses, with outputs of 8 * nf + 4 bytes per
+ * cell held against half of the free device memory -- all decided before anything is enqueued.  A refused launch leaves no result. */
+int d2d_frequency_response_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                                  const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude);
+/* Synchronises and copies the result of the last d2d_frequency_response_launch to the arrays that are not NULL (re, im: [nf][m][n]
+ * with that launch's nf; total: [m][n]).  D2D_ERR_STATE before a launch, after a launch that was refused, and after a d2d_set_grid
+ * of another grid (the result goes with the grid). */
+int d2d_get_frequency_response(d2d_ctx* ctx, float* re, float* im, float* total);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one

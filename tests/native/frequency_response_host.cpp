@@ -1,0 +1,135 @@
+// The host's share of d2d_frequency_response_launch (d2d_host.hpp: freq_params, freq_fits and the chunk plan freq_chunks /
+// freq_chunk), compiled with plain g++ into a stand-alone program by tests/test_frequency_response_cpu.py, which also builds it with
+// -fsanitize=address,undefined and runs it.  The product compiles the very same header into libd2d.so with hipcc, where the launch
+// walks the plan: one pass of the sink kernel per chunk.  The list handed to freq_params is a heap array of exactly nf entries, so
+// that a read past the list is the sanitizer's to report.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../differt2d_amd/csrc/d2d_host.hpp"
+
+static int failures = 0;
+#define EXPECT(x)                                                     \
+    do {                                                              \
+        if (!(x)) {                                                   \
+            std::printf("line %d: %s does not hold\n", __LINE__, #x); \
+            ++failures;                                               \
+        }                                                             \
+    } while (0)
+
+// the status of (list, amplitude); a refusal always says why
+static int params(const std::vector<float>& inv, int amplitude, std::string* why = nullptr) {
+    std::string err;
+    const int rc = d2d_host::freq_params(inv.data(), (int32_t)inv.size(), amplitude, err);
+    if (why) *why = err;
+    return (rc == D2D_OK) == err.empty() ? rc : -1000;
+}
+
+static std::vector<float> grid(int nf) {
+    std::vector<float> inv((size_t)nf);
+    for (int j = 0; j < nf; ++j) inv[(size_t)j] = 20.0f * (1.0f + (float)j / 64.0f);
+    return inv;
+}
+
+int main() {
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    const int NFS[] = {1, 7, 8, 9, 16, 17, 1024};
+    static_assert(D2D_FREQ_MAX == 1024, "the issue's limit");
+    const int C = d2d_host::FREQ_CHUNK;
+    EXPECT(C >= 1 && C <= 8 && (D2D_FREQ_MAX + C - 1) / C <= 1024);
+
+    // freq_params: both limits of nf (the list is not read when nf is out of range: a null pointer must do) ...
+    {
+        std::string err;
+        EXPECT(d2d_host::freq_params(nullptr, 0, D2D_FIELD_AMP_SQRT, err) == D2D_ERR_INVALID && err.find("nf") != std::string::npos);
+        err.clear();
+        EXPECT(d2d_host::freq_params(nullptr, D2D_FREQ_MAX + 1, D2D_FIELD_AMP_SQRT, err) == D2D_ERR_INVALID && err.find("nf") != std::string::npos);
+        err.clear();
+        EXPECT(d2d_host::freq_params(nullptr, -1, D2D_FIELD_AMP_LINEAR, err) == D2D_ERR_INVALID && err.find("nf") != std::string::npos);
+        err.clear();
+        EXPECT(d2d_host::freq_params(nullptr, std::numeric_limits<int32_t>::min(), D2D_FIELD_AMP_LINEAR, err) == D2D_ERR_INVALID);
+        err.clear();
+        EXPECT(d2d_host::freq_params(nullptr, std::numeric_limits<int32_t>::max(), D2D_FIELD_AMP_LINEAR, err) == D2D_ERR_INVALID);
+    }
+    EXPECT(params(grid(1), D2D_FIELD_AMP_SQRT) == D2D_OK);
+    EXPECT(params(grid(D2D_FREQ_MAX), D2D_FIELD_AMP_LINEAR) == D2D_OK);
+    // ... what is accepted: zero of either sign, denormals, the largest finite value, duplicates, any order ...
+    EXPECT(params({0.0f, -0.0f, std::numeric_limits<float>::denorm_min(), std::numeric_limits<float>::max(), 20.0f, 20.0f, 3.0f}, D2D_FIELD_AMP_SQRT) == D2D_OK);
+    // ... every bad entry at every position of every list length, named by its index ...
+    const float bads[] = {-1.0f, -std::numeric_limits<float>::denorm_min(), nan, inf, -inf};
+    for (int nf : NFS)
+        for (int at = 0; at < nf; ++at)
+            for (float bad : bads) {
+                std::vector<float> inv = grid(nf);
+                inv[(size_t)at] = bad;
+                std::string why;
+                EXPECT(params(inv, D2D_FIELD_AMP_SQRT, &why) == D2D_ERR_INVALID);
+                EXPECT(why.find("inv_wavelength") != std::string::npos);
+                const std::string idx = "index " + std::to_string(at);
+                const size_t pos = why.find(idx);
+                EXPECT(pos != std::string::npos && pos + idx.size() == why.size());  // (index 1 is not index 17)
+            }
+    // ... the first bad entry is the one named, and a good list with an unknown amplitude is refused for the amplitude
+    {
+        std::vector<float> inv = grid(17);
+        inv[8] = nan;
+        inv[12] = -1.0f;
+        std::string why;
+        EXPECT(params(inv, 7, &why) == D2D_ERR_INVALID && why.find("index 8") != std::string::npos);
+        for (int amp : {2, -1, 7}) {
+            EXPECT(params(grid(9), amp, &why) == D2D_ERR_INVALID && why.find("amplitude") != std::string::npos);
+        }
+    }
+
+    // freq_fits: 8 nf + 4 bytes per cell against half of (free + held), at the boundary byte and one past it
+    for (int nf : NFS) {
+        const size_t per = d2d_host::freq_bytes_per_cell(nf);
+        EXPECT(per == 8 * (size_t)nf + 4);
+        const size_t frees[] = {0, (size_t)1 << 20, (size_t)3 << 30, (size_t)288 << 30}, helds[] = {0, (size_t)1 << 16, (size_t)5 << 30};
+        for (size_t mem_free : frees)
+            for (size_t held : helds) {
+                const size_t edge = (mem_free / 2 + held / 2) / per;
+                EXPECT(d2d_host::freq_fits(edge, nf, mem_free, held));
+                EXPECT(!d2d_host::freq_fits(edge + 1, nf, mem_free, held));
+            }
+        // the boundary byte: cells * per == budget fits, a budget one byte short does not (free counts half: two bytes of it)
+        const size_t cells = 1000003;
+        EXPECT(d2d_host::freq_fits(cells, nf, 2 * cells * per, 0));
+        EXPECT(!d2d_host::freq_fits(cells, nf, 2 * cells * per - 2, 0));
+        EXPECT(d2d_host::freq_fits(cells, nf, 0, 2 * cells * per));
+        EXPECT(!d2d_host::freq_fits(cells, nf, 0, 2 * cells * per - 2));
+        // sizes whose products or sums would wrap 64 bits: cells * per, and free + held
+        const size_t big = std::numeric_limits<size_t>::max();
+        EXPECT(!d2d_host::freq_fits(big, nf, (size_t)288 << 30, 0));
+        EXPECT(!d2d_host::freq_fits(big / per + 1, nf, (size_t)288 << 30, 0));
+        EXPECT(!d2d_host::freq_fits(((size_t)1 << 63) / 4, nf, big, big));  // 2^61 cells of at least 12 bytes: more than 2^64 - 2
+        EXPECT(d2d_host::freq_fits((big / 2 + big / 2) / per, nf, big, big));
+        EXPECT(!d2d_host::freq_fits((big / 2 + big / 2) / per + 1, nf, big, big));
+    }
+    EXPECT(d2d_host::freq_fits(1024 * 1024, 64, (size_t)200 << 30, 0));
+    EXPECT(!d2d_host::freq_fits((size_t)1 << 30, 1024, (size_t)288 << 30, 0));
+    EXPECT(d2d_host::freq_fits(0, 1, 0, 0));
+
+    // the chunk plan: the chunks tile 0 .. nf in order, each of 1 .. C entries, all but the last full, total in the first alone
+    for (int nf : NFS) {
+        const int32_t n = d2d_host::freq_chunks(nf);
+        EXPECT(n == (nf + C - 1) / C && n >= 1 && n <= 128 * (8 / C));
+        int32_t next = 0, with_total = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            const d2d_host::FreqChunk ch = d2d_host::freq_chunk(nf, i);
+            EXPECT(ch.first == next && ch.first == i * C);
+            EXPECT(ch.count >= 1 && ch.count <= C && (i == n - 1 || ch.count == C));
+            EXPECT(ch.with_total == (i == 0));
+            with_total += ch.with_total ? 1 : 0;
+            next = ch.first + ch.count;
+        }
+        EXPECT(next == nf && with_total == 1);
+        EXPECT(d2d_host::freq_chunk(nf, n - 1).count == (nf % C ? nf % C : C));
+    }
+    std::printf("frequency_response_host: %d failures (FREQ_CHUNK %d)\n", failures, C);
+    return failures ? 1 : 0;
+}
