@@ -196,6 +196,14 @@ struct d2d_ctx {
         d_freq_re.release(); d_freq_im.release(); d_freq_total.release();
         freq_nf = 0;
     }
+    // power-angle profile (d2d_power_angle_launch): nbins planes and the total of every cell, kept until the next accepted launch,
+    // dropped with the grid
+    DevBuf<float> d_angle, d_angle_total;  // [angle_nbins][m][n], [m][n]
+    int32_t angle_nbins = 0;               // bins of the last accepted launch; 0: no result
+    void drop_angle() {
+        d_angle.release(); d_angle_total.release();
+        angle_nbins = 0;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -896,6 +904,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->drop_profile();  // ... and the profile's
         c->drop_top();      // ... and the strongest paths'
         c->drop_field();    // ... and the coherent field's
+        c->drop_angle();    // ... and the power-angle profile's
         c->drop_freq();     // ... and the frequency response's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
@@ -2423,9 +2432,75 @@ static int frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, const f
     return D2D_OK;
 }
 
+// Power-angle launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed
+// planes, every lane storing its cell's total at the end.  Asynchronous.  Every check comes before anything is enqueued, and a
+// refused launch leaves the previous result as it was.
+static int power_angle_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int32_t end, float origin, int32_t nbins) {
+    if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_power_angle_launch");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_power_angle_launch");
+    if ((rc = check_fused_sink(c, p_in, "d2d_power_angle_launch", "a host function's profile: bin the paths that d2d_trace_paths gives for the records of d2d_valid_paths",
+                               "a profile is always overwritten")))
+        return rc;
+    {
+        std::string err;
+        if ((rc = d2d_host::angle_params(end, origin, nbins, err))) return fail(rc, "d2d_power_angle_launch: %s", err.c_str());
+    }
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_angle.n + c->d_angle_total.n) * sizeof(float);
+        if (!d2d_host::angle_fits(cells, nbins, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_power_angle_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
+                        cells, d2d_host::angle_bytes_per_cell(nbins), mem_free);
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_power_angle_launch", lds))) return rc;
+    c->angle_nbins = 0;  // from here on the buffers change
+    const size_t planes = (size_t)nbins * cells;
+    if ((rc = c->d_angle.ensure(planes)) || (rc = c->d_angle_total.ensure(cells))) return rc;
+    d2d::AngleArgs g;
+    g.out = c->d_angle.p;
+    g.total = c->d_angle_total.p;
+    g.cells = (long)cells;
+    g.origin = origin;
+    g.nbins = nbins;
+    g.end = end;
+    HIP_TRY(hipMemsetAsync(c->d_angle.p, 0, planes * sizeof(float), c->stream));
+    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::AngleSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
+    else HIP_TRY(hipMemsetAsync(c->d_angle_total.p, 0, cells * sizeof(float), c->stream));
+    c->angle_nbins = nbins;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_power_angle_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t end, float origin, int32_t nbins) {
+    return power_angle_launch(c, p, fixed, end, origin, nbins);
+}
+
+int d2d_get_power_angle(d2d_ctx* c, float* out, float* total) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (c->angle_nbins < 1 || !c->d_angle.p) return fail(D2D_ERR_STATE, "d2d_power_angle_launch must come first (its result goes with the grid)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    if (out) HIP_TRY(hipMemcpyAsync(out, c->d_angle.p, bytes * (size_t)c->angle_nbins, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_angle_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude) {
     return frequency_response_launch(c, p, fixed, inv_wavelength, nf, amplitude);
@@ -2657,6 +2732,21 @@ int d2d_selftest_phasor(d2d_ctx* c, const float* f, int64_t n, float* cs, float*
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(cs, dc.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(sn, ds.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_angle(d2d_ctx* c, const float* dx, const float* dy, int64_t n, float* out) {
+    if (!c || !dx || !dy || !out || n <= 0) return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> ddx, ddy, dout;
+    if ((rc = ddx.ensure((size_t)n)) || (rc = ddy.ensure((size_t)n)) || (rc = dout.ensure((size_t)n))) return rc;
+    HIP_TRY(hipMemcpy(ddx.p, dx, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ddy.p, dy, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_angle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, ddx.p, ddy.p, dout.p, (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }
 

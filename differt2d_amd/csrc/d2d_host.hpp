@@ -310,6 +310,27 @@ inline FreqChunk freq_chunk(int32_t nf, int32_t i) {
     return ch;
 }
 
+// ---- parameters and outputs of the power-angle profile (d2d_power_angle_launch, d2d::AngleSink) ---------------------
+// D2D_ERR_INVALID: an end that is neither D2D_ANGLE_AT_TX nor D2D_ANGLE_AT_RX, an origin that is NaN or outside [0, 1) turns,
+// nbins outside 1 .. D2D_ANGLE_BINS_MAX.
+inline int angle_params(int32_t end, float origin, int32_t nbins, std::string& err) {
+    if (end != D2D_ANGLE_AT_TX && end != D2D_ANGLE_AT_RX)
+        return err = "the power-angle profile's end must be D2D_ANGLE_AT_TX (0) or D2D_ANGLE_AT_RX (1), got " + std::to_string(end), D2D_ERR_INVALID;
+    if (!(origin >= 0.0f && origin < 1.0f))
+        return err = "the power-angle profile needs an origin in [0, 1) turns, got " + std::to_string(origin), D2D_ERR_INVALID;
+    if (nbins < 1 || nbins > D2D_ANGLE_BINS_MAX)
+        return err = "the power-angle profile needs nbins in 1 .. " + std::to_string(D2D_ANGLE_BINS_MAX) + ", got " + std::to_string(nbins), D2D_ERR_INVALID;
+    return D2D_OK;
+}
+// Per cell: nbins planes and one total, 4 bytes each.  Refused like the coherent field: outputs above half of the device memory
+// that is free, counting what the buffers hold already as free (tests/native/power_angle_host.cpp).  No product is formed: cells
+// is held against a quotient.
+inline size_t angle_bytes_per_cell(int32_t nbins) { return 4 * (size_t)nbins + 4; }
+inline bool angle_fits(size_t cells, int32_t nbins, size_t mem_free, size_t held_bytes) {
+    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
+    return cells <= budget / angle_bytes_per_cell(nbins);
+}
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

@@ -35,6 +35,7 @@
 #include "d2d_div.hpp"
 #include "d2d_top.hpp"
 #include "d2d_phasor.hpp"
+#include "d2d_angle.hpp"
 
 namespace d2d {
 
@@ -443,10 +444,13 @@ template <int K, int MODE, bool STATS, bool GRAD = false, bool PREF = true, bool
 __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&cand)[D2D_MAX_ORDER],
                                                const float (&imgx)[D2D_MAX_ORDER], const float (&imgy)[D2D_MAX_ORDER],
                                                float txx, float txy, float rxx, float rxy, bool lane_bad, float& acc,
-                                               WaveStats& st, GradCtx* g = nullptr, float acc_floor = -1.0f, float* r_out = nullptr) {
+                                               WaveStats& st, GradCtx* g = nullptr, float acc_floor = -1.0f, float* r_out = nullptr,
+                                               float* dir_out = nullptr) {
     // r_out (power_sink_kernel, BinSink): receives the path length the path function is evaluated with -- written only where the
     // contribution is (a candidate that leaves early leaves both alone).  Null everywhere else, a constant of the inlined call:
     // it costs those instances no instruction.
+    // dir_out (power_sink_kernel, AngleSink): receives, where r_out is written, the two end directions of the path as fp32
+    // differences of its points, {p[1] - p[0], p[K] - p[K+1]} (x, y each; no D2D_EPS).  Null everywhere else, likewise.
     // acc_floor >= 0 (MODE_SIG, fun >= 0): the caller adds this candidate to a sum it does not hold -- `acc` is a scratch
     // that receives the contribution alone -- but knows that sum to be at least acc_floor when the addition happens
     const float zc_acc = (acc_floor >= 0.0f) ? acc_floor : acc;
@@ -1120,6 +1124,12 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
         r = r + sqrtf(vx * vx + vy * vy);
     }
     if (r_out != nullptr) *r_out = r;
+    if (dir_out != nullptr) {
+        dir_out[0] = px[1] - px[0];
+        dir_out[1] = py[1] - py[0];
+        dir_out[2] = px[K] - px[K + 1];
+        dir_out[3] = py[K] - py[K + 1];
+    }
     float f;
     float cf[K > 0 ? K : 1];  // D2D_FUN_RECEIVED_POWER_PER_OBJECT: the candidate's coefficients (wave-uniform)
     if (a.fun_id == D2D_FUN_RECEIVED_POWER) f = a.fnum[K] / (a.h2 + r * r);
@@ -1729,6 +1739,8 @@ struct ListSink {
 //     put(t, code, k, r)     one candidate's contribution t (every lane of the wave calls it, zeros included), the candidate's
 //                              code (12 bits per wall index, first wall lowest) and order, and -- WANTS_R -- its path length
 //     end(args, tile, lane)  after the last order
+//     WANTS_DIR              the sink takes put_dir(t, dir) in put's place (sink_put below): dir[4] is what eval_candidate hands out
+//                              where it hands out the length, the path's two end directions {p[1] - p[0], p[K] - p[K+1]}
 //
 // RecSink (d2d_valid_paths): every (cell, candidate) whose contribution is not exactly zero is handed out as a record
 // instead of being added.  Two passes of the same deterministic sweep: with rec == null the wave only counts (cnt is
@@ -1745,6 +1757,7 @@ struct RecArgs {
 struct RecSink {
     using Args = RecArgs;
     static constexpr bool WANTS_R = false;  // (the path length is not asked of eval_candidate)
+    static constexpr bool WANTS_DIR = false;  // (nor are the path's end directions)
     int4* rec;
     int base, limit;
     int cnt;
@@ -1789,6 +1802,7 @@ struct BinArgs {
 struct BinSink {
     using Args = BinArgs;
     static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
     float* out;  // [nbins][cells]
     long cells;
     int cell;
@@ -1836,6 +1850,7 @@ struct TopArgs {
 struct TopSink {
     using Args = TopArgs;
     static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
     static_assert(D2D_MAX_ORDER == 4, "a slot's wall indices are stored as one int4");
     static_assert(TOP_SLOTS == D2D_TOP_MAX, "d2d_top.hpp and include/d2d.h disagree");
     TopSlots s;
@@ -1903,6 +1918,7 @@ struct FieldArgs {
 struct FieldSink {
     using Args = FieldArgs;
     static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
     float re, im, total;
     float inv;
     bool root;
@@ -1959,6 +1975,7 @@ struct FreqArgs {
 struct FreqSink {
     using Args = FreqArgs;
     static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
     float re[FREQ_CHUNK], im[FREQ_CHUNK], total;
     float inv[FREQ_CHUNK];
     int nf;
@@ -2008,6 +2025,81 @@ struct FreqSink {
         });
     }
 };
+
+// AngleSink (d2d_power_angle_launch): every contribution that is not exactly zero is added to the bin of the direction in which its
+// path leaves the transmitter or reaches the receiver -- the power-angle profile out[nbins][cells] (include/d2d.h holds the
+// definition), zeroed on the stream in front of the launch -- beside the running fp32 sum of every contribution (the fused map, bit
+// for bit), which stays in a register until end():
+//     (dx, dy) = end == AT_TX ? dir[0..1] : dir[2..3] ;  f = turns(dx, dy) ;  g = f - origin ;  if (g < 0) g = g + 1
+//     u = g * (float)nbins ;  b = (int)floorf(u) ;  if (b >= nbins) b = nbins - 1 ;  if (f == f) out[b][cell] = out[b][cell] + t
+// in fp32 without contraction, candidates in the sweep's order.  turns (d2d_angle.hpp) is plain arithmetic with one IEEE division:
+// no atan2f of the device library is involved.  dir[] is what eval_candidate hands out through dir_out (WANTS_DIR, sink_put).  All of it is
+// skipped for a candidate that no lane of the wave has a non-zero contribution from, the common case.  A lane is the only writer of
+// its cell's column and reads back what it stored itself: plain loads and stores, the same bits run to run.  f is in [0, 1) or
+// NaN and origin in [0, 1), so 0 <= u <= nbins: the conversion is defined and 0 <= b < nbins after the clamp.  Lanes outside the
+// grid (cell < 0) never write.  end, origin and nbins come by value in the kernel argument: scalar loads.
+struct AngleArgs {
+    float* out;    // [nbins][cells]
+    float* total;  // [cells]
+    long cells;    // m * n
+    float origin;  // turns, in [0, 1)
+    int nbins;     // 1 .. D2D_ANGLE_BINS_MAX
+    int end;       // D2D_ANGLE_AT_TX / D2D_ANGLE_AT_RX
+};
+struct AngleSink {
+    using Args = AngleArgs;
+    static constexpr bool WANTS_R = false;
+    static constexpr bool WANTS_DIR = true;
+    float total;
+    float* out;
+    long cells;
+    float origin, fbins;
+    int nbins;
+    bool at_rx;
+    int cell;
+    __device__ __forceinline__ void begin(const AngleArgs& x, long /*tile*/, int lane_cell) {
+        total = 0.0f;
+        out = x.out;
+        cells = x.cells;
+        origin = x.origin;
+        nbins = x.nbins;
+        fbins = (float)x.nbins;
+        at_rx = x.end == D2D_ANGLE_AT_RX;
+        cell = lane_cell;
+    }
+    // dir: {p[1] - p[0], p[K] - p[K+1]} of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_dir(float t, const float (&dir)[4]) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        if (p && cell >= 0) {
+            const float f = turns(at_rx ? dir[2] : dir[0], at_rx ? dir[3] : dir[1]);
+            if (f == f) {
+                float g = f - origin;
+                if (g < 0.0f) g = g + 1.0f;
+                const float u = g * fbins;
+                int b = (int)floorf(u);
+                if (b >= nbins) b = nbins - 1;
+                if (b >= 0) {  // (always: see above)
+                    float* q = out + (size_t)b * (size_t)cells + (size_t)cell;
+                    *q = *q + t;
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void end(const AngleArgs& x, long, int) const {
+        if (cell < 0) return;
+        x.total[cell] = total;
+    }
+};
+
+// One candidate into a sink: a WANTS_DIR sink takes the contribution with the path's end directions, every other one the
+// contribution with the candidate's code, order and length
+template <class S>
+__device__ __forceinline__ void sink_put(S& s, float t, unsigned long long code, int k, float r, const float (&dir)[4]) {
+    if constexpr (S::WANTS_DIR) s.put_dir(t, dir);
+    else s.put(t, code, k, r);
+}
 
 // Survivors of a region's culling, in candidate order (region_list_kernel / region_refine_kernel): wave-uniform state
 // of the list being written.
@@ -2159,9 +2251,9 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 image_of(ldc4(a.refl, 2 * ce[d]), d == 0 ? a.txx : ex[d > 0 ? d - 1 : 0], d == 0 ? a.txy : ey[d > 0 ? d - 1 : 0], ex[d], ey[d]);
             }
             if constexpr (RECORD) {
-                float t = 0.0f, rl = 0.0f;
-                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr);
-                rsink->put(t, cu, K, rl);
+                float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr);
+                sink_put(*rsink, t, cu, K, rl, dv);
             } else if (LIST) {
                 float t = 0.0f;
                 eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
@@ -2298,12 +2390,12 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), pIx, pIy, imgx[K - 1], imgy[K - 1]);
                 if constexpr (RECORD) {
-                    float t = 0.0f, rl = 0.0f;
-                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr);
+                    float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr);
                     unsigned long long cu = 0ull;
 #pragma unroll
                     for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
-                    rsink->put(t, cu, K, rl);
+                    sink_put(*rsink, t, cu, K, rl, dv);
                 } else if (LIST) {
                     float t = 0.0f;
                     eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
@@ -3430,12 +3522,12 @@ __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), K == 1 ? cx : imgx[K >= 2 ? K - 2 : 0], K == 1 ? cy : imgy[K >= 2 ? K - 2 : 0], imgx[K - 1], imgy[K - 1]);
                 if constexpr (RECORD) {
-                    float t = 0.0f, rl = 0.0f;
-                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr);
+                    float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr);
                     unsigned long long cu = 0ull;
 #pragma unroll
                     for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
-                    rsink->put(t, cu, K, rl);
+                    sink_put(*rsink, t, cu, K, rl, dv);
                 } else {
                     eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, acc, st, g);
                 }
@@ -3692,11 +3784,12 @@ __global__ void __launch_bounds__(64) power_sink_kernel(SweepArgs a, typename Si
         // (sweep_order<0>'s one candidate, with the length handed out where the sink wants it)
         const int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
         const float imgx[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f}, imgy[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f};
-        float t = 0.0f, rl = 0.0f;
+        float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         float* const r_out = Sink::WANTS_R ? &rl : nullptr;
-        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, r_out);
-        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, r_out);
-        sink.put(t, 0ull, 0, rl);
+        float* const dir_out = Sink::WANTS_DIR ? dv : nullptr;
+        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, r_out, dir_out);
+        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, r_out, dir_out);
+        sink_put(sink, t, 0ull, 0, rl, dv);
     }
     static_for<1, MAXK + 1>([&](auto KK) {
         constexpr int K = decltype(KK)::value;
@@ -3995,6 +4088,12 @@ __global__ void selftest_expf_kernel(const float* __restrict__ x, float* __restr
 __global__ void selftest_phasor_kernel(const float* __restrict__ f, float* __restrict__ c, float* __restrict__ s, long n) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) phasor(f[i], c[i], s[i]);
+}
+
+// turns (d2d_angle.hpp) on the device, for comparison with its host build (tests/test_gpu_power_angle.py)
+__global__ void selftest_angle_kernel(const float* __restrict__ dx, const float* __restrict__ dy, float* __restrict__ out, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = turns(dx[i], dy[i]);
 }
 
 // Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per

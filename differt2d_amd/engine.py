@@ -94,7 +94,15 @@ class FrequencyResponse(NamedTuple):
     total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
 
 
+class PowerAngleProfile(NamedTuple):
+    """Result of :meth:`Context.power_angle` (include/d2d.h: d2d_power_angle_launch)."""
+
+    bins: np.ndarray   # fp32 [nbins, m, n]: the contributions whose direction at the chosen end falls into the bin
+    total: np.ndarray  # fp32 [m, n]: the sum over all candidates, the fused map bit for bit
+
+
 FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
+ANGLE_ENDS = {"tx": L.D2D_ANGLE_AT_TX, "rx": L.D2D_ANGLE_AT_RX}
 
 
 def _immutable(a: np.ndarray) -> bool:
@@ -121,6 +129,7 @@ class Context:
         self._top_k = 0  # slots per cell of the last launch_strongest_paths that was accepted
         self._field = False  # a launch_coherent_field was accepted
         self._freq_nf = 0  # planes of the last launch_frequency_response that was accepted
+        self._angle_nbins = 0  # bins of the last launch_power_angle that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -399,6 +408,17 @@ class Context:
         L.check(self._lib.d2d_selftest_phasor(self._ctx, f, f.size, c, s))
         return c, s
 
+    def selftest_angle(self, dx, dy):
+        """``turns(dx, dy)``, the angle of the vectors in turns in [0, 1), as the power-angle profile computes it on the device
+        (include/d2d.h: must equal the host build of d2d_angle.hpp bit for bit)."""
+        dx = np.ascontiguousarray(dx, dtype=np.float32).reshape(-1)
+        dy = np.ascontiguousarray(dy, dtype=np.float32).reshape(-1)
+        if dx.size != dy.size:
+            raise ValueError("dx and dy must have one size")
+        out = np.empty_like(dx)
+        L.check(self._lib.d2d_selftest_angle(self._ctx, dx, dy, dx.size, out))
+        return out
+
     def get_map(self) -> np.ndarray:
         out = np.empty(self.shape, np.float32)
         L.check(self._lib.d2d_get_map(self._ctx, out))
@@ -661,6 +681,44 @@ class Context:
         fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_frequency_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
         return fr
+
+    def power_angle(self, params: L.Params, fixed, end, origin_turns: float, nbins: int) -> "PowerAngleProfile":
+        """The power-angle profile of every cell of the resident grid: the fused sweep's contributions ``valid * fun`` binned by
+        the direction in which their path leaves the transmitter (``end="tx"``, departure) or by the direction from the receiver
+        towards the last interaction point (``end="rx"``, arrival) -- one launch of the power-angle build of the culled sweep
+        (include/d2d.h: d2d_power_angle_launch holds the definition, the angle's arithmetic included; ImagePath, hard or
+        hard_sigmoid validity, every fused function).  ``end`` may also be the library's constant.  ``nbins`` equal bins cover the
+        full turn counter-clockwise from ``origin_turns`` (fp32, in turns, ``0 <= origin_turns < 1``, measured from +x);
+        ``1 <= nbins <= 4096``.  ``params.grid_role`` says which end of the paths the cells are, ``fixed`` is the other end:
+        ``"tx"`` over an RX grid and ``"rx"`` over a TX grid bin at the fixed end point, the other two at the cell.  A refused launch
+        leaves the previous result readable.  The resident value map, the records of :meth:`valid_paths`, the delay profile, the
+        strongest paths, the coherent field and the frequency response are not touched.
+
+        Returns a :class:`PowerAngleProfile`: ``bins`` fp32 ``[nbins, m, n]`` and ``total`` (the fused map, bit for bit), fp32
+        ``[m, n]``.  :func:`differt2d_amd.utils.angular_statistics` and :func:`differt2d_amd.utils.pattern_power` turn it into the
+        mean direction and angular spread and into the power a directional antenna receives."""
+        self.launch_power_angle(params, fixed, end, origin_turns, nbins)
+        return self.get_power_angle()
+
+    def launch_power_angle(self, params: L.Params, fixed, end, origin_turns: float, nbins: int):
+        """The launch of :meth:`power_angle` alone (asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        if isinstance(end, str):
+            if end not in ANGLE_ENDS:
+                raise L.D2DError(-1, f"power_angle: end must be one of {sorted(ANGLE_ENDS)}, got {end!r}")
+            end = ANGLE_ENDS[end]
+        L.check(self._lib.d2d_power_angle_launch(self._ctx, C.byref(params), fixed, int(end), float(origin_turns), int(nbins)))
+        self._angle_nbins = int(nbins)
+
+    def get_power_angle(self) -> "PowerAngleProfile":
+        """Synchronises and returns the result of the last :meth:`launch_power_angle` that was accepted."""
+        if not self._angle_nbins:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_power_angle(self._ctx, None, None))
+            raise L.D2DError(-5, "launch_power_angle must come first")
+        shape = tuple(self.shape)
+        pa = PowerAngleProfile(bins=np.empty((self._angle_nbins,) + shape, np.float32), total=np.empty(shape, np.float32))
+        L.check(self._lib.d2d_get_power_angle(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in pa)))
+        return pa
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

@@ -1215,6 +1215,71 @@ class Scene(Plottable):
         return self._grid_response(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
                                    amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
 
+    def _grid_angle(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, at, nbins, origin, path_cls, min_order, max_order, order,
+                    filter_objects, kwargs):
+        """Shared driver of the two power-angle sweeps: one launch of the power-angle build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the power-angle profile comes from a fused sweep (a "
+                                       "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+                                       "records (Context.valid_paths: every valid path of every cell), their points from "
+                                       "Context.trace_paths, and bin fun by direction on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the power-angle profile covers ImagePath only, not path_cls={path_cls.__name__}")
+        if at not in ("rx", "tx"):
+            raise L.D2DError(-1, f"the power-angle profile is taken at=\"rx\" (arrival) or at=\"tx\" (departure), got {at!r}")
+        # bin 0 begins at `origin` radians: in turns, reduced to [0, 1) in float64, then fp32 (a value that rounds to 1.0 is 0.0)
+        turns = F(np.mod(np.float64(origin) / (2.0 * np.pi), 1.0))
+        if turns >= 1:
+            turns = F(0)
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.power_angle(params, pt.xy, at, turns, nbins)
+
+        return results()
+
+    def power_angle_profile_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, at: str = "rx", nbins: int = 36, origin: float = 0.0,
+        path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The power-angle profile of every cell: for every transmitter, the contributions ``valid * fun`` of the paths to the
+        receiver ``(X[i, j], Y[i, j])`` binned by direction -- with ``at="rx"`` the direction of arrival (from the receiver towards
+        the last interaction point: where the wave comes from), with ``at="tx"`` the direction of departure (from the transmitter
+        towards the first interaction point).  ``nbins`` equal bins (1 .. 4096) cover the full turn counter-clockwise; ``origin``,
+        in radians counter-clockwise from +x, is where bin 0 begins.  Yields ``(tx name, PowerAngleProfile(bins, total))``
+        (:class:`differt2d_amd.engine.PowerAngleProfile`: ``bins`` fp32 ``[nbins, m, n]``, ``total`` fp32 ``[m, n]``, the fused map
+        bit for bit); one fused kernel launch per transmitter (include/d2d.h: d2d_power_angle_launch holds the exact definition, the
+        angle's arithmetic included).  :func:`differt2d_amd.utils.angular_statistics` gives the mean direction and the angular
+        spread, :func:`differt2d_amd.utils.pattern_power` the power a directional antenna receives.
+
+        The library takes ``float32((origin / 2 pi) mod 1)`` turns, computed in float64.  ``fun`` must be natively fused
+        (:mod:`differt2d_amd.utils`), the path class ``ImagePath``, the validity hard (``approx=False``) or ``hard_sigmoid``;
+        anything else raises :class:`D2DUnsupported`.  For another callable the sparse valid-path records
+        (:meth:`Context.valid_paths`, then :meth:`Context.trace_paths`) hold every valid path and its points for a loop on the
+        host."""
+        return self._grid_angle(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, at, nbins, origin, path_cls, min_order,
+                                max_order, order, filter_objects, kwargs)
+
+    def power_angle_profile_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, at: str = "rx", nbins: int = 36, origin: float = 0.0,
+        path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`power_angle_profile_on_receivers_grid`: one result per receiver, the transmitter sits at
+        ``(X[i, j], Y[i, j])`` (``at="tx"`` then bins at the cell, ``at="rx"`` at the fixed receiver); only where the TX-grid sweep
+        is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_angle(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, at, nbins, origin, path_cls, min_order,
+                                max_order, order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

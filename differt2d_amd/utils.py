@@ -6,6 +6,8 @@ inside the HIP kernel instead of being called from Python."""
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 from .defaults import DEFAULT_HEIGHT, DEFAULT_R_COEF
@@ -160,6 +162,45 @@ def impulse_response(fr, inv_wavelength_step):
     if not (np.isfinite(step) and step > 0.0):
         raise ValueError(f"impulse_response needs a finite inv_wavelength_step > 0, got {inv_wavelength_step!r}")
     return np.fft.ifft(h, axis=0), 1.0 / (nf * step)
+
+
+class AngularStatistics(NamedTuple):
+    """Result of :func:`angular_statistics`: float64 ``[m, n]`` each."""
+
+    power: np.ndarray   # the binned power, the sum of the bins
+    mean: np.ndarray    # the mean direction in radians, in (-pi, pi], counter-clockwise from +x; NaN where power is 0
+    spread: np.ndarray  # the circular spread sqrt(1 - |sum p_b e^(j theta_b)|^2 / (sum p_b)^2), 0 .. 1; NaN where power is 0
+
+
+def angular_statistics(profile, origin=0.0):
+    """The binned power, the mean direction and the angular spread per cell of a ``PowerAngleProfile``
+    (``Scene.power_angle_profile_on_receivers_grid``, ``Context.power_angle``) or any object with ``bins`` ``[nbins, m, n]``; ``origin``
+    is the profile's, in radians.  From the bin centres ``theta_b = origin + 2 pi (b + 1/2) / nbins``, on the host, in float64: the
+    power is ``sum_b bins[b]``, the mean direction the angle of ``sum_b bins[b] e^(j theta_b)``, and the circular spread
+    ``sqrt(1 - |sum_b bins[b] e^(j theta_b)|^2 / (sum_b bins[b])^2)`` -- 0 when all power sits in one bin, 1 when it is balanced
+    around the circle.  Mean and spread are NaN where the power is 0.  Returns an :class:`AngularStatistics`."""
+    bins = np.asarray(profile.bins, dtype=np.float64)
+    nbins = bins.shape[0]
+    theta = float(origin) + 2.0 * np.pi * (np.arange(nbins, dtype=np.float64) + 0.5) / nbins
+    phase = np.exp(1j * theta).reshape((nbins,) + (1,) * (bins.ndim - 1))
+    power = bins.sum(axis=0)
+    first = (bins * phase).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lit = power != 0.0
+        mean = np.where(lit, np.angle(first), np.nan)
+        spread = np.where(lit, np.sqrt(np.clip(1.0 - np.abs(first) ** 2 / power**2, 0.0, None)), np.nan)
+    return AngularStatistics(power, mean, spread)
+
+
+def pattern_power(profile, gains):
+    """The power a directional antenna receives: ``sum_b gains[b] * bins[b]`` per cell, for a ``PowerAngleProfile`` (or any object
+    with ``bins`` ``[nbins, m, n]``) and the antenna's power pattern sampled at the bin centres, ``gains[nbins]`` (linear, not dB).  On
+    the host, in float64; unit gains give the binned power."""
+    bins = np.asarray(profile.bins, dtype=np.float64)
+    g = np.asarray(gains, dtype=np.float64).reshape(-1)
+    if g.size != bins.shape[0]:
+        raise ValueError(f"pattern_power needs one gain per bin, got {g.size} gains for {bins.shape[0]} bins")
+    return np.tensordot(g, bins, axes=(0, 0))
 
 
 received_power._d2d_native = "received_power"

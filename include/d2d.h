@@ -27,9 +27,10 @@ extern "C" {
 
 #define D2D_MAX_ORDER 4 /* highest interaction order a sweep accepts */
 #define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile, d2d_strongest_paths_launch /
-                              d2d_get_strongest_paths, d2d_coherent_field_launch / d2d_get_coherent_field and
-                              d2d_frequency_response_launch / d2d_get_frequency_response are additive: no struct, enum or existing
-                              entry point changed with them, so the version did not) */
+                              d2d_get_strongest_paths, d2d_coherent_field_launch / d2d_get_coherent_field,
+                              d2d_frequency_response_launch / d2d_get_frequency_response and d2d_power_angle_launch /
+                              d2d_get_power_angle are additive: no struct, enum or existing entry point changed with them, so the
+                              version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -414,6 +415,10 @@ int d2d_selftest_expf(d2d_ctx* ctx, const float* x, int64_t n, float* y);
  * cos(2 pi f), s[n] = sin(2 pi f); must equal the header's host build bit for bit. */
 int d2d_selftest_phasor(d2d_ctx* ctx, const float* f, int64_t n, float* c, float* s);
 
+/* Diagnostic: the power-angle profile's direction (differt2d_amd/csrc/d2d_angle.hpp) on the device, (dx[n], dy[n]) -> out[n] =
+ * turns(dx, dy), the angle in turns in [0, 1) (NaN for (0, 0), NaN and inf); must equal the header's host build bit for bit. */
+int d2d_selftest_angle(d2d_ctx* ctx, const float* dx, const float* dy, int64_t n, float* out);
+
 /* Synchronises and copies the resident value map to out[m*n]. */
 int d2d_get_map(d2d_ctx* ctx, float* out);
 
@@ -636,6 +641,63 @@ int d2d_frequency_response_launch(d2d_ctx* ctx, const d2d_params* params, const 
  * with that launch's nf; total: [m][n]).  D2D_ERR_STATE before a launch, after a launch that was refused, and after a d2d_set_grid
  * of another grid (the result goes with the grid). */
 int d2d_get_frequency_response(d2d_ctx* ctx, float* re, float* im, float* total);
+
+/* ---- power-angle profile: the fused sweep binned by the direction in which a path leaves the transmitter or reaches the
+ *      receiver (no reference counterpart: angle-of-departure / angle-of-arrival spectra, angular spread, sector selection and
+ *      the power a directional antenna receives follow from it) ---- */
+
+#define D2D_ANGLE_AT_TX 0 /* bin by the direction of departure: from the transmitter towards the first interaction point */
+#define D2D_ANGLE_AT_RX 1 /* bin by the direction of arrival: from the receiver towards the last interaction point */
+#define D2D_ANGLE_BINS_MAX 4096
+/* Launches the power-angle build of the culled forward sweep for the fixed end point `fixed` on the ctx stream (asynchronous),
+ * for the current scene, candidate mask and grid.  `params`, `fixed` and the grid role are as for d2d_power_profile_launch.
+ * end: D2D_ANGLE_AT_TX or D2D_ANGLE_AT_RX; origin: fp32, in turns, 0 <= origin < 1 (where bin 0 begins, counter-clockwise from
+ * +x); nbins: in 1 .. D2D_ANGLE_BINS_MAX.
+ *
+ * A path's points are p[0] = TX, p[1..K], p[K+1] = RX: the fp32 points the path function's length is computed from.  They are
+ * the same in both grid roles: in a TX grid the cell is p[0].  Definition, per cell:
+ *
+ *     total = +0.0f ; out[0..nbins) = +0.0f
+ *     for candidates in the sweep's enumeration order:
+ *         t = valid * fun                     // exactly the fused sweep's contribution (nan_to_num rules included)
+ *         total = total + t                   // fp32: hence the fused map bit for bit
+ *         if (t == 0) continue                // exact zeros of either sign name no bin
+ *         (dx, dy) = end == AT_TX ? p[1] - p[0] : p[K] - p[K+1]
+ *                                             // fp32 differences, no D2D_EPS: the direction in which that terminal SEES the path
+ *                                             // (departure direction at TX; at RX the direction towards the last interaction
+ *                                             // point, i.e. where the wave comes from)
+ *         f = turns(dx, dy)                   // angle of (dx, dy) in turns, [0, 1), as d2d::turns of
+ *                                             // differt2d_amd/csrc/d2d_angle.hpp computes it: fp32 compares, multiplies, adds and
+ *                                             // one division, within 0.75 * 2^-24 turn of atan2; NaN for dx == dy == 0 and for
+ *                                             // any NaN / inf component
+ *         g = f - origin ; if (g < 0) g = g + 1.0f          // fp32, one rounding each
+ *         u = g * (float)nbins ; b = (int)floorf(u) ; if (b >= nbins) b = nbins - 1     // (g + 1 may round to 1.0: last bin)
+ *         if (f == f) out[b][cell] = out[b][cell] + t      // NaN f: no bin (total still has it)
+ *
+ * Outputs: out, fp32 [nbins][m][n], and total, fp32 [m][n].
+ *
+ *   - With nbins == 1, out[0] equals total bit for bit wherever no contribution has a zero or non-finite direction.  The dropped
+ *     share is the only difference.
+ *   - For any nbins, a cell's bins sum to that same value up to fp32 summation order.
+ *   - AT_TX over an RX grid and AT_RX over a TX grid bin the direction at the FIXED end point.
+ *   - The other two combinations bin at the cell.
+ *
+ * One pass of one kernel (one wave per 8 x 8 patch; out is zeroed on the stream in front of it, every lane is the only writer of
+ * its cell's column: plain loads and stores, no atomics, the same bits run to run).  The result is kept with the grid until the
+ * next such launch.  The resident value / gradient maps, the work history, the schedule of the fused sweeps, the records of
+ * d2d_valid_paths, the delay profile, the strongest paths, the coherent field and the frequency response are not touched.  Every
+ * fused function but D2D_FUN_CUSTOM; D2D_FUN_RECEIVED_POWER_PER_OBJECT with the coefficients of d2d_set_reflection_coefs,
+ * D2D_ERR_STATE without them.
+ * D2D_ERR_INVALID: an unknown end; an origin that is NaN or outside [0, 1); nbins outside 1 .. D2D_ANGLE_BINS_MAX.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): what d2d_power_profile_launch refuses, with outputs of 4 * nbins + 4 bytes
+ * per cell held against half of the free device memory -- all decided before anything is enqueued.  A refused launch leaves the
+ * previous result as it was. */
+int d2d_power_angle_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, int32_t end, float origin,
+                           int32_t nbins);
+/* Synchronises and copies the result of the last d2d_power_angle_launch that was accepted to the arrays that are not NULL
+ * (out: [nbins][m][n] with that launch's nbins, total: [m][n]).  D2D_ERR_STATE before a launch and after a d2d_set_grid of
+ * another grid (the result goes with the grid). */
+int d2d_get_power_angle(d2d_ctx* ctx, float* out, float* total);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
