@@ -216,6 +216,14 @@ struct SweepArgs {
 #define D2D_WORK(x) (st.work += (x))
 #define D2D_EPS 1.1920929e-07f  // jnp.finfo(float32).eps, geometry.py:200
 
+// The wall loop's segment filters (eval_candidate) compute every lane and every trip's second wall and mask afterwards.
+// -DD2D_MASKED_FILTERS=1 keeps the earlier form -- `active` and "is there a second wall" as conditions of the filters -- for a
+// translation unit one of whose instances would otherwise spill to scratch (the Makefile says which).
+#ifndef D2D_MASKED_FILTERS
+#define D2D_MASKED_FILTERS 0
+#endif
+constexpr bool MASKED_FILTERS = D2D_MASKED_FILTERS != 0;
+
 // Executed-work counters of one wave (wave-uniform, live in SGPRs). Only the STATS build of the
 // kernel touches them; the timed kernel is compiled without.
 //   [0] candidates evaluated (points + on_objects)      [1] candidates that reached the loss stage
@@ -767,9 +775,16 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
             bool miss = fmaxf(pa, pb) > 0.0f;
             if (MODE == MODE_SIG && !skip) any_test = true;
             if (STATS) stat_add<4>(st, skip ? 0 : 1);  // (branch-free on purpose: see the single-wall loop below)
-            wbits |= (!skip && active && (!miss || bad)) ? (1u << i) : 0u;
+            if constexpr (MASKED_FILTERS) wbits |= (!skip && active && (!miss || bad)) ? (1u << i) : 0u;
+            else wbits |= (!skip && (!miss || bad)) ? (1u << i) : 0u;
         }
-        return wbits;
+        // Every lane computes every segment; `active` clears the decided lanes' bits once, behind a fence.  As a term of each
+        // segment's condition it let the optimiser sink that segment's arithmetic under the lane mask: one exec region per
+        // segment (mask save, a branch on "no lane" that the loop never takes, restore), the K + 1 chains of a wall one
+        // behind the other.  A decided lane computes on its own operands -- finite or not, no side effects -- for nothing.
+        if constexpr (MASKED_FILTERS) return wbits;
+        asm volatile("" : "+v"(wbits));
+        return active ? wbits : 0u;
     };
     auto exact = [&](const float4& ww, int jj, unsigned wbits) {
 #pragma unroll
@@ -854,7 +869,15 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                 const int jB = jA + 1;
                 const bool hasB = jB < a.N;
                 unsigned ba = filt(wA, jA, FlagOff());
-                unsigned bb = hasB ? filt(wB, jB, FlagOff()) : 0u;
+                // (wall B unconditionally -- the spare rows make the one past an odd table loadable -- and its bits dropped by a
+                // scalar select: the trip is one block, only the last trip of an odd table computes a filter for nothing)
+                unsigned bb;
+                if constexpr (MASKED_FILTERS) bb = hasB ? filt(wB, jB, FlagOff()) : 0u;
+                else {
+                    bb = filt(wB, jB, FlagOff());
+                    bb = hasB ? bb : 0u;
+                    if (STATS) stat_add<4>(st, hasB ? 0ull : 0ull - (unsigned)(K + 1));  // (counted by hasB, as the work is)
+                }
                 D2D_WORK(hasB ? 2 * (K + 1) : (K + 1));
                 unsigned own_tests = 0u;  // (STATS: segment tests of this trip that were computed and masked)
                 if (K > 0 && jA == own_nxt) {  // wave-uniform, at most K trips of a loop
@@ -912,7 +935,13 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                 // (the next trip's walls: their loads fly while this trip computes)
                 const float4 wnA = ldc4(a.occl, nA < a.N ? nA : jA), wnB = ldc4(a.occl, nB < a.N ? nB : jA);
                 const unsigned ba = filt(wA, jA, FlagOn());
-                const unsigned bb = hasB ? filt(wB, jB, FlagOn()) : 0u;
+                unsigned bb;  // (without wall B: row jA again, as no wall's own -- computed and dropped)
+                if constexpr (MASKED_FILTERS) bb = hasB ? filt(wB, jB, FlagOn()) : 0u;
+                else {
+                    bb = filt(wB, jB, FlagOn());
+                    bb = hasB ? bb : 0u;
+                    if (STATS) stat_add<4>(st, hasB ? 0ull : 0ull - (unsigned)(K + 1));
+                }
                 D2D_WORK(hasB ? 2 * (K + 1) : (K + 1));
                 if (wave_any((ba | bb) != 0u)) {
                     if (wave_any(ba != 0u)) {
