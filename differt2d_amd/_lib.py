@@ -24,6 +24,7 @@ D2D_FIELD_AMP_SQRT, D2D_FIELD_AMP_LINEAR = 0, 1  # d2d_coherent_field_launch amp
 D2D_FREQ_MAX = 1024  # most wavelengths of one d2d_frequency_response_launch
 D2D_ANGLE_AT_TX, D2D_ANGLE_AT_RX = 0, 1  # d2d_power_angle_launch: the end of the path whose direction is binned
 D2D_ANGLE_BINS_MAX = 4096
+D2D_ARRAY_MAX = 8  # most elements of either array of one d2d_array_response_launch
 D2D_NUM_STATS = 16
 D2D_COMM_ID_BYTES = 128
 D2D_OPT_ADAM, D2D_OPT_SGD, D2D_OPT_SGD_MOMENTUM = 0, 1, 2  # d2d_set_optimizer kinds
@@ -132,6 +133,7 @@ SYMBOLS = [
     ("d2d_selftest_expf", C.c_int, [_ctx, _f32p, C.c_int64, _f32p]),
     ("d2d_selftest_phasor", C.c_int, [_ctx, _f32p, C.c_int64, _f32p, _f32p]),
     ("d2d_selftest_angle", C.c_int, [_ctx, _f32p, _f32p, C.c_int64, _f32p]),
+    ("d2d_selftest_steer", C.c_int, [_ctx, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p, _f32p, _f32p]),
     ("d2d_get_map", C.c_int, [_ctx, _f32p]),
     ("d2d_power_map", C.c_int, [_ctx, C.POINTER(Params), _f32p, _f32p, _f32p, C.c_int32, C.c_int32, _f32p]),
     ("d2d_trace_paths", C.c_int, [_ctx, C.POINTER(Params), _f32p, _f32p, C.c_int32, _i32p, _i32p, C.c_int32,
@@ -149,6 +151,8 @@ SYMBOLS = [
     ("d2d_get_coherent_field", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_power_angle_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_int32, C.c_float, C.c_int32]),
     ("d2d_get_power_angle", C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
+    ("d2d_array_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_float, C.c_int32, C.c_int32, _f32p, C.c_int32, _f32p]),
+    ("d2d_get_array_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32]),
     ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),

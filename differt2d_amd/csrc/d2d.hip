@@ -204,6 +204,14 @@ struct d2d_ctx {
         d_angle.release(); d_angle_total.release();
         angle_nbins = 0;
     }
+    // array response (d2d_array_response_launch): nr * nt planes of re and im and the total of every cell, kept until the next
+    // accepted launch, dropped with the grid
+    DevBuf<float> d_array_re, d_array_im, d_array_total;  // [array_nr][array_nt][m][n] twice, [m][n]
+    int32_t array_nt = 0, array_nr = 0;                   // counts of the last accepted launch; 0: no result
+    void drop_array() {
+        d_array_re.release(); d_array_im.release(); d_array_total.release();
+        array_nt = array_nr = 0;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -905,6 +913,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->drop_top();      // ... and the strongest paths'
         c->drop_field();    // ... and the coherent field's
         c->drop_angle();    // ... and the power-angle profile's
+        c->drop_array();    // ... and the array response's
         c->drop_freq();     // ... and the frequency response's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
@@ -2481,9 +2490,85 @@ static int power_angle_launch(d2d_ctx* c, const d2d_params* p_in, const float* f
     return D2D_OK;
 }
 
+// Array-response launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed
+// planes, every lane storing its cell's total at the end.  Asynchronous.  Every check comes before anything is enqueued, and a
+// refused launch leaves the previous result as it was.
+static int array_response_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float inv_wavelength, int32_t amplitude, int32_t nt,
+                                 const float* tx_elems, int32_t nr, const float* rx_elems) {
+    if (!c || !fixed || !tx_elems || !rx_elems) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_array_response_launch");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_array_response_launch");
+    if ((rc = check_fused_sink(c, p_in, "d2d_array_response_launch", "a host function's channel matrix: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths",
+                               "the channel matrix is always overwritten")))
+        return rc;
+    {
+        std::string err;
+        if ((rc = d2d_host::array_params(nt, tx_elems, nr, rx_elems, inv_wavelength, amplitude, err))) return fail(rc, "d2d_array_response_launch: %s", err.c_str());
+    }
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_array_re.n + c->d_array_im.n + c->d_array_total.n) * sizeof(float);
+        if (!d2d_host::array_fits(cells, nt, nr, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "d2d_array_response_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
+                        cells, d2d_host::array_bytes_per_cell(nt, nr), mem_free);
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, "d2d_array_response_launch", lds))) return rc;
+    c->array_nt = c->array_nr = 0;  // from here on the buffers change
+    const size_t planes = (size_t)nr * (size_t)nt * cells;
+    if ((rc = c->d_array_re.ensure(planes)) || (rc = c->d_array_im.ensure(planes)) || (rc = c->d_array_total.ensure(cells))) return rc;
+    d2d::ArrayArgs g = {};
+    g.re = c->d_array_re.p;
+    g.im = c->d_array_im.p;
+    g.total = c->d_array_total.p;
+    g.cells = (long)cells;
+    g.inv_wavelength = inv_wavelength;
+    g.amplitude = amplitude;
+    g.nt = nt;
+    g.nr = nr;
+    for (int32_t j = 0; j < nt; ++j) g.etx[j][0] = tx_elems[2 * j], g.etx[j][1] = tx_elems[2 * j + 1];
+    for (int32_t i = 0; i < nr; ++i) g.erx[i][0] = rx_elems[2 * i], g.erx[i][1] = rx_elems[2 * i + 1];
+    HIP_TRY(hipMemsetAsync(c->d_array_re.p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_array_im.p, 0, planes * sizeof(float), c->stream));
+    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::ArraySink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
+    else HIP_TRY(hipMemsetAsync(c->d_array_total.p, 0, cells * sizeof(float), c->stream));
+    c->array_nt = nt;
+    c->array_nr = nr;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_array_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude, int32_t nt,
+                              const float* tx_elems, int32_t nr, const float* rx_elems) {
+    return array_response_launch(c, p, fixed, inv_wavelength, amplitude, nt, tx_elems, nr, rx_elems);
+}
+
+int d2d_get_array_response(d2d_ctx* c, float* re, float* im, float* total) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (c->array_nt < 1 || c->array_nr < 1 || !c->d_array_re.p) return fail(D2D_ERR_STATE, "d2d_array_response_launch must come first (its result goes with the grid)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    const size_t pairs = (size_t)c->array_nt * (size_t)c->array_nr;
+    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_array_re.p, bytes * pairs, hipMemcpyDeviceToHost, c->stream));
+    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_array_im.p, bytes * pairs, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_array_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_power_angle_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t end, float origin, int32_t nbins) {
     return power_angle_launch(c, p, fixed, end, origin, nbins);
@@ -2747,6 +2832,23 @@ int d2d_selftest_angle(d2d_ctx* c, const float* dx, const float* dy, int64_t n, 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_steer(d2d_ctx* c, const float* dx, const float* dy, const float* f0, const float* qt, const float* qr, const float* inv, int64_t n,
+                       float* ux, float* uy, float* ok, float* f) {
+    if (!c || !dx || !dy || !f0 || !qt || !qr || !inv || !ux || !uy || !ok || !f || n <= 0) return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> din, dout;  // six inputs, four outputs, n each
+    if ((rc = din.ensure(6 * (size_t)n)) || (rc = dout.ensure(4 * (size_t)n))) return rc;
+    const float* in[6] = {dx, dy, f0, qt, qr, inv};
+    for (int k = 0; k < 6; ++k) HIP_TRY(hipMemcpy(din.p + (size_t)k * (size_t)n, in[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_steer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, din.p, dout.p, (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float* out[4] = {ux, uy, ok, f};
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }
 

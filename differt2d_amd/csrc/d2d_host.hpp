@@ -331,6 +331,41 @@ inline bool angle_fits(size_t cells, int32_t nbins, size_t mem_free, size_t held
     return cells <= budget / angle_bytes_per_cell(nbins);
 }
 
+// ---- parameters and outputs of the array response (d2d_array_response_launch, d2d::ArraySink) ------------------------
+// D2D_ERR_INVALID, in this order: nt, then nr outside 1 .. D2D_ARRAY_MAX; a transmit, then a receive element component that is NaN
+// or infinite (the message ends in the element's index); an inverse wavelength that is negative, NaN or infinite; an amplitude mode
+// that is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.  No list is read unless BOTH counts are in range.
+inline int array_params(int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems, float inv_wavelength, int32_t amplitude, std::string& err) {
+    if (nt < 1 || nt > D2D_ARRAY_MAX)
+        return err = "the array response needs nt in 1 .. " + std::to_string(D2D_ARRAY_MAX) + ", got " + std::to_string(nt), D2D_ERR_INVALID;
+    if (nr < 1 || nr > D2D_ARRAY_MAX)
+        return err = "the array response needs nr in 1 .. " + std::to_string(D2D_ARRAY_MAX) + ", got " + std::to_string(nr), D2D_ERR_INVALID;
+    for (int side = 0; side < 2; ++side) {
+        const float* e = side == 0 ? tx_elems : rx_elems;
+        const int32_t n = side == 0 ? nt : nr;
+        for (int32_t j = 0; j < n; ++j)
+            for (int k = 0; k < 2; ++k)
+                if (!std::isfinite(e[2 * j + k]))
+                    return err = std::string("the array response needs every element offset finite, got ") + std::to_string(e[2 * j + k]) + " as the " +
+                                 (k == 0 ? "x" : "y") + " of " + (side == 0 ? "tx_elems" : "rx_elems") + " at index " + std::to_string(j),
+                           D2D_ERR_INVALID;
+    }
+    if (!std::isfinite(inv_wavelength) || inv_wavelength < 0.0f)
+        return err = "the array response needs a finite inv_wavelength >= 0, got " + std::to_string(inv_wavelength), D2D_ERR_INVALID;
+    if (amplitude != D2D_FIELD_AMP_SQRT && amplitude != D2D_FIELD_AMP_LINEAR)
+        return err = "the array response's amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
+               D2D_ERR_INVALID;
+    return D2D_OK;
+}
+// Per cell: nr * nt planes of re and im and one total, 4 bytes each (at most 516: the counts are in range).  Refused like the
+// coherent field: outputs above half of the device memory that is free, counting what the buffers hold already as free
+// (tests/native/array_response_host.cpp).  No product with cells is formed: cells is held against a quotient.
+inline size_t array_bytes_per_cell(int32_t nt, int32_t nr) { return 8 * (size_t)nr * (size_t)nt + 4; }
+inline bool array_fits(size_t cells, int32_t nt, int32_t nr, size_t mem_free, size_t held_bytes) {
+    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
+    return cells <= budget / array_bytes_per_cell(nt, nr);
+}
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

@@ -36,6 +36,7 @@
 #include "d2d_top.hpp"
 #include "d2d_phasor.hpp"
 #include "d2d_angle.hpp"
+#include "d2d_steer.hpp"
 
 namespace d2d {
 
@@ -457,7 +458,7 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
     // r_out (power_sink_kernel, BinSink): receives the path length the path function is evaluated with -- written only where the
     // contribution is (a candidate that leaves early leaves both alone).  Null everywhere else, a constant of the inlined call:
     // it costs those instances no instruction.
-    // dir_out (power_sink_kernel, AngleSink): receives, where r_out is written, the two end directions of the path as fp32
+    // dir_out (power_sink_kernel, AngleSink and ArraySink): receives, where r_out is written, the two end directions of the path as fp32
     // differences of its points, {p[1] - p[0], p[K] - p[K+1]} (x, y each; no D2D_EPS).  Null everywhere else, likewise.
     // acc_floor >= 0 (MODE_SIG, fun >= 0): the caller adds this candidate to a sum it does not hold -- `acc` is a scratch
     // that receives the contribution alone -- but knows that sum to be at least acc_floor when the addition happens
@@ -1770,6 +1771,7 @@ struct ListSink {
 //     end(args, tile, lane)  after the last order
 //     WANTS_DIR              the sink takes put_dir(t, dir) in put's place (sink_put below): dir[4] is what eval_candidate hands out
 //                              where it hands out the length, the path's two end directions {p[1] - p[0], p[K] - p[K+1]}
+//                              -- or, with WANTS_R as well, put_rd(t, r, dir): the contribution, the length and the directions
 //
 // RecSink (d2d_valid_paths): every (cell, candidate) whose contribution is not exactly zero is handed out as a record
 // instead of being added.  Two passes of the same deterministic sweep: with rec == null the wave only counts (cnt is
@@ -2122,11 +2124,87 @@ struct AngleSink {
     }
 };
 
-// One candidate into a sink: a WANTS_DIR sink takes the contribution with the path's end directions, every other one the
-// contribution with the candidate's code, order and length
+// ArraySink (d2d_array_response_launch): the coherent sum of every cell for every pair of a transmit element j < nt and a receive
+// element i < nr -- the channel matrix re / im [nr][nt][cells] under the plane-wave model (d2d_steer.hpp holds the definition),
+// zeroed on the stream in front of the launch -- beside the running fp32 sum of every contribution (the fused map, bit for bit),
+// which stays in a register until end().  Per contribution that is not exactly zero, a and f0 are formed once as FieldSink forms
+// them, the two unit directions once (dir[] is what eval_candidate hands out through dir_out), and then
+//     for j < nt: qt = steer_dot(etx[j], utx, uty)
+//       for i < nr: qr = steer_dot(erx[i], urx, ury) ;  f = steer_phase(f0, qt, qr, inv) ;  (c, s) = phasor(f)
+//                   re[i][j][cell] = re[i][j][cell] + a * c ;  im[i][j][cell] = im[i][j][cell] - a * s
+// in fp32 without contraction, candidates in the sweep's order.  The two loops are wave-uniform run-time loops: no per-element
+// register array exists (one indexed at run time goes to scratch); qt is recomputed per j and qr per (i, j) from
+// the element offsets, which come by value in the kernel argument with nt and nr and are read by scalar loads.  All of it is skipped
+// for a candidate that no lane of the wave has a non-zero contribution from, the common case.  A lane is the only writer of its
+// cell's column and reads back what it stored itself: plain loads and stores, no atomics, the same bits run to run.  Lanes outside
+// the grid (cell < 0) never write.  i * nt + j < 64 and cell < cells, so every address is inside the 2 * nr * nt * cells planes.
+constexpr int ARRAY_MAX = 8;  // = D2D_ARRAY_MAX (include/d2d.h)
+struct ArrayArgs {
+    float* re;                // [nr][nt][cells]
+    float* im;                // [nr][nt][cells]
+    float* total;             // [cells]
+    long cells;               // m * n
+    float inv_wavelength;     // turns per unit length, finite and >= 0
+    int amplitude;            // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int nt, nr;               // 1 .. ARRAY_MAX each
+    float etx[ARRAY_MAX][2];  // (ex, ey) of the transmit elements; entries at and past nt are not read
+    float erx[ARRAY_MAX][2];  // (ex, ey) of the receive elements; entries at and past nr are not read
+};
+struct ArraySink {
+    using Args = ArrayArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = true;
+    static_assert(ARRAY_MAX == D2D_ARRAY_MAX, "d2d_kernels.hpp and include/d2d.h disagree");
+    float total;
+    const ArrayArgs* x;  // the kernel argument: wave-uniform, read where it is used
+    int cell;
+    __device__ __forceinline__ void begin(const ArrayArgs& xa, long /*tile*/, int lane_cell) {
+        total = 0.0f;
+        x = &xa;
+        cell = lane_cell;
+    }
+    // dir: {p[1] - p[0], p[K] - p[K+1]} of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_rd(float t, float r, const float (&dir)[4]) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        const float inv = x->inv_wavelength;
+        const float a = x->amplitude == D2D_FIELD_AMP_SQRT ? copysignf(sqrtf(fabsf(t)), t) : t;
+        const float u = r * inv;
+        const float f0 = u - floorf(u);
+        float utx, uty, urx, ury;
+        const bool okt = unit_dir(dir[0], dir[1], utx, uty);
+        const bool okr = unit_dir(dir[2], dir[3], urx, ury);
+        const bool go = p && okt && okr && cell >= 0;
+        if (!go) return;  // (per lane: the loops below are uniform for the lanes that stay)
+        const int nt = x->nt, nr = x->nr;
+        const size_t cells = (size_t)x->cells;
+        for (int j = 0; j < nt; ++j) {
+            const float qt = steer_dot(x->etx[j][0], x->etx[j][1], utx, uty);
+            for (int i = 0; i < nr; ++i) {
+                const float qr = steer_dot(x->erx[i][0], x->erx[i][1], urx, ury);
+                const float f = steer_phase(f0, qt, qr, inv);
+                float c, s;
+                phasor(f, c, s);
+                const float ac = a * c, as = a * s;
+                const size_t at = (size_t)(i * nt + j) * cells + (size_t)cell;
+                x->re[at] = x->re[at] + ac;
+                x->im[at] = x->im[at] - as;
+            }
+        }
+    }
+    __device__ __forceinline__ void end(const ArrayArgs& xa, long, int) const {
+        if (cell < 0) return;
+        xa.total[cell] = total;
+    }
+};
+
+// One candidate into a sink: a sink that wants both the length and the directions takes put_rd, a WANTS_DIR sink the contribution
+// with the path's end directions, every other one the contribution with the candidate's code, order and length
 template <class S>
 __device__ __forceinline__ void sink_put(S& s, float t, unsigned long long code, int k, float r, const float (&dir)[4]) {
-    if constexpr (S::WANTS_DIR) s.put_dir(t, dir);
+    if constexpr (S::WANTS_DIR && S::WANTS_R) s.put_rd(t, r, dir);
+    else if constexpr (S::WANTS_DIR) s.put_dir(t, dir);
     else s.put(t, code, k, r);
 }
 
@@ -4123,6 +4201,19 @@ __global__ void selftest_phasor_kernel(const float* __restrict__ f, float* __res
 __global__ void selftest_angle_kernel(const float* __restrict__ dx, const float* __restrict__ dy, float* __restrict__ out, long n) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = turns(dx[i], dy[i]);
+}
+
+// unit_dir and steer_phase (d2d_steer.hpp) on the device, for comparison with their host build (tests/test_gpu_array_response.py):
+// in = dx, dy, f0, qt, qr, inv and out = ux, uy, ok (0 / 1), f, n values each
+__global__ void selftest_steer_kernel(const float* __restrict__ in, float* __restrict__ out, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float ux, uy;
+    const bool ok = unit_dir(in[i], in[n + i], ux, uy);
+    out[i] = ux;
+    out[n + i] = uy;
+    out[2 * n + i] = ok ? 1.0f : 0.0f;
+    out[3 * n + i] = steer_phase(in[2 * n + i], in[3 * n + i], in[4 * n + i], in[5 * n + i]);
 }
 
 // Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per

@@ -101,6 +101,14 @@ class PowerAngleProfile(NamedTuple):
     total: np.ndarray  # fp32 [m, n]: the sum over all candidates, the fused map bit for bit
 
 
+class ArrayResponse(NamedTuple):
+    """Result of :meth:`Context.array_response` (include/d2d.h: d2d_array_response_launch)."""
+
+    re: np.ndarray     # fp32 [nr, nt, m, n]: real part of H[i, j], the coherent sum between transmit element j and receive element i
+    im: np.ndarray     # fp32 [nr, nt, m, n]: imaginary part
+    total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
+
+
 FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
 ANGLE_ENDS = {"tx": L.D2D_ANGLE_AT_TX, "rx": L.D2D_ANGLE_AT_RX}
 
@@ -130,6 +138,7 @@ class Context:
         self._field = False  # a launch_coherent_field was accepted
         self._freq_nf = 0  # planes of the last launch_frequency_response that was accepted
         self._angle_nbins = 0  # bins of the last launch_power_angle that was accepted
+        self._array_shape = None  # (nr, nt) of the last launch_array_response that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -418,6 +427,16 @@ class Context:
         out = np.empty_like(dx)
         L.check(self._lib.d2d_selftest_angle(self._ctx, dx, dy, dx.size, out))
         return out
+
+    def selftest_steer(self, dx, dy, f0, qt, qr, inv):
+        """``unit_dir(dx, dy)`` and ``steer_phase(f0, qt, qr, inv)`` as the array response computes them on the device
+        (include/d2d.h: must equal the host build of d2d_steer.hpp bit for bit).  Returns ``(ux, uy, ok, f)``, ``ok`` as bool."""
+        a = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (dx, dy, f0, qt, qr, inv)]
+        if any(v.size != a[0].size for v in a):
+            raise ValueError("the six inputs must have one size")
+        ux, uy, ok, f = (np.empty_like(a[0]) for _ in range(4))
+        L.check(self._lib.d2d_selftest_steer(self._ctx, *a, a[0].size, ux, uy, ok, f))
+        return ux, uy, ok != 0.0, f
 
     def get_map(self) -> np.ndarray:
         out = np.empty(self.shape, np.float32)
@@ -719,6 +738,53 @@ class Context:
         pa = PowerAngleProfile(bins=np.empty((self._angle_nbins,) + shape, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_power_angle(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in pa)))
         return pa
+
+    def array_response(self, params: L.Params, fixed, inv_wavelength: float, tx_elements, rx_elements, amplitude="sqrt") -> "ArrayResponse":
+        """The channel matrix of every cell of the resident grid between a transmit array and a receive array: the coherent sum of
+        :meth:`coherent_field` for every pair of a transmit element ``j`` and a receive element ``i``, each contribution's phase
+        steered by the plane-wave model, ``(r - e_tx[j] . u_tx - e_rx[i] . u_rx) * inv_wavelength`` turns with the unit directions
+        of departure and arrival -- one launch of the array-response build of the culled sweep (include/d2d.h:
+        d2d_array_response_launch holds the definition; ImagePath, hard or hard_sigmoid validity, every fused function).
+        ``tx_elements`` ``[nt, 2]`` and ``rx_elements`` ``[nr, 2]`` are element offsets ``(ex, ey)`` in length units from the
+        terminal's position, finite, 1 to ``D2D_ARRAY_MAX`` = 8 of each (:func:`differt2d_amd.utils.ula` makes a uniform linear
+        array); the transmit array sits at the transmitter and the receive array at the receiver in both grid roles.
+        ``inv_wavelength``, ``amplitude``, ``params`` and ``fixed`` as for :meth:`coherent_field`.  A pair of zero offsets equals
+        :meth:`coherent_field` bit for bit wherever every path has a direction at both ends.  A refused launch leaves the previous
+        result readable.  Every other product of the context is left untouched.
+
+        Returns an :class:`ArrayResponse`: ``re`` and ``im``, fp32 ``[nr, nt, m, n]``, and ``total`` (the fused map, bit for bit),
+        fp32 ``[m, n]``.  :func:`differt2d_amd.utils.channel_matrix`, :func:`differt2d_amd.utils.beamformed_power`,
+        :func:`differt2d_amd.utils.singular_values` and :func:`differt2d_amd.utils.mimo_capacity` turn it into complex ``H``, the
+        power behind two beamformers, the singular values and the capacity of every cell."""
+        self.launch_array_response(params, fixed, inv_wavelength, tx_elements, rx_elements, amplitude)
+        return self.get_array_response()
+
+    def launch_array_response(self, params: L.Params, fixed, inv_wavelength: float, tx_elements, rx_elements, amplitude="sqrt"):
+        """The launch of :meth:`array_response` alone (asynchronous, like :meth:`launch`; the lists are copied by the call)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        etx = np.ascontiguousarray(tx_elements, dtype=np.float32).reshape(-1, 2)
+        erx = np.ascontiguousarray(rx_elements, dtype=np.float32).reshape(-1, 2)
+        if isinstance(amplitude, str):
+            if amplitude not in FIELD_AMPLITUDES:
+                raise L.D2DError(-1, f"array_response: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
+            amplitude = FIELD_AMPLITUDES[amplitude]
+        # (an empty list still hands the library a pointer: it refuses a count of 0)
+        ktx = etx if etx.size else np.zeros((1, 2), np.float32)
+        krx = erx if erx.size else np.zeros((1, 2), np.float32)
+        L.check(self._lib.d2d_array_response_launch(self._ctx, C.byref(params), fixed, float(inv_wavelength), int(amplitude), int(etx.shape[0]),
+                                                    ktx, int(erx.shape[0]), krx))
+        self._array_shape = (int(erx.shape[0]), int(etx.shape[0]))
+
+    def get_array_response(self) -> "ArrayResponse":
+        """Synchronises and returns the result of the last :meth:`launch_array_response` that was accepted."""
+        if self._array_shape is None:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_array_response(self._ctx, None, None, None))
+            raise L.D2DError(-5, "launch_array_response must come first")
+        shape = tuple(self.shape)
+        planes = self._array_shape + shape
+        ar = ArrayResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
+        L.check(self._lib.d2d_get_array_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in ar)))
+        return ar
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

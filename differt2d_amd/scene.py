@@ -1280,6 +1280,67 @@ class Scene(Plottable):
         return self._grid_angle(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, at, nbins, origin, path_cls, min_order,
                                 max_order, order, filter_objects, kwargs)
 
+    def _grid_array(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelength, tx_elements, rx_elements, amplitude, path_cls,
+                    min_order, max_order, order, filter_objects, kwargs):
+        """Shared driver of the two array-response sweeps: one launch of the array-response build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the array response comes from a fused sweep (a function "
+                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+                                       "(Context.valid_paths: every valid path of every cell, with its length), their points "
+                                       "(Context.trace_paths) and add fun's steered phasors on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the array response covers ImagePath only, not path_cls={path_cls.__name__}")
+        with np.errstate(divide="ignore"):
+            inv = F(1) / F(wavelength)  # fp32: one division (an infinite wavelength gives 0: every phase is 0)
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.array_response(params, pt.xy, inv, tx_elements, rx_elements, amplitude)
+
+        return results()
+
+    def array_response_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelength: float, tx_elements, rx_elements,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The channel matrix of every cell between antenna arrays at one ``wavelength``: for every transmitter, ``H[i, j]`` is the
+        coherent field of :meth:`coherent_field_on_receivers_grid` between element ``j`` of a transmit array at the transmitter and
+        element ``i`` of a receive array at the receiver ``(X[i, j], Y[i, j])``, under the plane-wave (far-field) model: a path of
+        length ``r`` that leaves along the unit vector ``u_tx`` and is seen at the receiver along ``u_rx`` has the phase
+        ``(r - e_tx[j] . u_tx - e_rx[i] . u_rx) / wavelength`` turns.  ``tx_elements`` ``[nt, 2]`` and ``rx_elements`` ``[nr, 2]``
+        are the elements' offsets from the terminal's position in length units (:func:`differt2d_amd.utils.ula`), at most 8 each.
+        Yields ``(tx name, ArrayResponse(re, im, total))`` (:class:`differt2d_amd.engine.ArrayResponse`: ``re`` and ``im`` fp32
+        ``[nr, nt, m, n]``; ``total`` is the incoherent sum, the fused map bit for bit); one fused kernel launch per transmitter
+        (include/d2d.h: d2d_array_response_launch holds the exact definition).  :func:`differt2d_amd.utils.channel_matrix`,
+        :func:`differt2d_amd.utils.beamformed_power`, :func:`differt2d_amd.utils.singular_values` and
+        :func:`differt2d_amd.utils.mimo_capacity` work on the result.
+
+        The neglected spherical-wave phase is about ``pi |e_perp|**2 / (wavelength r)``; the phase resolution is the coherent
+        field's.  ``fun`` must be natively fused (:mod:`differt2d_amd.utils`), the path class ``ImagePath``, the validity hard
+        (``approx=False``) or ``hard_sigmoid``; anything else raises :class:`D2DUnsupported`.  For another callable
+        :meth:`Context.valid_paths` and :meth:`Context.trace_paths` hold every valid path and its points for a sum on the host."""
+        return self._grid_array(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, wavelength, tx_elements, rx_elements,
+                                amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def array_response_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelength: float, tx_elements, rx_elements,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`array_response_on_receivers_grid`: one result per receiver, the transmitter (and its
+        array) sits at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_array(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelength, tx_elements, rx_elements,
+                                amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

@@ -203,6 +203,65 @@ def pattern_power(profile, gains):
     return np.tensordot(g, bins, axes=(0, 0))
 
 
+def ula(n, spacing, orientation=0.0):
+    """The element offsets of a uniform linear array of ``n`` elements ``spacing`` apart (length units), centred on the terminal, along
+    the direction ``orientation`` (radians, counter-clockwise from +x): fp32 ``[n, 2]``, element ``k`` at
+    ``(k - (n - 1) / 2) * spacing * (cos, sin)(orientation)``.  Computed in float64 and rounded once; what
+    ``Scene.array_response_on_receivers_grid`` and ``Context.array_response`` take as ``tx_elements`` / ``rx_elements``."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"ula needs n >= 1, got {n}")
+    k = (np.arange(n, dtype=np.float64) - (n - 1) / 2.0) * float(spacing)
+    return np.stack([k * np.cos(float(orientation)), k * np.sin(float(orientation))], axis=1).astype(np.float32)
+
+
+def channel_matrix(ar):
+    """The complex channel matrix ``H = re + 1j * im``, complex64 ``[nr, nt, m, n]``, of an ``ArrayResponse``
+    (``Scene.array_response_on_receivers_grid``, ``Context.array_response``) or any object with ``re`` and ``im``."""
+    re = np.asarray(ar.re, dtype=np.float32)
+    im = np.asarray(ar.im, dtype=np.float32)
+    h = np.empty(re.shape, np.complex64)
+    h.real = re
+    h.imag = im
+    return h
+
+
+def _cells_last(ar):
+    """H of an ArrayResponse as complex128 [..., nr, nt]: the cells in front, one matrix per cell."""
+    return np.moveaxis(channel_matrix(ar).astype(np.complex128), (0, 1), (-2, -1))
+
+
+def beamformed_power(ar, w_rx, w_tx):
+    """The power behind two beamformers, ``|w_rx^H H w_tx|**2`` per cell, ``[m, n]``, for an ``ArrayResponse`` and the complex weights
+    ``w_rx[nr]`` and ``w_tx[nt]`` (not normalised here).  On the host, in float64 / complex128."""
+    h = _cells_last(ar)
+    wr = np.asarray(w_rx, dtype=np.complex128).reshape(-1)
+    wt = np.asarray(w_tx, dtype=np.complex128).reshape(-1)
+    if wr.size != h.shape[-2] or wt.size != h.shape[-1]:
+        raise ValueError(f"beamformed_power needs {h.shape[-2]} receive and {h.shape[-1]} transmit weights, got {wr.size} and {wt.size}")
+    y = np.einsum("i,...ij,j->...", wr.conj(), h, wt)
+    return y.real**2 + y.imag**2
+
+
+def singular_values(ar):
+    """The singular values of every cell's channel matrix, descending: float64 ``[min(nr, nt), m, n]``, for an ``ArrayResponse``.  A
+    cell with a non-finite entry gives NaN."""
+    h = _cells_last(ar)
+    bad = ~np.isfinite(h).all(axis=(-2, -1))
+    s = np.linalg.svd(np.where(bad[..., None, None], 0.0, h), compute_uv=False)
+    s[bad] = np.nan
+    return np.moveaxis(s, -1, 0)
+
+
+def mimo_capacity(ar, snr):
+    """The capacity of every cell's channel with equal power per transmit element and no channel knowledge at the transmitter,
+    ``log2 det(I + snr / nt * H H^H)`` in bit/s/Hz, float64 ``[m, n]``, for an ``ArrayResponse``; ``snr`` is linear (not dB), relative
+    to the units of ``|H|**2``.  From the singular values: ``sum_k log2(1 + snr / nt * s_k**2)``."""
+    s = singular_values(ar)
+    nt = np.asarray(ar.re).shape[1]
+    return np.log2(1.0 + float(snr) / nt * s * s).sum(axis=0)
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

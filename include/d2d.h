@@ -699,6 +699,67 @@ int d2d_power_angle_launch(d2d_ctx* ctx, const d2d_params* params, const float* 
  * another grid (the result goes with the grid). */
 int d2d_get_power_angle(d2d_ctx* ctx, float* out, float* total);
 
+/* ---- array response: the coherent field for every pair of a transmit and a receive antenna element (no reference counterpart:
+ *      the nr x nt channel matrix H per cell; beamforming gain, MIMO rank and capacity maps and spatial correlation follow from
+ *      it) ---- */
+
+#define D2D_ARRAY_MAX 8 /* most elements of either array of one d2d_array_response_launch */
+/* Launches the array-response build of the culled forward sweep for the fixed end point `fixed` on the ctx stream (asynchronous),
+ * for the current scene, candidate mask and grid.  `params`, `fixed`, the grid role, `inv_wavelength` and `amplitude` are exactly
+ * as for d2d_coherent_field_launch.  tx_elems: fp32 [nt][2], rx_elems: fp32 [nr][2]: element offsets (ex, ey) in length units
+ * from the terminal's position, every component finite; nt and nr each in 1 .. D2D_ARRAY_MAX.  The transmit array sits at p[0]
+ * and the receive array at p[K+1] in both grid roles (the points of d2d_power_angle_launch: in a TX grid the cell is p[0]).
+ * Definition, per cell:
+ *
+ *     total = +0.0f ; re[i][j] = im[i][j] = +0.0f
+ *     for candidates in the sweep's enumeration order:
+ *         t = valid * fun ; r = path_length(points)          // as d2d_coherent_field_launch gets them
+ *         total = total + t                                   // the fused map bit for bit
+ *         if (t == 0) continue
+ *         a  = amplitude == SQRT ? copysignf(sqrtf(fabsf(t)), t) : t
+ *         u  = r * inv_wavelength ; f0 = u - floorf(u)        // exactly the coherent field's phase
+ *         (utx, uty, okt) = unit(p[1]-p[0]) ; (urx, ury, okr) = unit(p[K]-p[K+1])
+ *             // unit(dx,dy): n = sqrtf(dx*dx + dy*dy) ; ok = n > 0 && n <= FLT_MAX ; ux = dx / n ; uy = dy / n   (IEEE sqrt and division)
+ *         if (!(okt && okr)) continue                         // a path without a direction at an end enters no pair (total has it)
+ *         for j < nt: qt = etx[j].x * utx + etx[j].y * uty
+ *           for i < nr: qr = erx[i].x * urx + erx[i].y * ury
+ *             w = (qt + qr) * inv_wavelength ; v = f0 - w ; f = v - floorf(v) ; if (f >= 1.0f) f = 0.0f   // (-tiny + 1 rounds to 1)
+ *             (c, s) = phasor(f)
+ *             re[i][j] = re[i][j] + a * c ; im[i][j] = im[i][j] - a * s
+ *
+ * All arithmetic is fp32 with one rounding per operation and no contraction; differt2d_amd/csrc/d2d_steer.hpp holds unit and the
+ * pair's phase for host and device.  Outputs: re and im, fp32 [nr][nt][m][n], and total, fp32 [m][n].
+ *
+ *   - Entry (i, j) depends only on etx[j] and erx[i]: permuted, duplicated or truncated element lists give permuted, equal or
+ *     leading planes, bit for bit.
+ *   - A pair whose two offsets are (+-0, +-0) equals d2d_coherent_field_launch bit for bit wherever no contribution lacks a
+ *     direction at an end (the line of sight of a cell that IS the fixed end point is such a contribution).
+ *   - This is the plane-wave (far-field) model: the phase of pair (i, j) is (r - etx[j] . u_tx - erx[i] . u_rx) / lambda, and the
+ *     neglected spherical-wave phase is about pi |e_perp|^2 / (lambda r) for an offset e_perp across the path.
+ *   - The phase resolution is that of the coherent field: ulp(r / lambda) turns.
+ *
+ * One pass of one kernel (one wave per 8 x 8 patch; re and im are zeroed on the stream in front of it, every lane is the only writer
+ * of its cell's column: plain loads and stores, no atomics, the same bits run to run).  The element lists are copied during the
+ * call.  The result is kept with the grid until the next such launch.  The resident value / gradient maps, the work history, the
+ * schedule of the fused sweeps, the records of d2d_valid_paths and every other product (delay profile, strongest paths, coherent
+ * field, frequency response, power-angle profile) are not touched.  Fused functions as for d2d_coherent_field_launch.
+ * D2D_ERR_INVALID: nt or nr outside 1 .. D2D_ARRAY_MAX; an element component that is NaN or infinite (the message ends in its
+ * index); inv_wavelength negative, NaN or infinite; an unknown amplitude.  No list is read unless its count is in range.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): what d2d_coherent_field_launch refuses, with outputs of 8 * nr * nt + 4
+ * bytes per cell held against half of the free device memory -- all decided before anything is enqueued.  A refused launch leaves
+ * the previous result as it was. */
+int d2d_array_response_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */, float inv_wavelength,
+                              int32_t amplitude, int32_t nt, const float* tx_elems /* [nt][2] */, int32_t nr,
+                              const float* rx_elems /* [nr][2] */);
+/* Synchronises and copies the result of the last d2d_array_response_launch that was accepted to the arrays that are not NULL
+ * (re, im: [nr][nt][m][n] with that launch's counts, total: [m][n]).  D2D_ERR_STATE before a launch and after a d2d_set_grid of
+ * another grid (the result goes with the grid). */
+int d2d_get_array_response(d2d_ctx* ctx, float* re, float* im, float* total);
+/* unit_dir and steer_phase of d2d_steer.hpp on the device, for comparison with their host build: ok[i] = unit_dir(dx[i], dy[i]) as
+ * 0 / 1 with ux[i], uy[i], and f[i] = steer_phase(f0[i], qt[i], qr[i], inv[i]). */
+int d2d_selftest_steer(d2d_ctx* ctx, const float* dx, const float* dy, const float* f0, const float* qt, const float* qr,
+                       const float* inv, int64_t n, float* ux, float* uy, float* ok, float* f);
+
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
  *      RCCL all-gather on the ctx stream; the scene VJP with one all-reduce) ------------------------------------- */
