@@ -155,6 +155,8 @@ SYMBOLS = [
     ("d2d_get_array_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32]),
     ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("d2d_field_coefs_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("d2d_get_field_coefs_vjp", C.c_int, [_ctx, C.c_void_p]),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),

@@ -212,6 +212,16 @@ struct d2d_ctx {
         d_array_re.release(); d_array_im.release(); d_array_total.release();
         array_nt = array_nr = 0;
     }
+    // coefficient adjoint of the frequency response (d2d_field_coefs_vjp_launch): the cotangent planes, the per-patch rows and the
+    // reduced result, kept until the next accepted launch, dropped with the grid and with the scene
+    DevBuf<float> d_cg_re, d_cg_im;  // [nf][m][n] each: the caller's cotangents
+    DevBuf<float> d_cg_partial;      // [patches][N]
+    DevBuf<double> d_cg_out;         // [N]
+    bool have_cg = false;            // d_cg_out holds the result of an accepted launch for the CURRENT grid and scene
+    void drop_cg() {
+        d_cg_re.release(); d_cg_im.release(); d_cg_partial.release(); d_cg_out.release();
+        have_cg = false;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -759,6 +769,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->coef.clear();              // (the reflection coefficients belong to the objects of the previous scene)
     c->cust_C = -1;               // (a host-evaluated path function's rows belong to the paths of the previous scene)
     c->have_vjp = false;          // d_vjp was sized for (and computed from) the previous scene
+    c->have_cg = false;           // (... and so was the frequency response's coefficient adjoint)
     c->have_kernel_time = false;
     c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
@@ -915,6 +926,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->drop_angle();    // ... and the power-angle profile's
         c->drop_array();    // ... and the array response's
         c->drop_freq();     // ... and the frequency response's
+        c->drop_cg();       // ... and its coefficient adjoint's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -2441,6 +2453,77 @@ static int frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, const f
     return D2D_OK;
 }
 
+// Coefficient adjoint of the frequency response: ONE preparation of the culled sweep with the coefficient-free contribution
+// valid / (h^2 + r^2) (D2D_FUN_RECEIVED_POWER with a numerator of 1, as d2d_valid_paths substitutes D2D_FUN_ONE), one pass of the
+// sink kernel per chunk of FREQ_CHUNK wavelengths into the zeroed per-patch rows, then the fixed-order fp64 reduction of the rows.
+// The cotangents are copied before the call returns; the launches are asynchronous.  Every check comes before anything is enqueued,
+// and a refused launch leaves the previous result as it was.
+static int field_coefs_vjp_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                                  const float* re_bar, const float* im_bar) {
+    static const char who[] = "d2d_field_coefs_vjp_launch";
+    if (!c || !fixed || !inv_wavelength || !re_bar || !im_bar) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before %s", who);
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before %s", who);
+    if (p_in->fun_id != D2D_FUN_RECEIVED_POWER_PER_OBJECT)
+        return fail(D2D_ERR_UNSUPPORTED, "%s: fun_id %d has no reflection coefficient per object to differentiate by (D2D_FUN_RECEIVED_POWER_PER_OBJECT only)",
+                    who, p_in->fun_id);
+    if ((rc = check_fused_sink(c, p_in, who, "a host function has no coefficients", "the gradient is always overwritten"))) return rc;
+    {
+        std::string err;
+        if ((rc = d2d_host::freq_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "%s: %s", who, err.c_str());
+    }
+    if ((rc = set_device(c))) return rc;
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    pp.fun_id = D2D_FUN_RECEIVED_POWER;  // with a numerator of 1: a contribution is then valid / (h^2 + r^2)
+    pp.r_coef = 1.0f;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    const size_t cells = (size_t)c->m * (size_t)c->n, N = (size_t)c->N, tiles = (size_t)s.tiles;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_cg_re.n + c->d_cg_im.n + c->d_cg_partial.n) * sizeof(float);
+        if (!d2d_host::coef_vjp_fits(cells, nf, tiles, N, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "%s: cotangents of %zu cells (%zu bytes per cell) and %zu rows of %zu partial sums exceed half of the free device memory (%zu bytes free)",
+                        who, cells, 8 * (size_t)nf, tiles, N, mem_free);
+    }
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, who, lds))) return rc;
+    c->have_cg = false;  // from here on the buffers change
+    const size_t planes = (size_t)nf * cells;
+    if ((rc = c->d_cg_re.ensure(planes)) || (rc = c->d_cg_im.ensure(planes)) || (rc = c->d_cg_partial.ensure(tiles * N)) || (rc = c->d_cg_out.ensure(N)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_cg_re.p, re_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_cg_im.p, im_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays are free again when the call returns
+    if (N > 0 && tiles > 0) {
+        HIP_TRY(hipMemsetAsync(c->d_cg_partial.p, 0, tiles * N * sizeof(float), c->stream));
+        for (int32_t i = 0; i < d2d_host::freq_chunks(nf); ++i) {
+            const d2d_host::FreqChunk ch = d2d_host::freq_chunk(nf, i);
+            d2d::CoefGradArgs g;
+            g.re_bar = c->d_cg_re.p + (size_t)ch.first * cells;
+            g.im_bar = c->d_cg_im.p + (size_t)ch.first * cells;
+            g.coef = c->d_coef.p;
+            g.partial = c->d_cg_partial.p;
+            g.cells = (long)cells;
+            for (int32_t j = 0; j < d2d::FREQ_CHUNK; ++j) g.inv[j] = j < ch.count ? inv_wavelength[ch.first + j] : 0.0f;
+            g.nf = ch.count;
+            g.amplitude = amplitude;
+            g.N = c->N;
+            HIP_TRY(d2d::launch_sink<d2d::CoefGradSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
+        }
+        hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)N), dim3(256), 0, c->stream, c->d_cg_partial.p, (long)tiles, c->N, c->d_cg_out.p, 0);
+        HIP_TRY(hipGetLastError());
+    } else {
+        HIP_TRY(hipMemsetAsync(c->d_cg_out.p, 0, (N ? N : 1) * sizeof(double), c->stream));
+    }
+    c->have_cg = true;
+    return D2D_OK;
+}
+
 // Power-angle launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed
 // planes, every lane storing its cell's total at the end.  Asynchronous.  Every check comes before anything is enqueued, and a
 // refused launch leaves the previous result as it was.
@@ -2583,6 +2666,24 @@ int d2d_get_power_angle(d2d_ctx* c, float* out, float* total) {
     const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
     if (out) HIP_TRY(hipMemcpyAsync(out, c->d_angle.p, bytes * (size_t)c->angle_nbins, hipMemcpyDeviceToHost, c->stream));
     if (total) HIP_TRY(hipMemcpyAsync(total, c->d_angle_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
+
+int d2d_field_coefs_vjp_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                               const float* re_bar, const float* im_bar) {
+    return field_coefs_vjp_launch(c, p, fixed, inv_wavelength, nf, amplitude, re_bar, im_bar);
+}
+
+int d2d_get_field_coefs_vjp(d2d_ctx* c, double* coef_bar) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (!c->have_scene || !c->have_cg || !c->d_cg_out.p)
+        return fail(D2D_ERR_STATE, "d2d_field_coefs_vjp_launch must come first (its result goes with the grid and the scene)");
+    if (!coef_bar) return fail(D2D_ERR_INVALID, "coef_bar is NULL");
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(coef_bar, c->d_cg_out.p, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return D2D_OK;
 }

@@ -310,6 +310,20 @@ inline FreqChunk freq_chunk(int32_t nf, int32_t i) {
     return ch;
 }
 
+// ---- memory of the frequency response's coefficient adjoint (d2d_field_coefs_vjp_launch, d2d::CoefGradSink) -----------
+// The cotangent planes take 8 nf bytes per cell and the partial rows 4 bytes per patch and object.  Refused like the frequency
+// response: above half of the device memory that is free, counting what the buffers hold already as free.  No product is formed
+// that could wrap: each share is held against a quotient of what the budget has left.
+inline bool coef_vjp_fits(size_t cells, int32_t nf, size_t patches, size_t n_objects, size_t mem_free, size_t held_bytes) {
+    size_t budget = mem_free / 2 + held_bytes / 2;
+    const size_t per_cell = 8 * (size_t)nf;
+    if (cells > budget / per_cell) return false;
+    budget -= cells * per_cell;
+    if (patches == 0 || n_objects == 0) return true;
+    if (patches > budget / sizeof(float)) return false;
+    return n_objects <= budget / sizeof(float) / patches;
+}
+
 // ---- parameters and outputs of the power-angle profile (d2d_power_angle_launch, d2d::AngleSink) ---------------------
 // D2D_ERR_INVALID: an end that is neither D2D_ANGLE_AT_TX nor D2D_ANGLE_AT_RX, an origin that is NaN or outside [0, 1) turns,
 // nbins outside 1 .. D2D_ANGLE_BINS_MAX.

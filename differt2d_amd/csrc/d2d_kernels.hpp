@@ -2057,6 +2057,111 @@ struct FreqSink {
     }
 };
 
+// CoefGradSink (d2d_field_coefs_vjp_launch): the reverse-mode product of the frequency response with respect to the per-object
+// reflection coefficients, for up to FREQ_CHUNK wavelengths of one sweep (include/d2d.h holds the definition).  The host runs the
+// sweep with D2D_FUN_RECEIVED_POWER and a numerator of 1, so a contribution is s = valid / (h^2 + r^2): what does not depend on the
+// coefficients.  begin() loads the lane's cotangents re_bar[j][cell], im_bar[j][cell] into registers (zeros for lanes outside the
+// grid, cell < 0, which evaluate a clamped copy of an edge cell and would count it twice).  Per candidate that some lane of the wave
+// has a non-zero s from: the candidate's coefficients, their left fold num and the products P_i of the OTHER coefficients are formed
+// on wave-uniform values (the walls come out of the wave-uniform code, the table is read with scalar loads; nothing is divided by a
+// coefficient); per lane g = sum_j (re_bar[j] * c_j - im_bar[j] * s_j) with the frequency response's own phasors, and the weight
+// W = g * s (SQRT: g * sqrtf(s)), forced to 0.0f in lanes that do not contribute.  wave_sum(W) runs in uniform control flow, and lane 0
+// adds S * Q_i to the patch's row partial[patch][cand[i]] for every position i: one writer per row, candidates in order, plain
+// load-add-store, no atomics -- the same bits run to run.  The rows are zeroed on the stream in front of the first chunk's launch,
+// accumulate over the chunks' launches and are reduced in patch order into fp64 by vjp_reduce_kernel.  j is a compile-time index
+// behind the wave-uniform guard j < nf, as in FreqSink.
+struct CoefGradArgs {
+    const float* re_bar;    // [nf][cells]: this chunk's cotangent planes
+    const float* im_bar;    // [nf][cells]
+    const float* coef;      // [N] reflection coefficients (wave-uniform index -> scalar loads)
+    float* partial;         // [patches][N] per-patch sums, zeroed in front of the first chunk
+    long cells;             // m * n
+    float inv[FREQ_CHUNK];  // turns per unit length, finite and >= 0; entries at and past nf are not read
+    int nf;                 // 1 .. FREQ_CHUNK
+    int amplitude;          // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int N;                  // objects: the length of a row
+};
+struct CoefGradSink {
+    using Args = CoefGradArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
+    float rb[FREQ_CHUNK], ib[FREQ_CHUNK];
+    float inv[FREQ_CHUNK];
+    const float* coef;
+    float* row;  // partial[patch]
+    int nf;
+    bool root;
+    bool live;  // cell >= 0
+    __device__ __forceinline__ void begin(const CoefGradArgs& x, long tile, int lane_cell) {
+        live = lane_cell >= 0;
+        static_for<0, FREQ_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            rb[J] = ib[J] = 0.0f;
+            inv[J] = x.inv[J];
+            if (J < x.nf && live) {
+                const size_t at = (size_t)J * (size_t)x.cells + (size_t)lane_cell;
+                rb[J] = x.re_bar[at];
+                ib[J] = x.im_bar[at];
+            }
+        });
+        coef = x.coef;
+        row = x.partial + (size_t)tile * (size_t)x.N;
+        nf = x.nf;
+        root = x.amplitude == D2D_FIELD_AMP_SQRT;
+    }
+    __device__ __forceinline__ void put(float t, unsigned long long code, int k, float r) {
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (k == 0 || __ballot(p) == 0ull) return;  // (the line of sight holds no coefficient)
+        // wave-uniform: the candidate's walls and coefficients, their fold and the products of the others
+        int w[D2D_MAX_ORDER];
+        float cf[D2D_MAX_ORDER], q[D2D_MAX_ORDER];
+        float num = 1.0f;
+#pragma unroll
+        for (int i = 0; i < D2D_MAX_ORDER; ++i) {
+            w[i] = __builtin_amdgcn_readfirstlane((int)((code >> (12 * i)) & 0xfffull));
+            cf[i] = 1.0f;
+            if (i < k) {
+                cf[i] = cmem(coef)[w[i]];
+                num = num * cf[i];
+            }
+        }
+        if (root && num == 0.0f) return;  // sign(num) sqrt|num| is not differentiable there: no term
+        const float half = root ? 2.0f * sqrtf(fabsf(num)) : 1.0f;
+#pragma unroll
+        for (int i = 0; i < D2D_MAX_ORDER; ++i) {
+            float others = 1.0f;
+#pragma unroll
+            for (int o = 0; o < D2D_MAX_ORDER; ++o)
+                if (o != i && o < k) others = others * cf[o];
+            q[i] = root ? others / half : others;
+        }
+        // per lane: the cotangents against this candidate's phasors
+        float g = 0.0f;
+        if (p) {
+            static_for<0, FREQ_CHUNK>([&](auto JJ) {
+                constexpr int J = decltype(JJ)::value;
+                if (J < nf) {
+                    const float u = r * inv[J];
+                    const float f = u - floorf(u);
+                    float c, s;
+                    phasor(f, c, s);
+                    const float rc = rb[J] * c, is = ib[J] * s;
+                    g = g + (rc - is);
+                }
+            });
+        }
+        const float sw = root ? sqrtf(t) : t;
+        const float W = (p && live) ? g * sw : 0.0f;
+        const float S = wave_sum(W);  // every lane of the wave is here: the exits above are wave-uniform
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < D2D_MAX_ORDER; ++i)
+                if (i < k) row[w[i]] = row[w[i]] + S * q[i];
+        }
+    }
+    __device__ __forceinline__ void end(const CoefGradArgs&, long, int) const {}
+};
+
 // AngleSink (d2d_power_angle_launch): every contribution that is not exactly zero is added to the bin of the direction in which its
 // path leaves the transmitter or reaches the receiver -- the power-angle profile out[nbins][cells] (include/d2d.h holds the
 // definition), zeroed on the stream in front of the launch -- beside the running fp32 sum of every contribution (the fused map, bit

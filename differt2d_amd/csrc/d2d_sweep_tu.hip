@@ -2,7 +2,7 @@
 // per-mode launcher (declared in d2d_launch.hpp) that d2d.hip's dispatchers call.  Compiled by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2
 //   taken from the region lists (LISTED), 9 fwd_coop}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}: all 27 pairs;
-//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (record, bin, strongest-path, coherent-field, frequency-response, power-angle and array-response builds) for modes 0 and 1 (no sigmoid instance)
+//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (record, bin, strongest-path, coherent-field, frequency-response, coefficient-adjoint, power-angle and array-response builds) for modes 0 and 1 (no sigmoid instance)
 #include <type_traits>
 
 #include "d2d_launch.hpp"
@@ -186,6 +186,10 @@ hipError_t launch_sink_m<TU_MODE, FieldSink>(bool txg, int max_order, dim3 grid,
 template <>
 hipError_t launch_sink_m<TU_MODE, FreqSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const FreqArgs& f) {
     return launch_sink_tu<FreqSink>(txg, max_order, grid, lds, s, a, f);
+}
+template <>
+hipError_t launch_sink_m<TU_MODE, CoefGradSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const CoefGradArgs& g) {
+    return launch_sink_tu<CoefGradSink>(txg, max_order, grid, lds, s, a, g);
 }
 template <>
 hipError_t launch_sink_m<TU_MODE, AngleSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const AngleArgs& g) {

@@ -701,6 +701,46 @@ class Context:
         L.check(self._lib.d2d_get_frequency_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
         return fr
 
+    def field_coefs_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt") -> np.ndarray:
+        """The reverse-mode product of :meth:`frequency_response` with respect to the per-object reflection coefficients:
+        ``coef_bar[w] = sum_j sum_cells (re_bar * d re / d coef[w] + im_bar * d im / d coef[w])``, float64 ``[N]``, from ONE
+        preparation of the culled sweep and one kernel pass per 8 wavelengths, as the forward product (include/d2d.h:
+        d2d_field_coefs_vjp_launch holds the definition).  ``params.fun`` must be ``received_power_per_object`` with the
+        coefficients of :meth:`set_reflection_coefs`; ``inv_wavelengths`` and ``amplitude`` as for :meth:`frequency_response`;
+        ``re_bar`` and ``im_bar`` are the cotangents of its planes, ``[nf, m, n]`` (taken as fp32, copied by the call; non-finite
+        values propagate).  A coefficient of zero has a gradient with ``"linear"``; with ``"sqrt"`` a candidate whose coefficients
+        multiply to zero adds no term.  Walls that no contributing path touches get exactly ``+0.0``.  A refused launch leaves the
+        previous result readable.  The resident value map, the scene VJP of :meth:`launch_vg` and the other products' results are
+        not touched.  :func:`differt2d_amd.utils.field_misfit` gives the loss and the cotangents of a least-squares fit."""
+        self.launch_field_coefs_vjp(params, fixed, inv_wavelengths, re_bar, im_bar, amplitude)
+        return self.get_field_coefs_vjp()
+
+    def launch_field_coefs_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt"):
+        """The launch of :meth:`field_coefs_vjp` alone (the list and the cotangents are copied by the call; the kernels are
+        asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        if isinstance(amplitude, str):
+            if amplitude not in FIELD_AMPLITUDES:
+                raise L.D2DError(-1, f"field_coefs_vjp: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
+            amplitude = FIELD_AMPLITUDES[amplitude]
+        rb = np.ascontiguousarray(re_bar, dtype=np.float32)
+        ib = np.ascontiguousarray(im_bar, dtype=np.float32)
+        planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
+        if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
+            raise L.D2DError(-1, f"field_coefs_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
+        keep = inv if inv.size else np.zeros(1, np.float32)  # (an empty list still hands the library pointers: it refuses nf = 0)
+        if not inv.size:
+            rb = ib = np.zeros(1, np.float32)
+        L.check(self._lib.d2d_field_coefs_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
+                                                     int(amplitude), rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
+
+    def get_field_coefs_vjp(self) -> np.ndarray:
+        """Synchronises and returns the result of the last :meth:`launch_field_coefs_vjp` that was accepted: float64 ``[N]``."""
+        out = np.zeros(max(self.n_objects, 1), np.float64)
+        L.check(self._lib.d2d_get_field_coefs_vjp(self._ctx, out.ctypes.data_as(C.c_void_p)))
+        return out[: self.n_objects]
+
     def power_angle(self, params: L.Params, fixed, end, origin_turns: float, nbins: int) -> "PowerAngleProfile":
         """The power-angle profile of every cell of the resident grid: the fused sweep's contributions ``valid * fun`` binned by
         the direction in which their path leaves the transmitter (``end="tx"``, departure) or by the direction from the receiver

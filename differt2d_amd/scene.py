@@ -1215,6 +1215,65 @@ class Scene(Plottable):
         return self._grid_response(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
                                    amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
 
+    def _grid_response_coefs_vjp(self, X, Y, fixed_items, grid_is_rx, fun_kwargs, re_bar, im_bar, wavelengths, inv_wavelengths,
+                                 amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
+        """Shared driver of the two coefficient adjoints of the frequency response: one launch per fixed end point."""
+        from .utils import received_power_per_object
+
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        if (wavelengths is None) == (inv_wavelengths is None):
+            raise ValueError("the frequency response takes exactly one of wavelengths= and inv_wavelengths=")
+        native, common = self._sweep_params(received_power_per_object, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun_kwargs={fun_kwargs!r}: received_power_per_object takes r_coef and height only")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the frequency response covers ImagePath only, not path_cls={path_cls.__name__}")
+        if wavelengths is not None:
+            with np.errstate(divide="ignore"):
+                inv = F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the forward product does
+        else:
+            inv = np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+        bar_of = lambda bar, pt_name: bar[pt_name] if isinstance(bar, Mapping) else bar
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.field_coefs_vjp(params, pt.xy, inv, bar_of(re_bar, pt_name), bar_of(im_bar, pt_name), amplitude)
+
+        return results()
+
+    def frequency_response_coefs_vjp_on_receivers_grid(
+        self, X, Y, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The gradient of a loss on :meth:`frequency_response_on_receivers_grid` with respect to the reflection coefficient of
+        every object, for ``fun=`` :func:`differt2d_amd.utils.received_power_per_object`: material calibration, one coefficient
+        per wall fitted to a measured channel.  ``re_bar`` and ``im_bar`` are the loss's derivatives with respect to the planes
+        ``re`` and ``im``, ``[nf, m, n]`` (:func:`differt2d_amd.utils.field_misfit` gives them for a least-squares fit) -- one
+        pair for every transmitter, or mappings from the transmitters' names to their pairs.  The coefficients and ``height`` are
+        passed exactly as for ``received_power_per_object``: ``coef[j] = getattr(objects[j], "r_coef", fun_kwargs["r_coef"])``.
+        The wavelengths, ``amplitude``, the path class and the validity are those of the forward method.  Yields ``(tx name,
+        coef_bar)``, float64 ``[len(objects)]``, from one sweep per 8 wavelengths (include/d2d.h: d2d_field_coefs_vjp_launch holds
+        the definition and what is exact about it).  Gradients with respect to the geometry are not computed."""
+        return self._grid_response_coefs_vjp(X, Y, list(self.transmitters.items()), True, fun_kwargs, re_bar, im_bar, wavelengths,
+                                             inv_wavelengths, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def frequency_response_coefs_vjp_on_transmitters_grid(
+        self, X, Y, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`frequency_response_coefs_vjp_on_receivers_grid`: one result per receiver, the
+        transmitter sits at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_response_coefs_vjp(X, Y, list(self.receivers.items()), False, fun_kwargs, re_bar, im_bar, wavelengths,
+                                             inv_wavelengths, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
     def _grid_angle(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, at, nbins, origin, path_cls, min_order, max_order, order,
                     filter_objects, kwargs):
         """Shared driver of the two power-angle sweeps: one launch of the power-angle build per fixed end point."""

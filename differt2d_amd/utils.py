@@ -164,6 +164,22 @@ def impulse_response(fr, inv_wavelength_step):
     return np.fft.ifft(h, axis=0), 1.0 / (nf * step)
 
 
+def field_misfit(fr, target, weights=None):
+    """The least-squares misfit of a ``FrequencyResponse`` to a measured complex channel, and its cotangents:
+    ``L = 1/2 * sum w * |H - target|**2`` over every plane and cell, with ``H = re + 1j * im``.  ``target`` is complex
+    ``[nf, m, n]`` (or broadcasts to it), ``weights`` real and non-negative with a shape that broadcasts too (``None``: 1).  Returns
+    ``(loss, re_bar, im_bar)``: the loss in float64 and ``d L / d re = w * (re - target.real)``, ``d L / d im = w * (im -
+    target.imag)`` as fp32 ``[nf, m, n]`` -- what ``Context.field_coefs_vjp`` and
+    ``Scene.frequency_response_coefs_vjp_on_receivers_grid`` take.  On the host, in float64, rounded to fp32 once."""
+    re = np.asarray(fr.re, dtype=np.float64)
+    im = np.asarray(fr.im, dtype=np.float64)
+    t = np.broadcast_to(np.asarray(target, dtype=np.complex128), re.shape)
+    w = np.ones(re.shape) if weights is None else np.broadcast_to(np.asarray(weights, dtype=np.float64), re.shape)
+    dr, di = re - t.real, im - t.imag
+    loss = 0.5 * float(np.sum(w * (dr * dr + di * di)))
+    return loss, np.ascontiguousarray(w * dr, dtype=np.float32), np.ascontiguousarray(w * di, dtype=np.float32)
+
+
 class AngularStatistics(NamedTuple):
     """Result of :func:`angular_statistics`: float64 ``[m, n]`` each."""
 

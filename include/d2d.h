@@ -642,6 +642,62 @@ int d2d_frequency_response_launch(d2d_ctx* ctx, const d2d_params* params, const 
  * of another grid (the result goes with the grid). */
 int d2d_get_frequency_response(d2d_ctx* ctx, float* re, float* im, float* total);
 
+/* ---- calibrating reflection coefficients: the reverse-mode product of the frequency response with respect to the per-object
+ *      coefficients (no reference counterpart: fit one coefficient per wall to a measured complex channel H_meas(f_j, cell)) ---- */
+
+/* Launches the coefficient adjoint of the frequency response for the fixed end point `fixed` on the ctx stream, for the current
+ * scene, candidate mask, grid and reflection coefficients.  Inputs: the cotangent planes re_bar, im_bar (host arrays, fp32
+ * [nf][m][n], copied before the call returns; the kernels that follow are asynchronous).  Output (d2d_get_field_coefs_vjp):
+ *     coef_bar[N] = sum_j sum_cells (re_bar * d re / d coef + im_bar * d im / d coef)
+ * where re and im are those of d2d_frequency_response_launch with fun_id = D2D_FUN_RECEIVED_POWER_PER_OBJECT.
+ * K3-G `d2d::CoefGradSink`, definition:
+ *
+ * - `params`, `fixed`, the grid role, `inv_wavelength[nf]` and `amplitude` are as for `d2d_frequency_response_launch`. `nf` lies in `1..D2D_FREQ_MAX`.
+ * - `params.fun_id` must be `D2D_FUN_RECEIVED_POWER_PER_OBJECT`.
+ * - Coefficients must be set with `d2d_set_reflection_coefs`. Without them the call returns `D2D_ERR_STATE`, as the sweeps do.
+ *
+ * Per cell, and per patch in the kernel:
+ *
+ *     for candidates in the sweep's enumeration order (walls cand[0..K)):
+ *         s = valid * (1 / (h² + r²))        // fp32: the sweep's own contribution for received_power with numerator 1
+ *                                             // (host: fun_id = RECEIVED_POWER, fnum[] = 1, the caller's h2 -- the way
+ *                                             //  d2d_valid_paths substitutes D2D_FUN_ONE); r = the fp32 path length the sinks get
+ *         if (s == 0) continue                // exact zeros of either sign; culled candidates are such zeros
+ *         num = left fold of coef over cand ; P_i = product of the coefficients at the OTHER positions, formed explicitly (K <= 4)
+ *         LINEAR:  Q_i = P_i                              // a = s*num ; d a / d coef[cand[i]] = s * P_i.  A zero coefficient is legal and HAS a gradient
+ *         SQRT:    if (num == 0) continue                 // a = sign(num) sqrt(s) sqrt|num| is not differentiable there: defined as no term
+ *                  Q_i = P_i / (2 sqrtf(|num|)) ; s := sqrtf(s)
+ *         g = sum_{j<nf} ( re_bar[j][cell] * c_j - im_bar[j][cell] * s_j )   with (c_j, s_j) = phasor(frac(r * inv_wavelength[j]))
+ *                                             // since re += a c and im -= a s
+ *         for every position i:  coef_bar[cand[i]] += g * s * Q_i          // a wall that occurs twice gets both terms
+ *
+ * - Nothing is ever divided by a coefficient.
+ * - `coef_bar` is fp64 `[N]`. Walls that no contributing candidate touches are exactly `+0.0`.
+ * - A NaN contribution makes the entries of that candidate's walls NaN and no others.
+ *
+ * Unlike the forward products this is a sum over cells: it is not defined bit for bit against an oracle but to a derived bound
+ * (tests/field_coefs_vjp_oracle.py).  What is exact: the same call gives the same bits run to run and whatever ran before it on the
+ * context; all-zero cotangents give all +0.0; cotangents scaled by 2 give exactly doubled entries.
+ *
+ * In the kernel the arithmetic above is fp32 without contraction: g is a left fold over j, the lanes' weights g * s are summed over
+ * the wave's 64 lanes (cells outside the grid weigh 0.0f), and one lane adds S * Q_i to the patch's row of a [patches][N] fp32 buffer
+ * -- one writer per row, candidates in order, chunks of 8 wavelengths in order, plain loads and stores, no atomics -- which a
+ * fixed-order reduction sums in patch order into fp64.  One preparation of the culled sweep and ceil(nf / 8) passes of one kernel,
+ * exactly as the frequency response does it.  The launch touches none of: the resident value / gradient maps, the scene VJP of
+ * d2d_power_map_vg_launch (d2d_get_reflection_coefs_vjp is unaffected), the work history, the other products' results.
+ * D2D_ERR_INVALID: nf outside 1 .. D2D_FREQ_MAX; an inv_wavelength entry that is negative, NaN or infinite (the message names its
+ * index); an unknown amplitude.  Non-finite cotangents are NOT refused: they propagate.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): any other fun_id, sigmoid validity, MinPath / FermatPath, D2D_OUT_ADD, a TX
+ * grid whose sweep would not be culled, more than 4 095 objects, or cotangents (8 * nf bytes per cell) plus partial rows
+ * (4 * patches * N bytes) above half of the free device memory -- all decided before anything is enqueued.  A refused launch
+ * leaves the previous result readable. */
+int d2d_field_coefs_vjp_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                               const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude,
+                               const float* re_bar /* [nf][m][n] */, const float* im_bar /* [nf][m][n] */);
+/* Synchronises and copies the result of the last accepted d2d_field_coefs_vjp_launch to coef_bar (fp64 [N]).  D2D_ERR_STATE before
+ * a launch and after a d2d_set_grid / d2d_set_scene of another grid or scene (the result goes with both). */
+int d2d_get_field_coefs_vjp(d2d_ctx* ctx, double* coef_bar /* [N] */);
+
 /* ---- power-angle profile: the fused sweep binned by the direction in which a path leaves the transmitter or reaches the
  *      receiver (no reference counterpart: angle-of-departure / angle-of-arrival spectra, angular spread, sector selection and
  *      the power a directional antenna receives follow from it) ---- */
