@@ -153,6 +153,9 @@ SYMBOLS = [
     ("d2d_get_power_angle", C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     ("d2d_array_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_float, C.c_int32, C.c_int32, _f32p, C.c_int32, _f32p]),
     ("d2d_get_array_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("d2d_array_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32, _f32p, C.c_int32,
+                                                      _f32p]),
+    ("d2d_get_array_frequency_response", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32]),
     ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_field_coefs_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -222,6 +222,14 @@ struct d2d_ctx {
         d_cg_re.release(); d_cg_im.release(); d_cg_partial.release(); d_cg_out.release();
         have_cg = false;
     }
+    // wideband array response (d2d_array_frequency_response_launch): nf * nr * nt planes of re and im and the total of every cell,
+    // kept until the next accepted launch, dropped with the grid
+    DevBuf<float> d_wide_re, d_wide_im, d_wide_total;  // [wide_nf][wide_nr][wide_nt][m][n] twice, [m][n]
+    int32_t wide_nf = 0, wide_nt = 0, wide_nr = 0;     // counts of the last accepted launch; 0: no result
+    void drop_wide() {
+        d_wide_re.release(); d_wide_im.release(); d_wide_total.release();
+        wide_nf = wide_nt = wide_nr = 0;
+    }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
         d_rec.release(); d_rec_xys.release(); d_rec_loss.release(); d_rec_valid.release(); d_rec_len.release();
@@ -926,6 +934,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->drop_angle();    // ... and the power-angle profile's
         c->drop_array();    // ... and the array response's
         c->drop_freq();     // ... and the frequency response's
+        c->drop_wide();     // ... and the wideband array response's
         c->drop_cg();       // ... and its coefficient adjoint's
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
@@ -2629,9 +2638,98 @@ static int array_response_launch(d2d_ctx* c, const d2d_params* p_in, const float
     return D2D_OK;
 }
 
+// Wideband array-response launch of the culled forward sweep with the caller's path function: ONE preparation, then one pass of
+// the sink kernel per chunk of WIDE_CHUNK wavelengths over the same SweepArgs (as d2d_frequency_response_launch does), every pass
+// adding into the zeroed plane blocks of its chunk and the first storing the total.  Asynchronous.  Every check comes before
+// anything is enqueued, and a refused launch leaves the previous result as it was.
+static_assert(d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK, "d2d_host.hpp and d2d_kernels.hpp disagree");
+static int array_frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, const float* inv_wavelength, int32_t nf,
+                                           int32_t amplitude, int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems) {
+    static const char who[] = "d2d_array_frequency_response_launch";
+    if (!c || !fixed || !inv_wavelength || !tx_elems || !rx_elems) return fail(D2D_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before %s", who);
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before %s", who);
+    if ((rc = check_fused_sink(c, p_in, who, "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths",
+                               "the channel matrices are always overwritten")))
+        return rc;
+    {
+        std::string err;
+        if ((rc = d2d_host::wide_params(inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems, err))) return fail(rc, "%s: %s", who, err.c_str());
+    }
+    if ((rc = set_device(c))) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = (c->d_wide_re.n + c->d_wide_im.n + c->d_wide_total.n) * sizeof(float);
+        if (!d2d_host::wide_fits(cells, nf, nt, nr, mem_free, held))
+            return fail(D2D_ERR_UNSUPPORTED, "%s: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)", who, cells,
+                        d2d_host::wide_bytes_per_cell(nf, nt, nr), mem_free);
+    }
+    d2d_params pp = *p_in;
+    pp.strict_nan = 0;
+    const d2d_params* p = &pp;
+    Sweep s(c, p, fixed);
+    size_t lds = 0;
+    if ((rc = prep_sink_sweep(c, s, who, lds))) return rc;
+    c->wide_nf = c->wide_nt = c->wide_nr = 0;  // from here on the buffers change
+    const size_t block = (size_t)nr * (size_t)nt * cells;  // one wavelength's planes
+    const size_t planes = (size_t)nf * block;
+    if ((rc = c->d_wide_re.ensure(planes)) || (rc = c->d_wide_im.ensure(planes)) || (rc = c->d_wide_total.ensure(cells))) return rc;
+    HIP_TRY(hipMemsetAsync(c->d_wide_re.p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_wide_im.p, 0, planes * sizeof(float), c->stream));
+    if (s.tiles > 0)
+        for (int32_t i = 0; i < d2d_host::wide_chunks(nf); ++i) {
+            const d2d_host::FreqChunk ch = d2d_host::wide_chunk(nf, i);
+            d2d::ArrayFreqArgs g = {};
+            g.re = c->d_wide_re.p + (size_t)ch.first * block;
+            g.im = c->d_wide_im.p + (size_t)ch.first * block;
+            g.total = ch.with_total ? c->d_wide_total.p : nullptr;
+            g.cells = (long)cells;
+            g.amplitude = amplitude;
+            g.nf = ch.count;
+            g.nt = nt;
+            g.nr = nr;
+            for (int32_t f = 0; f < ch.count; ++f) g.inv[f] = inv_wavelength[ch.first + f];
+            for (int32_t j = 0; j < nt; ++j) g.etx[j][0] = tx_elems[2 * j], g.etx[j][1] = tx_elems[2 * j + 1];
+            for (int32_t k = 0; k < nr; ++k) g.erx[k][0] = rx_elems[2 * k], g.erx[k][1] = rx_elems[2 * k + 1];
+            HIP_TRY(d2d::launch_sink<d2d::ArrayFreqSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
+        }
+    else HIP_TRY(hipMemsetAsync(c->d_wide_total.p, 0, cells * sizeof(float), c->stream));
+    c->wide_nf = nf;
+    c->wide_nt = nt;
+    c->wide_nr = nr;
+    return D2D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int d2d_array_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                                        int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems) {
+    return array_frequency_response_launch(c, p, fixed, inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems);
+}
+
+int d2d_get_array_frequency_response(d2d_ctx* c, int32_t first, int32_t count, float* re, float* im, float* total) {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (c->wide_nf < 1 || !c->d_wide_re.p) return fail(D2D_ERR_STATE, "d2d_array_frequency_response_launch must come first (its result goes with the grid)");
+    if (first < 0 || count < 1 || count > c->wide_nf - first)
+        return fail(D2D_ERR_INVALID, "d2d_get_array_frequency_response: first %d and count %d are no range of the result's %d wavelengths", first, count, c->wide_nf);
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t cells = (size_t)c->m * (size_t)c->n;
+    const size_t block = (size_t)c->wide_nr * (size_t)c->wide_nt * cells;
+    const size_t bytes = (size_t)count * block * sizeof(float);
+    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_wide_re.p + (size_t)first * block, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_wide_im.p + (size_t)first * block, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_wide_total.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
 
 int d2d_array_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude, int32_t nt,
                               const float* tx_elems, int32_t nr, const float* rx_elems) {

@@ -380,6 +380,43 @@ inline bool array_fits(size_t cells, int32_t nt, int32_t nr, size_t mem_free, si
     return cells <= budget / array_bytes_per_cell(nt, nr);
 }
 
+// ---- parameters, outputs and launch plan of the wideband array response (d2d_array_frequency_response_launch, d2d::ArrayFreqSink) ---
+// D2D_ERR_INVALID: what freq_params refuses of the list (nf outside 1 .. D2D_FREQ_MAX, an entry that is negative, NaN or infinite: the
+// message names its index; an unknown amplitude), then what array_params refuses of the element lists (a count outside
+// 1 .. D2D_ARRAY_MAX, a component that is NaN or infinite: the message ends in the element's index).  No list is read unless its
+// count is in range.
+inline int wide_params(const float* inv_wavelength, int32_t nf, int32_t amplitude, int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems,
+                       std::string& err) {
+    if (int rc = freq_params(inv_wavelength, nf, amplitude, err)) return rc;
+    return array_params(nt, tx_elems, nr, rx_elems, 0.0f, amplitude, err);
+}
+// Per cell: nf * nr * nt planes of re and im and one total, 4 bytes each (at most 524 292 with the counts in range; 0 with a count
+// that is not: wide_fits then refuses).  Refused like the array response: outputs above half of the device memory that is free,
+// counting what the buffers hold already as free (tests/native/array_frequency_response_host.cpp).  No product with cells is
+// formed: cells is held against a quotient.
+inline size_t wide_bytes_per_cell(int32_t nf, int32_t nt, int32_t nr) {
+    if (nf < 1 || nf > D2D_FREQ_MAX || nt < 1 || nt > D2D_ARRAY_MAX || nr < 1 || nr > D2D_ARRAY_MAX) return 0;
+    return 8 * (size_t)nf * (size_t)nr * (size_t)nt + 4;
+}
+inline bool wide_fits(size_t cells, int32_t nf, int32_t nt, int32_t nr, size_t mem_free, size_t held_bytes) {
+    const size_t per_cell = wide_bytes_per_cell(nf, nt, nr);
+    if (per_cell == 0) return false;
+    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
+    return cells <= budget / per_cell;
+}
+// The launches of one call: ceil(nf / WIDE_CHUNK) passes of the sink kernel over the same prepared sweep, as freq_chunk plans the
+// frequency response's.  Launch i takes the entries first .. first + count - 1 of the list, adds into their plane blocks from block
+// `first` on, and the first launch alone stores total.
+constexpr int32_t WIDE_CHUNK = 32;  // = d2d::WIDE_CHUNK (d2d_kernels.hpp)
+inline int32_t wide_chunks(int32_t nf) { return (nf + WIDE_CHUNK - 1) / WIDE_CHUNK; }
+inline FreqChunk wide_chunk(int32_t nf, int32_t i) {
+    FreqChunk ch;
+    ch.first = i * WIDE_CHUNK;
+    ch.count = std::min<int32_t>(WIDE_CHUNK, nf - ch.first);
+    ch.with_total = i == 0;
+    return ch;
+}
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

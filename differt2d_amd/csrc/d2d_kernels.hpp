@@ -2304,6 +2304,87 @@ struct ArraySink {
     }
 };
 
+// ArrayFreqSink (d2d_array_frequency_response_launch): ArraySink's channel matrix at up to WIDE_CHUNK wavelengths of one sweep --
+// plane block f is, bit for bit, ArraySink's re / im [nr][nt][cells] at inv[f] (include/d2d.h holds the definition).  The planes
+// re / im [nf][nr][nt][cells] of the chunk live in memory, zeroed on the stream in front of the passes; the running fp32 sum of
+// every contribution stays in a register until end(), which stores it where `total` is not null (the first chunk's pass).  Per
+// contribution that is not exactly zero, a and the two unit directions are formed once, and then
+//     for f < nf: u = r * inv[f] ;  f0 = u - floorf(u)
+//       for j < nt: qt = steer_dot(etx[j], utx, uty)
+//         for i < nr: qr = steer_dot(erx[i], urx, ury) ;  ph = steer_phase(f0, qt, qr, inv[f]) ;  (c, s) = phasor(ph)
+//                     re[f][i][j][cell] = re[f][i][j][cell] + a * c ;  im[f][i][j][cell] = im[f][i][j][cell] - a * s
+// in fp32 without contraction, candidates in the sweep's order.  The three loops are wave-uniform run-time loops over lists that
+// come by value in the kernel argument and are read by scalar loads: no per-lane array exists (one indexed at run time goes to
+// scratch), so registers do not bound the chunk.  Every plane is its own accumulator: the nesting does not reach
+// the result.  All of it is skipped for a candidate that no lane of the wave has a non-zero contribution from.  A lane is the only
+// writer of its cell's column and reads back what it stored itself: plain loads and stores, no atomics, the same bits run to run.
+// Lanes outside the grid (cell < 0) never write.  (f * nr + i) * nt + j < nf * nr * nt and cell < cells, so every address is
+// inside the chunk's 2 * nf * nr * nt * cells planes.
+constexpr int WIDE_CHUNK = 32;  // wavelengths per pass: internal, not in the ABI (d2d_host::WIDE_CHUNK is the host's copy)
+struct ArrayFreqArgs {
+    float* re;                // [nf][nr][nt][cells]: this chunk's planes
+    float* im;                // [nf][nr][nt][cells]
+    float* total;             // [cells] or null
+    long cells;               // m * n
+    int amplitude;            // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int nf;                   // 1 .. WIDE_CHUNK
+    int nt, nr;               // 1 .. ARRAY_MAX each
+    float inv[WIDE_CHUNK];    // turns per unit length, finite and >= 0; entries at and past nf are not read
+    float etx[ARRAY_MAX][2];  // (ex, ey) of the transmit elements; entries at and past nt are not read
+    float erx[ARRAY_MAX][2];  // (ex, ey) of the receive elements; entries at and past nr are not read
+};
+static_assert(WIDE_CHUNK >= 8 && WIDE_CHUNK <= 64 && (WIDE_CHUNK & (WIDE_CHUNK - 1)) == 0, "WIDE_CHUNK is a power of two in 8 .. 64");
+static_assert(sizeof(SweepArgs) + sizeof(ArrayFreqArgs) <= 4096, "power_sink_kernel's arguments must fit the 4 KiB kernel-argument segment");
+struct ArrayFreqSink {
+    using Args = ArrayFreqArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = true;
+    float total;
+    const ArrayFreqArgs* x;  // the kernel argument: wave-uniform, read where it is used
+    int cell;
+    __device__ __forceinline__ void begin(const ArrayFreqArgs& xa, long /*tile*/, int lane_cell) {
+        total = 0.0f;
+        x = &xa;
+        cell = lane_cell;
+    }
+    // dir: {p[1] - p[0], p[K] - p[K+1]} of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_rd(float t, float r, const float (&dir)[4]) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        const float a = x->amplitude == D2D_FIELD_AMP_SQRT ? copysignf(sqrtf(fabsf(t)), t) : t;
+        float utx, uty, urx, ury;
+        const bool okt = unit_dir(dir[0], dir[1], utx, uty);
+        const bool okr = unit_dir(dir[2], dir[3], urx, ury);
+        const bool go = p && okt && okr && cell >= 0;
+        if (!go) return;  // (per lane: the loops below are uniform for the lanes that stay)
+        const int nf = x->nf, nt = x->nt, nr = x->nr;
+        const size_t cells = (size_t)x->cells;
+        for (int f = 0; f < nf; ++f) {
+            const float inv = x->inv[f];
+            const float u = r * inv;
+            const float f0 = u - floorf(u);
+            for (int j = 0; j < nt; ++j) {
+                const float qt = steer_dot(x->etx[j][0], x->etx[j][1], utx, uty);
+                for (int i = 0; i < nr; ++i) {
+                    const float qr = steer_dot(x->erx[i][0], x->erx[i][1], urx, ury);
+                    const float ph = steer_phase(f0, qt, qr, inv);
+                    float c, s;
+                    phasor(ph, c, s);
+                    const float ac = a * c, as = a * s;
+                    const size_t at = (size_t)((f * nr + i) * nt + j) * cells + (size_t)cell;
+                    x->re[at] = x->re[at] + ac;
+                    x->im[at] = x->im[at] - as;
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void end(const ArrayFreqArgs& xa, long, int) const {
+        if (cell < 0 || xa.total == nullptr) return;
+        xa.total[cell] = total;
+    }
+};
+
 // One candidate into a sink: a sink that wants both the length and the directions takes put_rd, a WANTS_DIR sink the contribution
 // with the path's end directions, every other one the contribution with the candidate's code, order and length
 template <class S>

@@ -52,6 +52,8 @@ template <> hipError_t launch_sink_m<MODE_HARD, AngleSink>(bool, int, dim3, size
 template <> hipError_t launch_sink_m<MODE_HSIG, AngleSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const AngleArgs&);
 template <> hipError_t launch_sink_m<MODE_HARD, ArraySink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayArgs&);
 template <> hipError_t launch_sink_m<MODE_HSIG, ArraySink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayArgs&);
+template <> hipError_t launch_sink_m<MODE_HARD, ArrayFreqSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayFreqArgs&);
+template <> hipError_t launch_sink_m<MODE_HSIG, ArrayFreqSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayFreqArgs&);
 
 // ---- by-mode dispatchers ----
 // `listed`: the LISTED build (orders >= 2 from the region candidate lists, a.rl); otherwise the enumerating build, which
@@ -71,7 +73,8 @@ hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
 // power_sink_kernel<MODE, MAXK, TXG, Sink>: the culled sweep into a sink -- RecSink the record build, BinSink the per-cell
 // power-delay profile, TopSink the per-cell strongest paths, FieldSink the coherent field, FreqSink the frequency response, CoefGradSink its
-// adjoint w.r.t. the per-object reflection coefficients, AngleSink the power-angle profile, ArraySink the array response (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
+// adjoint w.r.t. the per-object reflection coefficients, AngleSink the power-angle profile, ArraySink the array response,
+// ArrayFreqSink the wideband array response (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
 template <class Sink>
 hipError_t launch_sink(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const typename Sink::Args& x);
 

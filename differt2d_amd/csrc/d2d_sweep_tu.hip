@@ -2,7 +2,7 @@
 // per-mode launcher (declared in d2d_launch.hpp) that d2d.hip's dispatchers call.  Compiled by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2
 //   taken from the region lists (LISTED), 9 fwd_coop}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}: all 27 pairs;
-//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (record, bin, strongest-path, coherent-field, frequency-response, coefficient-adjoint, power-angle and array-response builds) for modes 0 and 1 (no sigmoid instance)
+//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (record, bin, strongest-path, coherent-field, frequency-response, coefficient-adjoint, power-angle, array-response and wideband array-response builds) for modes 0 and 1 (no sigmoid instance)
 #include <type_traits>
 
 #include "d2d_launch.hpp"
@@ -198,6 +198,10 @@ hipError_t launch_sink_m<TU_MODE, AngleSink>(bool txg, int max_order, dim3 grid,
 template <>
 hipError_t launch_sink_m<TU_MODE, ArraySink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const ArrayArgs& g) {
     return launch_sink_tu<ArraySink>(txg, max_order, grid, lds, s, a, g);
+}
+template <>
+hipError_t launch_sink_m<TU_MODE, ArrayFreqSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const ArrayFreqArgs& g) {
+    return launch_sink_tu<ArrayFreqSink>(txg, max_order, grid, lds, s, a, g);
 }
 #else
 #error "unknown D2D_TU_FAMILY"

@@ -109,6 +109,14 @@ class ArrayResponse(NamedTuple):
     total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
 
 
+class ArrayFrequencyResponse(NamedTuple):
+    """Result of :meth:`Context.array_frequency_response` (include/d2d.h: d2d_array_frequency_response_launch)."""
+
+    re: np.ndarray     # fp32 [nf, nr, nt, m, n]: real part of H[f, i, j], the array response's H[i, j] at inv_wavelengths[f]
+    im: np.ndarray     # fp32 [nf, nr, nt, m, n]: imaginary part
+    total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit (None where not asked for)
+
+
 FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
 ANGLE_ENDS = {"tx": L.D2D_ANGLE_AT_TX, "rx": L.D2D_ANGLE_AT_RX}
 
@@ -139,6 +147,7 @@ class Context:
         self._freq_nf = 0  # planes of the last launch_frequency_response that was accepted
         self._angle_nbins = 0  # bins of the last launch_power_angle that was accepted
         self._array_shape = None  # (nr, nt) of the last launch_array_response that was accepted
+        self._wide_shape = None  # (nf, nr, nt) of the last launch_array_frequency_response that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -825,6 +834,65 @@ class Context:
         ar = ArrayResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_array_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in ar)))
         return ar
+
+    def array_frequency_response(self, params: L.Params, fixed, inv_wavelengths, tx_elements, rx_elements,
+                                 amplitude="sqrt") -> "ArrayFrequencyResponse":
+        """The channel matrices of every cell of the resident grid at many wavelengths: :meth:`array_response` at every entry of
+        ``inv_wavelengths`` (``1 / lambda_f`` in turns per unit length: fp32, finite and ``>= 0``, 1 to ``D2D_FREQ_MAX`` = 1024
+        entries) from ONE check, preparation and zeroing and one kernel pass per chunk of entries, where an :meth:`array_response`
+        call per entry repeats them and the whole culled sweep (include/d2d.h: d2d_array_frequency_response_launch holds the
+        definition).  Plane block ``f`` equals ``array_response(params, fixed, inv_wavelengths[f], tx_elements, rx_elements,
+        amplitude)`` bit for bit, whatever else the lists hold; a pair of zero offsets equals :meth:`frequency_response` bit for
+        bit wherever every path has a direction at both ends.  ``tx_elements``, ``rx_elements``, ``amplitude``, ``params`` and
+        ``fixed`` as for :meth:`array_response`.  A refused launch leaves the previous result readable.  Every other product of
+        the context is left untouched.
+
+        Returns an :class:`ArrayFrequencyResponse`: ``re`` and ``im``, fp32 ``[nf, nr, nt, m, n]``, and ``total`` (the fused map,
+        bit for bit), fp32 ``[m, n]``.  :func:`differt2d_amd.utils.channel_tensor`, :func:`differt2d_amd.utils.array_response_at`
+        and :func:`differt2d_amd.utils.wideband_capacity` turn it into complex ``H``, the :class:`ArrayResponse` of one
+        wavelength and the capacity averaged over the band.  The result takes ``8 * nf * nr * nt`` bytes per cell:
+        :meth:`get_array_frequency_response` reads a range of wavelengths where the whole does not fit the host."""
+        self.launch_array_frequency_response(params, fixed, inv_wavelengths, tx_elements, rx_elements, amplitude)
+        return self.get_array_frequency_response()
+
+    def launch_array_frequency_response(self, params: L.Params, fixed, inv_wavelengths, tx_elements, rx_elements, amplitude="sqrt"):
+        """The launch of :meth:`array_frequency_response` alone (asynchronous, like :meth:`launch`; the lists are copied by the call)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        etx = np.ascontiguousarray(tx_elements, dtype=np.float32).reshape(-1, 2)
+        erx = np.ascontiguousarray(rx_elements, dtype=np.float32).reshape(-1, 2)
+        if isinstance(amplitude, str):
+            if amplitude not in FIELD_AMPLITUDES:
+                raise L.D2DError(-1, f"array_frequency_response: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
+            amplitude = FIELD_AMPLITUDES[amplitude]
+        # (an empty list still hands the library a pointer: it refuses a count of 0)
+        kinv = inv if inv.size else np.zeros(1, np.float32)
+        ktx = etx if etx.size else np.zeros((1, 2), np.float32)
+        krx = erx if erx.size else np.zeros((1, 2), np.float32)
+        L.check(self._lib.d2d_array_frequency_response_launch(self._ctx, C.byref(params), fixed, kinv, int(inv.size), int(amplitude),
+                                                              int(etx.shape[0]), ktx, int(erx.shape[0]), krx))
+        self._wide_shape = (int(inv.size), int(erx.shape[0]), int(etx.shape[0]))
+
+    def get_array_frequency_response(self, first=0, count=None, with_total=True) -> "ArrayFrequencyResponse":
+        """Synchronises and returns wavelengths ``first .. first + count - 1`` (``count=None``: all from ``first`` on) of the result
+        of the last :meth:`launch_array_frequency_response` that was accepted: ``re`` and ``im`` are ``[count, nr, nt, m, n]``.
+        ``with_total=False`` leaves ``total`` out (``None``).  A range outside the result is refused by the library."""
+        if self._wide_shape is None:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_array_frequency_response(self._ctx, 0, 1, None, None, None))
+            raise L.D2DError(-5, "launch_array_frequency_response must come first")
+        nf, nr, nt = self._wide_shape
+        first = int(first)
+        count = nf - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > nf:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_array_frequency_response(self._ctx, first, count, None, None, None))
+            raise L.D2DError(-1, f"get_array_frequency_response: first={first}, count={count} are no range of {nf} wavelengths")
+        shape = tuple(self.shape)
+        planes = (count, nr, nt) + shape
+        afr = ArrayFrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32),
+                                     total=np.empty(shape, np.float32) if with_total else None)
+        L.check(self._lib.d2d_get_array_frequency_response(self._ctx, first, count,
+                                                           *(None if a is None else a.ctypes.data_as(C.c_void_p) for a in afr)))
+        return afr
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

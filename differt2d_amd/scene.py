@@ -1400,6 +1400,73 @@ class Scene(Plottable):
         return self._grid_array(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelength, tx_elements, rx_elements,
                                 amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
 
+    def _grid_array_response(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelengths, inv_wavelengths, tx_elements,
+                             rx_elements, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
+        """Shared driver of the two wideband array-response sweeps: one launch of the wideband build per fixed end point."""
+        X = np.ascontiguousarray(X, dtype=F)
+        Y = np.ascontiguousarray(Y, dtype=F)
+        if (wavelengths is None) == (inv_wavelengths is None):
+            raise ValueError("the array frequency response takes exactly one of wavelengths= and inv_wavelengths=")
+        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
+        if native is None:
+            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the array frequency response comes from a fused sweep (a "
+                                       "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+                                       "records (Context.valid_paths: every valid path of every cell, with its length), their "
+                                       "points (Context.trace_paths) and add fun's steered phasors on the host")
+        if self._solver_of(path_cls) != "image":
+            raise L.D2DUnsupported(-4, f"the array frequency response covers ImagePath only, not path_cls={path_cls.__name__}")
+        if wavelengths is not None:
+            with np.errstate(divide="ignore"):
+                inv = F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the frequency response does
+        else:
+            inv = np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
+        name, extra = native
+        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
+        ctx = self._ctx()
+
+        def results():
+            for pt_name, pt in fixed_items:
+                self._upload_for(ctx, native, filter_objects)
+                ctx.set_grid(X, Y)
+                yield pt_name, ctx.array_frequency_response(params, pt.xy, inv, tx_elements, rx_elements, amplitude)
+
+        return results()
+
+    def array_frequency_response_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None, tx_elements,
+        rx_elements, amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1,
+        order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The channel matrices of every cell at many wavelengths: the ``H`` of :meth:`array_response_on_receivers_grid` at every
+        entry of a list from one preparation of the sweep, instead of one whole call each.  Exactly one of ``wavelengths`` (each
+        becomes ``float32(1) / float32(w)``, as the frequency response makes them) and ``inv_wavelengths`` (``1 / lambda`` in turns
+        per unit length, passed as fp32 unchanged) must be given: 1 to 1024 entries, each inverse finite and ``>= 0``.
+        ``tx_elements`` and ``rx_elements`` as for :meth:`array_response_on_receivers_grid`.  Yields ``(tx name,
+        ArrayFrequencyResponse(re, im, total))`` (:class:`differt2d_amd.engine.ArrayFrequencyResponse`: ``re`` and ``im`` fp32
+        ``[nf, nr, nt, m, n]``, ``total`` fp32 ``[m, n]``, the fused map bit for bit).  Plane block ``f`` equals the array response at
+        entry ``f`` bit for bit, whatever else the lists hold (include/d2d.h: d2d_array_frequency_response_launch).
+        :func:`differt2d_amd.utils.channel_tensor`, :func:`differt2d_amd.utils.array_response_at` and
+        :func:`differt2d_amd.utils.wideband_capacity` give complex ``H``, one wavelength's :class:`ArrayResponse` and the capacity
+        averaged over the band.  The result takes ``8 * nf * nr * nt`` bytes per cell on the device and on the host.
+
+        ``fun``, ``amplitude``, the path class and the validity as for :meth:`array_response_on_receivers_grid`; anything else raises
+        :class:`D2DUnsupported`.  For another callable :meth:`Context.valid_paths` and :meth:`Context.trace_paths` hold every valid
+        path and its points for a sum on the host."""
+        return self._grid_array_response(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                         tx_elements, rx_elements, amplitude, path_cls, min_order, max_order, order, filter_objects,
+                                         kwargs)
+
+    def array_frequency_response_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None, tx_elements,
+        rx_elements, amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1,
+        order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`array_frequency_response_on_receivers_grid`: one result per receiver, the transmitter (and
+        its array) sits at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_array_response(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                         tx_elements, rx_elements, amplitude, path_cls, min_order, max_order, order, filter_objects,
+                                         kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

@@ -278,6 +278,31 @@ def mimo_capacity(ar, snr):
     return np.log2(1.0 + float(snr) / nt * s * s).sum(axis=0)
 
 
+def channel_tensor(afr):
+    """The complex channel tensor ``H = re + 1j * im``, complex64 ``[nf, nr, nt, m, n]``, of an ``ArrayFrequencyResponse``
+    (``Scene.array_frequency_response_on_receivers_grid``, ``Context.array_frequency_response``) or any object with ``re`` and ``im``."""
+    return channel_matrix(afr)
+
+
+def array_response_at(afr, f):
+    """Wavelength ``f`` of an ``ArrayFrequencyResponse`` as an ``engine.ArrayResponse`` of views (``re`` and ``im`` ``[nr, nt, m, n]``,
+    nothing is copied), so that ``beamformed_power``, ``singular_values`` and ``mimo_capacity`` apply per wavelength unchanged."""
+    from .engine import ArrayResponse
+
+    return ArrayResponse(re=afr.re[f], im=afr.im[f], total=afr.total)
+
+
+def wideband_capacity(afr, snr):
+    """The capacity of every cell averaged over the band: the mean over the wavelengths ``f`` of ``mimo_capacity`` of
+    ``array_response_at(afr, f)``, float64 ``[m, n]`` in bit/s/Hz, for an ``ArrayFrequencyResponse`` and a linear ``snr``.  NaN where
+    any plane of the cell is not finite."""
+    nf = np.asarray(afr.re).shape[0]
+    acc = mimo_capacity(array_response_at(afr, 0), snr)
+    for f in range(1, nf):
+        acc = acc + mimo_capacity(array_response_at(afr, f), snr)
+    return acc / nf
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

@@ -29,8 +29,9 @@ extern "C" {
 #define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile, d2d_strongest_paths_launch /
                               d2d_get_strongest_paths, d2d_coherent_field_launch / d2d_get_coherent_field,
                               d2d_frequency_response_launch / d2d_get_frequency_response and d2d_power_angle_launch /
-                              d2d_get_power_angle are additive: no struct, enum or existing entry point changed with them, so the
-                              version did not) */
+                              d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response and
+                              d2d_array_frequency_response_launch / d2d_get_array_frequency_response are additive: no struct, enum or
+                              existing entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -811,6 +812,57 @@ int d2d_array_response_launch(d2d_ctx* ctx, const d2d_params* params, const floa
  * (re, im: [nr][nt][m][n] with that launch's counts, total: [m][n]).  D2D_ERR_STATE before a launch and after a d2d_set_grid of
  * another grid (the result goes with the grid). */
 int d2d_get_array_response(d2d_ctx* ctx, float* re, float* im, float* total);
+/* ---- K3-W, wideband array response: the channel matrices at many wavelengths from one preparation of the culled sweep (the
+ *      nf x nr x nt channel tensor per cell: per-subcarrier capacity, wideband beamforming, spatial correlation across a band) ---- */
+
+/* Launches the wideband array-response build of the culled forward sweep for the fixed end point `fixed` on the ctx stream
+ * (asynchronous), for the current scene, candidate mask and grid.
+ *
+ * - `params`, `fixed`, the grid role, `amplitude`, `tx_elems`, `rx_elems`, `nt` and `nr` are exactly as for
+ *   d2d_array_response_launch.
+ * - `inv_wavelength[nf]` and `nf` are exactly as for d2d_frequency_response_launch: `1..D2D_FREQ_MAX`, each entry finite and `>= 0`.
+ * - Per cell and for every `f < nf`, the planes `(re[f][i][j], im[f][i][j])` are the `(re[i][j], im[i][j])` of the array-response
+ *   definition evaluated with `inv_wavelength[f]`.
+ * - That means the same loop over candidates in the sweep's order and the same skip of exact zeros.
+ * - It means the same `a`, and `f0 = u - floorf(u)` with `u = r * inv_wavelength[f]`.
+ * - It means the same `unit_dir`, `steer_dot`, `steer_phase(f0, qt, qr, inv_wavelength[f])` and `phasor`.
+ * - It means the same fp32 adds without contraction.
+ * - `total` is the array response's `total`: the fused map, bit for bit.
+ * - Outputs are `re` and `im`, fp32 `[nf][nr][nt][m][n]`, and `total`, fp32 `[m][n]`.
+ *
+ * These properties follow from the definition:
+ *
+ * - Independence.  Plane `(f, i, j)` depends on `inv_wavelength[f]`, `etx[j]` and `erx[i]` only.  Permuted, duplicated or
+ *   truncated lists on any of the three axes give permuted, equal or leading planes, bit for bit.
+ * - Slice.  Plane block `f` equals d2d_array_response_launch at `inv_wavelength[f]`, bit for bit.
+ * - Zero offsets.  A pair of `(+-0, +-0)` offsets gives the planes of d2d_frequency_response_launch, bit for bit, wherever no
+ *   contribution lacks a direction.
+ * - Zero entry.  An entry `0` with `LINEAR` and zero offsets gives the fused map in `re` and `+0.0` in `im`.
+ *
+ * One preparation of the sweep, then one kernel pass per chunk of wavelengths (the chunk's size is internal) over the same
+ * arguments; re and im are zeroed on the stream in front of the passes, every lane is the only writer of its cell's column: plain
+ * loads and stores, no atomics, the same bits run to run.  The lists are copied during the call.  The result is kept with the grid
+ * until the next such launch.  The launch touches no other product's result: not the resident value / gradient maps, not the
+ * results of d2d_array_response_launch, d2d_frequency_response_launch or d2d_coherent_field_launch, nor any other.
+ * D2D_ERR_INVALID: what d2d_frequency_response_launch refuses of the list and the amplitude (nf outside 1 .. D2D_FREQ_MAX; an entry
+ * that is negative, NaN or infinite: the message names its index), then what d2d_array_response_launch refuses of the element
+ * lists (nt or nr outside 1 .. D2D_ARRAY_MAX; a component that is NaN or infinite: the message ends in its index).  No list is
+ * read unless its count is in range.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): what d2d_array_response_launch refuses (sigmoid validity, MinPath /
+ * FermatPath, D2D_OUT_ADD, a function that is not fused -- the message names d2d_valid_paths and d2d_trace_paths --, a TX grid
+ * whose sweep is not culled), with outputs of 8 * nf * nr * nt + 4 bytes per cell held against half of the free device memory --
+ * all decided before anything is enqueued.  A refused launch leaves the previous result as it was. */
+int d2d_array_frequency_response_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                                        const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude, int32_t nt,
+                                        const float* tx_elems /* [nt][2] */, int32_t nr, const float* rx_elems /* [nr][2] */);
+/* Synchronises and copies wavelengths first .. first + count - 1 of the result of the last d2d_array_frequency_response_launch
+ * that was accepted to the arrays that are not NULL (re, im: [count][nr][nt][m][n] with that launch's counts; total: [m][n], may
+ * be NULL).  0 <= first, count >= 1 and first + count <= nf; anything else is D2D_ERR_INVALID.  The range exists so that a
+ * result far larger than host memory can be read block by block: at 1024^2, 64 wavelengths of a 4 x 4 matrix are 8 GiB.
+ * D2D_ERR_STATE before a launch and after a d2d_set_grid of another grid (the result goes with the grid). */
+int d2d_get_array_frequency_response(d2d_ctx* ctx, int32_t first, int32_t count, float* re /* [count][nr][nt][m][n] */,
+                                     float* im /* same */, float* total /* [m][n] or NULL */);
+
 /* unit_dir and steer_phase of d2d_steer.hpp on the device, for comparison with their host build: ok[i] = unit_dir(dx[i], dy[i]) as
  * 0 / 1 with ux[i], uy[i], and f[i] = steer_phase(f0[i], qt[i], qr[i], inv[i]). */
 int d2d_selftest_steer(d2d_ctx* ctx, const float* dx, const float* dy, const float* f0, const float* qt, const float* qr,
