@@ -164,71 +164,81 @@ struct d2d_ctx {
     long long rec_n = -1;  // records the buffers hold (-1: none)
     Event ev_rec[6];  // "time_kernel": around pass 1, pass 2 and the trace
     bool have_rec_time = false;
-    // per-cell power-delay profile (d2d_power_profile_launch): [prof_nbins][m][n], kept until the next launch, dropped with the grid
-    DevBuf<float> d_profile;
-    int prof_nbins = 0;  // bins the buffer holds a profile of (0: none)
-    void drop_profile() {
-        d_profile.release();
-        prof_nbins = 0;
-    }
-    // per-cell strongest paths (d2d_strongest_paths_launch): the first top_k slots of every cell, kept until the next launch,
-    // dropped with the grid
-    DevBuf<float> d_top_power, d_top_len, d_top_total;  // [top_k][m][n], [top_k][m][n], [m][n]
-    DevBuf<int> d_top_cand, d_top_order, d_top_count;   // [top_k][m][n][D2D_MAX_ORDER], [top_k][m][n], [m][n]
-    int top_k = 0;  // slots per cell the buffers hold a result of (0: none)
-    void drop_top() {
-        d_top_power.release(); d_top_len.release(); d_top_total.release(); d_top_cand.release(); d_top_order.release(); d_top_count.release();
-        top_k = 0;
-    }
-    // coherent field (d2d_coherent_field_launch): re, im and the incoherent total of every cell, kept until the next launch,
-    // dropped with the grid
-    DevBuf<float> d_field_re, d_field_im, d_field_total;  // [m][n] each
-    bool have_field = false;
-    void drop_field() {
-        d_field_re.release(); d_field_im.release(); d_field_total.release();
-        have_field = false;
-    }
-    // frequency response (d2d_frequency_response_launch): nf planes of re and im and the incoherent total of every cell, kept until
-    // the next launch, dropped with the grid
-    DevBuf<float> d_freq_re, d_freq_im, d_freq_total;  // [nf][m][n], [nf][m][n], [m][n]
-    int32_t freq_nf = 0;                               // planes of the last accepted launch; 0: no result
-    void drop_freq() {
-        d_freq_re.release(); d_freq_im.release(); d_freq_total.release();
-        freq_nf = 0;
-    }
-    // power-angle profile (d2d_power_angle_launch): nbins planes and the total of every cell, kept until the next accepted launch,
-    // dropped with the grid
-    DevBuf<float> d_angle, d_angle_total;  // [angle_nbins][m][n], [m][n]
-    int32_t angle_nbins = 0;               // bins of the last accepted launch; 0: no result
-    void drop_angle() {
-        d_angle.release(); d_angle_total.release();
-        angle_nbins = 0;
-    }
-    // array response (d2d_array_response_launch): nr * nt planes of re and im and the total of every cell, kept until the next
-    // accepted launch, dropped with the grid
-    DevBuf<float> d_array_re, d_array_im, d_array_total;  // [array_nr][array_nt][m][n] twice, [m][n]
-    int32_t array_nt = 0, array_nr = 0;                   // counts of the last accepted launch; 0: no result
-    void drop_array() {
-        d_array_re.release(); d_array_im.release(); d_array_total.release();
-        array_nt = array_nr = 0;
-    }
+    // ---- results of the products of the sink kernel: buffers and what they hold, one struct each.  forget() ends the result's
+    // validity and keeps the buffers (a launch that is about to change them), drop() releases them as well (another grid).
+    struct Planes {  // planes of re and im and the total of every cell
+        DevBuf<float> re, im, total;
+        size_t bytes() const { return (re.n + im.n + total.n) * sizeof(float); }
+        int ensure(size_t planes, size_t cells) {
+            int rc;
+            return (rc = re.ensure(planes)) || (rc = im.ensure(planes)) ? rc : total.ensure(cells);
+        }
+        void release() { re.release(); im.release(); total.release(); }
+    };
+    // per-cell power-delay profile (d2d_power_profile_launch), kept until the next launch
+    struct Profile {
+        DevBuf<float> out;  // [nbins][m][n]
+        int nbins = 0;      // bins the buffer holds a profile of (0: none)
+        void forget() { nbins = 0; }
+        void drop() { out.release(); forget(); }
+    } prof;
+    // per-cell strongest paths (d2d_strongest_paths_launch): the first k slots of every cell, kept until the next launch
+    struct Top {
+        DevBuf<float> power, len, total;  // [k][m][n], [k][m][n], [m][n]
+        DevBuf<int> cand, order, count;   // [k][m][n][D2D_MAX_ORDER], [k][m][n], [m][n]
+        int k = 0;  // slots per cell the buffers hold a result of (0: none)
+        size_t bytes() const { return (power.n + len.n + total.n + cand.n + order.n + count.n) * 4; }
+        void forget() { k = 0; }
+        void drop() { power.release(); len.release(); total.release(); cand.release(); order.release(); count.release(); forget(); }
+    } top;
+    // coherent field (d2d_coherent_field_launch): re, im and the incoherent total of every cell, kept until the next launch
+    struct Field {
+        Planes out;  // [m][n] each
+        bool have = false;
+        void forget() { have = false; }
+        void drop() { out.release(); forget(); }
+    } field;
+    // frequency response (d2d_frequency_response_launch): nf planes of re and im and the incoherent total, kept until the next launch
+    struct Freq {
+        Planes out;      // [nf][m][n], [nf][m][n], [m][n]
+        int32_t nf = 0;  // planes of the last accepted launch; 0: no result
+        void forget() { nf = 0; }
+        void drop() { out.release(); forget(); }
+    } freq;
+    // power-angle profile (d2d_power_angle_launch): nbins planes and the total of every cell, kept until the next accepted launch
+    struct Angle {
+        DevBuf<float> out, total;  // [nbins][m][n], [m][n]
+        int32_t nbins = 0;         // bins of the last accepted launch; 0: no result
+        void forget() { nbins = 0; }
+        void drop() { out.release(); total.release(); forget(); }
+    } angle;
+    // array response (d2d_array_response_launch): nr * nt planes of re and im and the total, kept until the next accepted launch
+    struct Array {
+        Planes out;              // [nr][nt][m][n] twice, [m][n]
+        int32_t nt = 0, nr = 0;  // counts of the last accepted launch; 0: no result
+        void forget() { nt = nr = 0; }
+        void drop() { out.release(); forget(); }
+    } array;
     // coefficient adjoint of the frequency response (d2d_field_coefs_vjp_launch): the cotangent planes, the per-patch rows and the
-    // reduced result, kept until the next accepted launch, dropped with the grid and with the scene
-    DevBuf<float> d_cg_re, d_cg_im;  // [nf][m][n] each: the caller's cotangents
-    DevBuf<float> d_cg_partial;      // [patches][N]
-    DevBuf<double> d_cg_out;         // [N]
-    bool have_cg = false;            // d_cg_out holds the result of an accepted launch for the CURRENT grid and scene
-    void drop_cg() {
-        d_cg_re.release(); d_cg_im.release(); d_cg_partial.release(); d_cg_out.release();
-        have_cg = false;
-    }
-    // wideband array response (d2d_array_frequency_response_launch): nf * nr * nt planes of re and im and the total of every cell,
-    // kept until the next accepted launch, dropped with the grid
-    DevBuf<float> d_wide_re, d_wide_im, d_wide_total;  // [wide_nf][wide_nr][wide_nt][m][n] twice, [m][n]
-    int32_t wide_nf = 0, wide_nt = 0, wide_nr = 0;     // counts of the last accepted launch; 0: no result
-    void drop_wide() {
-        d_wide_re.release(); d_wide_im.release(); d_wide_total.release();
-        wide_nf = wide_nt = wide_nr = 0;
+    // reduced result, kept until the next accepted launch; the scene forgets it too
+    struct CoefGrad {
+        DevBuf<float> re, im;    // [nf][m][n] each: the caller's cotangents
+        DevBuf<float> partial;   // [patches][N]
+        DevBuf<double> out;      // [N]
+        bool have = false;       // out holds the result of an accepted launch for the CURRENT grid and scene
+        void forget() { have = false; }
+        void drop() { re.release(); im.release(); partial.release(); out.release(); forget(); }
+    } cg;
+    // wideband array response (d2d_array_frequency_response_launch): nf * nr * nt planes of re and im and the total, kept until
+    // the next accepted launch
+    struct Wide {
+        Planes out;                      // [nf][nr][nt][m][n] twice, [m][n]
+        int32_t nf = 0, nt = 0, nr = 0;  // counts of the last accepted launch; 0: no result
+        void forget() { nf = nt = nr = 0; }
+        void drop() { out.release(); forget(); }
+    } wide;
+    void drop_products() {  // every one of them goes with the grid
+        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop();
     }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -777,7 +787,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->coef.clear();              // (the reflection coefficients belong to the objects of the previous scene)
     c->cust_C = -1;               // (a host-evaluated path function's rows belong to the paths of the previous scene)
     c->have_vjp = false;          // d_vjp was sized for (and computed from) the previous scene
-    c->have_cg = false;           // (... and so was the frequency response's coefficient adjoint)
+    c->cg.forget();               // (... and so was the frequency response's coefficient adjoint)
     c->have_kernel_time = false;
     c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
@@ -928,14 +938,7 @@ static int set_grid_impl(d2d_ctx* c, const float* X, const float* Y, int32_t m, 
         c->grid_version += 1;  // ... and the regions' bounding boxes another grid
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->drop_records();  // ... and the records' cells
-        c->drop_profile();  // ... and the profile's
-        c->drop_top();      // ... and the strongest paths'
-        c->drop_field();    // ... and the coherent field's
-        c->drop_angle();    // ... and the power-angle profile's
-        c->drop_array();    // ... and the array response's
-        c->drop_freq();     // ... and the frequency response's
-        c->drop_wide();     // ... and the wideband array response's
-        c->drop_cg();       // ... and its coefficient adjoint's
+        c->drop_products(); // ... and the results of the sink kernel's products
         if ((rc = c->d_X.ensure(cells))) return rc;
         if ((rc = c->d_Y.ensure(cells))) return rc;
         if ((rc = c->d_out.ensure(cells))) return rc;
@@ -2113,7 +2116,7 @@ static int sweep_launch(d2d_ctx* c, const d2d_params* p, const float* tx, unsign
     return launch_rx_values(c, s, pr);
 }
 
-// What the two sink launches (d2d_valid_paths, d2d_power_profile_launch: `who` in the messages) share, from the validity mode on.
+// What every launch of the sink kernel shares (d2d_valid_paths and the products below: `who` in the messages), from the validity mode on.
 // Every refusal that the arguments and the context decide comes first, before anything is uploaded or enqueued; a TX grid is swept
 // by the culled kernels only, and refusing one is not a fall-back.  Then the launch is prepared on the main stream, behind whatever
 // the context has in flight, with masks of its own: the sweeps' rotating sets, work history, schedule and value map are not touched.
@@ -2142,6 +2145,12 @@ static int prep_sink_sweep(d2d_ctx* c, Sweep& s, const char* who, size_t& lds) {
     return D2D_OK;
 }
 
+// One pass of the sink kernel over the prepared sweep `s` (prep_sink_sweep gave `lds`), on the main stream.
+template <class Sink>
+static hipError_t sink_pass(const d2d_ctx* c, const Sweep& s, size_t lds, const typename Sink::Args& x) {
+    return d2d::launch_sink<Sink>(s.th.mode, s.txg, s.p->max_order, s.grid_patches, lds, c->stream, s.a, x);
+}
+
 // Record launch of the culled forward sweep: pass 1 counts the (cell, candidate) pairs with valid != 0 per patch, the host scans
 // the counts, pass 2 writes the records, trace_rec_kernel solves their paths.
 static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int64_t* count) {
@@ -2162,7 +2171,6 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     Sweep s(c, p, fixed);
     size_t lds = 0;
     if ((rc = prep_sink_sweep(c, s, "d2d_valid_paths", lds))) return rc;
-    const d2d::SweepArgs& a = s.a;
     const size_t tiles = (size_t)s.tiles;
     if ((rc = c->d_rec_counts.ensure(tiles)) || (rc = c->d_rec_offs.ensure(tiles + 1)) || (rc = c->d_rec_flag.ensure(1))) return rc;
     const bool timed = c->time_kernel;
@@ -2177,7 +2185,7 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     r.flag = c->d_rec_flag.p;
     // pass 1: count
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[0], c->stream));
-    HIP_TRY(d2d::launch_sink<d2d::RecSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
+    HIP_TRY(sink_pass<d2d::RecSink>(c, s, lds, r));
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[1], c->stream));
     std::vector<int> offs(tiles + 1);
     HIP_TRY(hipMemcpyAsync(offs.data() + 1, c->d_rec_counts.p, tiles * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2217,7 +2225,7 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     // pass 2: the same sweep, writing
     r.rec = c->d_rec.p;
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[2], c->stream));
-    HIP_TRY(d2d::launch_sink<d2d::RecSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, a, r));
+    HIP_TRY(sink_pass<d2d::RecSink>(c, s, lds, r));
     if (timed) HIP_TRY(hipEventRecord(c->ev_rec[3], c->stream));
     // stage 2: the paths of the records
     d2d::TraceArgs t;
@@ -2255,439 +2263,423 @@ static int valid_paths(d2d_ctx* c, const d2d_params* p_in, const float* fixed, i
     return D2D_OK;
 }
 
-// What the fused sinks (d2d_power_profile_launch, d2d_strongest_paths_launch, d2d_coherent_field_launch, d2d_frequency_response_launch: `who`) refuse of the caller's parameters before
-// prep_sink_sweep's share; `custom_route` and `add_why` end the two messages that say what to do instead.
-static int check_fused_sink(d2d_ctx* c, const d2d_params* p, const char* who, const char* custom_route, const char* add_why) {
+// ---- the products of the sink kernel ---------------------------------------------------------------------------------
+// Every product is one more sink of power_sink_kernel behind the same host path; DESIGN.md ("Adding a product of the sink kernel")
+// says what a new one writes and where.
+struct SinkProduct {
+    const char* who;           // the launch's name in the messages
+    const char* custom_route;  // how check_fused_sink's refusal of D2D_FUN_CUSTOM ends: what to do instead
+    const char* add_why;       // ... and its refusal of D2D_OUT_ADD
+    bool early_discard;        // when a launch forgets the previous result (below)
+};
+// Discard timing is behaviour, and it differs for historical reasons only: the four older products forget the previous result as
+// soon as the state checks pass (EARLY: any later refusal leaves nothing to get), the four newer ones when the launch is accepted
+// and the buffers are about to change (LATE: a refused launch leaves the previous result readable).  Callers may rely on either.
+constexpr bool EARLY = true, LATE = false;
+constexpr SinkProduct PROFILE = {"d2d_power_profile_launch", "a host function's profile: bin the records of d2d_valid_paths", "a profile is always overwritten", EARLY};
+constexpr SinkProduct TOP = {"d2d_strongest_paths_launch", "a host function's strongest paths: sort the records of d2d_valid_paths", "the slots are always overwritten", EARLY};
+constexpr SinkProduct FIELD = {"d2d_coherent_field_launch", "a host function's field: add the phasors of the records of d2d_valid_paths", "the field is always overwritten", EARLY};
+constexpr SinkProduct FREQ = {"d2d_frequency_response_launch", "a host function's response: add the phasors of the records of d2d_valid_paths", "the response is always overwritten", EARLY};
+constexpr SinkProduct COEF_VJP = {"d2d_field_coefs_vjp_launch", "a host function has no coefficients", "the gradient is always overwritten", LATE};
+constexpr SinkProduct ANGLE = {"d2d_power_angle_launch", "a host function's profile: bin the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "a profile is always overwritten", LATE};
+constexpr SinkProduct ARRAY = {"d2d_array_response_launch", "a host function's channel matrix: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrix is always overwritten", LATE};
+constexpr SinkProduct WIDE = {"d2d_array_frequency_response_launch", "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrices are always overwritten", LATE};
+
+// What the products refuse of the caller's parameters before prep_sink_sweep's share.
+static int check_fused_sink(d2d_ctx* c, const d2d_params* p, const SinkProduct& pr) {
     if (p->solver == D2D_SOLVER_MINPATH || p->solver == D2D_SOLVER_FERMAT)
-        return fail(D2D_ERR_UNSUPPORTED, "%s covers ImagePath only, not the MinPath / FermatPath solvers (solver %d)", who, p->solver);
+        return fail(D2D_ERR_UNSUPPORTED, "%s covers ImagePath only, not the MinPath / FermatPath solvers (solver %d)", pr.who, p->solver);
     if (p->fun_id == D2D_FUN_CUSTOM)
-        return fail(D2D_ERR_UNSUPPORTED, "%s: fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only (%s)", who, custom_route);
-    if (p->out_mode == D2D_OUT_ADD) return fail(D2D_ERR_UNSUPPORTED, "%s: D2D_OUT_ADD is not supported, %s", who, add_why);
+        return fail(D2D_ERR_UNSUPPORTED, "%s: fun_id D2D_FUN_CUSTOM is for d2d_power_map_vg_launch only (%s)", pr.who, pr.custom_route);
+    if (p->out_mode == D2D_OUT_ADD) return fail(D2D_ERR_UNSUPPORTED, "%s: D2D_OUT_ADD is not supported, %s", pr.who, pr.add_why);
     if (p->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT && ((int)c->coef.size() != c->N || (c->N > 0 && !c->d_coef.p)))
         return fail(D2D_ERR_STATE, "fun_id D2D_FUN_RECEIVED_POWER_PER_OBJECT needs d2d_set_reflection_coefs for the resident scene");
     return D2D_OK;
 }
 
-// Bin launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed profile.
-// Asynchronous.  Every check comes before anything is enqueued.
-static int power_profile_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float r_min, float r_max, int32_t nbins) {
-    if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_power_profile_launch");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_power_profile_launch");
-    c->prof_nbins = 0;  // whatever this launch turns out to be, the previous profile is gone
-    if ((rc = check_fused_sink(c, p_in, "d2d_power_profile_launch", "a host function's profile: bin the records of d2d_valid_paths",
-                               "a profile is always overwritten")))
-        return rc;
-    d2d_host::ProfileBins bins;
-    {
-        std::string err;
-        if ((rc = d2d_host::profile_bins(r_min, r_max, nbins, bins, err))) return fail(rc, "%s", err.c_str());
+// One launch of a product, whose result is the context's `r`: the stages every product walks in the same order, with the product's
+// own steps between them (the NULL-argument check comes before a SinkLaunch exists).  Every check comes before anything is
+// enqueued; the launches are asynchronous.
+//   begin    check_params, the state checks, the EARLY discard, the product's pre-check if it has one, check_fused_sink
+//            -- the product's parameter check --
+//   device   set_device and the free device memory, for
+//            -- the product's memory check (fits: the rule and the message that five products share) --
+//   prepare  the sweep's preparation (prep_sink_sweep), then the LATE discard
+//            -- ensure the buffers, zero what the sink adds into, the passes, mark the result --
+template <class Result>
+struct SinkLaunch {
+    d2d_ctx* const c;
+    const SinkProduct& pr;
+    Result& r;
+    d2d_params pp;  // the caller's parameters with strict_nan = 0; a product may substitute more between begin and prepare
+    // Built before any check, and from pp while it is still zero: sound only because Sweep's constructor reads nothing but the
+    // grid's shape (c->m, c->n: s.tiles, for a memory check that needs the patch count) and STORES the pointer to the parameters.
+    // A constructor that ever read *p would have to move into begin, behind the state checks.
+    Sweep s;
+    const size_t cells;
+    size_t lds = 0, mem_free = 0;
+    SinkLaunch(d2d_ctx* c, const SinkProduct& pr, Result& r, const float* fixed)
+        : c(c), pr(pr), r(r), pp(), s(c, &pp, fixed), cells((size_t)c->m * (size_t)c->n) {}
+    SinkLaunch(const SinkLaunch&) = delete;  // (s points at pp)
+
+    template <class Pre>
+    int begin(const d2d_params* p_in, Pre pre) {
+        int rc = check_params(p_in);
+        if (rc) return rc;
+        if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before %s", pr.who);
+        if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before %s", pr.who);
+        if (pr.early_discard) r.forget();  // whatever this launch turns out to be, the previous result is gone
+        if ((rc = pre()) || (rc = check_fused_sink(c, p_in, pr))) return rc;
+        pp = *p_in;
+        pp.strict_nan = 0;
+        return D2D_OK;
     }
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
+    int begin(const d2d_params* p_in) { return begin(p_in, [] { return D2D_OK; }); }
+    int device() {
+        if (int rc = set_device(c)) return rc;
+        size_t mem_total = 0;
         HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        // (half of what is free, plus what the buffer holds already)
-        const size_t held = c->d_profile.n * sizeof(float);
-        const size_t budget = (mem_free + held) / 2;
-        if (cells > 0 && (size_t)nbins > budget / sizeof(float) / cells)
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: %d bins of %zu cells (4 bytes each) exceed half of the free device memory (%zu bytes free)",
-                        nbins, cells, mem_free);
+        return D2D_OK;
     }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, "d2d_power_profile_launch", lds))) return rc;
-    if ((rc = c->d_profile.ensure((size_t)nbins * cells))) return rc;
+    int fits(size_t bytes_per_cell, size_t held) const {
+        if (d2d_host::outputs_fit(cells, bytes_per_cell, mem_free, held)) return D2D_OK;
+        return fail(D2D_ERR_UNSUPPORTED, "%s: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)", pr.who, cells,
+                    bytes_per_cell, mem_free);
+    }
+    int prepare() {
+        if (int rc = prep_sink_sweep(c, s, pr.who, lds)) return rc;
+        if (!pr.early_discard) r.forget();  // from here on the buffers change
+        return D2D_OK;
+    }
+    template <class Sink>
+    hipError_t pass(const typename Sink::Args& x) const {
+        return sink_pass<Sink>(c, s, lds, x);
+    }
+};
+
+// The getters: no result without a context, a grid and an accepted launch (`holds`; `goes_with` ends the message) ...
+static int result_state(const d2d_ctx* c, bool holds, const SinkProduct& pr, const char* goes_with = "result goes with the grid") {
+    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
+    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
+    if (!holds) return fail(D2D_ERR_STATE, "%s must come first (its %s)", pr.who, goes_with);
+    return D2D_OK;
+}
+// ... then the copies the caller asked for (dst not NULL), behind whatever is in flight, and one synchronisation.
+struct CopyOut {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+static int copy_out(d2d_ctx* c, std::initializer_list<CopyOut> copies) {
+    if (int rc = set_device(c)) return rc;
+    for (const CopyOut& x : copies)
+        if (x.dst) HIP_TRY(hipMemcpyAsync(x.dst, x.src, x.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return D2D_OK;
+}
+
+static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK && d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK, "d2d_host.hpp and d2d_kernels.hpp disagree");
+
+}  // namespace
+
+extern "C" {
+
+// Bin build: ONE pass into the zeroed profile.  (Its memory check keeps arithmetic of its own: (free + held) / 2 against a
+// product of quotients, where outputs_fit halves both terms.)
+int d2d_power_profile_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float r_min, float r_max, int32_t nbins) {
+    if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
+    SinkLaunch<d2d_ctx::Profile> L(c, PROFILE, c->prof, fixed);
+    d2d_host::ProfileBins bins;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::profile_bins(r_min, r_max, nbins, bins, err))) return fail(rc, "%s", err.c_str());
+    if ((rc = L.device())) return rc;
+    const size_t budget = (L.mem_free + c->prof.out.n * sizeof(float)) / 2;  // (half of what is free, plus what the buffer holds already)
+    if (L.cells > 0 && (size_t)nbins > budget / sizeof(float) / L.cells)
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_power_profile_launch: %d bins of %zu cells (4 bytes each) exceed half of the free device memory (%zu bytes free)",
+                    nbins, L.cells, L.mem_free);
+    if ((rc = L.prepare()) || (rc = c->prof.out.ensure((size_t)nbins * L.cells))) return rc;
     d2d::BinArgs b;
-    b.out = c->d_profile.p;
-    b.cells = (long)cells;
+    b.out = c->prof.out.p;
+    b.cells = (long)L.cells;
     b.r_min = bins.r_min;
     b.inv = bins.inv;
     b.nbins = bins.nbins;
-    HIP_TRY(hipMemsetAsync(c->d_profile.p, 0, (size_t)nbins * cells * sizeof(float), c->stream));
-    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::BinSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, b));
-    c->prof_nbins = nbins;
+    HIP_TRY(hipMemsetAsync(c->prof.out.p, 0, (size_t)nbins * L.cells * sizeof(float), c->stream));
+    if (L.s.tiles > 0) HIP_TRY(L.pass<d2d::BinSink>(b));
+    c->prof.nbins = nbins;
     return D2D_OK;
 }
 
-// Top-k launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel, every lane writing the
-// whole of its cell (no zeroing in front).  Asynchronous.  Every check comes before anything is enqueued.
-static int strongest_paths_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int32_t k) {
+int d2d_get_power_profile(d2d_ctx* c, float* out) {
+    if (!c || !out) return fail(D2D_ERR_INVALID, "NULL argument");
+    if (int rc = result_state(c, c->prof.nbins >= 1 && c->prof.out.p, PROFILE, "profile goes with the grid")) return rc;
+    return copy_out(c, {{out, c->prof.out.p, (size_t)c->prof.nbins * (size_t)c->m * c->n * sizeof(float)}});
+}
+
+// Top-k build: ONE pass, every lane writing the whole of its cell (no zeroing in front).
+int d2d_strongest_paths_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t k) {
     if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_strongest_paths_launch");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_strongest_paths_launch");
-    c->top_k = 0;  // whatever this launch turns out to be, the previous result is gone
-    if ((rc = check_fused_sink(c, p_in, "d2d_strongest_paths_launch", "a host function's strongest paths: sort the records of d2d_valid_paths",
-                               "the slots are always overwritten")))
-        return rc;
+    SinkLaunch<d2d_ctx::Top> L(c, TOP, c->top, fixed);
+    d2d_ctx::Top& r = c->top;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
     if (k < 1 || k > D2D_TOP_MAX) return fail(D2D_ERR_INVALID, "d2d_strongest_paths_launch: k = %d is outside 1..D2D_TOP_MAX (%d)", k, D2D_TOP_MAX);
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_top_power.n + c->d_top_len.n + c->d_top_total.n + c->d_top_cand.n + c->d_top_order.n + c->d_top_count.n) * 4;
-        if (!d2d_host::top_fits(cells, k, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_strongest_paths_launch: %d slots of %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
-                        k, cells, d2d_host::top_bytes_per_cell(k), mem_free);
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, "d2d_strongest_paths_launch", lds))) return rc;
-    const size_t kc = (size_t)k * cells;
-    if ((rc = c->d_top_power.ensure(kc)) || (rc = c->d_top_len.ensure(kc)) || (rc = c->d_top_cand.ensure(kc * D2D_MAX_ORDER)) ||
-        (rc = c->d_top_order.ensure(kc)) || (rc = c->d_top_total.ensure(cells)) || (rc = c->d_top_count.ensure(cells)))
+    if ((rc = L.device())) return rc;
+    if (!d2d_host::outputs_fit(L.cells, d2d_host::top_bytes_per_cell(k), L.mem_free, r.bytes()))
+        return fail(D2D_ERR_UNSUPPORTED, "d2d_strongest_paths_launch: %d slots of %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
+                    k, L.cells, d2d_host::top_bytes_per_cell(k), L.mem_free);
+    if ((rc = L.prepare())) return rc;
+    const size_t kc = (size_t)k * L.cells;
+    if ((rc = r.power.ensure(kc)) || (rc = r.len.ensure(kc)) || (rc = r.cand.ensure(kc * D2D_MAX_ORDER)) || (rc = r.order.ensure(kc)) ||
+        (rc = r.total.ensure(L.cells)) || (rc = r.count.ensure(L.cells)))
         return rc;
     d2d::TopArgs t;
-    t.power = c->d_top_power.p;
-    t.length = c->d_top_len.p;
-    t.cand = c->d_top_cand.p;
-    t.order = c->d_top_order.p;
-    t.total = c->d_top_total.p;
-    t.count = c->d_top_count.p;
-    t.cells = (long)cells;
+    t.power = r.power.p;
+    t.length = r.len.p;
+    t.cand = r.cand.p;
+    t.order = r.order.p;
+    t.total = r.total.p;
+    t.count = r.count.p;
+    t.cells = (long)L.cells;
     t.k = k;
-    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::TopSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, t));
-    c->top_k = k;
+    if (L.s.tiles > 0) HIP_TRY(L.pass<d2d::TopSink>(t));
+    r.k = k;
     return D2D_OK;
 }
 
-// Coherent-field launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel, every lane
-// writing the three values of its cell (no zeroing in front).  Asynchronous.  Every check comes before anything is enqueued.
-static int coherent_field_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float inv_wavelength, int32_t amplitude) {
+int d2d_get_strongest_paths(d2d_ctx* c, float* power, float* length, int32_t* cand, int32_t* order, float* total, int32_t* count) {
+    if (int rc = result_state(c, c && c->top.k >= 1 && c->top.power.p, TOP)) return rc;
+    const d2d_ctx::Top& r = c->top;
+    const size_t cells = (size_t)c->m * (size_t)c->n, kc = (size_t)r.k * cells;
+    return copy_out(c, {{power, r.power.p, kc * sizeof(float)}, {length, r.len.p, kc * sizeof(float)}, {cand, r.cand.p, kc * D2D_MAX_ORDER * sizeof(int)},
+                        {order, r.order.p, kc * sizeof(int)}, {total, r.total.p, cells * sizeof(float)}, {count, r.count.p, cells * sizeof(int)}});
+}
+
+// Coherent-field build: ONE pass, every lane writing the three values of its cell (no zeroing in front).
+int d2d_coherent_field_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude) {
     if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_coherent_field_launch");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_coherent_field_launch");
-    c->have_field = false;  // whatever this launch turns out to be, the previous result is gone
-    if ((rc = check_fused_sink(c, p_in, "d2d_coherent_field_launch", "a host function's field: add the phasors of the records of d2d_valid_paths",
-                               "the field is always overwritten")))
-        return rc;
-    {
-        std::string err;
-        if ((rc = d2d_host::field_params(inv_wavelength, amplitude, err))) return fail(rc, "d2d_coherent_field_launch: %s", err.c_str());
-    }
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_field_re.n + c->d_field_im.n + c->d_field_total.n) * sizeof(float);
-        if (!d2d_host::field_fits(cells, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_coherent_field_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
-                        cells, d2d_host::FIELD_BYTES_PER_CELL, mem_free);
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, "d2d_coherent_field_launch", lds))) return rc;
-    if ((rc = c->d_field_re.ensure(cells)) || (rc = c->d_field_im.ensure(cells)) || (rc = c->d_field_total.ensure(cells))) return rc;
+    SinkLaunch<d2d_ctx::Field> L(c, FIELD, c->field, fixed);
+    d2d_ctx::Planes& o = c->field.out;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::field_params(inv_wavelength, amplitude, err))) return fail(rc, "d2d_coherent_field_launch: %s", err.c_str());
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::FIELD_BYTES_PER_CELL, o.bytes())) || (rc = L.prepare()) || (rc = o.ensure(L.cells, L.cells))) return rc;
     d2d::FieldArgs f;
-    f.re = c->d_field_re.p;
-    f.im = c->d_field_im.p;
-    f.total = c->d_field_total.p;
-    f.cells = (long)cells;
+    f.re = o.re.p;
+    f.im = o.im.p;
+    f.total = o.total.p;
+    f.cells = (long)L.cells;
     f.inv_wavelength = inv_wavelength;
     f.amplitude = amplitude;
-    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::FieldSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, f));
-    c->have_field = true;
+    if (L.s.tiles > 0) HIP_TRY(L.pass<d2d::FieldSink>(f));
+    c->field.have = true;
     return D2D_OK;
 }
 
-// Frequency-response launch of the culled forward sweep with the caller's path function: ONE preparation, then one pass of the sink
-// kernel per chunk of FREQ_CHUNK wavelengths over the same SweepArgs (as d2d_valid_paths launches its two passes: the sink kernel
-// writes nothing that a later pass reads), every lane writing its cell's planes of the chunk and, in the first pass, the total.
-// Asynchronous.  Every check comes before anything is enqueued.
-static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK, "d2d_host.hpp and d2d_kernels.hpp disagree");
-static int frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude) {
+int d2d_get_coherent_field(d2d_ctx* c, float* re, float* im, float* total) {
+    if (int rc = result_state(c, c && c->field.have && c->field.out.re.p, FIELD)) return rc;
+    const d2d_ctx::Planes& o = c->field.out;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    return copy_out(c, {{re, o.re.p, bytes}, {im, o.im.p, bytes}, {total, o.total.p, bytes}});
+}
+
+// Frequency-response build: ONE preparation, then one pass per chunk of FREQ_CHUNK wavelengths over the same SweepArgs (as
+// d2d_valid_paths launches its two passes: the sink kernel writes nothing that a later pass reads), every lane writing its cell's
+// planes of the chunk and, in the first pass, the total.
+int d2d_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude) {
     if (!c || !fixed || !inv_wavelength) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_frequency_response_launch");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_frequency_response_launch");
-    c->freq_nf = 0;  // whatever this launch turns out to be, the previous result is gone
-    if ((rc = check_fused_sink(c, p_in, "d2d_frequency_response_launch",
-                               "a host function's response: add the phasors of the records of d2d_valid_paths", "the response is always overwritten")))
+    SinkLaunch<d2d_ctx::Freq> L(c, FREQ, c->freq, fixed);
+    d2d_ctx::Planes& o = c->freq.out;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::freq_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "d2d_frequency_response_launch: %s", err.c_str());
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::freq_bytes_per_cell(nf), o.bytes())) || (rc = L.prepare()) || (rc = o.ensure((size_t)nf * L.cells, L.cells)))
         return rc;
-    {
-        std::string err;
-        if ((rc = d2d_host::freq_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "d2d_frequency_response_launch: %s", err.c_str());
-    }
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_freq_re.n + c->d_freq_im.n + c->d_freq_total.n) * sizeof(float);
-        if (!d2d_host::freq_fits(cells, nf, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_frequency_response_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
-                        cells, d2d_host::freq_bytes_per_cell(nf), mem_free);
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, "d2d_frequency_response_launch", lds))) return rc;
-    const size_t planes = (size_t)nf * cells;
-    if ((rc = c->d_freq_re.ensure(planes)) || (rc = c->d_freq_im.ensure(planes)) || (rc = c->d_freq_total.ensure(cells))) return rc;
-    if (s.tiles > 0)
-        for (int32_t i = 0; i < d2d_host::freq_chunks(nf); ++i) {
-            const d2d_host::FreqChunk ch = d2d_host::freq_chunk(nf, i);
+    if (L.s.tiles > 0)
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::FREQ_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::FREQ_CHUNK);
             d2d::FreqArgs f;
-            f.re = c->d_freq_re.p + (size_t)ch.first * cells;
-            f.im = c->d_freq_im.p + (size_t)ch.first * cells;
-            f.total = ch.with_total ? c->d_freq_total.p : nullptr;
-            f.cells = (long)cells;
+            f.re = o.re.p + (size_t)ch.first * L.cells;
+            f.im = o.im.p + (size_t)ch.first * L.cells;
+            f.total = ch.with_total ? o.total.p : nullptr;
+            f.cells = (long)L.cells;
             for (int32_t j = 0; j < d2d::FREQ_CHUNK; ++j) f.inv[j] = j < ch.count ? inv_wavelength[ch.first + j] : 0.0f;
             f.nf = ch.count;
             f.amplitude = amplitude;
-            HIP_TRY(d2d::launch_sink<d2d::FreqSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, f));
+            HIP_TRY(L.pass<d2d::FreqSink>(f));
         }
-    c->freq_nf = nf;
+    c->freq.nf = nf;
     return D2D_OK;
 }
 
+int d2d_get_frequency_response(d2d_ctx* c, float* re, float* im, float* total) {
+    if (int rc = result_state(c, c && c->freq.nf >= 1 && c->freq.out.re.p, FREQ)) return rc;
+    const d2d_ctx::Planes& o = c->freq.out;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    return copy_out(c, {{re, o.re.p, bytes * (size_t)c->freq.nf}, {im, o.im.p, bytes * (size_t)c->freq.nf}, {total, o.total.p, bytes}});
+}
+
 // Coefficient adjoint of the frequency response: ONE preparation of the culled sweep with the coefficient-free contribution
-// valid / (h^2 + r^2) (D2D_FUN_RECEIVED_POWER with a numerator of 1, as d2d_valid_paths substitutes D2D_FUN_ONE), one pass of the
-// sink kernel per chunk of FREQ_CHUNK wavelengths into the zeroed per-patch rows, then the fixed-order fp64 reduction of the rows.
-// The cotangents are copied before the call returns; the launches are asynchronous.  Every check comes before anything is enqueued,
-// and a refused launch leaves the previous result as it was.
-static int field_coefs_vjp_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
-                                  const float* re_bar, const float* im_bar) {
-    static const char who[] = "d2d_field_coefs_vjp_launch";
+// valid / (h^2 + r^2) (D2D_FUN_RECEIVED_POWER with a numerator of 1, as d2d_valid_paths substitutes D2D_FUN_ONE), one pass per
+// chunk of FREQ_CHUNK wavelengths into the zeroed per-patch rows, then the fixed-order fp64 reduction of the rows.  The cotangents
+// are copied before the call returns.
+int d2d_field_coefs_vjp_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                               const float* re_bar, const float* im_bar) {
     if (!c || !fixed || !inv_wavelength || !re_bar || !im_bar) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before %s", who);
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before %s", who);
-    if (p_in->fun_id != D2D_FUN_RECEIVED_POWER_PER_OBJECT)
-        return fail(D2D_ERR_UNSUPPORTED, "%s: fun_id %d has no reflection coefficient per object to differentiate by (D2D_FUN_RECEIVED_POWER_PER_OBJECT only)",
-                    who, p_in->fun_id);
-    if ((rc = check_fused_sink(c, p_in, who, "a host function has no coefficients", "the gradient is always overwritten"))) return rc;
-    {
-        std::string err;
-        if ((rc = d2d_host::freq_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "%s: %s", who, err.c_str());
-    }
-    if ((rc = set_device(c))) return rc;
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    pp.fun_id = D2D_FUN_RECEIVED_POWER;  // with a numerator of 1: a contribution is then valid / (h^2 + r^2)
-    pp.r_coef = 1.0f;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    const size_t cells = (size_t)c->m * (size_t)c->n, N = (size_t)c->N, tiles = (size_t)s.tiles;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_cg_re.n + c->d_cg_im.n + c->d_cg_partial.n) * sizeof(float);
-        if (!d2d_host::coef_vjp_fits(cells, nf, tiles, N, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "%s: cotangents of %zu cells (%zu bytes per cell) and %zu rows of %zu partial sums exceed half of the free device memory (%zu bytes free)",
-                        who, cells, 8 * (size_t)nf, tiles, N, mem_free);
-    }
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, who, lds))) return rc;
-    c->have_cg = false;  // from here on the buffers change
-    const size_t planes = (size_t)nf * cells;
-    if ((rc = c->d_cg_re.ensure(planes)) || (rc = c->d_cg_im.ensure(planes)) || (rc = c->d_cg_partial.ensure(tiles * N)) || (rc = c->d_cg_out.ensure(N)))
+    SinkLaunch<d2d_ctx::CoefGrad> L(c, COEF_VJP, c->cg, fixed);
+    d2d_ctx::CoefGrad& r = c->cg;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p, [&] {
+            if (p->fun_id == D2D_FUN_RECEIVED_POWER_PER_OBJECT) return (int)D2D_OK;
+            return fail(D2D_ERR_UNSUPPORTED, "%s: fun_id %d has no reflection coefficient per object to differentiate by (D2D_FUN_RECEIVED_POWER_PER_OBJECT only)",
+                        COEF_VJP.who, p->fun_id);
+        })))
         return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_cg_re.p, re_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_cg_im.p, im_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = d2d_host::freq_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "%s: %s", COEF_VJP.who, err.c_str());
+    if ((rc = L.device())) return rc;
+    L.pp.fun_id = D2D_FUN_RECEIVED_POWER;  // with a numerator of 1: a contribution is then valid / (h^2 + r^2)
+    L.pp.r_coef = 1.0f;
+    const size_t cells = L.cells, N = (size_t)c->N, tiles = (size_t)L.s.tiles;
+    if (!d2d_host::coef_vjp_fits(cells, nf, tiles, N, L.mem_free, (r.re.n + r.im.n + r.partial.n) * sizeof(float)))
+        return fail(D2D_ERR_UNSUPPORTED, "%s: cotangents of %zu cells (%zu bytes per cell) and %zu rows of %zu partial sums exceed half of the free device memory (%zu bytes free)",
+                    COEF_VJP.who, cells, 8 * (size_t)nf, tiles, N, L.mem_free);
+    if ((rc = L.prepare())) return rc;
+    const size_t planes = (size_t)nf * cells;
+    if ((rc = r.re.ensure(planes)) || (rc = r.im.ensure(planes)) || (rc = r.partial.ensure(tiles * N)) || (rc = r.out.ensure(N))) return rc;
+    HIP_TRY(hipMemcpyAsync(r.re.p, re_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.im.p, im_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays are free again when the call returns
     if (N > 0 && tiles > 0) {
-        HIP_TRY(hipMemsetAsync(c->d_cg_partial.p, 0, tiles * N * sizeof(float), c->stream));
-        for (int32_t i = 0; i < d2d_host::freq_chunks(nf); ++i) {
-            const d2d_host::FreqChunk ch = d2d_host::freq_chunk(nf, i);
+        HIP_TRY(hipMemsetAsync(r.partial.p, 0, tiles * N * sizeof(float), c->stream));
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::FREQ_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::FREQ_CHUNK);
             d2d::CoefGradArgs g;
-            g.re_bar = c->d_cg_re.p + (size_t)ch.first * cells;
-            g.im_bar = c->d_cg_im.p + (size_t)ch.first * cells;
+            g.re_bar = r.re.p + (size_t)ch.first * cells;
+            g.im_bar = r.im.p + (size_t)ch.first * cells;
             g.coef = c->d_coef.p;
-            g.partial = c->d_cg_partial.p;
+            g.partial = r.partial.p;
             g.cells = (long)cells;
             for (int32_t j = 0; j < d2d::FREQ_CHUNK; ++j) g.inv[j] = j < ch.count ? inv_wavelength[ch.first + j] : 0.0f;
             g.nf = ch.count;
             g.amplitude = amplitude;
             g.N = c->N;
-            HIP_TRY(d2d::launch_sink<d2d::CoefGradSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
+            HIP_TRY(L.pass<d2d::CoefGradSink>(g));
         }
-        hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)N), dim3(256), 0, c->stream, c->d_cg_partial.p, (long)tiles, c->N, c->d_cg_out.p, 0);
+        hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)N), dim3(256), 0, c->stream, r.partial.p, (long)tiles, c->N, r.out.p, 0);
         HIP_TRY(hipGetLastError());
     } else {
-        HIP_TRY(hipMemsetAsync(c->d_cg_out.p, 0, (N ? N : 1) * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(r.out.p, 0, (N ? N : 1) * sizeof(double), c->stream));
     }
-    c->have_cg = true;
+    r.have = true;
     return D2D_OK;
 }
 
-// Power-angle launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed
-// planes, every lane storing its cell's total at the end.  Asynchronous.  Every check comes before anything is enqueued, and a
-// refused launch leaves the previous result as it was.
-static int power_angle_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, int32_t end, float origin, int32_t nbins) {
+int d2d_get_field_coefs_vjp(d2d_ctx* c, double* coef_bar) {
+    if (int rc = result_state(c, c && c->have_scene && c->cg.have && c->cg.out.p, COEF_VJP, "result goes with the grid and the scene")) return rc;
+    if (!coef_bar) return fail(D2D_ERR_INVALID, "coef_bar is NULL");
+    return copy_out(c, {{coef_bar, c->cg.out.p, (size_t)c->N * sizeof(double)}});
+}
+
+// Power-angle build: ONE pass into the zeroed planes, every lane storing its cell's total at the end.
+int d2d_power_angle_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t end, float origin, int32_t nbins) {
     if (!c || !fixed) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_power_angle_launch");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_power_angle_launch");
-    if ((rc = check_fused_sink(c, p_in, "d2d_power_angle_launch", "a host function's profile: bin the paths that d2d_trace_paths gives for the records of d2d_valid_paths",
-                               "a profile is always overwritten")))
-        return rc;
-    {
-        std::string err;
-        if ((rc = d2d_host::angle_params(end, origin, nbins, err))) return fail(rc, "d2d_power_angle_launch: %s", err.c_str());
-    }
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_angle.n + c->d_angle_total.n) * sizeof(float);
-        if (!d2d_host::angle_fits(cells, nbins, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_power_angle_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
-                        cells, d2d_host::angle_bytes_per_cell(nbins), mem_free);
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, "d2d_power_angle_launch", lds))) return rc;
-    c->angle_nbins = 0;  // from here on the buffers change
-    const size_t planes = (size_t)nbins * cells;
-    if ((rc = c->d_angle.ensure(planes)) || (rc = c->d_angle_total.ensure(cells))) return rc;
+    SinkLaunch<d2d_ctx::Angle> L(c, ANGLE, c->angle, fixed);
+    d2d_ctx::Angle& r = c->angle;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::angle_params(end, origin, nbins, err))) return fail(rc, "d2d_power_angle_launch: %s", err.c_str());
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::angle_bytes_per_cell(nbins), (r.out.n + r.total.n) * sizeof(float))) || (rc = L.prepare())) return rc;
+    const size_t planes = (size_t)nbins * L.cells;
+    if ((rc = r.out.ensure(planes)) || (rc = r.total.ensure(L.cells))) return rc;
     d2d::AngleArgs g;
-    g.out = c->d_angle.p;
-    g.total = c->d_angle_total.p;
-    g.cells = (long)cells;
+    g.out = r.out.p;
+    g.total = r.total.p;
+    g.cells = (long)L.cells;
     g.origin = origin;
     g.nbins = nbins;
     g.end = end;
-    HIP_TRY(hipMemsetAsync(c->d_angle.p, 0, planes * sizeof(float), c->stream));
-    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::AngleSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
-    else HIP_TRY(hipMemsetAsync(c->d_angle_total.p, 0, cells * sizeof(float), c->stream));
-    c->angle_nbins = nbins;
+    HIP_TRY(hipMemsetAsync(r.out.p, 0, planes * sizeof(float), c->stream));
+    if (L.s.tiles > 0) HIP_TRY(L.pass<d2d::AngleSink>(g));
+    else HIP_TRY(hipMemsetAsync(r.total.p, 0, L.cells * sizeof(float), c->stream));
+    r.nbins = nbins;
     return D2D_OK;
 }
 
-// Array-response launch of the culled forward sweep with the caller's path function: ONE pass of the sink kernel into the zeroed
-// planes, every lane storing its cell's total at the end.  Asynchronous.  Every check comes before anything is enqueued, and a
-// refused launch leaves the previous result as it was.
-static int array_response_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, float inv_wavelength, int32_t amplitude, int32_t nt,
-                                 const float* tx_elems, int32_t nr, const float* rx_elems) {
+int d2d_get_power_angle(d2d_ctx* c, float* out, float* total) {
+    if (int rc = result_state(c, c && c->angle.nbins >= 1 && c->angle.out.p, ANGLE)) return rc;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    return copy_out(c, {{out, c->angle.out.p, bytes * (size_t)c->angle.nbins}, {total, c->angle.total.p, bytes}});
+}
+
+// Array-response build: ONE pass into the zeroed planes, every lane storing its cell's total at the end.
+int d2d_array_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude, int32_t nt,
+                              const float* tx_elems, int32_t nr, const float* rx_elems) {
     if (!c || !fixed || !tx_elems || !rx_elems) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before d2d_array_response_launch");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before d2d_array_response_launch");
-    if ((rc = check_fused_sink(c, p_in, "d2d_array_response_launch", "a host function's channel matrix: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths",
-                               "the channel matrix is always overwritten")))
-        return rc;
-    {
-        std::string err;
-        if ((rc = d2d_host::array_params(nt, tx_elems, nr, rx_elems, inv_wavelength, amplitude, err))) return fail(rc, "d2d_array_response_launch: %s", err.c_str());
-    }
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_array_re.n + c->d_array_im.n + c->d_array_total.n) * sizeof(float);
-        if (!d2d_host::array_fits(cells, nt, nr, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "d2d_array_response_launch: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)",
-                        cells, d2d_host::array_bytes_per_cell(nt, nr), mem_free);
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, "d2d_array_response_launch", lds))) return rc;
-    c->array_nt = c->array_nr = 0;  // from here on the buffers change
-    const size_t planes = (size_t)nr * (size_t)nt * cells;
-    if ((rc = c->d_array_re.ensure(planes)) || (rc = c->d_array_im.ensure(planes)) || (rc = c->d_array_total.ensure(cells))) return rc;
+    SinkLaunch<d2d_ctx::Array> L(c, ARRAY, c->array, fixed);
+    d2d_ctx::Planes& o = c->array.out;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::array_params(nt, tx_elems, nr, rx_elems, inv_wavelength, amplitude, err))) return fail(rc, "d2d_array_response_launch: %s", err.c_str());
+    const size_t planes = (size_t)nr * (size_t)nt * L.cells;
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::array_bytes_per_cell(nt, nr), o.bytes())) || (rc = L.prepare()) || (rc = o.ensure(planes, L.cells))) return rc;
     d2d::ArrayArgs g = {};
-    g.re = c->d_array_re.p;
-    g.im = c->d_array_im.p;
-    g.total = c->d_array_total.p;
-    g.cells = (long)cells;
+    g.re = o.re.p;
+    g.im = o.im.p;
+    g.total = o.total.p;
+    g.cells = (long)L.cells;
     g.inv_wavelength = inv_wavelength;
     g.amplitude = amplitude;
     g.nt = nt;
     g.nr = nr;
     for (int32_t j = 0; j < nt; ++j) g.etx[j][0] = tx_elems[2 * j], g.etx[j][1] = tx_elems[2 * j + 1];
     for (int32_t i = 0; i < nr; ++i) g.erx[i][0] = rx_elems[2 * i], g.erx[i][1] = rx_elems[2 * i + 1];
-    HIP_TRY(hipMemsetAsync(c->d_array_re.p, 0, planes * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_array_im.p, 0, planes * sizeof(float), c->stream));
-    if (s.tiles > 0) HIP_TRY(d2d::launch_sink<d2d::ArraySink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
-    else HIP_TRY(hipMemsetAsync(c->d_array_total.p, 0, cells * sizeof(float), c->stream));
-    c->array_nt = nt;
-    c->array_nr = nr;
+    HIP_TRY(hipMemsetAsync(o.re.p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(o.im.p, 0, planes * sizeof(float), c->stream));
+    if (L.s.tiles > 0) HIP_TRY(L.pass<d2d::ArraySink>(g));
+    else HIP_TRY(hipMemsetAsync(o.total.p, 0, L.cells * sizeof(float), c->stream));
+    c->array.nt = nt;
+    c->array.nr = nr;
     return D2D_OK;
 }
 
-// Wideband array-response launch of the culled forward sweep with the caller's path function: ONE preparation, then one pass of
-// the sink kernel per chunk of WIDE_CHUNK wavelengths over the same SweepArgs (as d2d_frequency_response_launch does), every pass
-// adding into the zeroed plane blocks of its chunk and the first storing the total.  Asynchronous.  Every check comes before
-// anything is enqueued, and a refused launch leaves the previous result as it was.
-static_assert(d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK, "d2d_host.hpp and d2d_kernels.hpp disagree");
-static int array_frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, const float* fixed, const float* inv_wavelength, int32_t nf,
-                                           int32_t amplitude, int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems) {
-    static const char who[] = "d2d_array_frequency_response_launch";
+int d2d_get_array_response(d2d_ctx* c, float* re, float* im, float* total) {
+    if (int rc = result_state(c, c && c->array.nt >= 1 && c->array.nr >= 1 && c->array.out.re.p, ARRAY)) return rc;
+    const d2d_ctx::Planes& o = c->array.out;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float), pairs = (size_t)c->array.nt * (size_t)c->array.nr;
+    return copy_out(c, {{re, o.re.p, bytes * pairs}, {im, o.im.p, bytes * pairs}, {total, o.total.p, bytes}});
+}
+
+// Wideband array-response build: ONE preparation, then one pass per chunk of WIDE_CHUNK wavelengths over the same SweepArgs (as
+// d2d_frequency_response_launch does), every pass adding into the zeroed plane blocks of its chunk and the first storing the total.
+int d2d_array_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                                        int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems) {
     if (!c || !fixed || !inv_wavelength || !tx_elems || !rx_elems) return fail(D2D_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (!c->have_scene) return fail(D2D_ERR_STATE, "d2d_set_scene must come before %s", who);
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "d2d_set_grid must come before %s", who);
-    if ((rc = check_fused_sink(c, p_in, who, "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths",
-                               "the channel matrices are always overwritten")))
-        return rc;
-    {
-        std::string err;
-        if ((rc = d2d_host::wide_params(inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems, err))) return fail(rc, "%s: %s", who, err.c_str());
-    }
-    if ((rc = set_device(c))) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    {
-        size_t mem_free = 0, mem_total = 0;
-        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = (c->d_wide_re.n + c->d_wide_im.n + c->d_wide_total.n) * sizeof(float);
-        if (!d2d_host::wide_fits(cells, nf, nt, nr, mem_free, held))
-            return fail(D2D_ERR_UNSUPPORTED, "%s: %zu cells (%zu bytes per cell) exceed half of the free device memory (%zu bytes free)", who, cells,
-                        d2d_host::wide_bytes_per_cell(nf, nt, nr), mem_free);
-    }
-    d2d_params pp = *p_in;
-    pp.strict_nan = 0;
-    const d2d_params* p = &pp;
-    Sweep s(c, p, fixed);
-    size_t lds = 0;
-    if ((rc = prep_sink_sweep(c, s, who, lds))) return rc;
-    c->wide_nf = c->wide_nt = c->wide_nr = 0;  // from here on the buffers change
-    const size_t block = (size_t)nr * (size_t)nt * cells;  // one wavelength's planes
+    SinkLaunch<d2d_ctx::Wide> L(c, WIDE, c->wide, fixed);
+    d2d_ctx::Planes& o = c->wide.out;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::wide_params(inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems, err))) return fail(rc, "%s: %s", WIDE.who, err.c_str());
+    const size_t block = (size_t)nr * (size_t)nt * L.cells;  // one wavelength's planes
     const size_t planes = (size_t)nf * block;
-    if ((rc = c->d_wide_re.ensure(planes)) || (rc = c->d_wide_im.ensure(planes)) || (rc = c->d_wide_total.ensure(cells))) return rc;
-    HIP_TRY(hipMemsetAsync(c->d_wide_re.p, 0, planes * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_wide_im.p, 0, planes * sizeof(float), c->stream));
-    if (s.tiles > 0)
-        for (int32_t i = 0; i < d2d_host::wide_chunks(nf); ++i) {
-            const d2d_host::FreqChunk ch = d2d_host::wide_chunk(nf, i);
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::wide_bytes_per_cell(nf, nt, nr), o.bytes())) || (rc = L.prepare()) || (rc = o.ensure(planes, L.cells))) return rc;
+    HIP_TRY(hipMemsetAsync(o.re.p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(o.im.p, 0, planes * sizeof(float), c->stream));
+    if (L.s.tiles > 0)
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::WIDE_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::WIDE_CHUNK);
             d2d::ArrayFreqArgs g = {};
-            g.re = c->d_wide_re.p + (size_t)ch.first * block;
-            g.im = c->d_wide_im.p + (size_t)ch.first * block;
-            g.total = ch.with_total ? c->d_wide_total.p : nullptr;
-            g.cells = (long)cells;
+            g.re = o.re.p + (size_t)ch.first * block;
+            g.im = o.im.p + (size_t)ch.first * block;
+            g.total = ch.with_total ? o.total.p : nullptr;
+            g.cells = (long)L.cells;
             g.amplitude = amplitude;
             g.nf = ch.count;
             g.nt = nt;
@@ -2695,165 +2687,23 @@ static int array_frequency_response_launch(d2d_ctx* c, const d2d_params* p_in, c
             for (int32_t f = 0; f < ch.count; ++f) g.inv[f] = inv_wavelength[ch.first + f];
             for (int32_t j = 0; j < nt; ++j) g.etx[j][0] = tx_elems[2 * j], g.etx[j][1] = tx_elems[2 * j + 1];
             for (int32_t k = 0; k < nr; ++k) g.erx[k][0] = rx_elems[2 * k], g.erx[k][1] = rx_elems[2 * k + 1];
-            HIP_TRY(d2d::launch_sink<d2d::ArrayFreqSink>(s.th.mode, s.txg, p->max_order, s.grid_patches, lds, c->stream, s.a, g));
+            HIP_TRY(L.pass<d2d::ArrayFreqSink>(g));
         }
-    else HIP_TRY(hipMemsetAsync(c->d_wide_total.p, 0, cells * sizeof(float), c->stream));
-    c->wide_nf = nf;
-    c->wide_nt = nt;
-    c->wide_nr = nr;
+    else HIP_TRY(hipMemsetAsync(o.total.p, 0, L.cells * sizeof(float), c->stream));
+    c->wide.nf = nf;
+    c->wide.nt = nt;
+    c->wide.nr = nr;
     return D2D_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int d2d_array_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
-                                        int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems) {
-    return array_frequency_response_launch(c, p, fixed, inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems);
 }
 
 int d2d_get_array_frequency_response(d2d_ctx* c, int32_t first, int32_t count, float* re, float* im, float* total) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (c->wide_nf < 1 || !c->d_wide_re.p) return fail(D2D_ERR_STATE, "d2d_array_frequency_response_launch must come first (its result goes with the grid)");
-    if (first < 0 || count < 1 || count > c->wide_nf - first)
-        return fail(D2D_ERR_INVALID, "d2d_get_array_frequency_response: first %d and count %d are no range of the result's %d wavelengths", first, count, c->wide_nf);
-    int rc = set_device(c);
-    if (rc) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n;
-    const size_t block = (size_t)c->wide_nr * (size_t)c->wide_nt * cells;
+    if (int rc = result_state(c, c && c->wide.nf >= 1 && c->wide.out.re.p, WIDE)) return rc;
+    if (first < 0 || count < 1 || count > c->wide.nf - first)
+        return fail(D2D_ERR_INVALID, "d2d_get_array_frequency_response: first %d and count %d are no range of the result's %d wavelengths", first, count, c->wide.nf);
+    const d2d_ctx::Planes& o = c->wide.out;
+    const size_t cells = (size_t)c->m * (size_t)c->n, block = (size_t)c->wide.nr * (size_t)c->wide.nt * cells;
     const size_t bytes = (size_t)count * block * sizeof(float);
-    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_wide_re.p + (size_t)first * block, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_wide_im.p + (size_t)first * block, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_wide_total.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_array_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude, int32_t nt,
-                              const float* tx_elems, int32_t nr, const float* rx_elems) {
-    return array_response_launch(c, p, fixed, inv_wavelength, amplitude, nt, tx_elems, nr, rx_elems);
-}
-
-int d2d_get_array_response(d2d_ctx* c, float* re, float* im, float* total) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (c->array_nt < 1 || c->array_nr < 1 || !c->d_array_re.p) return fail(D2D_ERR_STATE, "d2d_array_response_launch must come first (its result goes with the grid)");
-    int rc = set_device(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
-    const size_t pairs = (size_t)c->array_nt * (size_t)c->array_nr;
-    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_array_re.p, bytes * pairs, hipMemcpyDeviceToHost, c->stream));
-    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_array_im.p, bytes * pairs, hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_array_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_power_angle_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t end, float origin, int32_t nbins) {
-    return power_angle_launch(c, p, fixed, end, origin, nbins);
-}
-
-int d2d_get_power_angle(d2d_ctx* c, float* out, float* total) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (c->angle_nbins < 1 || !c->d_angle.p) return fail(D2D_ERR_STATE, "d2d_power_angle_launch must come first (its result goes with the grid)");
-    int rc = set_device(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
-    if (out) HIP_TRY(hipMemcpyAsync(out, c->d_angle.p, bytes * (size_t)c->angle_nbins, hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_angle_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_field_coefs_vjp_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
-                               const float* re_bar, const float* im_bar) {
-    return field_coefs_vjp_launch(c, p, fixed, inv_wavelength, nf, amplitude, re_bar, im_bar);
-}
-
-int d2d_get_field_coefs_vjp(d2d_ctx* c, double* coef_bar) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (!c->have_scene || !c->have_cg || !c->d_cg_out.p)
-        return fail(D2D_ERR_STATE, "d2d_field_coefs_vjp_launch must come first (its result goes with the grid and the scene)");
-    if (!coef_bar) return fail(D2D_ERR_INVALID, "coef_bar is NULL");
-    int rc = set_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(coef_bar, c->d_cg_out.p, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_frequency_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude) {
-    return frequency_response_launch(c, p, fixed, inv_wavelength, nf, amplitude);
-}
-
-int d2d_get_frequency_response(d2d_ctx* c, float* re, float* im, float* total) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (c->freq_nf < 1 || !c->d_freq_re.p) return fail(D2D_ERR_STATE, "d2d_frequency_response_launch must come first (its result goes with the grid)");
-    int rc = set_device(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
-    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_freq_re.p, bytes * (size_t)c->freq_nf, hipMemcpyDeviceToHost, c->stream));
-    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_freq_im.p, bytes * (size_t)c->freq_nf, hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_freq_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_coherent_field_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float inv_wavelength, int32_t amplitude) {
-    return coherent_field_launch(c, p, fixed, inv_wavelength, amplitude);
-}
-
-int d2d_get_coherent_field(d2d_ctx* c, float* re, float* im, float* total) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (!c->have_field || !c->d_field_re.p) return fail(D2D_ERR_STATE, "d2d_coherent_field_launch must come first (its result goes with the grid)");
-    int rc = set_device(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
-    if (re) HIP_TRY(hipMemcpyAsync(re, c->d_field_re.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (im) HIP_TRY(hipMemcpyAsync(im, c->d_field_im.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_field_total.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_strongest_paths_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, int32_t k) { return strongest_paths_launch(c, p, fixed, k); }
-
-int d2d_get_strongest_paths(d2d_ctx* c, float* power, float* length, int32_t* cand, int32_t* order, float* total, int32_t* count) {
-    if (!c) return fail(D2D_ERR_INVALID, "ctx is NULL");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (c->top_k < 1 || !c->d_top_power.p) return fail(D2D_ERR_STATE, "d2d_strongest_paths_launch must come first (its result goes with the grid)");
-    int rc = set_device(c);
-    if (rc) return rc;
-    const size_t cells = (size_t)c->m * (size_t)c->n, kc = (size_t)c->top_k * cells;
-    if (power) HIP_TRY(hipMemcpyAsync(power, c->d_top_power.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (length) HIP_TRY(hipMemcpyAsync(length, c->d_top_len.p, kc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (cand) HIP_TRY(hipMemcpyAsync(cand, c->d_top_cand.p, kc * D2D_MAX_ORDER * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (order) HIP_TRY(hipMemcpyAsync(order, c->d_top_order.p, kc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(hipMemcpyAsync(total, c->d_top_total.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (count) HIP_TRY(hipMemcpyAsync(count, c->d_top_count.p, cells * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
-}
-
-int d2d_power_profile_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, float r_min, float r_max, int32_t nbins) {
-    return power_profile_launch(c, p, fixed, r_min, r_max, nbins);
-}
-
-int d2d_get_power_profile(d2d_ctx* c, float* out) {
-    if (!c || !out) return fail(D2D_ERR_INVALID, "NULL argument");
-    if (!c->have_grid) return fail(D2D_ERR_STATE, "no grid set");
-    if (c->prof_nbins < 1 || !c->d_profile.p) return fail(D2D_ERR_STATE, "d2d_power_profile_launch must come first (its profile goes with the grid)");
-    int rc = set_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->d_profile.p, (size_t)c->prof_nbins * (size_t)c->m * c->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
+    return copy_out(c, {{re, o.re.p + (size_t)first * block, bytes}, {im, o.im.p + (size_t)first * block, bytes}, {total, o.total.p, cells * sizeof(float)}});
 }
 
 int d2d_valid_paths(d2d_ctx* c, const d2d_params* p, const float* fixed, int64_t* count) { return valid_paths(c, p, fixed, count); }
@@ -2865,18 +2715,10 @@ int d2d_get_valid_paths(d2d_ctx* c, int64_t capacity, int32_t* cell, int32_t* ca
     if (capacity < c->rec_n) return fail(D2D_ERR_INVALID, "capacity %lld is less than the %lld records held", (long long)capacity, c->rec_n);
     const size_t n = (size_t)c->rec_n;
     if (n == 0) return D2D_OK;
-    int rc = set_device(c);
-    if (rc) return rc;
     constexpr size_t NPTS = D2D_MAX_ORDER + 2;
-    if (cell) HIP_TRY(hipMemcpyAsync(cell, c->d_rec_cell.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (cand) HIP_TRY(hipMemcpyAsync(cand, c->d_rec_cand.p, n * D2D_MAX_ORDER * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (order) HIP_TRY(hipMemcpyAsync(order, c->d_rec_order.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (xys) HIP_TRY(hipMemcpyAsync(xys, c->d_rec_xys.p, n * NPTS * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (loss) HIP_TRY(hipMemcpyAsync(loss, c->d_rec_loss.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (valid) HIP_TRY(hipMemcpyAsync(valid, c->d_rec_valid.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (length) HIP_TRY(hipMemcpyAsync(length, c->d_rec_len.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return D2D_OK;
+    return copy_out(c, {{cell, c->d_rec_cell.p, n * sizeof(int)}, {cand, c->d_rec_cand.p, n * D2D_MAX_ORDER * sizeof(int)}, {order, c->d_rec_order.p, n * sizeof(int)},
+                        {xys, c->d_rec_xys.p, n * NPTS * 2 * sizeof(float)}, {loss, c->d_rec_loss.p, n * sizeof(float)}, {valid, c->d_rec_valid.p, n * sizeof(float)},
+                        {length, c->d_rec_len.p, n * sizeof(float)}});
 }
 
 int d2d_debug_valid_paths_ms(d2d_ctx* c, float* ms) {

@@ -241,34 +241,56 @@ inline int profile_bins(float r_min, float r_max, int32_t nbins, ProfileBins& b,
     return D2D_OK;
 }
 
+// ---- what the products of the sink kernel share on the host -------------------------------------------------------------
+// The memory check: a launch is refused when its outputs, bytes_per_cell for each of the grid's cells (a product's
+// *_bytes_per_cell below; 0 stands for counts out of range and refuses), exceed half of the device memory that is free, counting
+// what the product's buffers hold already as free.  No sum or product is formed that could wrap: cells is held against a quotient.
+inline bool outputs_fit(size_t cells, size_t bytes_per_cell, size_t mem_free, size_t held_bytes) {
+    if (bytes_per_cell == 0) return false;
+    return cells <= (mem_free / 2 + held_bytes / 2) / bytes_per_cell;
+}
+// D2D_ERR_INVALID: an inverse wavelength that is negative, NaN or infinite (0 is allowed: every phase is 0), an amplitude mode that
+// is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.  `noun` is the product in the message ("the coherent field").
+inline bool inv_wavelength_ok(float v) { return std::isfinite(v) && v >= 0.0f; }
+inline int check_inv_wavelength(const char* noun, float v, std::string& err) {
+    if (inv_wavelength_ok(v)) return D2D_OK;
+    return err = std::string(noun) + " needs a finite inv_wavelength >= 0, got " + std::to_string(v), D2D_ERR_INVALID;
+}
+inline int check_amplitude(const char* noun, int32_t amplitude, std::string& err) {
+    if (amplitude == D2D_FIELD_AMP_SQRT || amplitude == D2D_FIELD_AMP_LINEAR) return D2D_OK;
+    return err = std::string(noun) + "'s amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
+           D2D_ERR_INVALID;
+}
+// The launches of a product that takes its wavelengths `chunk` at a time: chunks(nf, chunk) passes of the sink kernel over the same
+// prepared sweep.  Pass i takes the entries first .. first + count - 1 of the list, writes their planes from plane (block) `first`
+// on, and the first pass alone stores total.
+struct Chunk {
+    int32_t first = 0, count = 0;
+    bool with_total = false;
+};
+inline int32_t chunks(int32_t nf, int32_t chunk) { return (nf + chunk - 1) / chunk; }
+inline Chunk chunk_plan(int32_t nf, int32_t i, int32_t chunk) {
+    Chunk ch;
+    ch.first = i * chunk;
+    ch.count = std::min<int32_t>(chunk, nf - ch.first);
+    ch.with_total = i == 0;
+    return ch;
+}
+
 // ---- outputs of the per-cell strongest paths (d2d_strongest_paths_launch, d2d::TopSink) ------------------------------
 // Per cell: k slots of power, length, order (4 bytes each) and D2D_MAX_ORDER wall indices, then total and count.  The launch is
 // refused when the outputs exceed half of the device memory that is free, counting what the buffers hold already as free
 // (tests/native/strongest_paths_host.cpp: a grid large enough to be refused does not fit a quick test).
 inline size_t top_bytes_per_cell(int32_t k) { return (size_t)k * (3 + D2D_MAX_ORDER) * 4 + 8; }
-inline bool top_fits(size_t cells, int32_t k, size_t mem_free, size_t held_bytes) {
-    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
-    return cells <= budget / top_bytes_per_cell(k);
-}
 
 // ---- parameters and outputs of the coherent field (d2d_coherent_field_launch, d2d::FieldSink) -----------------------
-// D2D_ERR_INVALID: an inverse wavelength that is negative, NaN or infinite (0 is allowed: every phase is 0), an amplitude
-// mode that is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.
+// D2D_ERR_INVALID: the inverse wavelength, then the amplitude mode (check_inv_wavelength, check_amplitude).
 inline int field_params(float inv_wavelength, int32_t amplitude, std::string& err) {
-    if (!std::isfinite(inv_wavelength) || inv_wavelength < 0.0f)
-        return err = "the coherent field needs a finite inv_wavelength >= 0, got " + std::to_string(inv_wavelength), D2D_ERR_INVALID;
-    if (amplitude != D2D_FIELD_AMP_SQRT && amplitude != D2D_FIELD_AMP_LINEAR)
-        return err = "the coherent field's amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
-               D2D_ERR_INVALID;
-    return D2D_OK;
+    if (int rc = check_inv_wavelength("the coherent field", inv_wavelength, err)) return rc;
+    return check_amplitude("the coherent field", amplitude, err);
 }
-// Per cell: re, im and total, 4 bytes each.  Refused like the strongest paths: outputs above half of the device memory that is
-// free, counting what the buffers hold already as free (tests/native/coherent_field_host.cpp).
+// Per cell: re, im and total, 4 bytes each (outputs_fit; tests/native/coherent_field_host.cpp).
 constexpr size_t FIELD_BYTES_PER_CELL = 12;
-inline bool field_fits(size_t cells, size_t mem_free, size_t held_bytes) {
-    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
-    return cells <= budget / FIELD_BYTES_PER_CELL;
-}
 
 // ---- parameters, outputs and launch plan of the frequency response (d2d_frequency_response_launch, d2d::FreqSink) ---
 // D2D_ERR_INVALID: nf outside 1 .. D2D_FREQ_MAX, an entry that is negative, NaN or infinite (the message names its index; 0 is
@@ -277,38 +299,16 @@ inline int freq_params(const float* inv_wavelength, int32_t nf, int32_t amplitud
     if (nf < 1 || nf > D2D_FREQ_MAX)
         return err = "the frequency response needs nf in 1 .. " + std::to_string(D2D_FREQ_MAX) + ", got " + std::to_string(nf), D2D_ERR_INVALID;
     for (int32_t j = 0; j < nf; ++j)
-        if (!std::isfinite(inv_wavelength[j]) || inv_wavelength[j] < 0.0f)
+        if (!inv_wavelength_ok(inv_wavelength[j]))
             return err = "the frequency response needs every inv_wavelength finite and >= 0, got " + std::to_string(inv_wavelength[j]) +
                          " at index " + std::to_string(j),
                    D2D_ERR_INVALID;
-    if (amplitude != D2D_FIELD_AMP_SQRT && amplitude != D2D_FIELD_AMP_LINEAR)
-        return err = "the frequency response's amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
-               D2D_ERR_INVALID;
-    return D2D_OK;
+    return check_amplitude("the frequency response", amplitude, err);
 }
-// Per cell: nf planes of re and im and one total, 4 bytes each.  Refused like the coherent field: outputs above half of the device
-// memory that is free, counting what the buffers hold already as free (tests/native/frequency_response_host.cpp).  No product is
-// formed: cells is held against a quotient.
+// Per cell: nf planes of re and im and one total, 4 bytes each (outputs_fit; tests/native/frequency_response_host.cpp).
 inline size_t freq_bytes_per_cell(int32_t nf) { return 8 * (size_t)nf + 4; }
-inline bool freq_fits(size_t cells, int32_t nf, size_t mem_free, size_t held_bytes) {
-    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
-    return cells <= budget / freq_bytes_per_cell(nf);
-}
-// The launches of one call: ceil(nf / FREQ_CHUNK) passes of the sink kernel over the same prepared sweep.  Launch i takes the entries
-// first .. first + count - 1 of the list, stores their planes from plane `first` on, and the first launch alone stores total.
+// One pass of the sink kernel per FREQ_CHUNK wavelengths (chunk_plan).
 constexpr int32_t FREQ_CHUNK = 8;  // = d2d::FREQ_CHUNK (d2d_kernels.hpp)
-struct FreqChunk {
-    int32_t first = 0, count = 0;
-    bool with_total = false;
-};
-inline int32_t freq_chunks(int32_t nf) { return (nf + FREQ_CHUNK - 1) / FREQ_CHUNK; }
-inline FreqChunk freq_chunk(int32_t nf, int32_t i) {
-    FreqChunk ch;
-    ch.first = i * FREQ_CHUNK;
-    ch.count = std::min<int32_t>(FREQ_CHUNK, nf - ch.first);
-    ch.with_total = i == 0;
-    return ch;
-}
 
 // ---- memory of the frequency response's coefficient adjoint (d2d_field_coefs_vjp_launch, d2d::CoefGradSink) -----------
 // The cotangent planes take 8 nf bytes per cell and the partial rows 4 bytes per patch and object.  Refused like the frequency
@@ -336,14 +336,8 @@ inline int angle_params(int32_t end, float origin, int32_t nbins, std::string& e
         return err = "the power-angle profile needs nbins in 1 .. " + std::to_string(D2D_ANGLE_BINS_MAX) + ", got " + std::to_string(nbins), D2D_ERR_INVALID;
     return D2D_OK;
 }
-// Per cell: nbins planes and one total, 4 bytes each.  Refused like the coherent field: outputs above half of the device memory
-// that is free, counting what the buffers hold already as free (tests/native/power_angle_host.cpp).  No product is formed: cells
-// is held against a quotient.
+// Per cell: nbins planes and one total, 4 bytes each (outputs_fit; tests/native/power_angle_host.cpp).
 inline size_t angle_bytes_per_cell(int32_t nbins) { return 4 * (size_t)nbins + 4; }
-inline bool angle_fits(size_t cells, int32_t nbins, size_t mem_free, size_t held_bytes) {
-    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
-    return cells <= budget / angle_bytes_per_cell(nbins);
-}
 
 // ---- parameters and outputs of the array response (d2d_array_response_launch, d2d::ArraySink) ------------------------
 // D2D_ERR_INVALID, in this order: nt, then nr outside 1 .. D2D_ARRAY_MAX; a transmit, then a receive element component that is NaN
@@ -364,21 +358,12 @@ inline int array_params(int32_t nt, const float* tx_elems, int32_t nr, const flo
                                  (k == 0 ? "x" : "y") + " of " + (side == 0 ? "tx_elems" : "rx_elems") + " at index " + std::to_string(j),
                            D2D_ERR_INVALID;
     }
-    if (!std::isfinite(inv_wavelength) || inv_wavelength < 0.0f)
-        return err = "the array response needs a finite inv_wavelength >= 0, got " + std::to_string(inv_wavelength), D2D_ERR_INVALID;
-    if (amplitude != D2D_FIELD_AMP_SQRT && amplitude != D2D_FIELD_AMP_LINEAR)
-        return err = "the array response's amplitude must be D2D_FIELD_AMP_SQRT (0) or D2D_FIELD_AMP_LINEAR (1), got " + std::to_string(amplitude),
-               D2D_ERR_INVALID;
-    return D2D_OK;
+    if (int rc = check_inv_wavelength("the array response", inv_wavelength, err)) return rc;
+    return check_amplitude("the array response", amplitude, err);
 }
-// Per cell: nr * nt planes of re and im and one total, 4 bytes each (at most 516: the counts are in range).  Refused like the
-// coherent field: outputs above half of the device memory that is free, counting what the buffers hold already as free
-// (tests/native/array_response_host.cpp).  No product with cells is formed: cells is held against a quotient.
+// Per cell: nr * nt planes of re and im and one total, 4 bytes each (at most 516: the counts are in range; outputs_fit;
+// tests/native/array_response_host.cpp).
 inline size_t array_bytes_per_cell(int32_t nt, int32_t nr) { return 8 * (size_t)nr * (size_t)nt + 4; }
-inline bool array_fits(size_t cells, int32_t nt, int32_t nr, size_t mem_free, size_t held_bytes) {
-    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
-    return cells <= budget / array_bytes_per_cell(nt, nr);
-}
 
 // ---- parameters, outputs and launch plan of the wideband array response (d2d_array_frequency_response_launch, d2d::ArrayFreqSink) ---
 // D2D_ERR_INVALID: what freq_params refuses of the list (nf outside 1 .. D2D_FREQ_MAX, an entry that is negative, NaN or infinite: the
@@ -391,31 +376,13 @@ inline int wide_params(const float* inv_wavelength, int32_t nf, int32_t amplitud
     return array_params(nt, tx_elems, nr, rx_elems, 0.0f, amplitude, err);
 }
 // Per cell: nf * nr * nt planes of re and im and one total, 4 bytes each (at most 524 292 with the counts in range; 0 with a count
-// that is not: wide_fits then refuses).  Refused like the array response: outputs above half of the device memory that is free,
-// counting what the buffers hold already as free (tests/native/array_frequency_response_host.cpp).  No product with cells is
-// formed: cells is held against a quotient.
+// that is not: outputs_fit then refuses; tests/native/array_frequency_response_host.cpp).
 inline size_t wide_bytes_per_cell(int32_t nf, int32_t nt, int32_t nr) {
     if (nf < 1 || nf > D2D_FREQ_MAX || nt < 1 || nt > D2D_ARRAY_MAX || nr < 1 || nr > D2D_ARRAY_MAX) return 0;
     return 8 * (size_t)nf * (size_t)nr * (size_t)nt + 4;
 }
-inline bool wide_fits(size_t cells, int32_t nf, int32_t nt, int32_t nr, size_t mem_free, size_t held_bytes) {
-    const size_t per_cell = wide_bytes_per_cell(nf, nt, nr);
-    if (per_cell == 0) return false;
-    const size_t budget = mem_free / 2 + held_bytes / 2;  // (no sum that could wrap)
-    return cells <= budget / per_cell;
-}
-// The launches of one call: ceil(nf / WIDE_CHUNK) passes of the sink kernel over the same prepared sweep, as freq_chunk plans the
-// frequency response's.  Launch i takes the entries first .. first + count - 1 of the list, adds into their plane blocks from block
-// `first` on, and the first launch alone stores total.
+// One pass of the sink kernel per WIDE_CHUNK wavelengths (chunk_plan), each adding into the plane blocks of its chunk.
 constexpr int32_t WIDE_CHUNK = 32;  // = d2d::WIDE_CHUNK (d2d_kernels.hpp)
-inline int32_t wide_chunks(int32_t nf) { return (nf + WIDE_CHUNK - 1) / WIDE_CHUNK; }
-inline FreqChunk wide_chunk(int32_t nf, int32_t i) {
-    FreqChunk ch;
-    ch.first = i * WIDE_CHUNK;
-    ch.count = std::min<int32_t>(WIDE_CHUNK, nf - ch.first);
-    ch.with_total = i == 0;
-    return ch;
-}
 
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)

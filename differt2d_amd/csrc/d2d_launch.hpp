@@ -35,25 +35,24 @@ hipError_t launch_sink_m(bool txg, int max_order, dim3 grid, size_t lds, hipStre
 D2D_DECLARE_MODE(MODE_HARD)
 D2D_DECLARE_MODE(MODE_HSIG)
 D2D_DECLARE_MODE(MODE_SIG)
-#undef D2D_DECLARE_MODE  // (the sink kernel has no sigmoid instance: launch_sink answers hipErrorInvalidValue)
-template <> hipError_t launch_sink_m<MODE_HARD, RecSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, RecSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const RecArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, BinSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const BinArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, BinSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const BinArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, TopSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const TopArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, TopSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const TopArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, FieldSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const FieldArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, FieldSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const FieldArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, FreqSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const FreqArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, FreqSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const FreqArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, CoefGradSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const CoefGradArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, CoefGradSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const CoefGradArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, AngleSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const AngleArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, AngleSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const AngleArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, ArraySink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, ArraySink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayArgs&);
-template <> hipError_t launch_sink_m<MODE_HARD, ArrayFreqSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayFreqArgs&);
-template <> hipError_t launch_sink_m<MODE_HSIG, ArrayFreqSink>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const ArrayFreqArgs&);
+#undef D2D_DECLARE_MODE
+// The sinks of power_sink_kernel (d2d_kernels.hpp), stated once: this list declares the per-mode launchers here and defines them
+// in d2d_sweep_tu.hip.  A new sink is one more line.  (Hard and hard_sigmoid only: launch_sink answers hipErrorInvalidValue otherwise.)
+#define D2D_SINKS(X)                                                                                          \
+    X(RecSink)       /* the record build (d2d_valid_paths) */                                                 \
+    X(BinSink)       /* the per-cell power-delay profile */                                                   \
+    X(TopSink)       /* the per-cell strongest paths */                                                       \
+    X(FieldSink)     /* the coherent field */                                                                 \
+    X(FreqSink)      /* the frequency response */                                                             \
+    X(CoefGradSink)  /* its adjoint w.r.t. the per-object reflection coefficients */                          \
+    X(AngleSink)     /* the power-angle profile */                                                            \
+    X(ArraySink)     /* the array response */                                                                 \
+    X(ArrayFreqSink) /* the wideband array response */
+#define D2D_DECLARE_SINK(S)                                                                                                      \
+    template <> hipError_t launch_sink_m<MODE_HARD, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&); \
+    template <> hipError_t launch_sink_m<MODE_HSIG, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&);
+D2D_SINKS(D2D_DECLARE_SINK)
+#undef D2D_DECLARE_SINK
 
 // ---- by-mode dispatchers ----
 // `listed`: the LISTED build (orders >= 2 from the region candidate lists, a.rl); otherwise the enumerating build, which
@@ -71,10 +70,7 @@ hipError_t launch_fwd_coop(int mode, int max_order, int W, dim3 grid, size_t lds
 hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
 // power_vg_kernel<MODE, TXG, GRADK>: exhaustive sweeps (strict_nan value+grad; "txg_exhaustive" values)
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
-// power_sink_kernel<MODE, MAXK, TXG, Sink>: the culled sweep into a sink -- RecSink the record build, BinSink the per-cell
-// power-delay profile, TopSink the per-cell strongest paths, FieldSink the coherent field, FreqSink the frequency response, CoefGradSink its
-// adjoint w.r.t. the per-object reflection coefficients, AngleSink the power-angle profile, ArraySink the array response,
-// ArrayFreqSink the wideband array response (hard / hard_sigmoid; any other mode: hipErrorInvalidValue)
+// power_sink_kernel<MODE, MAXK, TXG, Sink>: the culled sweep into one of D2D_SINKS (any other mode: hipErrorInvalidValue)
 template <class Sink>
 hipError_t launch_sink(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const typename Sink::Args& x);
 

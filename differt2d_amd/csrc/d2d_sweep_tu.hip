@@ -2,7 +2,7 @@
 // per-mode launcher (declared in d2d_launch.hpp) that d2d.hip's dispatchers call.  Compiled by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2
 //   taken from the region lists (LISTED), 9 fwd_coop}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}: all 27 pairs;
-//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (record, bin, strongest-path, coherent-field, frequency-response, coefficient-adjoint, power-angle, array-response and wideband array-response builds) for modes 0 and 1 (no sigmoid instance)
+//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (every sink of D2D_SINKS, d2d_launch.hpp) for modes 0 and 1 (no sigmoid instance)
 #include <type_traits>
 
 #include "d2d_launch.hpp"
@@ -167,42 +167,13 @@ static hipError_t launch_sink_tu(bool txg, int max_order, dim3 grid, size_t lds,
     else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_sink_kernel<TU_MODE, decltype(K)::value, false, Sink>), grid, block, lds, s, a, x); });
     return hipGetLastError();
 }
-template <>
-hipError_t launch_sink_m<TU_MODE, RecSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const RecArgs& r) {
-    return launch_sink_tu<RecSink>(txg, max_order, grid, lds, s, a, r);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, BinSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const BinArgs& b) {
-    return launch_sink_tu<BinSink>(txg, max_order, grid, lds, s, a, b);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, TopSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const TopArgs& t) {
-    return launch_sink_tu<TopSink>(txg, max_order, grid, lds, s, a, t);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, FieldSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const FieldArgs& f) {
-    return launch_sink_tu<FieldSink>(txg, max_order, grid, lds, s, a, f);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, FreqSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const FreqArgs& f) {
-    return launch_sink_tu<FreqSink>(txg, max_order, grid, lds, s, a, f);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, CoefGradSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const CoefGradArgs& g) {
-    return launch_sink_tu<CoefGradSink>(txg, max_order, grid, lds, s, a, g);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, AngleSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const AngleArgs& g) {
-    return launch_sink_tu<AngleSink>(txg, max_order, grid, lds, s, a, g);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, ArraySink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const ArrayArgs& g) {
-    return launch_sink_tu<ArraySink>(txg, max_order, grid, lds, s, a, g);
-}
-template <>
-hipError_t launch_sink_m<TU_MODE, ArrayFreqSink>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const ArrayFreqArgs& g) {
-    return launch_sink_tu<ArrayFreqSink>(txg, max_order, grid, lds, s, a, g);
-}
+#define D2D_DEFINE_SINK(S)                                                                                                                      \
+    template <>                                                                                                                                 \
+    hipError_t launch_sink_m<TU_MODE, S>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const S::Args& x) { \
+        return launch_sink_tu<S>(txg, max_order, grid, lds, s, a, x);                                                                           \
+    }
+D2D_SINKS(D2D_DEFINE_SINK)
+#undef D2D_DEFINE_SINK
 #else
 #error "unknown D2D_TU_FAMILY"
 #endif

@@ -121,6 +121,26 @@ FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINE
 ANGLE_ENDS = {"tx": L.D2D_ANGLE_AT_TX, "rx": L.D2D_ANGLE_AT_RX}
 
 
+def _amplitude_id(method: str, amplitude) -> int:
+    """The library's constant of an amplitude mode that may be given by name; ``method`` begins the refusal of an unknown name."""
+    if isinstance(amplitude, str):
+        if amplitude not in FIELD_AMPLITUDES:
+            raise L.D2DError(-1, f"{method}: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
+        amplitude = FIELD_AMPLITUDES[amplitude]
+    return int(amplitude)
+
+
+def _keep_pointer(a: np.ndarray, *shape) -> np.ndarray:
+    """An empty list still hands the library a pointer: it refuses a count of 0 itself."""
+    return a if a.size else np.zeros(shape, np.float32)
+
+
+def _no_result(ctx, getter, launch_name: str, *nulls):
+    """A getter without an accepted launch: the library says why (nothing is copied: ``nulls`` are its buffers)."""
+    L.check(getter(ctx, *nulls))
+    raise L.D2DError(-5, f"{launch_name} must come first")
+
+
 def _immutable(a: np.ndarray) -> bool:
     """Nobody can write to this array's memory through NumPy: it and every array it is a view of are read-only."""
     while isinstance(a, np.ndarray):
@@ -617,9 +637,8 @@ class Context:
     def get_strongest_paths(self) -> "StrongestPaths":
         """Synchronises and returns the result of the last :meth:`launch_strongest_paths`."""
         k = self._top_k
-        if k < 1:  # (the library says why: nothing is copied)
-            L.check(self._lib.d2d_get_strongest_paths(self._ctx, None, None, None, None, None, None))
-            raise L.D2DError(-5, "launch_strongest_paths must come first")
+        if k < 1:
+            _no_result(self._ctx, self._lib.d2d_get_strongest_paths, "launch_strongest_paths", None, None, None, None, None, None)
         shape = tuple(self.shape)
         sp = StrongestPaths(
             power=np.empty((k,) + shape, np.float32),
@@ -652,18 +671,14 @@ class Context:
         """The launch of :meth:`coherent_field` alone (asynchronous, like :meth:`launch`)."""
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         self._field = False
-        if isinstance(amplitude, str):
-            if amplitude not in FIELD_AMPLITUDES:
-                raise L.D2DError(-1, f"coherent_field: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
-            amplitude = FIELD_AMPLITUDES[amplitude]
-        L.check(self._lib.d2d_coherent_field_launch(self._ctx, C.byref(params), fixed, float(inv_wavelength), int(amplitude)))
+        amplitude = _amplitude_id("coherent_field", amplitude)
+        L.check(self._lib.d2d_coherent_field_launch(self._ctx, C.byref(params), fixed, float(inv_wavelength), amplitude))
         self._field = True
 
     def get_coherent_field(self) -> "CoherentField":
         """Synchronises and returns the result of the last :meth:`launch_coherent_field`."""
-        if not self._field:  # (the library says why: nothing is copied)
-            L.check(self._lib.d2d_get_coherent_field(self._ctx, None, None, None))
-            raise L.D2DError(-5, "launch_coherent_field must come first")
+        if not self._field:
+            _no_result(self._ctx, self._lib.d2d_get_coherent_field, "launch_coherent_field", None, None, None)
         shape = tuple(self.shape)
         cf = CoherentField(re=np.empty(shape, np.float32), im=np.empty(shape, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_coherent_field(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in cf)))
@@ -690,20 +705,16 @@ class Context:
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
         self._freq_nf = 0
-        if isinstance(amplitude, str):
-            if amplitude not in FIELD_AMPLITUDES:
-                raise L.D2DError(-1, f"frequency_response: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
-            amplitude = FIELD_AMPLITUDES[amplitude]
-        keep = inv if inv.size else np.zeros(1, np.float32)  # (an empty list still hands the library a pointer: it refuses nf = 0)
+        amplitude = _amplitude_id("frequency_response", amplitude)
+        keep = _keep_pointer(inv, 1)
         L.check(self._lib.d2d_frequency_response_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
-                                                        int(amplitude)))
+                                                        amplitude))
         self._freq_nf = int(inv.size)
 
     def get_frequency_response(self) -> "FrequencyResponse":
         """Synchronises and returns the result of the last :meth:`launch_frequency_response`."""
-        if not self._freq_nf:  # (the library says why: nothing is copied)
-            L.check(self._lib.d2d_get_frequency_response(self._ctx, None, None, None))
-            raise L.D2DError(-5, "launch_frequency_response must come first")
+        if not self._freq_nf:
+            _no_result(self._ctx, self._lib.d2d_get_frequency_response, "launch_frequency_response", None, None, None)
         shape = tuple(self.shape)
         planes = (self._freq_nf,) + shape
         fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
@@ -729,20 +740,17 @@ class Context:
         asynchronous, like :meth:`launch`)."""
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
-        if isinstance(amplitude, str):
-            if amplitude not in FIELD_AMPLITUDES:
-                raise L.D2DError(-1, f"field_coefs_vjp: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
-            amplitude = FIELD_AMPLITUDES[amplitude]
+        amplitude = _amplitude_id("field_coefs_vjp", amplitude)
         rb = np.ascontiguousarray(re_bar, dtype=np.float32)
         ib = np.ascontiguousarray(im_bar, dtype=np.float32)
         planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
         if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
             raise L.D2DError(-1, f"field_coefs_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
-        keep = inv if inv.size else np.zeros(1, np.float32)  # (an empty list still hands the library pointers: it refuses nf = 0)
+        keep = _keep_pointer(inv, 1)
         if not inv.size:
-            rb = ib = np.zeros(1, np.float32)
+            rb = ib = keep
         L.check(self._lib.d2d_field_coefs_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
-                                                     int(amplitude), rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
+                                                     amplitude, rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
 
     def get_field_coefs_vjp(self) -> np.ndarray:
         """Synchronises and returns the result of the last :meth:`launch_field_coefs_vjp` that was accepted: float64 ``[N]``."""
@@ -780,9 +788,8 @@ class Context:
 
     def get_power_angle(self) -> "PowerAngleProfile":
         """Synchronises and returns the result of the last :meth:`launch_power_angle` that was accepted."""
-        if not self._angle_nbins:  # (the library says why: nothing is copied)
-            L.check(self._lib.d2d_get_power_angle(self._ctx, None, None))
-            raise L.D2DError(-5, "launch_power_angle must come first")
+        if not self._angle_nbins:
+            _no_result(self._ctx, self._lib.d2d_get_power_angle, "launch_power_angle", None, None)
         shape = tuple(self.shape)
         pa = PowerAngleProfile(bins=np.empty((self._angle_nbins,) + shape, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_power_angle(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in pa)))
@@ -813,22 +820,16 @@ class Context:
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         etx = np.ascontiguousarray(tx_elements, dtype=np.float32).reshape(-1, 2)
         erx = np.ascontiguousarray(rx_elements, dtype=np.float32).reshape(-1, 2)
-        if isinstance(amplitude, str):
-            if amplitude not in FIELD_AMPLITUDES:
-                raise L.D2DError(-1, f"array_response: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
-            amplitude = FIELD_AMPLITUDES[amplitude]
-        # (an empty list still hands the library a pointer: it refuses a count of 0)
-        ktx = etx if etx.size else np.zeros((1, 2), np.float32)
-        krx = erx if erx.size else np.zeros((1, 2), np.float32)
-        L.check(self._lib.d2d_array_response_launch(self._ctx, C.byref(params), fixed, float(inv_wavelength), int(amplitude), int(etx.shape[0]),
+        amplitude = _amplitude_id("array_response", amplitude)
+        ktx, krx = _keep_pointer(etx, 1, 2), _keep_pointer(erx, 1, 2)
+        L.check(self._lib.d2d_array_response_launch(self._ctx, C.byref(params), fixed, float(inv_wavelength), amplitude, int(etx.shape[0]),
                                                     ktx, int(erx.shape[0]), krx))
         self._array_shape = (int(erx.shape[0]), int(etx.shape[0]))
 
     def get_array_response(self) -> "ArrayResponse":
         """Synchronises and returns the result of the last :meth:`launch_array_response` that was accepted."""
-        if self._array_shape is None:  # (the library says why: nothing is copied)
-            L.check(self._lib.d2d_get_array_response(self._ctx, None, None, None))
-            raise L.D2DError(-5, "launch_array_response must come first")
+        if self._array_shape is None:
+            _no_result(self._ctx, self._lib.d2d_get_array_response, "launch_array_response", None, None, None)
         shape = tuple(self.shape)
         planes = self._array_shape + shape
         ar = ArrayResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
@@ -861,15 +862,9 @@ class Context:
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
         etx = np.ascontiguousarray(tx_elements, dtype=np.float32).reshape(-1, 2)
         erx = np.ascontiguousarray(rx_elements, dtype=np.float32).reshape(-1, 2)
-        if isinstance(amplitude, str):
-            if amplitude not in FIELD_AMPLITUDES:
-                raise L.D2DError(-1, f"array_frequency_response: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
-            amplitude = FIELD_AMPLITUDES[amplitude]
-        # (an empty list still hands the library a pointer: it refuses a count of 0)
-        kinv = inv if inv.size else np.zeros(1, np.float32)
-        ktx = etx if etx.size else np.zeros((1, 2), np.float32)
-        krx = erx if erx.size else np.zeros((1, 2), np.float32)
-        L.check(self._lib.d2d_array_frequency_response_launch(self._ctx, C.byref(params), fixed, kinv, int(inv.size), int(amplitude),
+        amplitude = _amplitude_id("array_frequency_response", amplitude)
+        kinv, ktx, krx = _keep_pointer(inv, 1), _keep_pointer(etx, 1, 2), _keep_pointer(erx, 1, 2)
+        L.check(self._lib.d2d_array_frequency_response_launch(self._ctx, C.byref(params), fixed, kinv, int(inv.size), amplitude,
                                                               int(etx.shape[0]), ktx, int(erx.shape[0]), krx))
         self._wide_shape = (int(inv.size), int(erx.shape[0]), int(etx.shape[0]))
 
@@ -877,9 +872,8 @@ class Context:
         """Synchronises and returns wavelengths ``first .. first + count - 1`` (``count=None``: all from ``first`` on) of the result
         of the last :meth:`launch_array_frequency_response` that was accepted: ``re`` and ``im`` are ``[count, nr, nt, m, n]``.
         ``with_total=False`` leaves ``total`` out (``None``).  A range outside the result is refused by the library."""
-        if self._wide_shape is None:  # (the library says why: nothing is copied)
-            L.check(self._lib.d2d_get_array_frequency_response(self._ctx, 0, 1, None, None, None))
-            raise L.D2DError(-5, "launch_array_frequency_response must come first")
+        if self._wide_shape is None:
+            _no_result(self._ctx, self._lib.d2d_get_array_frequency_response, "launch_array_frequency_response", 0, 1, None, None, None)
         nf, nr, nt = self._wide_shape
         first = int(first)
         count = nf - first if count is None else int(count)

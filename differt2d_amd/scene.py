@@ -984,19 +984,20 @@ class Scene(Plottable):
                 out["r_coef_bar"] = ctx.get_reflection_coefs_vjp()  # <cot, dZ/d coefficient of every object> [N]
             yield tx_name, out
 
-    def _grid_profile(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, length_range, nbins, path_cls, min_order, max_order,
-                      order, filter_objects, kwargs):
-        """Shared driver of the two power-delay profiles: one launch of the bin build per fixed end point."""
+    def _grid_product(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects,
+                      kwargs, unfused, covers, prepare):
+        """Shared driver of the grid methods of the sink kernel's products: one launch per fixed end point.  ``unfused`` is the
+        refusal of a ``fun`` that is not fused natively, ``covers`` ("the coherent field covers") begins the refusal of another
+        path class; ``prepare()`` runs after both, converts the product's arguments and returns ``launch(ctx, params, name, xy)``,
+        the call of the product's :class:`Context` method for the fixed end point ``name`` at ``xy``."""
         X = np.ascontiguousarray(X, dtype=F)
         Y = np.ascontiguousarray(Y, dtype=F)
         native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
         if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the power-delay profile is a fused sweep (a function "
-                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
-                                       "(Context.valid_paths: every valid path with its length) and bin fun's values on the host")
+            raise L.D2DUnsupported(-4, unfused)
         if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the power-delay profile covers ImagePath only, not path_cls={path_cls.__name__}")
-        r_min, r_max = length_range
+            raise L.D2DUnsupported(-4, f"{covers} ImagePath only, not path_cls={path_cls.__name__}")
+        launch = prepare()
         name, extra = native
         params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
         ctx = self._ctx()
@@ -1005,9 +1006,43 @@ class Scene(Plottable):
             for pt_name, pt in fixed_items:
                 self._upload_for(ctx, native, filter_objects)
                 ctx.set_grid(X, Y)
-                yield pt_name, ctx.power_profile(params, pt.xy, r_min, r_max, nbins)
+                yield pt_name, launch(ctx, params, pt_name, pt.xy)
 
         return results()
+
+    @staticmethod
+    def _inverse_wavelengths(noun, wavelengths, inv_wavelengths):
+        """``prepare``'s share of the products that take a list: raises unless exactly one of the two is given (at once, before
+        any other refusal), and returns the conversion to the fp32 list that the library takes."""
+        if (wavelengths is None) == (inv_wavelengths is None):
+            raise ValueError(f"{noun} takes exactly one of wavelengths= and inv_wavelengths=")
+
+        def convert():
+            if wavelengths is None:
+                return np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
+            with np.errstate(divide="ignore"):
+                return F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the coherent field does
+
+        return convert
+
+    @staticmethod
+    def _inverse_wavelength(wavelength):
+        with np.errstate(divide="ignore"):
+            return F(1) / F(wavelength)  # fp32: one division (an infinite wavelength gives 0: every phase is 0)
+
+    def _grid_profile(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, length_range, nbins, path_cls, min_order, max_order,
+                      order, filter_objects, kwargs):
+        """The two power-delay profiles: one launch of the bin build per fixed end point."""
+        def prepare():
+            r_min, r_max = length_range
+            return lambda ctx, params, _, xy: ctx.power_profile(params, xy, r_min, r_max, nbins)
+
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the power-delay profile is a fused sweep (a function "
+            "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+            "(Context.valid_paths: every valid path with its length) and bin fun's values on the host",
+            "the power-delay profile covers", prepare)
 
     def power_delay_profile_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, length_range, nbins: int, path_cls: type = ImagePath,
@@ -1039,27 +1074,13 @@ class Scene(Plottable):
 
     def _grid_strongest(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, k, path_cls, min_order, max_order, order,
                         filter_objects, kwargs):
-        """Shared driver of the two strongest-path sweeps: one launch of the top-k build per fixed end point."""
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the strongest paths come from a fused sweep (a function "
-                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
-                                       "(Context.valid_paths: every valid path of every cell) and sort fun's values on the host")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the strongest paths cover ImagePath only, not path_cls={path_cls.__name__}")
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
-
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.strongest_paths(params, pt.xy, k)
-
-        return results()
+        """The two strongest-path sweeps: one launch of the top-k build per fixed end point."""
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the strongest paths come from a fused sweep (a function "
+            "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+            "(Context.valid_paths: every valid path of every cell) and sort fun's values on the host",
+            "the strongest paths cover", lambda: lambda ctx, params, _, xy: ctx.strongest_paths(params, xy, k))
 
     def strongest_paths_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, k: int, path_cls: type = ImagePath,
@@ -1093,30 +1114,18 @@ class Scene(Plottable):
 
     def _grid_field(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelength, amplitude, path_cls, min_order, max_order,
                     order, filter_objects, kwargs):
-        """Shared driver of the two coherent-field sweeps: one launch of the coherent-field build per fixed end point."""
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the coherent field comes from a fused sweep (a function "
-                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
-                                       "(Context.valid_paths: every valid path of every cell, with its length) and add fun's "
-                                       "phasors on the host")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the coherent field covers ImagePath only, not path_cls={path_cls.__name__}")
-        with np.errstate(divide="ignore"):
-            inv = F(1) / F(wavelength)  # fp32: one division (an infinite wavelength gives 0: every phase is 0)
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
+        """The two coherent-field sweeps: one launch of the coherent-field build per fixed end point."""
+        def prepare():
+            inv = self._inverse_wavelength(wavelength)
+            return lambda ctx, params, _, xy: ctx.coherent_field(params, xy, inv, amplitude)
 
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.coherent_field(params, pt.xy, inv, amplitude)
-
-        return results()
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the coherent field comes from a fused sweep (a function "
+            "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+            "(Context.valid_paths: every valid path of every cell, with its length) and add fun's "
+            "phasors on the host",
+            "the coherent field covers", prepare)
 
     def coherent_field_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelength: float, amplitude: str = "sqrt",
@@ -1153,35 +1162,20 @@ class Scene(Plottable):
 
     def _grid_response(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelengths, inv_wavelengths, amplitude, path_cls,
                        min_order, max_order, order, filter_objects, kwargs):
-        """Shared driver of the two frequency-response sweeps: one launch of the frequency-response build per fixed end point."""
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        if (wavelengths is None) == (inv_wavelengths is None):
-            raise ValueError("the frequency response takes exactly one of wavelengths= and inv_wavelengths=")
-        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the frequency response comes from a fused sweep (a "
-                                       "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
-                                       "records (Context.valid_paths: every valid path of every cell, with its length) and add "
-                                       "fun's phasors on the host")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the frequency response covers ImagePath only, not path_cls={path_cls.__name__}")
-        if wavelengths is not None:
-            with np.errstate(divide="ignore"):
-                inv = F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the coherent field does
-        else:
-            inv = np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
+        """The two frequency-response sweeps: one launch of the frequency-response build per fixed end point."""
+        convert = self._inverse_wavelengths("the frequency response", wavelengths, inv_wavelengths)
 
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.frequency_response(params, pt.xy, inv, amplitude)
+        def prepare():
+            inv = convert()
+            return lambda ctx, params, _, xy: ctx.frequency_response(params, xy, inv, amplitude)
 
-        return results()
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the frequency response comes from a fused sweep (a "
+            "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+            "records (Context.valid_paths: every valid path of every cell, with its length) and add "
+            "fun's phasors on the host",
+            "the frequency response covers", prepare)
 
     def frequency_response_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None,
@@ -1217,35 +1211,20 @@ class Scene(Plottable):
 
     def _grid_response_coefs_vjp(self, X, Y, fixed_items, grid_is_rx, fun_kwargs, re_bar, im_bar, wavelengths, inv_wavelengths,
                                  amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
-        """Shared driver of the two coefficient adjoints of the frequency response: one launch per fixed end point."""
+        """The two coefficient adjoints of the frequency response: one launch per fixed end point."""
         from .utils import received_power_per_object
 
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        if (wavelengths is None) == (inv_wavelengths is None):
-            raise ValueError("the frequency response takes exactly one of wavelengths= and inv_wavelengths=")
-        native, common = self._sweep_params(received_power_per_object, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun_kwargs={fun_kwargs!r}: received_power_per_object takes r_coef and height only")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the frequency response covers ImagePath only, not path_cls={path_cls.__name__}")
-        if wavelengths is not None:
-            with np.errstate(divide="ignore"):
-                inv = F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the forward product does
-        else:
-            inv = np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
+        convert = self._inverse_wavelengths("the frequency response", wavelengths, inv_wavelengths)
         bar_of = lambda bar, pt_name: bar[pt_name] if isinstance(bar, Mapping) else bar
 
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.field_coefs_vjp(params, pt.xy, inv, bar_of(re_bar, pt_name), bar_of(im_bar, pt_name), amplitude)
+        def prepare():
+            inv = convert()
+            return lambda ctx, params, name, xy: ctx.field_coefs_vjp(params, xy, inv, bar_of(re_bar, name), bar_of(im_bar, name), amplitude)
 
-        return results()
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, received_power_per_object, fun_kwargs, path_cls, min_order, max_order, order, filter_objects,
+            kwargs, f"fun_kwargs={fun_kwargs!r}: received_power_per_object takes r_coef and height only",
+            "the frequency response covers", prepare)
 
     def frequency_response_coefs_vjp_on_receivers_grid(
         self, X, Y, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
@@ -1276,34 +1255,23 @@ class Scene(Plottable):
 
     def _grid_angle(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, at, nbins, origin, path_cls, min_order, max_order, order,
                     filter_objects, kwargs):
-        """Shared driver of the two power-angle sweeps: one launch of the power-angle build per fixed end point."""
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the power-angle profile comes from a fused sweep (a "
-                                       "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
-                                       "records (Context.valid_paths: every valid path of every cell), their points from "
-                                       "Context.trace_paths, and bin fun by direction on the host")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the power-angle profile covers ImagePath only, not path_cls={path_cls.__name__}")
-        if at not in ("rx", "tx"):
-            raise L.D2DError(-1, f"the power-angle profile is taken at=\"rx\" (arrival) or at=\"tx\" (departure), got {at!r}")
-        # bin 0 begins at `origin` radians: in turns, reduced to [0, 1) in float64, then fp32 (a value that rounds to 1.0 is 0.0)
-        turns = F(np.mod(np.float64(origin) / (2.0 * np.pi), 1.0))
-        if turns >= 1:
-            turns = F(0)
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
+        """The two power-angle sweeps: one launch of the power-angle build per fixed end point."""
+        def prepare():
+            if at not in ("rx", "tx"):
+                raise L.D2DError(-1, f"the power-angle profile is taken at=\"rx\" (arrival) or at=\"tx\" (departure), got {at!r}")
+            # bin 0 begins at `origin` radians: in turns, reduced to [0, 1) in float64, then fp32 (a value that rounds to 1.0 is 0.0)
+            turns = F(np.mod(np.float64(origin) / (2.0 * np.pi), 1.0))
+            if turns >= 1:
+                turns = F(0)
+            return lambda ctx, params, _, xy: ctx.power_angle(params, xy, at, turns, nbins)
 
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.power_angle(params, pt.xy, at, turns, nbins)
-
-        return results()
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the power-angle profile comes from a fused sweep (a "
+            "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+            "records (Context.valid_paths: every valid path of every cell), their points from "
+            "Context.trace_paths, and bin fun by direction on the host",
+            "the power-angle profile covers", prepare)
 
     def power_angle_profile_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, at: str = "rx", nbins: int = 36, origin: float = 0.0,
@@ -1341,30 +1309,18 @@ class Scene(Plottable):
 
     def _grid_array(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelength, tx_elements, rx_elements, amplitude, path_cls,
                     min_order, max_order, order, filter_objects, kwargs):
-        """Shared driver of the two array-response sweeps: one launch of the array-response build per fixed end point."""
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the array response comes from a fused sweep (a function "
-                                       "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
-                                       "(Context.valid_paths: every valid path of every cell, with its length), their points "
-                                       "(Context.trace_paths) and add fun's steered phasors on the host")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the array response covers ImagePath only, not path_cls={path_cls.__name__}")
-        with np.errstate(divide="ignore"):
-            inv = F(1) / F(wavelength)  # fp32: one division (an infinite wavelength gives 0: every phase is 0)
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
+        """The two array-response sweeps: one launch of the array-response build per fixed end point."""
+        def prepare():
+            inv = self._inverse_wavelength(wavelength)
+            return lambda ctx, params, _, xy: ctx.array_response(params, xy, inv, tx_elements, rx_elements, amplitude)
 
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.array_response(params, pt.xy, inv, tx_elements, rx_elements, amplitude)
-
-        return results()
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the array response comes from a fused sweep (a function "
+            "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+            "(Context.valid_paths: every valid path of every cell, with its length), their points "
+            "(Context.trace_paths) and add fun's steered phasors on the host",
+            "the array response covers", prepare)
 
     def array_response_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelength: float, tx_elements, rx_elements,
@@ -1402,35 +1358,20 @@ class Scene(Plottable):
 
     def _grid_array_response(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelengths, inv_wavelengths, tx_elements,
                              rx_elements, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
-        """Shared driver of the two wideband array-response sweeps: one launch of the wideband build per fixed end point."""
-        X = np.ascontiguousarray(X, dtype=F)
-        Y = np.ascontiguousarray(Y, dtype=F)
-        if (wavelengths is None) == (inv_wavelengths is None):
-            raise ValueError("the array frequency response takes exactly one of wavelengths= and inv_wavelengths=")
-        native, common = self._sweep_params(fun, (), fun_kwargs, path_cls, None, min_order, max_order, order, kwargs)
-        if native is None:
-            raise L.D2DUnsupported(-4, f"fun={fun!r} is not fused natively: the array frequency response comes from a fused sweep (a "
-                                       "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
-                                       "records (Context.valid_paths: every valid path of every cell, with its length), their "
-                                       "points (Context.trace_paths) and add fun's steered phasors on the host")
-        if self._solver_of(path_cls) != "image":
-            raise L.D2DUnsupported(-4, f"the array frequency response covers ImagePath only, not path_cls={path_cls.__name__}")
-        if wavelengths is not None:
-            with np.errstate(divide="ignore"):
-                inv = F(1) / np.asarray(wavelengths, dtype=F).reshape(-1)  # fp32: one division each, as the frequency response does
-        else:
-            inv = np.asarray(inv_wavelengths, dtype=F).reshape(-1)  # fp32, unchanged
-        name, extra = native
-        params = make_params(fun=name, solver="image", grid_role=L.GRID_RX if grid_is_rx else L.GRID_TX, **extra, **common)
-        ctx = self._ctx()
+        """The two wideband array-response sweeps: one launch of the wideband build per fixed end point."""
+        convert = self._inverse_wavelengths("the array frequency response", wavelengths, inv_wavelengths)
 
-        def results():
-            for pt_name, pt in fixed_items:
-                self._upload_for(ctx, native, filter_objects)
-                ctx.set_grid(X, Y)
-                yield pt_name, ctx.array_frequency_response(params, pt.xy, inv, tx_elements, rx_elements, amplitude)
+        def prepare():
+            inv = convert()
+            return lambda ctx, params, _, xy: ctx.array_frequency_response(params, xy, inv, tx_elements, rx_elements, amplitude)
 
-        return results()
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the array frequency response comes from a fused sweep (a "
+            "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+            "records (Context.valid_paths: every valid path of every cell, with its length), their "
+            "points (Context.trace_paths) and add fun's steered phasors on the host",
+            "the array frequency response covers", prepare)
 
     def array_frequency_response_on_receivers_grid(
         self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None, tx_elements,

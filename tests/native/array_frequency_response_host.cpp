@@ -1,5 +1,5 @@
-// The host's share of d2d_array_frequency_response_launch (d2d_host.hpp: wide_params, wide_bytes_per_cell, wide_fits, wide_chunks,
-// wide_chunk), compiled with plain g++.  Two builds of this file by tests/test_array_frequency_response_cpu.py: a shared library
+// The host's share of d2d_array_frequency_response_launch (d2d_host.hpp: wide_params, wide_bytes_per_cell with outputs_fit, and
+// chunks / chunk_plan with WIDE_CHUNK), compiled with plain g++.  Two builds of this file by tests/test_array_frequency_response_cpu.py: a shared library
 // driven through ctypes, and -- with -DAFR_MAIN -- a stand-alone program that checks the same functions, refusals included; the
 // program is also built with -fsanitize=address,undefined and run.  The product compiles the very same header into libd2d.so with
 // hipcc.
@@ -35,12 +35,12 @@ int afr_params(const float* inv, int nf, int amplitude, int nt, const float* tx,
 }
 long long afr_bytes_per_cell(int nf, int nt, int nr) { return (long long)d2d_host::wide_bytes_per_cell(nf, nt, nr); }
 int afr_fits(unsigned long long cells, int nf, int nt, int nr, unsigned long long mem_free, unsigned long long held) {
-    return d2d_host::wide_fits((size_t)cells, nf, nt, nr, (size_t)mem_free, (size_t)held) ? 1 : 0;
+    return d2d_host::outputs_fit((size_t)cells, d2d_host::wide_bytes_per_cell(nf, nt, nr), (size_t)mem_free, (size_t)held) ? 1 : 0;
 }
 int afr_chunk_size() { return d2d_host::WIDE_CHUNK; }
-int afr_chunks(int nf) { return d2d_host::wide_chunks(nf); }
+int afr_chunks(int nf) { return d2d_host::chunks(nf, d2d_host::WIDE_CHUNK); }
 void afr_chunk(int nf, int i, int* first, int* count, int* with_total) {
-    const d2d_host::FreqChunk ch = d2d_host::wide_chunk(nf, i);
+    const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d_host::WIDE_CHUNK);
     *first = ch.first, *count = ch.count, *with_total = ch.with_total ? 1 : 0;
 }
 }
@@ -112,7 +112,7 @@ int main() {
         EXPECT(afr_params(badinv, 3, 0, 1, one, 2, badrx, &at, msg, 256) == D2D_ERR_INVALID && at == 2 && has(msg, "inv_wavelength"));
         EXPECT(afr_params(badinv, 2, 0, 1, one, 2, badrx, &at, msg, 256) == D2D_ERR_INVALID && at == 1 && has(msg, "rx_elems"));
     }
-    // wide_bytes_per_cell and wide_fits: 8 * nf * nr * nt + 4 bytes per cell against half of (free + held), at the boundary and one past it
+    // wide_bytes_per_cell and outputs_fit: 8 * nf * nr * nt + 4 bytes per cell against half of (free + held), at the boundary and one past it
     EXPECT(D2D_FREQ_MAX == 1024 && D2D_ARRAY_MAX == 8);
     EXPECT(afr_bytes_per_cell(1, 1, 1) == 12 && afr_bytes_per_cell(64, 4, 4) == 8196 && afr_bytes_per_cell(9, 4, 3) == 868);
     EXPECT(afr_bytes_per_cell(1024, 8, 8) == 524292);

@@ -1,5 +1,5 @@
 // The steering arithmetic of d2d_array_response_launch's sink (differt2d_amd/csrc/d2d_steer.hpp: the kernel's own text) and the
-// host's share of the launch (d2d_host.hpp: array_params, array_fits), compiled with plain g++ -ffp-contract=off.  Two builds of this
+// host's share of the launch (d2d_host.hpp: array_params, outputs_fit with array_bytes_per_cell), compiled with plain g++ -ffp-contract=off.  Two builds of this
 // file by tests/test_array_response_cpu.py: a shared library driven through ctypes, and -- with -DAR_MAIN -- a stand-alone program
 // that checks the host functions, refusals included, and the exact cases of the header; the program is also built with
 // -fsanitize=address,undefined and run.  The product compiles the very same headers into libd2d.so with hipcc, where
@@ -48,7 +48,7 @@ int ar_array_params(int nt, const float* tx, int nr, const float* rx, float inv,
 }
 long long ar_bytes_per_cell(int nt, int nr) { return (long long)d2d_host::array_bytes_per_cell(nt, nr); }
 int ar_array_fits(unsigned long long cells, int nt, int nr, unsigned long long mem_free, unsigned long long held) {
-    return d2d_host::array_fits((size_t)cells, nt, nr, (size_t)mem_free, (size_t)held) ? 1 : 0;
+    return d2d_host::outputs_fit((size_t)cells, d2d_host::array_bytes_per_cell(nt, nr), (size_t)mem_free, (size_t)held) ? 1 : 0;
 }
 }
 
@@ -121,7 +121,7 @@ int main() {
         err.clear();
         EXPECT(d2d_host::array_params(1, one, 1, one, nan, 7, err) == D2D_ERR_INVALID && err.find("inv_wavelength") != std::string::npos);
     }
-    // array_fits: 8 * nr * nt + 4 bytes per cell against half of (free + held), at the boundary and one past it
+    // outputs_fit: 8 * nr * nt + 4 bytes per cell against half of (free + held), at the boundary and one past it
     EXPECT(D2D_ARRAY_MAX == 8);
     EXPECT(ar_bytes_per_cell(1, 1) == 12 && ar_bytes_per_cell(4, 3) == 100 && ar_bytes_per_cell(4, 4) == 132 && ar_bytes_per_cell(8, 8) == 516);
     const unsigned long long all = ~0ull;

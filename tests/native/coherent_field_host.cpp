@@ -1,5 +1,5 @@
 // The phasor of d2d_coherent_field_launch's sink (differt2d_amd/csrc/d2d_phasor.hpp: the kernel's own text) and the host's share
-// of the launch (d2d_host.hpp: field_params, field_fits), compiled with plain g++ -ffp-contract=off.  Two builds of this file by
+// of the launch (d2d_host.hpp: field_params, outputs_fit with FIELD_BYTES_PER_CELL), compiled with plain g++ -ffp-contract=off.  Two builds of this file by
 // tests/test_coherent_field_cpu.py: a shared library driven through ctypes, and -- with -DCF_MAIN -- a stand-alone program that
 // checks the host functions, refusals included, and walks the phasor over a sweep of phases; the program is also built with
 // -fsanitize=address,undefined and run.  The product compiles the very same headers into libd2d.so with hipcc, where
@@ -32,7 +32,7 @@ int cf_field_params(float inv_wavelength, int amplitude) {
 }
 long long cf_bytes_per_cell() { return (long long)d2d_host::FIELD_BYTES_PER_CELL; }
 int cf_field_fits(long long cells, long long mem_free, long long held) {
-    return d2d_host::field_fits((size_t)cells, (size_t)mem_free, (size_t)held) ? 1 : 0;
+    return d2d_host::outputs_fit((size_t)cells, d2d_host::FIELD_BYTES_PER_CELL, (size_t)mem_free, (size_t)held) ? 1 : 0;
 }
 }
 
@@ -68,7 +68,7 @@ int main() {
         err.clear();
         EXPECT(d2d_host::field_params(1.0f, 7, err) == D2D_ERR_INVALID && err.find("amplitude") != std::string::npos);
     }
-    // field_fits: re, im, total -- 12 bytes per cell against half of (free + held), at the edge and one past it
+    // outputs_fit: re, im, total -- 12 bytes per cell against half of (free + held), at the edge and one past it
     EXPECT(cf_bytes_per_cell() == 12);
     const long long frees[] = {0, 1ll << 20, 3ll << 30, 288ll << 30}, helds[] = {0, 1ll << 16, 5ll << 30};
     for (long long mem_free : frees)

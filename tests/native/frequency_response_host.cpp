@@ -1,5 +1,5 @@
-// The host's share of d2d_frequency_response_launch (d2d_host.hpp: freq_params, freq_fits and the chunk plan freq_chunks /
-// freq_chunk), compiled with plain g++ into a stand-alone program by tests/test_frequency_response_cpu.py, which also builds it with
+// The host's share of d2d_frequency_response_launch (d2d_host.hpp: freq_params, outputs_fit with freq_bytes_per_cell and the chunk
+// plan chunks / chunk_plan with FREQ_CHUNK), compiled with plain g++ into a stand-alone program by tests/test_frequency_response_cpu.py, which also builds it with
 // -fsanitize=address,undefined and runs it.  The product compiles the very same header into libd2d.so with hipcc, where the launch
 // walks the plan: one pass of the sink kernel per chunk.  The list handed to freq_params is a heap array of exactly nf entries, so
 // that a read past the list is the sanitizer's to report.
@@ -29,6 +29,9 @@ static int params(const std::vector<float>& inv, int amplitude, std::string* why
     return (rc == D2D_OK) == err.empty() ? rc : -1000;
 }
 
+static bool freq_fits(size_t cells, int32_t nf, size_t mem_free, size_t held) {
+    return d2d_host::outputs_fit(cells, d2d_host::freq_bytes_per_cell(nf), mem_free, held);
+}
 static std::vector<float> grid(int nf) {
     std::vector<float> inv((size_t)nf);
     for (int j = 0; j < nf; ++j) inv[(size_t)j] = 20.0f * (1.0f + (float)j / 64.0f);
@@ -85,7 +88,7 @@ int main() {
         }
     }
 
-    // freq_fits: 8 nf + 4 bytes per cell against half of (free + held), at the boundary byte and one past it
+    // outputs_fit: 8 nf + 4 bytes per cell against half of (free + held), at the boundary byte and one past it
     for (int nf : NFS) {
         const size_t per = d2d_host::freq_bytes_per_cell(nf);
         EXPECT(per == 8 * (size_t)nf + 4);
@@ -93,34 +96,34 @@ int main() {
         for (size_t mem_free : frees)
             for (size_t held : helds) {
                 const size_t edge = (mem_free / 2 + held / 2) / per;
-                EXPECT(d2d_host::freq_fits(edge, nf, mem_free, held));
-                EXPECT(!d2d_host::freq_fits(edge + 1, nf, mem_free, held));
+                EXPECT(freq_fits(edge, nf, mem_free, held));
+                EXPECT(!freq_fits(edge + 1, nf, mem_free, held));
             }
         // the boundary byte: cells * per == budget fits, a budget one byte short does not (free counts half: two bytes of it)
         const size_t cells = 1000003;
-        EXPECT(d2d_host::freq_fits(cells, nf, 2 * cells * per, 0));
-        EXPECT(!d2d_host::freq_fits(cells, nf, 2 * cells * per - 2, 0));
-        EXPECT(d2d_host::freq_fits(cells, nf, 0, 2 * cells * per));
-        EXPECT(!d2d_host::freq_fits(cells, nf, 0, 2 * cells * per - 2));
+        EXPECT(freq_fits(cells, nf, 2 * cells * per, 0));
+        EXPECT(!freq_fits(cells, nf, 2 * cells * per - 2, 0));
+        EXPECT(freq_fits(cells, nf, 0, 2 * cells * per));
+        EXPECT(!freq_fits(cells, nf, 0, 2 * cells * per - 2));
         // sizes whose products or sums would wrap 64 bits: cells * per, and free + held
         const size_t big = std::numeric_limits<size_t>::max();
-        EXPECT(!d2d_host::freq_fits(big, nf, (size_t)288 << 30, 0));
-        EXPECT(!d2d_host::freq_fits(big / per + 1, nf, (size_t)288 << 30, 0));
-        EXPECT(!d2d_host::freq_fits(((size_t)1 << 63) / 4, nf, big, big));  // 2^61 cells of at least 12 bytes: more than 2^64 - 2
-        EXPECT(d2d_host::freq_fits((big / 2 + big / 2) / per, nf, big, big));
-        EXPECT(!d2d_host::freq_fits((big / 2 + big / 2) / per + 1, nf, big, big));
+        EXPECT(!freq_fits(big, nf, (size_t)288 << 30, 0));
+        EXPECT(!freq_fits(big / per + 1, nf, (size_t)288 << 30, 0));
+        EXPECT(!freq_fits(((size_t)1 << 63) / 4, nf, big, big));  // 2^61 cells of at least 12 bytes: more than 2^64 - 2
+        EXPECT(freq_fits((big / 2 + big / 2) / per, nf, big, big));
+        EXPECT(!freq_fits((big / 2 + big / 2) / per + 1, nf, big, big));
     }
-    EXPECT(d2d_host::freq_fits(1024 * 1024, 64, (size_t)200 << 30, 0));
-    EXPECT(!d2d_host::freq_fits((size_t)1 << 30, 1024, (size_t)288 << 30, 0));
-    EXPECT(d2d_host::freq_fits(0, 1, 0, 0));
+    EXPECT(freq_fits(1024 * 1024, 64, (size_t)200 << 30, 0));
+    EXPECT(!freq_fits((size_t)1 << 30, 1024, (size_t)288 << 30, 0));
+    EXPECT(freq_fits(0, 1, 0, 0));
 
     // the chunk plan: the chunks tile 0 .. nf in order, each of 1 .. C entries, all but the last full, total in the first alone
     for (int nf : NFS) {
-        const int32_t n = d2d_host::freq_chunks(nf);
+        const int32_t n = d2d_host::chunks(nf, d2d_host::FREQ_CHUNK);
         EXPECT(n == (nf + C - 1) / C && n >= 1 && n <= 128 * (8 / C));
         int32_t next = 0, with_total = 0;
         for (int32_t i = 0; i < n; ++i) {
-            const d2d_host::FreqChunk ch = d2d_host::freq_chunk(nf, i);
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d_host::FREQ_CHUNK);
             EXPECT(ch.first == next && ch.first == i * C);
             EXPECT(ch.count >= 1 && ch.count <= C && (i == n - 1 || ch.count == C));
             EXPECT(ch.with_total == (i == 0));
@@ -128,7 +131,7 @@ int main() {
             next = ch.first + ch.count;
         }
         EXPECT(next == nf && with_total == 1);
-        EXPECT(d2d_host::freq_chunk(nf, n - 1).count == (nf % C ? nf % C : C));
+        EXPECT(d2d_host::chunk_plan(nf, n - 1, d2d_host::FREQ_CHUNK).count == (nf % C ? nf % C : C));
     }
     std::printf("frequency_response_host: %d failures (FREQ_CHUNK %d)\n", failures, C);
     return failures ? 1 : 0;

@@ -1,5 +1,5 @@
 // The direction of d2d_power_angle_launch's sink (differt2d_amd/csrc/d2d_angle.hpp: the kernel's own text) and the host's share of
-// the launch (d2d_host.hpp: angle_params, angle_fits), compiled with plain g++ -ffp-contract=off.  Two builds of this file by
+// the launch (d2d_host.hpp: angle_params, outputs_fit with angle_bytes_per_cell), compiled with plain g++ -ffp-contract=off.  Two builds of this file by
 // tests/test_power_angle_cpu.py: a shared library driven through ctypes, and -- with -DPA_MAIN -- a stand-alone program that checks
 // the host functions, refusals included, and the exact cases of turns; the program is also built with
 // -fsanitize=address,undefined and run.  The product compiles the very same headers into libd2d.so with hipcc, where
@@ -72,7 +72,7 @@ int pa_angle_params(int end, float origin, int nbins) {
 }
 long long pa_bytes_per_cell(int nbins) { return (long long)d2d_host::angle_bytes_per_cell(nbins); }
 int pa_angle_fits(long long cells, int nbins, long long mem_free, long long held) {
-    return d2d_host::angle_fits((size_t)cells, nbins, (size_t)mem_free, (size_t)held) ? 1 : 0;
+    return d2d_host::outputs_fit((size_t)cells, d2d_host::angle_bytes_per_cell(nbins), (size_t)mem_free, (size_t)held) ? 1 : 0;
 }
 }
 
@@ -117,7 +117,7 @@ int main() {
         err.clear();
         EXPECT(d2d_host::angle_params(0, 0.0f, 5000, err) == D2D_ERR_INVALID && err.find("nbins") != std::string::npos);
     }
-    // angle_fits: nbins planes and total -- 4 * nbins + 4 bytes per cell against half of (free + held), at the edge and one past it
+    // outputs_fit: nbins planes and total -- 4 * nbins + 4 bytes per cell against half of (free + held), at the edge and one past it
     EXPECT(D2D_ANGLE_BINS_MAX == 4096);
     EXPECT(pa_bytes_per_cell(1) == 8 && pa_bytes_per_cell(36) == 148 && pa_bytes_per_cell(4096) == 16388);
     const long long frees[] = {0, 1ll << 20, 3ll << 30, 288ll << 30}, helds[] = {0, 1ll << 16, 5ll << 30};

@@ -1,5 +1,5 @@
 // The insertion of d2d_strongest_paths_launch's sink (differt2d_amd/csrc/d2d_top.hpp: top_insert, the kernel's own text) and the
-// host's memory check (d2d_host.hpp: top_fits), compiled with plain g++ and driven through ctypes by
+// host's memory check (d2d_host.hpp: outputs_fit with top_bytes_per_cell), compiled with plain g++ and driven through ctypes by
 // tests/test_strongest_paths_cpu.py.  The product compiles the very same headers into libd2d.so with hipcc, where
 // d2d::TopSink::put calls top_insert once per candidate and lane.
 #include <cstring>
@@ -12,7 +12,7 @@ extern "C" {
 // d2d_host.hpp's share of the launch: what the outputs take per cell, and whether they fit half of the free device memory
 long long sp_bytes_per_cell(int k) { return (long long)d2d_host::top_bytes_per_cell(k); }
 int sp_top_fits(long long cells, int k, long long mem_free, long long held) {
-    return d2d_host::top_fits((size_t)cells, k, (size_t)mem_free, (size_t)held) ? 1 : 0;
+    return d2d_host::outputs_fit((size_t)cells, d2d_host::top_bytes_per_cell(k), (size_t)mem_free, (size_t)held) ? 1 : 0;
 }
 
 int sp_top_slots() { return d2d::TOP_SLOTS; }
