@@ -237,8 +237,17 @@ struct d2d_ctx {
         void forget() { nf = nt = nr = 0; }
         void drop() { out.release(); forget(); }
     } wide;
+    // beam-space response (d2d_beam_response_launch): nf * nbr * nbt planes of re and im and the total, kept until the next accepted
+    // launch
+    struct Beam {
+        Planes out;                        // [nf][nbr][nbt][m][n] twice, [m][n]
+        DevBuf<float> w;                   // [2][BEAM_MAX][ARRAY_MAX][2]: the two weight tables of the launch in flight
+        int32_t nf = 0, nbt = 0, nbr = 0;  // counts of the last accepted launch; 0: no result
+        void forget() { nf = nbt = nbr = 0; }
+        void drop() { out.release(); w.release(); forget(); }
+    } beam;
     void drop_products() {  // every one of them goes with the grid
-        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop();
+        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop();
     }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -2273,7 +2282,7 @@ struct SinkProduct {
     bool early_discard;        // when a launch forgets the previous result (below)
 };
 // Discard timing is behaviour, and it differs for historical reasons only: the four older products forget the previous result as
-// soon as the state checks pass (EARLY: any later refusal leaves nothing to get), the four newer ones when the launch is accepted
+// soon as the state checks pass (EARLY: any later refusal leaves nothing to get), the five newer ones when the launch is accepted
 // and the buffers are about to change (LATE: a refused launch leaves the previous result readable).  Callers may rely on either.
 constexpr bool EARLY = true, LATE = false;
 constexpr SinkProduct PROFILE = {"d2d_power_profile_launch", "a host function's profile: bin the records of d2d_valid_paths", "a profile is always overwritten", EARLY};
@@ -2284,6 +2293,7 @@ constexpr SinkProduct COEF_VJP = {"d2d_field_coefs_vjp_launch", "a host function
 constexpr SinkProduct ANGLE = {"d2d_power_angle_launch", "a host function's profile: bin the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "a profile is always overwritten", LATE};
 constexpr SinkProduct ARRAY = {"d2d_array_response_launch", "a host function's channel matrix: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrix is always overwritten", LATE};
 constexpr SinkProduct WIDE = {"d2d_array_frequency_response_launch", "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrices are always overwritten", LATE};
+constexpr SinkProduct BEAM = {"d2d_beam_response_launch", "a host function's beam response: add the beamformed phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the beam response is always overwritten", LATE};
 
 // What the products refuse of the caller's parameters before prep_sink_sweep's share.
 static int check_fused_sink(d2d_ctx* c, const d2d_params* p, const SinkProduct& pr) {
@@ -2378,7 +2388,8 @@ static int copy_out(d2d_ctx* c, std::initializer_list<CopyOut> copies) {
     return D2D_OK;
 }
 
-static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK && d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK, "d2d_host.hpp and d2d_kernels.hpp disagree");
+static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK && d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK && d2d_host::BEAM_CHUNK == d2d::BEAM_CHUNK,
+              "d2d_host.hpp and d2d_kernels.hpp disagree");
 
 }  // namespace
 
@@ -2702,6 +2713,75 @@ int d2d_get_array_frequency_response(d2d_ctx* c, int32_t first, int32_t count, f
         return fail(D2D_ERR_INVALID, "d2d_get_array_frequency_response: first %d and count %d are no range of the result's %d wavelengths", first, count, c->wide.nf);
     const d2d_ctx::Planes& o = c->wide.out;
     const size_t cells = (size_t)c->m * (size_t)c->n, block = (size_t)c->wide.nr * (size_t)c->wide.nt * cells;
+    const size_t bytes = (size_t)count * block * sizeof(float);
+    return copy_out(c, {{re, o.re.p + (size_t)first * block, bytes}, {im, o.im.p + (size_t)first * block, bytes}, {total, o.total.p, cells * sizeof(float)}});
+}
+
+// Beam-response build: ONE preparation, then one pass per chunk of BEAM_CHUNK wavelengths over the same SweepArgs (as
+// d2d_array_frequency_response_launch does), every pass adding into the zeroed plane blocks of its chunk and the first storing the
+// total.  The lists travel by value in the kernel argument, the two weight tables in a device buffer of the result (copied from the
+// caller's during the call).
+int d2d_beam_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude, int32_t nt,
+                             const float* tx_elems, int32_t nr, const float* rx_elems, int32_t nbt, const float* tx_weights, int32_t nbr,
+                             const float* rx_weights) {
+    if (!c || !fixed || !inv_wavelength || !tx_elems || !rx_elems || !tx_weights || !rx_weights) return fail(D2D_ERR_INVALID, "NULL argument");
+    SinkLaunch<d2d_ctx::Beam> L(c, BEAM, c->beam, fixed);
+    d2d_ctx::Planes& o = c->beam.out;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::beam_params(inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems, nbt, tx_weights, nbr, rx_weights, err)))
+        return fail(rc, "%s: %s", BEAM.who, err.c_str());
+    const size_t block = (size_t)nbr * (size_t)nbt * L.cells;  // one wavelength's planes
+    const size_t planes = (size_t)nf * block;
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::beam_bytes_per_cell(nf, nbt, nbr), o.bytes())) || (rc = L.prepare()) || (rc = o.ensure(planes, L.cells)) ||
+        (rc = c->beam.w.ensure(2 * d2d::BEAM_TABLE)))
+        return rc;
+    // the two weight tables, padded to the limits, behind whatever pass still reads the previous launch's
+    float w[2 * d2d::BEAM_TABLE] = {};
+    for (int32_t b = 0; b < nbt; ++b)
+        for (int32_t j = 0; j < 2 * nt; ++j) w[b * 2 * d2d::ARRAY_MAX + j] = tx_weights[b * 2 * nt + j];
+    for (int32_t b = 0; b < nbr; ++b)
+        for (int32_t k = 0; k < 2 * nr; ++k) w[d2d::BEAM_TABLE + b * 2 * d2d::ARRAY_MAX + k] = rx_weights[b * 2 * nr + k];
+    HIP_TRY(hipMemcpyAsync(c->beam.w.p, w, sizeof w, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(o.re.p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(o.im.p, 0, planes * sizeof(float), c->stream));
+    if (L.s.tiles > 0)
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::BEAM_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::BEAM_CHUNK);
+            d2d::BeamArgs g = {};
+            g.re = o.re.p + (size_t)ch.first * block;
+            g.im = o.im.p + (size_t)ch.first * block;
+            g.total = ch.with_total ? o.total.p : nullptr;
+            g.cells = (long)L.cells;
+            g.amplitude = amplitude;
+            g.nf = ch.count;
+            g.nt = nt;
+            g.nr = nr;
+            g.nbt = nbt;
+            g.nbr = nbr;
+            for (int32_t f = 0; f < ch.count; ++f) g.inv[f] = inv_wavelength[ch.first + f];
+            for (int32_t j = 0; j < nt; ++j) g.etx[j][0] = tx_elems[2 * j], g.etx[j][1] = tx_elems[2 * j + 1];
+            for (int32_t k = 0; k < nr; ++k) g.erx[k][0] = rx_elems[2 * k], g.erx[k][1] = rx_elems[2 * k + 1];
+            g.w = c->beam.w.p;
+            HIP_TRY(L.pass<d2d::BeamSink>(g));
+        }
+    // (No patch at all: as in the siblings above, what a sweep without contributions would leave.  d2d_set_grid refuses a grid of
+    // less than 1 x 1, so tiles == 0 cannot arise today and no test reaches this line; it stands for a context that ever holds an
+    // empty share of a grid.)
+    else HIP_TRY(hipMemsetAsync(o.total.p, 0, L.cells * sizeof(float), c->stream));
+    c->beam.nf = nf;
+    c->beam.nbt = nbt;
+    c->beam.nbr = nbr;
+    return D2D_OK;
+}
+
+int d2d_get_beam_response(d2d_ctx* c, int32_t first, int32_t count, float* re, float* im, float* total) {
+    if (int rc = result_state(c, c && c->beam.nf >= 1 && c->beam.out.re.p, BEAM)) return rc;
+    if (first < 0 || count < 1 || count > c->beam.nf - first)
+        return fail(D2D_ERR_INVALID, "d2d_get_beam_response: first %d and count %d are no range of the result's %d wavelengths", first, count, c->beam.nf);
+    const d2d_ctx::Planes& o = c->beam.out;
+    const size_t cells = (size_t)c->m * (size_t)c->n, block = (size_t)c->beam.nbr * (size_t)c->beam.nbt * cells;
     const size_t bytes = (size_t)count * block * sizeof(float);
     return copy_out(c, {{re, o.re.p + (size_t)first * block, bytes}, {im, o.im.p + (size_t)first * block, bytes}, {total, o.total.p, cells * sizeof(float)}});
 }

@@ -384,6 +384,43 @@ inline size_t wide_bytes_per_cell(int32_t nf, int32_t nt, int32_t nr) {
 // One pass of the sink kernel per WIDE_CHUNK wavelengths (chunk_plan), each adding into the plane blocks of its chunk.
 constexpr int32_t WIDE_CHUNK = 32;  // = d2d::WIDE_CHUNK (d2d_kernels.hpp)
 
+// ---- parameters, outputs and launch plan of the beam-space response (d2d_beam_response_launch, d2d::BeamSink) ---------
+// D2D_ERR_INVALID: what wide_params refuses, in its order (the list, the amplitude, the element counts and lists), then nbt, then nbr
+// outside 1 .. D2D_BEAM_MAX, then a transmit, then a receive weight component that is NaN or infinite (the message names the beam and
+// ends in the element's index).  The weight tables are fp32 [nbt][nt][2] and [nbr][nr][2]; neither is read unless every count is in
+// range.
+inline int beam_params(const float* inv_wavelength, int32_t nf, int32_t amplitude, int32_t nt, const float* tx_elems, int32_t nr, const float* rx_elems,
+                       int32_t nbt, const float* tx_weights, int32_t nbr, const float* rx_weights, std::string& err) {
+    if (int rc = wide_params(inv_wavelength, nf, amplitude, nt, tx_elems, nr, rx_elems, err)) return rc;
+    if (nbt < 1 || nbt > D2D_BEAM_MAX)
+        return err = "the beam response needs nbt in 1 .. " + std::to_string(D2D_BEAM_MAX) + ", got " + std::to_string(nbt), D2D_ERR_INVALID;
+    if (nbr < 1 || nbr > D2D_BEAM_MAX)
+        return err = "the beam response needs nbr in 1 .. " + std::to_string(D2D_BEAM_MAX) + ", got " + std::to_string(nbr), D2D_ERR_INVALID;
+    for (int side = 0; side < 2; ++side) {
+        const float* w = side == 0 ? tx_weights : rx_weights;
+        const int32_t nb = side == 0 ? nbt : nbr, n = side == 0 ? nt : nr;
+        for (int32_t b = 0; b < nb; ++b)
+            for (int32_t j = 0; j < n; ++j)
+                for (int k = 0; k < 2; ++k) {
+                    const float v = w[2 * (b * n + j) + k];
+                    if (!std::isfinite(v))
+                        return err = std::string("the beam response needs every weight finite, got ") + std::to_string(v) + " as the " +
+                                     (k == 0 ? "re" : "im") + " of " + (side == 0 ? "tx_weights" : "rx_weights") + " of beam " + std::to_string(b) +
+                                     " at index " + std::to_string(j),
+                               D2D_ERR_INVALID;
+                }
+    }
+    return D2D_OK;
+}
+// Per cell: nf * nbr * nbt planes of re and im and one total, 4 bytes each (at most 524 292 with the counts in range; 0 with a count
+// that is not: outputs_fit then refuses; tests/native/beam_response_host.cpp).
+inline size_t beam_bytes_per_cell(int32_t nf, int32_t nbt, int32_t nbr) {
+    if (nf < 1 || nf > D2D_FREQ_MAX || nbt < 1 || nbt > D2D_BEAM_MAX || nbr < 1 || nbr > D2D_BEAM_MAX) return 0;
+    return 8 * (size_t)nf * (size_t)nbr * (size_t)nbt + 4;
+}
+// One pass of the sink kernel per BEAM_CHUNK wavelengths (chunk_plan), each adding into the plane blocks of its chunk.
+constexpr int32_t BEAM_CHUNK = 64;  // = d2d::BEAM_CHUNK (d2d_kernels.hpp)
+
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)
 struct SweepThresholds {

@@ -37,6 +37,7 @@
 #include "d2d_phasor.hpp"
 #include "d2d_angle.hpp"
 #include "d2d_steer.hpp"
+#include "d2d_beam.hpp"
 
 namespace d2d {
 
@@ -2380,6 +2381,139 @@ struct ArrayFreqSink {
         }
     }
     __device__ __forceinline__ void end(const ArrayFreqArgs& xa, long, int) const {
+        if (cell < 0 || xa.total == nullptr) return;
+        xa.total[cell] = total;
+    }
+};
+
+// BeamSink (d2d_beam_response_launch): what comes out behind a codebook of nbt transmit beams and one of nbr receive beams,
+// y = w_rx^H H w_tx, at up to BEAM_CHUNK wavelengths of one sweep, without the channel matrix H: every contribution to H has rank one
+// under the plane-wave model, so its share of y is a e^(-j 2 pi f0) times the two array factors (d2d_beam.hpp holds the definition).
+// The planes re / im [nf][nbr][nbt][cells] of the chunk live in memory, zeroed on the stream in front of the passes; the running fp32
+// sum of every contribution stays in a register until end(), which stores it where `total` is not null (the first chunk's pass).  Per
+// contribution that is not exactly zero, a and the two unit directions are formed once, and then, per wavelength f < nf:
+//     (c0, s0) = phasor(f0)
+//     for i < nr:   (c, s) = beam_steer(steer_dot(erx[i], urx, ury), inv[f]) ;  for br < nbr: beam_fold_rx(Ar[br], rx_weights[br][i], c, s)
+//     for j < nt:   (ct[j], st[j]) = beam_steer(steer_dot(etx[j], utx, uty), inv[f])
+//     for bt < nbt: At = fold of beam_fold_tx over j ;  load the nbr planes of this bt ;  for br < nbr: beam_pair, add, store
+// -- 1 + nr + nt phasors per wavelength, whatever the codebooks hold; the receive steering is folded into Ar[] and dropped, the
+// transmit steering is kept, so that no phasor is formed twice.  The per-lane arrays Ar[BEAM_MAX], (ct, st)[ARRAY_MAX] and the loaded
+// planes are indexed at compile time only (a per-lane array indexed at run time goes to scratch): the loops over i, j
+// (forming the steering) and bt are wave-uniform run-time loops, the loops that touch an array are unrolled over BEAM_MAX / ARRAY_MAX
+// with wave-uniform guards, and the run-time j writes (ct, st)[j] through a chain of selects.  The order of the two folds is the
+// definition's (i and j ascending); every other nesting cannot reach the bits, each plane being its own accumulator.  The loads of
+// one bt's nbr planes are issued BEAM_LOADS at a time, ahead of their adds.  The lists and the counts come by value in the kernel
+// argument and are read by scalar loads; the two weight tables (1 KiB at the limits) live in a device buffer of the result, uploaded
+// on the stream in front of the passes, and are read at wave-uniform addresses -- by value they made the compiler copy the whole
+// argument to the stack in three of the twelve instances.  All of it is skipped for a candidate that no lane of the wave has a non-zero
+// contribution from.  A lane is the only writer of its cell's column and reads back what it stored itself: plain loads and stores,
+// no atomics, the same bits run to run.  Lanes outside the grid (cell < 0) never write.  (f * nbr + br) * nbt + bt < nf * nbr * nbt
+// and cell < cells, so every address is inside the chunk's 2 * nf * nbr * nbt * cells planes.
+constexpr int BEAM_MAX = 8;     // = D2D_BEAM_MAX (include/d2d.h)
+constexpr int BEAM_CHUNK = 64;  // wavelengths per pass: internal, not in the ABI (d2d_host::BEAM_CHUNK is the host's copy)
+constexpr int BEAM_LOADS = 4;   // planes of one transmit beam whose loads are issued together, ahead of their adds (2 registers each)
+struct BeamArgs {
+    float* re;                          // [nf][nbr][nbt][cells]: this chunk's planes
+    float* im;                          // [nf][nbr][nbt][cells]
+    float* total;                       // [cells] or null
+    long cells;                         // m * n
+    int amplitude;                      // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int nf;                             // 1 .. BEAM_CHUNK
+    int nt, nr;                         // 1 .. ARRAY_MAX each
+    int nbt, nbr;                       // 1 .. BEAM_MAX each
+    float inv[BEAM_CHUNK];              // turns per unit length, finite and >= 0; entries at and past nf are not read
+    float etx[ARRAY_MAX][2];            // (ex, ey) of the transmit elements; entries at and past nt are not read
+    float erx[ARRAY_MAX][2];            // (ex, ey) of the receive elements; entries at and past nr are not read
+    const float* w;                     // device memory, [2][BEAM_MAX][ARRAY_MAX][2]: (re, im) of transmit beam bt at element j, then of
+                                        // receive beam br at element i; rows at and past nbt / nbr, entries at and past nt / nr are not read
+};
+constexpr int BEAM_TABLE = BEAM_MAX * ARRAY_MAX * 2;  // floats of one weight table
+static_assert(BEAM_CHUNK >= 8 && BEAM_CHUNK <= 64 && (BEAM_CHUNK & (BEAM_CHUNK - 1)) == 0, "BEAM_CHUNK is a power of two in 8 .. 64");
+static_assert(sizeof(SweepArgs) + sizeof(BeamArgs) <= 4096, "power_sink_kernel's arguments must fit the 4 KiB kernel-argument segment");
+struct BeamSink {
+    using Args = BeamArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = true;
+    static_assert(BEAM_MAX == D2D_BEAM_MAX, "d2d_kernels.hpp and include/d2d.h disagree");
+    float total;
+    const BeamArgs* x;  // the kernel argument: wave-uniform, read where it is used
+    int cell;
+    __device__ __forceinline__ void begin(const BeamArgs& xa, long /*tile*/, int lane_cell) {
+        total = 0.0f;
+        x = &xa;
+        cell = lane_cell;
+    }
+    // dir: {p[1] - p[0], p[K] - p[K+1]} of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_rd(float t, float r, const float (&dir)[4]) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        const float a = x->amplitude == D2D_FIELD_AMP_SQRT ? copysignf(sqrtf(fabsf(t)), t) : t;
+        float utx, uty, urx, ury;
+        const bool okt = unit_dir(dir[0], dir[1], utx, uty);
+        const bool okr = unit_dir(dir[2], dir[3], urx, ury);
+        const bool go = p && okt && okr && cell >= 0;
+        if (!go) return;  // (per lane: the loops below are uniform for the lanes that stay)
+        const int nf = x->nf, nt = x->nt, nr = x->nr, nbt = x->nbt, nbr = x->nbr;
+        const size_t cells = (size_t)x->cells;
+        const float* const wtx = x->w;
+        const float* const wrx = x->w + BEAM_TABLE;
+        for (int f = 0; f < nf; ++f) {
+            const float inv = x->inv[f];
+            const float u = r * inv;
+            const float f0 = u - floorf(u);
+            float c0, s0;
+            phasor(f0, c0, s0);
+            // the receive array factors of every beam: the steering of element i is folded into them and dropped
+            float arr[BEAM_MAX], ari[BEAM_MAX];
+#pragma unroll
+            for (int b = 0; b < BEAM_MAX; ++b) arr[b] = ari[b] = 0.0f;
+            for (int i = 0; i < nr; ++i) {
+                float c, s;
+                beam_steer(steer_dot(x->erx[i][0], x->erx[i][1], urx, ury), inv, c, s);
+#pragma unroll
+                for (int b = 0; b < BEAM_MAX; ++b)
+                    if (b < nbr) beam_fold_rx(arr[b], ari[b], wrx[(b * ARRAY_MAX + i) * 2], wrx[(b * ARRAY_MAX + i) * 2 + 1], c, s);
+            }
+            // the transmit steering, kept: (ct, st)[j] through a chain of selects, so that j stays a run-time loop
+            float ct[ARRAY_MAX], st[ARRAY_MAX];
+#pragma unroll
+            for (int k = 0; k < ARRAY_MAX; ++k) ct[k] = st[k] = 0.0f;
+            for (int j = 0; j < nt; ++j) {
+                float c, s;
+                beam_steer(steer_dot(x->etx[j][0], x->etx[j][1], utx, uty), inv, c, s);
+#pragma unroll
+                for (int k = 0; k < ARRAY_MAX; ++k)
+                    if (k == j) ct[k] = c, st[k] = s;
+            }
+            for (int bt = 0; bt < nbt; ++bt) {
+                float atr = 0.0f, ati = 0.0f;
+#pragma unroll
+                for (int j = 0; j < ARRAY_MAX; ++j)
+                    if (j < nt) beam_fold_tx(atr, ati, wtx[(bt * ARRAY_MAX + j) * 2], wtx[(bt * ARRAY_MAX + j) * 2 + 1], ct[j], st[j]);
+                // plane (f, br, bt): this bt's nbr planes are loaded together, ahead of the adds
+                const size_t first = (size_t)(f * nbr * nbt + bt) * cells + (size_t)cell, step = (size_t)nbt * cells;
+#pragma unroll
+                for (int g = 0; g < BEAM_MAX; g += BEAM_LOADS) {
+                    if (g >= nbr) break;
+                    float lre[BEAM_LOADS], lim[BEAM_LOADS];
+#pragma unroll
+                    for (int k = 0; k < BEAM_LOADS; ++k)
+                        if (g + k < nbr) lre[k] = x->re[first + (size_t)(g + k) * step], lim[k] = x->im[first + (size_t)(g + k) * step];
+#pragma unroll
+                    for (int k = 0; k < BEAM_LOADS; ++k)
+                        if (g + k < nbr) {
+                            float zr, zs;
+                            beam_pair(arr[g + k], ari[g + k], atr, ati, c0, s0, zr, zs);
+                            const float azr = a * zr, azs = a * zs;
+                            x->re[first + (size_t)(g + k) * step] = lre[k] + azr;
+                            x->im[first + (size_t)(g + k) * step] = lim[k] - azs;
+                        }
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void end(const BeamArgs& xa, long, int) const {
         if (cell < 0 || xa.total == nullptr) return;
         xa.total[cell] = total;
     }

@@ -47,7 +47,8 @@ D2D_DECLARE_MODE(MODE_SIG)
     X(CoefGradSink)  /* its adjoint w.r.t. the per-object reflection coefficients */                          \
     X(AngleSink)     /* the power-angle profile */                                                            \
     X(ArraySink)     /* the array response */                                                                 \
-    X(ArrayFreqSink) /* the wideband array response */
+    X(ArrayFreqSink) /* the wideband array response */                                                        \
+    X(BeamSink)      /* the beam-space response */
 #define D2D_DECLARE_SINK(S)                                                                                                      \
     template <> hipError_t launch_sink_m<MODE_HARD, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&); \
     template <> hipError_t launch_sink_m<MODE_HSIG, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&);

@@ -117,6 +117,14 @@ class ArrayFrequencyResponse(NamedTuple):
     total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit (None where not asked for)
 
 
+class BeamResponse(NamedTuple):
+    """Result of :meth:`Context.beam_response` (include/d2d.h: d2d_beam_response_launch)."""
+
+    re: np.ndarray     # fp32 [nf, nbr, nbt, m, n]: real part of y[f, br, bt] = w_rx[br]^H H[f] w_tx[bt]
+    im: np.ndarray     # fp32 [nf, nbr, nbt, m, n]: imaginary part
+    total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit (None where not asked for)
+
+
 FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
 ANGLE_ENDS = {"tx": L.D2D_ANGLE_AT_TX, "rx": L.D2D_ANGLE_AT_RX}
 
@@ -133,6 +141,17 @@ def _amplitude_id(method: str, amplitude) -> int:
 def _keep_pointer(a: np.ndarray, *shape) -> np.ndarray:
     """An empty list still hands the library a pointer: it refuses a count of 0 itself."""
     return a if a.size else np.zeros(shape, np.float32)
+
+
+def _beam_weights(name: str, w, n: int) -> np.ndarray:
+    """A codebook as contiguous complex64 ``[nb, n]``: ``[n]`` is one beam; any other shape is refused here (the library sees only
+    counts).  An empty codebook stays empty: the library refuses a count of 0 itself."""
+    w = np.asarray(w)
+    if w.ndim == 1 and w.size:
+        w = w.reshape(1, -1)
+    if w.ndim != 2 or (w.size and w.shape[1] != n):
+        raise L.D2DError(-1, f"beam_response: {name} must be complex [nb, {n}] (or [{n}] for one beam), got shape {tuple(w.shape)}")
+    return np.ascontiguousarray(w, dtype=np.complex64).reshape(w.shape[0], n)
 
 
 def _no_result(ctx, getter, launch_name: str, *nulls):
@@ -168,6 +187,7 @@ class Context:
         self._angle_nbins = 0  # bins of the last launch_power_angle that was accepted
         self._array_shape = None  # (nr, nt) of the last launch_array_response that was accepted
         self._wide_shape = None  # (nf, nr, nt) of the last launch_array_frequency_response that was accepted
+        self._beam_shape = None  # (nf, nbr, nbt) of the last launch_beam_response that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -887,6 +907,64 @@ class Context:
         L.check(self._lib.d2d_get_array_frequency_response(self._ctx, first, count,
                                                            *(None if a is None else a.ctypes.data_as(C.c_void_p) for a in afr)))
         return afr
+
+    def beam_response(self, params: L.Params, fixed, inv_wavelengths, tx_elements, rx_elements, tx_weights, rx_weights,
+                      amplitude="sqrt") -> "BeamResponse":
+        """What comes out behind beamformers at both ends, ``y[f, br, bt] = w_rx[br]^H H[f] w_tx[bt]`` for every cell of the resident
+        grid, every entry of ``inv_wavelengths`` and every pair of a receive beam and a transmit beam -- the channel tensor ``H`` of
+        :meth:`array_frequency_response` contracted with two codebooks inside the sweep, without ``H`` ever being formed, stored or
+        downloaded (include/d2d.h: d2d_beam_response_launch holds the definition; ImagePath, hard or hard_sigmoid validity, every
+        fused function).  Under the plane-wave model every path's contribution to ``H`` has rank one, so per contribution and
+        wavelength ``nt + nr + 1`` phasors are formed instead of ``nr * nt``, and ``nbr * nbt`` planes are written instead of
+        ``nr * nt``.  ``tx_weights`` is complex ``[nbt, nt]`` (or ``[nt]`` for one beam) and ``rx_weights`` complex ``[nbr, nr]``
+        (or ``[nr]``), 1 to ``D2D_BEAM_MAX`` = 8 beams each, every component finite; they are passed as complex64.  The receive
+        weights are conjugated, the convention of :func:`differt2d_amd.utils.beamformed_power`;
+        :func:`differt2d_amd.utils.steering_weights` makes matched beams.  ``inv_wavelengths``, ``tx_elements``, ``rx_elements``,
+        ``amplitude``, ``params`` and ``fixed`` as for :meth:`array_frequency_response`.  Plane ``(f, br, bt)`` depends only on
+        ``inv_wavelengths[f]``, ``rx_weights[br]``, ``tx_weights[bt]`` and the element lists: a larger codebook is several calls.
+        A refused launch leaves the previous result readable.  Every other product of the context is left untouched.
+
+        Returns a :class:`BeamResponse`: ``re`` and ``im``, fp32 ``[nf, nbr, nbt, m, n]``, and ``total`` (the fused map, bit for
+        bit), fp32 ``[m, n]``.  :func:`differt2d_amd.utils.beam_response`, :func:`differt2d_amd.utils.beam_power` and
+        :func:`differt2d_amd.utils.best_beam` turn it into complex ``y``, the power of every pair and the best pair of every
+        cell.  The result takes ``8 * nf * nbr * nbt`` bytes per cell: :meth:`get_beam_response` reads a range of wavelengths."""
+        self.launch_beam_response(params, fixed, inv_wavelengths, tx_elements, rx_elements, tx_weights, rx_weights, amplitude)
+        return self.get_beam_response()
+
+    def launch_beam_response(self, params: L.Params, fixed, inv_wavelengths, tx_elements, rx_elements, tx_weights, rx_weights,
+                             amplitude="sqrt"):
+        """The launch of :meth:`beam_response` alone (asynchronous, like :meth:`launch`; the lists are copied by the call)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        etx = np.ascontiguousarray(tx_elements, dtype=np.float32).reshape(-1, 2)
+        erx = np.ascontiguousarray(rx_elements, dtype=np.float32).reshape(-1, 2)
+        wtx = _beam_weights("tx_weights", tx_weights, int(etx.shape[0]))
+        wrx = _beam_weights("rx_weights", rx_weights, int(erx.shape[0]))
+        amplitude = _amplitude_id("beam_response", amplitude)
+        kinv, ktx, krx = _keep_pointer(inv, 1), _keep_pointer(etx, 1, 2), _keep_pointer(erx, 1, 2)
+        kwt, kwr = _keep_pointer(wtx.view(np.float32), 2), _keep_pointer(wrx.view(np.float32), 2)
+        L.check(self._lib.d2d_beam_response_launch(self._ctx, C.byref(params), fixed, kinv, int(inv.size), amplitude, int(etx.shape[0]), ktx,
+                                                   int(erx.shape[0]), krx, int(wtx.shape[0]), kwt, int(wrx.shape[0]), kwr))
+        self._beam_shape = (int(inv.size), int(wrx.shape[0]), int(wtx.shape[0]))
+
+    def get_beam_response(self, first=0, count=None, with_total=True) -> "BeamResponse":
+        """Synchronises and returns wavelengths ``first .. first + count - 1`` (``count=None``: all from ``first`` on) of the result
+        of the last :meth:`launch_beam_response` that was accepted: ``re`` and ``im`` are ``[count, nbr, nbt, m, n]``.
+        ``with_total=False`` leaves ``total`` out (``None``).  A range outside the result is refused by the library."""
+        if self._beam_shape is None:
+            _no_result(self._ctx, self._lib.d2d_get_beam_response, "launch_beam_response", 0, 1, None, None, None)
+        nf, nbr, nbt = self._beam_shape
+        first = int(first)
+        count = nf - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > nf:  # (the library says why: nothing is copied)
+            L.check(self._lib.d2d_get_beam_response(self._ctx, first, count, None, None, None))
+            raise L.D2DError(-1, f"get_beam_response: first={first}, count={count} are no range of {nf} wavelengths")
+        shape = tuple(self.shape)
+        planes = (count, nbr, nbt) + shape
+        br = BeamResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32),
+                          total=np.empty(shape, np.float32) if with_total else None)
+        L.check(self._lib.d2d_get_beam_response(self._ctx, first, count, *(None if a is None else a.ctypes.data_as(C.c_void_p) for a in br)))
+        return br
 
     # -- RCCL ---------------------------------------------------------------------------
     @staticmethod

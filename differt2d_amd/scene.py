@@ -1408,6 +1408,61 @@ class Scene(Plottable):
                                          tx_elements, rx_elements, amplitude, path_cls, min_order, max_order, order, filter_objects,
                                          kwargs)
 
+    def _grid_beam_response(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelengths, inv_wavelengths, tx_elements, rx_elements,
+                            tx_weights, rx_weights, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
+        """The two beam-response sweeps: one launch of the beam-response build per fixed end point."""
+        convert = self._inverse_wavelengths("the beam response", wavelengths, inv_wavelengths)
+
+        def prepare():
+            inv = convert()
+            return lambda ctx, params, _, xy: ctx.beam_response(params, xy, inv, tx_elements, rx_elements, tx_weights, rx_weights, amplitude)
+
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the beam response comes from a fused sweep (a function "
+            "from differt2d_amd.utils).  For any other callable take the sparse valid-path records "
+            "(Context.valid_paths: every valid path of every cell, with its length), their points "
+            "(Context.trace_paths) and add fun's beamformed phasors on the host",
+            "the beam response covers", prepare)
+
+    def beam_response_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None, tx_elements,
+        rx_elements, tx_weights, rx_weights, amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0,
+        max_order: int = 1, order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """What comes out behind beamformers at both ends, for every cell, wavelength and beam pair: ``y[f, br, bt] = w_rx[br]^H
+        H[f] w_tx[bt]`` with the ``H`` of :meth:`array_frequency_response_on_receivers_grid`, contracted with a codebook of transmit
+        beams ``tx_weights`` (complex ``[nbt, nt]``, or ``[nt]`` for one beam) and one of receive beams ``rx_weights`` (complex
+        ``[nbr, nr]``; conjugated, the convention of :func:`differt2d_amd.utils.beamformed_power`) inside the sweep: ``H`` is never
+        formed, stored or downloaded.  At most 8 beams per codebook; a larger one is several calls, whose planes are exactly those
+        of one.  :func:`differt2d_amd.utils.steering_weights` makes matched beams.  Exactly one of ``wavelengths`` and
+        ``inv_wavelengths`` must be given, and ``tx_elements`` and ``rx_elements``, all as for
+        :meth:`array_frequency_response_on_receivers_grid`.  Yields ``(tx name, BeamResponse(re, im, total))``
+        (:class:`differt2d_amd.engine.BeamResponse`: ``re`` and ``im`` fp32 ``[nf, nbr, nbt, m, n]``, ``total`` fp32 ``[m, n]``, the
+        fused map bit for bit); include/d2d.h: d2d_beam_response_launch holds the exact definition.
+        :func:`differt2d_amd.utils.beam_response`, :func:`differt2d_amd.utils.beam_power` and :func:`differt2d_amd.utils.best_beam`
+        give complex ``y``, the power of every pair and the best pair of every cell.  The result takes ``8 * nf * nbr * nbt`` bytes
+        per cell on the device and on the host.
+
+        ``fun``, ``amplitude``, the path class and the validity as for :meth:`array_response_on_receivers_grid`; anything else raises
+        :class:`D2DUnsupported`.  For another callable :meth:`Context.valid_paths` and :meth:`Context.trace_paths` hold every valid
+        path and its points for a sum on the host."""
+        return self._grid_beam_response(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                        tx_elements, rx_elements, tx_weights, rx_weights, amplitude, path_cls, min_order, max_order,
+                                        order, filter_objects, kwargs)
+
+    def beam_response_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None, tx_elements,
+        rx_elements, tx_weights, rx_weights, amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0,
+        max_order: int = 1, order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`beam_response_on_receivers_grid`: one result per receiver, the transmitter (and its array
+        and transmit beams) sits at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h:
+        d2d_params.grid_role)."""
+        return self._grid_beam_response(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                        tx_elements, rx_elements, tx_weights, rx_weights, amplitude, path_cls, min_order, max_order,
+                                        order, filter_objects, kwargs)
+
     def accumulate_on_transmitters_grid_over_paths(
         self, X, Y, fun: PathFun, fun_args: tuple = (), fun_kwargs: Optional[Mapping] = None, *, reduce_all: bool = False,
         grad: bool = False, value_and_grad: bool = False, path_cls: type = ImagePath,

@@ -303,6 +303,50 @@ def wideband_capacity(afr, snr):
     return acc / nf
 
 
+def steering_weights(elements, angles, wavelength):
+    """Matched (conjugate-steering) beam weights of an array: complex64 ``[len(angles), n]``,
+    ``w[k, i] = exp(+2j pi e[i] . u(angles[k]) / wavelength) / sqrt(n)`` with ``u(a) = (cos a, sin a)``, for ``elements`` ``[n, 2]``
+    (offsets in length units, :func:`ula`) and ``angles`` in radians counter-clockwise from +x.  Computed in float64 and rounded once.
+
+    The same function serves either end of ``y = w_rx^H H w_tx`` (``Context.beam_response``, :func:`beamformed_power`), but ``angle``
+    means something else at each.  The receive weights are conjugated by the product, so as ``rx_weights`` the beam points AT
+    ``angle``: it is matched to a wave that the receiver sees along ``angle``, the direction from the receiver towards the last
+    interaction point (where the wave comes from).  The transmit weights are not conjugated, so as ``tx_weights`` the beam points at
+    ``angle + pi``: a transmit beam towards the direction of departure ``d`` (from the transmitter towards the first interaction
+    point) is built from ``angle = d + pi``.  With both ends matched to a path, that path contributes ``sqrt(nt * nr)`` times its
+    amplitude."""
+    e = np.asarray(elements, dtype=np.float64).reshape(-1, 2)
+    a = np.asarray(angles, dtype=np.float64).reshape(-1)
+    q = np.cos(a)[:, None] * e[None, :, 0] + np.sin(a)[:, None] * e[None, :, 1]
+    return (np.exp(2j * np.pi * q / float(wavelength)) / np.sqrt(e.shape[0])).astype(np.complex64)
+
+
+def beam_response(br):
+    """The complex beam-space response ``y = re + 1j * im``, complex64 ``[nf, nbr, nbt, m, n]``, of a ``BeamResponse``
+    (``Scene.beam_response_on_receivers_grid``, ``Context.beam_response``) or any object with ``re`` and ``im``."""
+    return channel_matrix(br)
+
+
+def beam_power(br):
+    """The power behind every beam pair, ``|y|**2 = re**2 + im**2``, float64 ``[nf, nbr, nbt, m, n]``, for a ``BeamResponse``."""
+    re = np.asarray(br.re, dtype=np.float64)
+    im = np.asarray(br.im, dtype=np.float64)
+    return re * re + im * im
+
+
+def best_beam(br):
+    """The best beam pair of every cell: ``(rx_beam, tx_beam, power)`` with the ``(br, bt)`` of the largest mean of
+    :func:`beam_power` over the wavelengths (int64 ``[m, n]`` each) and that mean (float64 ``[m, n]``), for a ``BeamResponse``.  Ties
+    go to the lowest flat index ``br * nbt + bt``.  A cell with a non-finite plane gives ``-1``, ``-1`` and NaN."""
+    p = beam_power(br)
+    nbr, nbt = p.shape[1], p.shape[2]
+    bad = ~np.isfinite(p).all(axis=(0, 1, 2))
+    mean = np.where(bad, 0.0, p).mean(axis=0).reshape((nbr * nbt,) + p.shape[3:])
+    flat = mean.argmax(axis=0)  # (the first of equal maxima)
+    power = np.where(bad, np.nan, np.take_along_axis(mean, flat[None], axis=0)[0])
+    return np.where(bad, -1, flat // nbt), np.where(bad, -1, flat % nbt), power
+
+
 received_power._d2d_native = "received_power"
 received_power_per_object._d2d_native = "received_power_per_object"
 path_length_squared._d2d_native = "length_squared"

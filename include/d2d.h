@@ -29,8 +29,9 @@ extern "C" {
 #define D2D_ABI_VERSION 12 /* (d2d_power_profile_launch / d2d_get_power_profile, d2d_strongest_paths_launch /
                               d2d_get_strongest_paths, d2d_coherent_field_launch / d2d_get_coherent_field,
                               d2d_frequency_response_launch / d2d_get_frequency_response and d2d_power_angle_launch /
-                              d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response and
-                              d2d_array_frequency_response_launch / d2d_get_array_frequency_response are additive: no struct, enum or
+                              d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response,
+                              d2d_array_frequency_response_launch / d2d_get_array_frequency_response and
+                              d2d_beam_response_launch / d2d_get_beam_response are additive: no struct, enum or
                               existing entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
@@ -862,6 +863,95 @@ int d2d_array_frequency_response_launch(d2d_ctx* ctx, const d2d_params* params, 
  * D2D_ERR_STATE before a launch and after a d2d_set_grid of another grid (the result goes with the grid). */
 int d2d_get_array_frequency_response(d2d_ctx* ctx, int32_t first, int32_t count, float* re /* [count][nr][nt][m][n] */,
                                      float* im /* same */, float* total /* [m][n] or NULL */);
+
+/* ---- K3-B, beam-space response: codebook beamforming fused into the culled sweep (y = w_rx^H H w_tx per cell, wavelength and
+ *      beam pair without the channel matrix: beam-sweep coverage maps, the best beam pair per cell, beamformed wideband power) ---- */
+
+#define D2D_BEAM_MAX 8 /* most beams of either codebook of one d2d_beam_response_launch */
+
+/* Launches the beam-response build of the culled forward sweep for the fixed end point `fixed` on the ctx stream (asynchronous),
+ * for the current scene, candidate mask and grid.
+ *
+ * Existing arguments:
+ *
+ * - `params`, `fixed`, the grid role and `amplitude` are exactly as for `d2d_array_frequency_response_launch`.
+ * - So are `inv_wavelength[nf]` (`1..D2D_FREQ_MAX`, each finite and `>= 0`), `tx_elems[nt][2]` and `rx_elems[nr][2]`
+ *   (`1..D2D_ARRAY_MAX` each).
+ *
+ * New arguments:
+ *
+ * - `tx_weights`: fp32 `[nbt][nt][2]`, the `(re, im)` of transmit beam `bt` at element `j`.
+ * - `rx_weights`: fp32 `[nbr][nr][2]`.
+ * - Every component must be finite.
+ * - `nbt` and `nbr` each lie in `1..D2D_BEAM_MAX`, with `D2D_BEAM_MAX = 8`. A larger codebook is several calls, which the
+ *   independence property below makes exact.
+ *
+ * Per cell, all in fp32, one rounding per operation, no contraction, candidates in the sweep's enumeration order:
+ *
+ *   total = +0.0f ; re[f][br][bt] = im[f][br][bt] = +0.0f
+ *   for candidates:
+ *       t = valid * fun ; r = path_length(points)            // as ArrayFreqSink gets them
+ *       total = total + t                                     // the fused map, bit for bit
+ *       if (t == 0) continue
+ *       a = amplitude == SQRT ? copysignf(sqrtf(fabsf(t)), t) : t
+ *       (utx, uty, okt) = unit_dir(p[1]-p[0]) ; (urx, ury, okr) = unit_dir(p[K]-p[K+1])     // d2d_steer.hpp, unchanged
+ *       if (!(okt && okr)) continue
+ *       for f < nf:
+ *           inv = inv_wavelength[f] ; u = r * inv ; f0 = u - floorf(u) ; (c0, s0) = phasor(f0)
+ *           steer(q):  v = q * inv ; g = v - floorf(v) ; if (g >= 1.0f) g = 0.0f ; (c, s) = phasor(g)      // e^(+j 2 pi q / lambda) = c + j s
+ *           for bt < nbt:  At = (+0, +0) ; for j < nt in order:  (c, s) = steer(steer_dot(etx[j], utx, uty)) ; w = tx_weights[bt][j]
+ *                              At.re = At.re + (w.re * c - w.im * s) ;  At.im = At.im + (w.re * s + w.im * c)
+ *           for br < nbr:  Ar = (+0, +0) ; for i < nr in order:  (c, s) = steer(steer_dot(erx[i], urx, ury)) ; w = rx_weights[br][i]
+ *                              Ar.re = Ar.re + (w.re * c + w.im * s) ;  Ar.im = Ar.im + (w.re * s - w.im * c)       // conj(w) * steer
+ *           for (br, bt):  P.re = Ar.re * At.re - Ar.im * At.im ;  P.im = Ar.re * At.im + Ar.im * At.re
+ *                          zr = P.re * c0 + P.im * s0 ;  zs = P.re * s0 - P.im * c0                                  // P e^(-j 2 pi f0) = zr - j zs
+ *                          re[f][br][bt] = re[f][br][bt] + a * zr ;  im[f][br][bt] = im[f][br][bt] - a * zs
+ *
+ * Outputs:
+ *
+ * - `re` and `im`: fp32 `[nf][nbr][nbt][m][n]`.
+ * - `total`: fp32 `[m][n]`.
+ * - This is `y = w_rx^H H w_tx` with the conjugate on the receive weights, the convention of `utils.beamformed_power`.
+ *
+ * The arithmetic is that of differt2d_amd/csrc/d2d_beam.hpp (steer, the two folds and the pair product), host and device alike;
+ * its text is the definition. Because every parenthesised product and every add above is one stated operation, the bits do not
+ * depend on how the kernel nests or recomputes things.
+ *
+ * Properties:
+ *
+ * - Total. `total` is the fused map, bit for bit.
+ * - Independence. Plane `(f, br, bt)` depends only on `inv_wavelength[f]`, row `br` of `rx_weights`, row `bt` of `tx_weights` and
+ *   the two element lists. Permuted, duplicated or truncated wavelength or beam lists give permuted, equal or leading planes, bit
+ *   for bit. The element order is part of the definition, because it is a left fold.
+ * - One antenna. Take `nt = nr = nbt = nbr = 1`, offsets `(+-0, +-0)` and weights `(1, 0)`. The planes then equal
+ *   `d2d_frequency_response_launch`'s, bit for bit, wherever no contribution lacks a direction and no contribution is NaN:
+ *   `phasor(0) = (1, +0)` exactly, so `At = Ar = P = (1, +0)`, `zr = c0` and `zs = s0` as values, and the accumulation absorbs
+ *   signs of zero.
+ * - Element space. Against the float64 contraction `conj(w_rx) . H . w_tx` of `d2d_array_frequency_response_launch`'s planes, the
+ *   beam planes agree within a derived bound (tests/beam_response_oracle.py), not bit for bit.
+ *
+ * One preparation of the sweep, then one kernel pass per chunk of wavelengths (the chunk's size is internal) over the same
+ * arguments; re and im are zeroed on the stream in front of the passes, every lane is the only writer of its cell's column: plain
+ * loads and stores, no atomics, the same bits run to run.  The lists and the weights are copied during the call.  The result is
+ * kept with the grid until the next such launch; d2d_set_grid of another grid drops it.  The launch touches no other product's
+ * result, and no other product's launch touches this one.
+ * D2D_ERR_INVALID: a NULL argument; what d2d_array_frequency_response_launch refuses of the list, the amplitude and the element
+ * lists, in its order; then nbt, then nbr outside 1 .. D2D_BEAM_MAX; then a weight component that is NaN or infinite (the message
+ * names the table and the beam and ends in the element's index).  No list is read unless its count is in range.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): what d2d_array_frequency_response_launch refuses (sigmoid validity, MinPath /
+ * FermatPath, D2D_OUT_ADD, a function that is not fused -- the message names d2d_valid_paths and d2d_trace_paths --, a TX grid
+ * whose sweep is not culled), with outputs of 8 * nf * nbr * nbt + 4 bytes per cell held against half of the free device memory --
+ * all decided before anything is enqueued.  A refused launch leaves the previous result as it was. */
+int d2d_beam_response_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                             const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude, int32_t nt,
+                             const float* tx_elems /* [nt][2] */, int32_t nr, const float* rx_elems /* [nr][2] */, int32_t nbt,
+                             const float* tx_weights /* [nbt][nt][2] */, int32_t nbr, const float* rx_weights /* [nbr][nr][2] */);
+/* Synchronises and copies wavelengths first .. first + count - 1 of the result of the last d2d_beam_response_launch that was
+ * accepted to the arrays that are not NULL (re, im: [count][nbr][nbt][m][n] with that launch's counts; total: [m][n], may be
+ * NULL).  0 <= first, count >= 1 and first + count <= nf; anything else is D2D_ERR_INVALID.  D2D_ERR_STATE before a launch and
+ * after a d2d_set_grid of another grid (the result goes with the grid). */
+int d2d_get_beam_response(d2d_ctx* ctx, int32_t first, int32_t count, float* re /* [count][nbr][nbt][m][n] */, float* im /* same */,
+                          float* total /* [m][n] or NULL */);
 
 /* unit_dir and steer_phase of d2d_steer.hpp on the device, for comparison with their host build: ok[i] = unit_dir(dx[i], dy[i]) as
  * 0 / 1 with ux[i], uy[i], and f[i] = steer_phase(f0[i], qt[i], qr[i], inv[i]). */
