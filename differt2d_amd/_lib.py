@@ -26,6 +26,7 @@ D2D_ANGLE_AT_TX, D2D_ANGLE_AT_RX = 0, 1  # d2d_power_angle_launch: the end of th
 D2D_ANGLE_BINS_MAX = 4096
 D2D_ARRAY_MAX = 8  # most elements of either array of one d2d_array_response_launch
 D2D_BEAM_MAX = 8  # most beams of either codebook of one d2d_beam_response_launch
+D2D_POL_TE, D2D_POL_TM = 0, 1  # d2d_material_response_launch polarisations
 D2D_NUM_STATS = 16
 D2D_COMM_ID_BYTES = 128
 D2D_OPT_ADAM, D2D_OPT_SGD, D2D_OPT_SGD_MOMENTUM = 0, 1, 2  # d2d_set_optimizer kinds
@@ -160,6 +161,9 @@ SYMBOLS = [
     ("d2d_beam_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32, _f32p, C.c_int32, _f32p,
                                            C.c_int32, _f32p, C.c_int32, _f32p]),
     ("d2d_get_beam_response", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("d2d_material_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
+    ("d2d_get_material_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("d2d_selftest_fresnel", C.c_int, [_ctx, _f32p, _f32p, _f32p, C.c_int32, C.c_int64, _f32p, _f32p]),
     ("d2d_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32]),
     ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_field_coefs_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -246,8 +246,18 @@ struct d2d_ctx {
         void forget() { nf = nbt = nbr = 0; }
         void drop() { out.release(); w.release(); forget(); }
     } beam;
+    // material response (d2d_material_response_launch): nf planes of re and im and the total, kept until the next accepted launch;
+    // the scene forgets it too (it depends on the walls' count)
+    struct Material {
+        Planes out;          // [nf][m][n], [nf][m][n], [m][n]
+        DevBuf<float> eps;   // [nf][N][2]: the permittivity table of the launch in flight
+        int32_t nf = 0;      // planes of the last accepted launch; 0: no result
+        size_t bytes() const { return out.bytes() + eps.n * sizeof(float); }
+        void forget() { nf = 0; }
+        void drop() { out.release(); eps.release(); forget(); }
+    } mat;
     void drop_products() {  // every one of them goes with the grid
-        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop();
+        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop();
     }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -797,6 +807,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->cust_C = -1;               // (a host-evaluated path function's rows belong to the paths of the previous scene)
     c->have_vjp = false;          // d_vjp was sized for (and computed from) the previous scene
     c->cg.forget();               // (... and so was the frequency response's coefficient adjoint)
+    c->mat.forget();              // (... and the material response, whose table has one entry per wall)
     c->have_kernel_time = false;
     c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
@@ -2293,6 +2304,7 @@ constexpr SinkProduct COEF_VJP = {"d2d_field_coefs_vjp_launch", "a host function
 constexpr SinkProduct ANGLE = {"d2d_power_angle_launch", "a host function's profile: bin the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "a profile is always overwritten", LATE};
 constexpr SinkProduct ARRAY = {"d2d_array_response_launch", "a host function's channel matrix: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrix is always overwritten", LATE};
 constexpr SinkProduct WIDE = {"d2d_array_frequency_response_launch", "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrices are always overwritten", LATE};
+constexpr SinkProduct MATERIAL = {"d2d_material_response_launch", "a host function's response: add the phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths, each times its walls' Fresnel coefficients", "the response is always overwritten", LATE};
 constexpr SinkProduct BEAM = {"d2d_beam_response_launch", "a host function's beam response: add the beamformed phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the beam response is always overwritten", LATE};
 
 // What the products refuse of the caller's parameters before prep_sink_sweep's share.
@@ -2388,7 +2400,8 @@ static int copy_out(d2d_ctx* c, std::initializer_list<CopyOut> copies) {
     return D2D_OK;
 }
 
-static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK && d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK && d2d_host::BEAM_CHUNK == d2d::BEAM_CHUNK,
+static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK && d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK && d2d_host::BEAM_CHUNK == d2d::BEAM_CHUNK &&
+                  d2d_host::MAT_CHUNK == d2d::MAT_CHUNK,
               "d2d_host.hpp and d2d_kernels.hpp disagree");
 
 }  // namespace
@@ -2786,6 +2799,57 @@ int d2d_get_beam_response(d2d_ctx* c, int32_t first, int32_t count, float* re, f
     return copy_out(c, {{re, o.re.p + (size_t)first * block, bytes}, {im, o.im.p + (size_t)first * block, bytes}, {total, o.total.p, cells * sizeof(float)}});
 }
 
+// Material-response build: ONE preparation, then one pass per chunk of MAT_CHUNK wavelengths over the same SweepArgs (as
+// d2d_frequency_response_launch does), every lane writing its cell's planes of the chunk and, in the first pass, the total.  The
+// permittivity table lives in a device buffer of the result, copied from the caller's during the call and uploaded on the stream in
+// front of the passes; the wall normals are the context's own table.
+int d2d_material_response_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                                 int32_t polarization, const float* eps, int32_t n_objects) {
+    if (!c || !fixed || !inv_wavelength || !eps) return fail(D2D_ERR_INVALID, "NULL argument");
+    SinkLaunch<d2d_ctx::Material> L(c, MATERIAL, c->mat, fixed);
+    d2d_ctx::Planes& o = c->mat.out;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::material_params(inv_wavelength, nf, amplitude, polarization, eps, n_objects, c->N, err))) return fail(rc, "%s: %s", MATERIAL.who, err.c_str());
+    if ((rc = L.device())) return rc;
+    if (!d2d_host::material_fits(L.cells, nf, (size_t)n_objects, L.mem_free, c->mat.bytes()))
+        return fail(D2D_ERR_UNSUPPORTED, "%s: %zu cells (%zu bytes per cell) and a table of %zu bytes exceed half of the free device memory (%zu bytes free)",
+                    MATERIAL.who, L.cells, d2d_host::freq_bytes_per_cell(nf), 8 * (size_t)nf * (size_t)n_objects, L.mem_free);
+    const size_t table = 2 * (size_t)nf * (size_t)n_objects;  // floats
+    if ((rc = L.prepare()) || (rc = o.ensure((size_t)nf * L.cells, L.cells)) || (rc = c->mat.eps.ensure(table + 2))) return rc;
+    const bool constant = d2d_host::material_constant_band(eps, nf, n_objects);
+    // behind whatever pass still reads the previous launch's table (the copy leaves the caller's memory during the call: pageable)
+    if (table > 0) HIP_TRY(hipMemcpyAsync(c->mat.eps.p, eps, table * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (L.s.tiles > 0)
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::MAT_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::MAT_CHUNK);
+            d2d::MaterialArgs g = {};
+            g.re = o.re.p + (size_t)ch.first * L.cells;
+            g.im = o.im.p + (size_t)ch.first * L.cells;
+            g.total = ch.with_total ? o.total.p : nullptr;
+            g.cells = (long)L.cells;
+            g.refl = c->d_refl.p;
+            g.eps = c->mat.eps.p + (size_t)ch.first * 2 * (size_t)n_objects;
+            for (int32_t j = 0; j < ch.count; ++j) g.inv[j] = inv_wavelength[ch.first + j];
+            g.nf = ch.count;
+            g.N = n_objects;
+            g.amplitude = amplitude;
+            g.pol = polarization;
+            g.constant = constant ? 1 : 0;
+            HIP_TRY(L.pass<d2d::MaterialSink>(g));
+        }
+    c->mat.nf = nf;
+    return D2D_OK;
+}
+
+int d2d_get_material_response(d2d_ctx* c, float* re, float* im, float* total) {
+    if (int rc = result_state(c, c && c->mat.nf >= 1 && c->mat.out.re.p, MATERIAL, "result goes with the grid and the scene")) return rc;
+    const d2d_ctx::Planes& o = c->mat.out;
+    const size_t bytes = (size_t)c->m * (size_t)c->n * sizeof(float);
+    return copy_out(c, {{re, o.re.p, bytes * (size_t)c->mat.nf}, {im, o.im.p, bytes * (size_t)c->mat.nf}, {total, o.total.p, bytes}});
+}
+
 int d2d_valid_paths(d2d_ctx* c, const d2d_params* p, const float* fixed, int64_t* count) { return valid_paths(c, p, fixed, count); }
 
 int d2d_get_valid_paths(d2d_ctx* c, int64_t capacity, int32_t* cell, int32_t* cand, int32_t* order, float* xys, float* loss, float* valid,
@@ -2970,6 +3034,22 @@ int d2d_selftest_steer(d2d_ctx* c, const float* dx, const float* dy, const float
     HIP_TRY(hipStreamSynchronize(c->stream));
     float* out[4] = {ux, uy, ok, f};
     for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_fresnel(d2d_ctx* c, const float* er, const float* ei, const float* cs, int32_t pol, int64_t n, float* gr, float* gi) {
+    if (!c || !er || !ei || !cs || !gr || !gi || n <= 0 || (pol != D2D_POL_TE && pol != D2D_POL_TM)) return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> din, dout;  // three inputs, two outputs, n each
+    if ((rc = din.ensure(3 * (size_t)n)) || (rc = dout.ensure(2 * (size_t)n))) return rc;
+    const float* in[3] = {er, ei, cs};
+    for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpy(din.p + (size_t)k * (size_t)n, in[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_fresnel_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, din.p, dout.p, (int)pol, (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float* out[2] = {gr, gi};
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -309,6 +310,58 @@ inline int freq_params(const float* inv_wavelength, int32_t nf, int32_t amplitud
 inline size_t freq_bytes_per_cell(int32_t nf) { return 8 * (size_t)nf + 4; }
 // One pass of the sink kernel per FREQ_CHUNK wavelengths (chunk_plan).
 constexpr int32_t FREQ_CHUNK = 8;  // = d2d::FREQ_CHUNK (d2d_kernels.hpp)
+
+// ---- parameters, outputs and launch plan of the material response (d2d_material_response_launch, d2d::MaterialSink) ---
+// D2D_ERR_INVALID, in this order: what freq_params refuses (through it); a polarization that is neither D2D_POL_TE nor D2D_POL_TM; an
+// n_objects that is not the scene's; an eps component that is NaN, infinite or above 2^50 in magnitude, or an imaginary part > 0
+// (the library's time convention makes a lossy medium eps' - j eps''): the message ends with the wavelength index and the wall index.
+// The table is fp32 [nf][n_objects][2] and is not read unless the counts are in range.
+constexpr float MAT_EPS_MAX = 1125899906842624.0f;  // 2^50: d2d_fresnel.hpp's squares stay finite
+inline int material_params(const float* inv_wavelength, int32_t nf, int32_t amplitude, int32_t polarization, const float* eps, int32_t n_objects,
+                           int32_t scene_objects, std::string& err) {
+    if (int rc = freq_params(inv_wavelength, nf, amplitude, err)) return rc;
+    if (polarization != D2D_POL_TE && polarization != D2D_POL_TM)
+        return err = "the material response's polarization must be D2D_POL_TE (0) or D2D_POL_TM (1), got " + std::to_string(polarization), D2D_ERR_INVALID;
+    if (n_objects != scene_objects)
+        return err = "the material response needs one permittivity per object of the resident scene (" + std::to_string(scene_objects) + "), got n_objects = " +
+                     std::to_string(n_objects),
+               D2D_ERR_INVALID;
+    for (int32_t f = 0; f < nf; ++f)
+        for (int32_t w = 0; w < n_objects; ++w) {
+            const float er = eps[2 * ((size_t)f * n_objects + w)], ei = eps[2 * ((size_t)f * n_objects + w) + 1];
+            const char* what = nullptr;
+            if (!std::isfinite(er) || !std::isfinite(ei)) what = "finite";
+            else if (std::fabs(er) > MAT_EPS_MAX || std::fabs(ei) > MAT_EPS_MAX) what = "at most 2^50 in magnitude";
+            if (what)
+                return err = std::string("the material response needs every permittivity component ") + what + ", got (" + std::to_string(er) + ", " +
+                             std::to_string(ei) + ") at wavelength index " + std::to_string(f) + ", wall index " + std::to_string(w),
+                       D2D_ERR_INVALID;
+            if (ei > 0.0f)
+                return err = "the material response needs Im eps <= 0 (a lossy medium is eps' - j eps'' under e^(-j 2 pi r / lambda)), got " +
+                             std::to_string(ei) + " at wavelength index " + std::to_string(f) + ", wall index " + std::to_string(w),
+                       D2D_ERR_INVALID;
+        }
+    return D2D_OK;
+}
+// Every row of the table equals row 0 in bits (one permittivity per wall for the whole band): the kernel then forms the product of
+// coefficients once per contribution.  Bits, not values: -0 and +0 differ (they choose different signs of zero downstream).
+inline bool material_constant_band(const float* eps, int32_t nf, int32_t n_objects) {
+    const size_t row = 2 * (size_t)n_objects * sizeof(float);
+    for (int32_t f = 1; f < nf; ++f)
+        if (row && std::memcmp(eps, reinterpret_cast<const char*>(eps) + (size_t)f * row, row) != 0) return false;
+    return true;
+}
+// Per cell: nf planes of re and im and one total, 4 bytes each; beside them the table, 8 nf bytes per object.  Refused above half
+// of the device memory that is free, counting what the buffers hold already as free; no product is formed that could wrap.
+inline bool material_fits(size_t cells, int32_t nf, size_t n_objects, size_t mem_free, size_t held_bytes) {
+    if (nf < 1) return false;
+    const size_t budget = mem_free / 2 + held_bytes / 2;
+    const size_t per_object = 8 * (size_t)nf;
+    if (n_objects > budget / per_object) return false;
+    return cells <= (budget - n_objects * per_object) / freq_bytes_per_cell(nf);
+}
+// One pass of the sink kernel per MAT_CHUNK wavelengths (chunk_plan).
+constexpr int32_t MAT_CHUNK = 8;  // = d2d::MAT_CHUNK (d2d_kernels.hpp)
 
 // ---- memory of the frequency response's coefficient adjoint (d2d_field_coefs_vjp_launch, d2d::CoefGradSink) -----------
 // The cotangent planes take 8 nf bytes per cell and the partial rows 4 bytes per patch and object.  Refused like the frequency

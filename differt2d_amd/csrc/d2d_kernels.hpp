@@ -38,6 +38,7 @@
 #include "d2d_angle.hpp"
 #include "d2d_steer.hpp"
 #include "d2d_beam.hpp"
+#include "d2d_fresnel.hpp"
 
 namespace d2d {
 
@@ -455,12 +456,14 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
                                                const float (&imgx)[D2D_MAX_ORDER], const float (&imgy)[D2D_MAX_ORDER],
                                                float txx, float txy, float rxx, float rxy, bool lane_bad, float& acc,
                                                WaveStats& st, GradCtx* g = nullptr, float acc_floor = -1.0f, float* r_out = nullptr,
-                                               float* dir_out = nullptr) {
+                                               float* dir_out = nullptr, float* seg_out = nullptr) {
     // r_out (power_sink_kernel, BinSink): receives the path length the path function is evaluated with -- written only where the
     // contribution is (a candidate that leaves early leaves both alone).  Null everywhere else, a constant of the inlined call:
     // it costs those instances no instruction.
     // dir_out (power_sink_kernel, AngleSink and ArraySink): receives, where r_out is written, the two end directions of the path as fp32
     // differences of its points, {p[1] - p[0], p[K] - p[K+1]} (x, y each; no D2D_EPS).  Null everywhere else, likewise.
+    // seg_out (power_sink_kernel, MaterialSink): receives, where r_out is written, the incoming segment of every bounce as fp32
+    // differences of the path's points, (p[i+1] - p[i]) for i = 0 .. K-1 (x, y each; no D2D_EPS).  Null everywhere else, likewise.
     // acc_floor >= 0 (MODE_SIG, fun >= 0): the caller adds this candidate to a sum it does not hold -- `acc` is a scratch
     // that receives the contribution alone -- but knows that sum to be at least acc_floor when the addition happens
     const float zc_acc = (acc_floor >= 0.0f) ? acc_floor : acc;
@@ -1161,6 +1164,13 @@ __device__ __forceinline__ void eval_candidate(const SweepArgs& a, const int (&c
         dir_out[2] = px[K] - px[K + 1];
         dir_out[3] = py[K] - py[K + 1];
     }
+    if (seg_out != nullptr) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            seg_out[2 * i] = px[i + 1] - px[i];
+            seg_out[2 * i + 1] = py[i + 1] - py[i];
+        }
+    }
     float f;
     float cf[K > 0 ? K : 1];  // D2D_FUN_RECEIVED_POWER_PER_OBJECT: the candidate's coefficients (wave-uniform)
     if (a.fun_id == D2D_FUN_RECEIVED_POWER) f = a.fnum[K] / (a.h2 + r * r);
@@ -1790,6 +1800,7 @@ struct RecSink {
     using Args = RecArgs;
     static constexpr bool WANTS_R = false;  // (the path length is not asked of eval_candidate)
     static constexpr bool WANTS_DIR = false;  // (nor are the path's end directions)
+    static constexpr bool WANTS_SEG = false;  // (nor are the segments that reach its bounces)
     int4* rec;
     int base, limit;
     int cnt;
@@ -1835,6 +1846,7 @@ struct BinSink {
     using Args = BinArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = false;
     float* out;  // [nbins][cells]
     long cells;
     int cell;
@@ -1883,6 +1895,7 @@ struct TopSink {
     using Args = TopArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = false;
     static_assert(D2D_MAX_ORDER == 4, "a slot's wall indices are stored as one int4");
     static_assert(TOP_SLOTS == D2D_TOP_MAX, "d2d_top.hpp and include/d2d.h disagree");
     TopSlots s;
@@ -1951,6 +1964,7 @@ struct FieldSink {
     using Args = FieldArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = false;
     float re, im, total;
     float inv;
     bool root;
@@ -2008,6 +2022,7 @@ struct FreqSink {
     using Args = FreqArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = false;
     float re[FREQ_CHUNK], im[FREQ_CHUNK], total;
     float inv[FREQ_CHUNK];
     int nf;
@@ -2086,6 +2101,7 @@ struct CoefGradSink {
     using Args = CoefGradArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = false;
     float rb[FREQ_CHUNK], ib[FREQ_CHUNK];
     float inv[FREQ_CHUNK];
     const float* coef;
@@ -2187,6 +2203,7 @@ struct AngleSink {
     using Args = AngleArgs;
     static constexpr bool WANTS_R = false;
     static constexpr bool WANTS_DIR = true;
+    static constexpr bool WANTS_SEG = false;
     float total;
     float* out;
     long cells;
@@ -2260,6 +2277,7 @@ struct ArraySink {
     using Args = ArrayArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = true;
+    static constexpr bool WANTS_SEG = false;
     static_assert(ARRAY_MAX == D2D_ARRAY_MAX, "d2d_kernels.hpp and include/d2d.h disagree");
     float total;
     const ArrayArgs* x;  // the kernel argument: wave-uniform, read where it is used
@@ -2340,6 +2358,7 @@ struct ArrayFreqSink {
     using Args = ArrayFreqArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = true;
+    static constexpr bool WANTS_SEG = false;
     float total;
     const ArrayFreqArgs* x;  // the kernel argument: wave-uniform, read where it is used
     int cell;
@@ -2434,6 +2453,7 @@ struct BeamSink {
     using Args = BeamArgs;
     static constexpr bool WANTS_R = true;
     static constexpr bool WANTS_DIR = true;
+    static constexpr bool WANTS_SEG = false;
     static_assert(BEAM_MAX == D2D_BEAM_MAX, "d2d_kernels.hpp and include/d2d.h disagree");
     float total;
     const BeamArgs* x;  // the kernel argument: wave-uniform, read where it is used
@@ -2519,11 +2539,137 @@ struct BeamSink {
     }
 };
 
-// One candidate into a sink: a sink that wants both the length and the directions takes put_rd, a WANTS_DIR sink the contribution
-// with the path's end directions, every other one the contribution with the candidate's code, order and length
+// MaterialSink (d2d_material_response_launch): FreqSink's coherent sum with every contribution multiplied by the product of the
+// Fresnel reflection coefficients of the walls it bounces off, for up to MAT_CHUNK wavelengths of one sweep (include/d2d.h holds
+// the definition, d2d_fresnel.hpp the coefficient).  Per lane, in registers: re[C], im[C] and the running fp32 sum of every
+// contribution (the fused map, bit for bit).  Per candidate that some lane has a non-zero contribution from: the walls come out of the
+// wave-uniform code (readfirstlane), their unit normals refl[2 w].zw and their permittivities eps[j][w] are read at wave-uniform
+// addresses (scalar loads); per lane the cosines c_i = |unit_dir(seg_i) . n_i| of the K angles of incidence, formed once from what
+// eval_candidate hands out through seg_out (WANTS_SEG, sink_put), and then for every j < nf
+//     G = (1, +0) ; for i < K: G = G * fresnel(eps[j][w_i], c_i, pol) ; u = r * inv[j] ; f0 = u - floorf(u) ; (c0, s0) = phasor(f0)
+//     zr = G.re*c0 + G.im*s0 ; zs = G.re*s0 - G.im*c0 ; re[j] = re[j] + a * zr ; im[j] = im[j] - a * zs
+// in fp32 without contraction.  With `constant` set (the host found the rows of eps equal in bits) G is formed once, from row 0,
+// in front of the loop over j: the same bits by definition.  i and j are compile-time indices (static_for) behind the wave-uniform
+// guards i < k and j < nf: a register array indexed at run time goes to scratch.  A lane whose path has a segment
+// without a direction, or a NaN cosine, adds nothing to the planes (total has its contribution).  end() stores planes 0 .. nf-1 and
+// total where its pointer is not null (the first chunk's pass): every lane is the only writer of its cell, no atomics, no zeroing
+// pass; lanes outside the grid (cell < 0) never write.  Wall indices come from the sweep's own candidates, 0 <= w < N.
+constexpr int MAT_CHUNK = 8;  // wavelengths per pass: internal, not in the ABI (d2d_host::MAT_CHUNK is the host's copy)
+struct MaterialArgs {
+    float* re;             // [nf][cells]: this chunk's planes
+    float* im;             // [nf][cells]
+    float* total;          // [cells] or null
+    long cells;            // m * n
+    const float4* refl;    // the context's wall table: row 2 w = {ox, oy, nx, ny}
+    const float* eps;      // device memory, [nf][N][2]: this chunk's rows of (re, im); row 0 alone is read when `constant`
+    float inv[MAT_CHUNK];  // turns per unit length, finite and >= 0; entries at and past nf are not read
+    int nf;                // 1 .. MAT_CHUNK
+    int N;                 // objects: the length of a row of eps
+    int amplitude;         // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int pol;               // D2D_POL_TE / D2D_POL_TM
+    int constant;          // != 0: every row of eps equals row 0 in bits
+};
+static_assert(sizeof(SweepArgs) + sizeof(MaterialArgs) <= 4096, "power_sink_kernel's arguments must fit the 4 KiB kernel-argument segment");
+struct MaterialSink {
+    using Args = MaterialArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = true;
+    static_assert(POL_TE == D2D_POL_TE && POL_TM == D2D_POL_TM, "d2d_fresnel.hpp and include/d2d.h disagree");
+    float re[MAT_CHUNK], im[MAT_CHUNK], total;
+    const MaterialArgs* x;  // the kernel argument: wave-uniform, read where it is used
+    int cell;
+    __device__ __forceinline__ void begin(const MaterialArgs& xa, long /*tile*/, int lane_cell) {
+        static_for<0, MAT_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            re[J] = im[J] = 0.0f;
+        });
+        total = 0.0f;
+        x = &xa;
+        cell = lane_cell;
+    }
+    // G = prod_i fresnel(row[w_i], ci_i, pol), folded from the left; row and w are wave-uniform
+    __device__ __forceinline__ void fold(const float* row, const int (&w)[D2D_MAX_ORDER], const float (&ci)[D2D_MAX_ORDER], int k, int pol, float& Gr,
+                                         float& Gi) const {
+        Gr = 1.0f;
+        Gi = 0.0f;
+        static_for<0, D2D_MAX_ORDER>([&](auto II) {
+            constexpr int I = decltype(II)::value;
+            if (I < k) {
+                const float er = cmem(row)[2 * w[I]], ei = cmem(row)[2 * w[I] + 1];
+                float gr, gi;
+                fresnel(er, ei, ci[I], pol, gr, gi);
+                fresnel_fold(Gr, Gi, gr, gi);
+            }
+        });
+    }
+    // seg: (p[i+1] - p[i]) for i < k of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_seg(float t, unsigned long long code, int k, float r, const float (&seg)[2 * D2D_MAX_ORDER]) {
+        total = total + t;
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        int w[D2D_MAX_ORDER];
+        float ci[D2D_MAX_ORDER];
+        bool ok = true;
+        static_for<0, D2D_MAX_ORDER>([&](auto II) {
+            constexpr int I = decltype(II)::value;
+            w[I] = 0;
+            ci[I] = 0.0f;
+            if (I < k) {
+                w[I] = __builtin_amdgcn_readfirstlane((int)((code >> (12 * I)) & 0xfffull));
+                const float4 n = ldc4(x->refl, 2 * w[I]);
+                float ux, uy;
+                const bool oki = unit_dir(seg[2 * I], seg[2 * I + 1], ux, uy);
+                const float c = fabsf(steer_dot(ux, uy, n.z, n.w));
+                ci[I] = c;
+                ok = ok && oki && c == c;
+            }
+        });
+        if (!(p && ok)) return;  // (per lane: what follows is uniform for the lanes that stay)
+        const float a = x->amplitude == D2D_FIELD_AMP_SQRT ? copysignf(sqrtf(fabsf(t)), t) : t;
+        const int nf = x->nf, pol = x->pol;
+        const bool constant = x->constant != 0;
+        const size_t stride = 2 * (size_t)x->N;
+        float G0r = 1.0f, G0i = 0.0f;
+        if (constant) fold(x->eps, w, ci, k, pol, G0r, G0i);
+        static_for<0, MAT_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            if (J < nf) {
+                float Gr = G0r, Gi = G0i;
+                if (!constant) fold(x->eps + (size_t)J * stride, w, ci, k, pol, Gr, Gi);
+                const float u = r * x->inv[J];
+                const float f0 = u - floorf(u);
+                float c0, s0, zr, zs;
+                phasor(f0, c0, s0);
+                fresnel_turn(Gr, Gi, c0, s0, zr, zs);
+                const float azr = a * zr, azs = a * zs;
+                re[J] = re[J] + azr;
+                im[J] = im[J] - azs;
+            }
+        });
+    }
+    __device__ __forceinline__ void end(const MaterialArgs& xa, long, int) const {
+        if (cell < 0) return;
+        if (xa.total != nullptr) xa.total[cell] = total;
+        static_for<0, MAT_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            if (J < xa.nf) {
+                const size_t at = (size_t)J * (size_t)xa.cells + (size_t)cell;
+                xa.re[at] = re[J];
+                xa.im[at] = im[J];
+            }
+        });
+    }
+};
+
+// One candidate into a sink: a WANTS_SEG sink takes put_seg (the contribution, the candidate's code and order, the length and the
+// segments that reach its bounces), a sink that wants both the length and the directions takes put_rd, a WANTS_DIR sink the
+// contribution with the path's end directions, every other one the contribution with the candidate's code, order and length
 template <class S>
-__device__ __forceinline__ void sink_put(S& s, float t, unsigned long long code, int k, float r, const float (&dir)[4]) {
-    if constexpr (S::WANTS_DIR && S::WANTS_R) s.put_rd(t, r, dir);
+__device__ __forceinline__ void sink_put(S& s, float t, unsigned long long code, int k, float r, const float (&dir)[4],
+                                         const float (&seg)[2 * D2D_MAX_ORDER]) {
+    if constexpr (S::WANTS_SEG) s.put_seg(t, code, k, r, seg);
+    else if constexpr (S::WANTS_DIR && S::WANTS_R) s.put_rd(t, r, dir);
     else if constexpr (S::WANTS_DIR) s.put_dir(t, dir);
     else s.put(t, code, k, r);
 }
@@ -2678,9 +2824,9 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 image_of(ldc4(a.refl, 2 * ce[d]), d == 0 ? a.txx : ex[d > 0 ? d - 1 : 0], d == 0 ? a.txy : ey[d > 0 ? d - 1 : 0], ex[d], ey[d]);
             }
             if constexpr (RECORD) {
-                float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr);
-                sink_put(*rsink, t, cu, K, rl, dv);
+                float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sg[2 * D2D_MAX_ORDER] = {};
+                eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr, RS::WANTS_SEG ? sg : nullptr);
+                sink_put(*rsink, t, cu, K, rl, dv, sg);
             } else if (LIST) {
                 float t = 0.0f;
                 eval_candidate<K, MODE, STATS, GRAD, false, false>(a, ce, ex, ey, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
@@ -2817,12 +2963,12 @@ __device__ __forceinline__ void sweep_order_culled(const SweepArgs& a, const flo
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), pIx, pIy, imgx[K - 1], imgy[K - 1]);
                 if constexpr (RECORD) {
-                    float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr);
+                    float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sg[2 * D2D_MAX_ORDER] = {};
+                    eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr, RS::WANTS_SEG ? sg : nullptr);
                     unsigned long long cu = 0ull;
 #pragma unroll
                     for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
-                    sink_put(*rsink, t, cu, K, rl, dv);
+                    sink_put(*rsink, t, cu, K, rl, dv, sg);
                 } else if (LIST) {
                     float t = 0.0f;
                     eval_candidate<K, MODE, STATS, GRAD, false, false>(a, cand, imgx, imgy, a.txx, a.txy, rxx, rxy, lane_bad, t, st, g);
@@ -3949,12 +4095,12 @@ __device__ __forceinline__ void sweep_order_culled_txg(const SweepArgs& a, const
                 cand[K - 1] = cmem(a.cw)[chunk * 64 + b];
                 image_of(ldc4(a.refl, 2 * cand[K - 1]), K == 1 ? cx : imgx[K >= 2 ? K - 2 : 0], K == 1 ? cy : imgy[K >= 2 ? K - 2 : 0], imgx[K - 1], imgy[K - 1]);
                 if constexpr (RECORD) {
-                    float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr);
+                    float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sg[2 * D2D_MAX_ORDER] = {};
+                    eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, g, -1.0f, RS::WANTS_R ? &rl : nullptr, RS::WANTS_DIR ? dv : nullptr, RS::WANTS_SEG ? sg : nullptr);
                     unsigned long long cu = 0ull;
 #pragma unroll
                     for (int d = 0; d < K; ++d) cu |= (unsigned long long)cand[d] << (12 * d);
-                    sink_put(*rsink, t, cu, K, rl, dv);
+                    sink_put(*rsink, t, cu, K, rl, dv, sg);
                 } else {
                     eval_candidate<K, MODE, false, GRAD, false, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, acc, st, g);
                 }
@@ -4211,12 +4357,13 @@ __global__ void __launch_bounds__(64) power_sink_kernel(SweepArgs a, typename Si
         // (sweep_order<0>'s one candidate, with the length handed out where the sink wants it)
         const int cand[D2D_MAX_ORDER] = {-1, -1, -1, -1};
         const float imgx[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f}, imgy[D2D_MAX_ORDER] = {0.0f, 0.0f, 0.0f, 0.0f};
-        float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float t = 0.0f, rl = 0.0f, dv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sg[2 * D2D_MAX_ORDER] = {};
         float* const r_out = Sink::WANTS_R ? &rl : nullptr;
         float* const dir_out = Sink::WANTS_DIR ? dv : nullptr;
-        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, r_out, dir_out);
-        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, r_out, dir_out);
-        sink_put(sink, t, 0ull, 0, rl, dv);
+        float* const seg_out = Sink::WANTS_SEG ? sg : nullptr;
+        if constexpr (TXG) eval_candidate<0, MODE, false, false, true, true>(a, cand, imgx, imgy, cx, cy, a.txx, a.txy, lane_bad, t, st, nullptr, -1.0f, r_out, dir_out, seg_out);
+        else eval_candidate<0, MODE, false, false, true, false>(a, cand, imgx, imgy, a.txx, a.txy, cx, cy, lane_bad, t, st, nullptr, -1.0f, r_out, dir_out, seg_out);
+        sink_put(sink, t, 0ull, 0, rl, dv, sg);
     }
     static_for<1, MAXK + 1>([&](auto KK) {
         constexpr int K = decltype(KK)::value;
@@ -4534,6 +4681,17 @@ __global__ void selftest_steer_kernel(const float* __restrict__ in, float* __res
     out[n + i] = uy;
     out[2 * n + i] = ok ? 1.0f : 0.0f;
     out[3 * n + i] = steer_phase(in[2 * n + i], in[3 * n + i], in[4 * n + i], in[5 * n + i]);
+}
+
+// fresnel (d2d_fresnel.hpp) on the device, for comparison with its host build (tests/test_gpu_material_response.py):
+// in = er, ei, c and out = gr, gi, n values each
+__global__ void selftest_fresnel_kernel(const float* __restrict__ in, float* __restrict__ out, int pol, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float gr, gi;
+    fresnel(in[i], in[n + i], in[2 * n + i], pol, gr, gi);
+    out[i] = gr;
+    out[n + i] = gi;
 }
 
 // Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per

@@ -127,6 +127,7 @@ class BeamResponse(NamedTuple):
 
 FIELD_AMPLITUDES = {"sqrt": L.D2D_FIELD_AMP_SQRT, "linear": L.D2D_FIELD_AMP_LINEAR}
 ANGLE_ENDS = {"tx": L.D2D_ANGLE_AT_TX, "rx": L.D2D_ANGLE_AT_RX}
+POLARIZATIONS = {"te": L.D2D_POL_TE, "tm": L.D2D_POL_TM}
 
 
 def _amplitude_id(method: str, amplitude) -> int:
@@ -136,6 +137,15 @@ def _amplitude_id(method: str, amplitude) -> int:
             raise L.D2DError(-1, f"{method}: amplitude must be one of {sorted(FIELD_AMPLITUDES)}, got {amplitude!r}")
         amplitude = FIELD_AMPLITUDES[amplitude]
     return int(amplitude)
+
+
+def _polarization_id(method: str, polarization) -> int:
+    """The library's constant of a polarisation that may be given by name; ``method`` begins the refusal of an unknown name."""
+    if isinstance(polarization, str):
+        if polarization.lower() not in POLARIZATIONS:
+            raise L.D2DError(-1, f"{method}: polarization must be one of {sorted(POLARIZATIONS)}, got {polarization!r}")
+        polarization = POLARIZATIONS[polarization.lower()]
+    return int(polarization)
 
 
 def _keep_pointer(a: np.ndarray, *shape) -> np.ndarray:
@@ -188,6 +198,7 @@ class Context:
         self._array_shape = None  # (nr, nt) of the last launch_array_response that was accepted
         self._wide_shape = None  # (nf, nr, nt) of the last launch_array_frequency_response that was accepted
         self._beam_shape = None  # (nf, nbr, nbt) of the last launch_beam_response that was accepted
+        self._mat_nf = 0  # planes of the last launch_material_response that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -487,6 +498,16 @@ class Context:
         L.check(self._lib.d2d_selftest_steer(self._ctx, *a, a[0].size, ux, uy, ok, f))
         return ux, uy, ok != 0.0, f
 
+    def selftest_fresnel(self, er, ei, c, polarization="te"):
+        """``fresnel(er, ei, c, polarization)`` as the material response computes it on the device (include/d2d.h: must equal the
+        host build of d2d_fresnel.hpp bit for bit).  Returns ``(gr, gi)``."""
+        a = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (er, ei, c)]
+        if any(v.size != a[0].size for v in a):
+            raise ValueError("the three inputs must have one size")
+        gr, gi = np.empty_like(a[0]), np.empty_like(a[0])
+        L.check(self._lib.d2d_selftest_fresnel(self._ctx, *a, _polarization_id("selftest_fresnel", polarization), a[0].size, gr, gi))
+        return gr, gi
+
     def get_map(self) -> np.ndarray:
         out = np.empty(self.shape, np.float32)
         L.check(self._lib.d2d_get_map(self._ctx, out))
@@ -739,6 +760,57 @@ class Context:
         planes = (self._freq_nf,) + shape
         fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_frequency_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
+        return fr
+
+    def material_response(self, params: L.Params, fixed, inv_wavelengths, permittivity, polarization="te",
+                          amplitude="sqrt") -> "FrequencyResponse":
+        """:meth:`frequency_response` with Fresnel reflection per wall: every contribution is multiplied by the product of the
+        complex reflection coefficients of the walls it bounces off, each a function of the angle of incidence, of
+        ``polarization`` (``"te"``: E perpendicular to the plane of incidence -- for vertical antennas over a 2-D floor plan E
+        out of the plane, the default; ``"tm"``: E in the plane of incidence) and of the wall's complex relative permittivity
+        (include/d2d.h: d2d_material_response_launch holds the definition, differt2d_amd/csrc/d2d_fresnel.hpp the coefficient;
+        :func:`differt2d_amd.utils.fresnel_coefficient` is the same formula in complex128).  ONE preparation of the culled
+        sweep, one kernel pass per 8 wavelengths.
+
+        ``permittivity``: complex ``[N]``, one value per object of the scene for the whole band, or ``[nf, N]``, a row per entry
+        of ``inv_wavelengths``.  The time convention is the library's, ``e^(-j 2 pi r / lambda)``: a lossy medium is
+        ``eps' - 1j * eps''``, so the imaginary part is ``<= 0`` (:func:`differt2d_amd.utils.complex_permittivity`).  Pass
+        ``params`` whose path function holds no reflection loss of its own (``received_power`` with ``r_coef = 1``, or
+        ``one``), so that walls are not counted twice.  ``amplitude``, ``params`` and ``fixed`` as for :meth:`coherent_field`.
+        No other product's result is touched.  Values only, one GPU.
+
+        Returns a :class:`FrequencyResponse`: ``re`` and ``im``, fp32 ``[nf, m, n]``, and ``total`` (the fused map, bit for bit),
+        fp32 ``[m, n]`` -- :func:`differt2d_amd.utils.frequency_response`, :func:`~differt2d_amd.utils.wideband_power`,
+        :func:`~differt2d_amd.utils.impulse_response` and :func:`~differt2d_amd.utils.field_misfit` apply unchanged."""
+        self.launch_material_response(params, fixed, inv_wavelengths, permittivity, polarization, amplitude)
+        return self.get_material_response()
+
+    def launch_material_response(self, params: L.Params, fixed, inv_wavelengths, permittivity, polarization="te", amplitude="sqrt"):
+        """The launch of :meth:`material_response` alone (asynchronous, like :meth:`launch`; the lists are copied by the call).  A
+        refused launch leaves the previous result readable."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        eps = np.asarray(permittivity)
+        if eps.ndim == 1:
+            eps = np.broadcast_to(eps, (max(int(inv.size), 1), eps.size))
+        if eps.ndim != 2 or eps.shape[0] != max(int(inv.size), 1):
+            raise L.D2DError(-1, f"material_response: permittivity must be complex [N] or [nf, N] with nf = {inv.size}, got shape {tuple(eps.shape)}")
+        eps = np.ascontiguousarray(eps, dtype=np.complex64)
+        amplitude = _amplitude_id("material_response", amplitude)
+        polarization = _polarization_id("material_response", polarization)
+        keep, table = _keep_pointer(inv, 1), _keep_pointer(eps.view(np.float32), 2)
+        L.check(self._lib.d2d_material_response_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size), amplitude,
+                                                       polarization, table.ctypes.data_as(C.c_void_p), int(eps.shape[1])))
+        self._mat_nf = int(inv.size)
+
+    def get_material_response(self) -> "FrequencyResponse":
+        """Synchronises and returns the result of the last :meth:`launch_material_response` that was accepted."""
+        if not self._mat_nf:
+            _no_result(self._ctx, self._lib.d2d_get_material_response, "launch_material_response", None, None, None)
+        shape = tuple(self.shape)
+        planes = (self._mat_nf,) + shape
+        fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
+        L.check(self._lib.d2d_get_material_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
         return fr
 
     def field_coefs_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt") -> np.ndarray:

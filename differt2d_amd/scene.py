@@ -1209,6 +1209,86 @@ class Scene(Plottable):
         return self._grid_response(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
                                    amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
 
+    def _permittivity_table(self, permittivity, nf: int) -> np.ndarray:
+        """The material response's table, complex64 ``[nf, N]`` or ``[N]``: ``permittivity`` as given, or with ``None`` every
+        object's ``permittivity`` attribute, a complex scalar or ``nf`` values (read the way ``r_coef`` is read from a
+        ``CoatedWall``).  ``ValueError`` names the first object that has none."""
+        n = len(self.objects)
+        if permittivity is not None:
+            eps = np.asarray(permittivity, dtype=np.complex64)
+            if eps.shape not in ((n,), (nf, n)):
+                raise ValueError(f"permittivity must be complex [{n}] (one value per object) or [{nf}, {n}] (a row per wavelength), "
+                                 f"got shape {tuple(eps.shape)}")
+            return eps
+        table = np.empty((nf, n), np.complex64)
+        for j, o in enumerate(self.objects):
+            if getattr(o, "permittivity", None) is None:
+                raise ValueError(f"object {j} ({type(o).__name__}) has no permittivity attribute: pass permittivity= or give every "
+                                 "object one")
+            e = np.asarray(o.permittivity, dtype=np.complex64).reshape(-1)
+            if e.size not in (1, nf):
+                raise ValueError(f"object {j} ({type(o).__name__}): permittivity must be a complex scalar or {nf} values (one per "
+                                 f"wavelength), got {e.size}")
+            table[:, j] = e
+        return table
+
+    def _grid_material(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, wavelengths, inv_wavelengths, permittivity, polarization,
+                       amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
+        """The two material-response sweeps: one launch of the material-response build per fixed end point."""
+        convert = self._inverse_wavelengths("the material response", wavelengths, inv_wavelengths)
+
+        def prepare():
+            inv = convert()
+            eps = self._permittivity_table(permittivity, int(inv.size))
+            return lambda ctx, params, _, xy: ctx.material_response(params, xy, inv, eps, polarization, amplitude)
+
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the material response comes from a fused sweep (a "
+            "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+            "records (Context.valid_paths: every valid path of every cell, with its length), their "
+            "points (Context.trace_paths) and add fun's phasors times the walls' Fresnel coefficients "
+            "(utils.fresnel_coefficient) on the host",
+            "the material response covers", prepare)
+
+    def material_response_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None,
+        permittivity=None, polarization: str = "te", amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0,
+        max_order: int = 1, order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The channel frequency response of every cell with Fresnel reflection per wall:
+        :meth:`frequency_response_on_receivers_grid` with every path's amplitude multiplied by the product of the complex
+        reflection coefficients of the walls it bounces off.  Each coefficient depends on the angle of incidence, on
+        ``polarization`` (``"te"``: E perpendicular to the plane of incidence -- vertical antennas over a floor plan, the default;
+        ``"tm"``: E in the plane of incidence, with its Brewster angle) and on the wall's complex relative permittivity
+        (include/d2d.h: d2d_material_response_launch; :func:`differt2d_amd.utils.fresnel_coefficient` is the formula).
+
+        ``permittivity``: complex ``[N]``, one value per object for the whole band, or ``[nf, N]``, a row per wavelength; with
+        ``None`` every object's ``permittivity`` attribute is read (a complex scalar or ``nf`` values; ``ValueError`` names the
+        first object without one).  The time convention is ``e^(-j 2 pi r / lambda)``: a lossy medium has ``Im eps <= 0``
+        (:func:`differt2d_amd.utils.complex_permittivity`).  Pass ``fun=received_power`` with ``r_coef=1``, or ``one``, so that
+        walls are not counted twice: the reflection loss is the coefficients'.  Wavelengths, ``amplitude``, the path class and
+        the validity as for :meth:`frequency_response_on_receivers_grid`; anything else raises :class:`D2DUnsupported`, and for
+        another callable :meth:`Context.valid_paths` / :meth:`Context.trace_paths` hold every valid path and its points for a sum
+        on the host.  Values only, one GPU: no gradients with respect to the permittivity or the geometry, no array or beam
+        variant, no transmission, finite slabs or roughness.
+
+        Yields ``(tx name, FrequencyResponse(re, im, total))``: ``re`` and ``im`` fp32 ``[nf, m, n]``, ``total`` fp32 ``[m, n]``,
+        the fused map bit for bit.  :func:`differt2d_amd.utils.frequency_response`, :func:`~differt2d_amd.utils.wideband_power`,
+        :func:`~differt2d_amd.utils.impulse_response` and :func:`~differt2d_amd.utils.field_misfit` apply unchanged."""
+        return self._grid_material(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                   permittivity, polarization, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def material_response_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping] = None, *, wavelengths=None, inv_wavelengths=None,
+        permittivity=None, polarization: str = "te", amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0,
+        max_order: int = 1, order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`material_response_on_receivers_grid`: one result per receiver, the transmitter sits at
+        ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_material(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
+                                   permittivity, polarization, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
     def _grid_response_coefs_vjp(self, X, Y, fixed_items, grid_is_rx, fun_kwargs, re_bar, im_bar, wavelengths, inv_wavelengths,
                                  amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
         """The two coefficient adjoints of the frequency response: one launch per fixed end point."""

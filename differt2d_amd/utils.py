@@ -180,6 +180,46 @@ def field_misfit(fr, target, weights=None):
     return loss, np.ascontiguousarray(w * dr, dtype=np.float32), np.ascontiguousarray(w * di, dtype=np.float32)
 
 
+VACUUM_PERMITTIVITY = 8.8541878128e-12  # F/m
+
+
+def complex_permittivity(eps_r, conductivity, frequency_hz):
+    """The complex relative permittivity of a material of real relative permittivity ``eps_r`` and conductivity ``sigma`` (S/m) at
+    ``frequency_hz``: ``eps_r - 1j * sigma / (2 pi f eps_0)`` with ``eps_0 = 8.8541878128e-12`` F/m.  The sign is the library's time
+    convention, ``e^(-j 2 pi r / lambda)``: loss is a NEGATIVE imaginary part, what ``Context.material_response`` takes.  The
+    arguments broadcast; complex128."""
+    f = np.asarray(frequency_hz, dtype=np.float64)
+    loss = np.asarray(conductivity, dtype=np.float64) / (2.0 * np.pi * f * VACUUM_PERMITTIVITY)
+    return np.asarray(eps_r, dtype=np.float64) - 1j * loss
+
+
+def fresnel_coefficient(eps, cos_theta, polarization="te"):
+    """The Fresnel reflection coefficient of a half space of complex relative permittivity ``eps`` (``Im eps <= 0`` for a lossy
+    medium: the library's time convention) seen from vacuum at the cosine ``cos_theta`` of the angle of incidence, in complex128:
+    the reference formula of ``Context.material_response`` (differt2d_amd/csrc/d2d_fresnel.hpp is its fp32 definition), and
+    what one plots.  With ``q = sqrt(eps - sin(theta)**2)``, the root with ``Im q <= 0`` (the wave that decays into the wall),
+
+    * ``"te"`` (E perpendicular to the plane of incidence): ``(cos - q) / (cos + q)``;
+    * ``"tm"`` (E in the plane of incidence): ``(eps cos - q) / (eps cos + q)``.
+
+    At normal incidence TE is ``(1 - sqrt(eps)) / (1 + sqrt(eps))`` and TM is its negative: the convention that measures TM's
+    field by its component along the wall, under which TM tends to +1 and TE to -1 as ``|eps|`` grows.  TM vanishes at the
+    Brewster angle, ``cos_theta = 1 / sqrt(1 + eps)`` for real ``eps``; both tend to -1 at grazing incidence.  The arguments
+    broadcast."""
+    pol = str(polarization).lower()
+    if pol not in ("te", "tm"):
+        raise ValueError(f"polarization must be 'te' or 'tm', got {polarization!r}")
+    eps = np.asarray(eps, dtype=np.complex128)
+    c = np.minimum(np.asarray(cos_theta, dtype=np.float64), 1.0)
+    q = np.sqrt((eps - 1.0) + c * c)
+    # the decaying branch, Im q <= 0: the principal root has it for Im eps <= 0, except +j|q| for a real eps below sin^2 with Im = +0
+    q = np.where(q.imag > 0.0, -q, q)
+    a = eps * c if pol == "tm" else c + 0j
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = (a - q) / (a + q)
+    return np.where(a + q == 0, -1.0 + 0j, g)
+
+
 class AngularStatistics(NamedTuple):
     """Result of :func:`angular_statistics`: float64 ``[m, n]`` each."""
 

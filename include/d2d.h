@@ -30,9 +30,10 @@ extern "C" {
                               d2d_get_strongest_paths, d2d_coherent_field_launch / d2d_get_coherent_field,
                               d2d_frequency_response_launch / d2d_get_frequency_response and d2d_power_angle_launch /
                               d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response,
-                              d2d_array_frequency_response_launch / d2d_get_array_frequency_response and
-                              d2d_beam_response_launch / d2d_get_beam_response are additive: no struct, enum or
-                              existing entry point changed with them, so the version did not) */
+                              d2d_array_frequency_response_launch / d2d_get_array_frequency_response,
+                              d2d_beam_response_launch / d2d_get_beam_response and d2d_material_response_launch /
+                              d2d_get_material_response are additive: no struct, enum or existing entry point changed
+                              with them, so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -957,6 +958,81 @@ int d2d_get_beam_response(d2d_ctx* ctx, int32_t first, int32_t count, float* re 
  * 0 / 1 with ux[i], uy[i], and f[i] = steer_phase(f0[i], qt[i], qr[i], inv[i]). */
 int d2d_selftest_steer(d2d_ctx* ctx, const float* dx, const float* dy, const float* f0, const float* qt, const float* qr,
                        const float* inv, int64_t n, float* ux, float* uy, float* ok, float* f);
+
+/* ---- material response: the frequency response with Fresnel reflection per wall ------------------------------------------------
+ *
+ * d2d_frequency_response_launch with every contribution multiplied by the product of the complex Fresnel reflection coefficients of
+ * the walls it bounces off: the coefficient depends on the angle of incidence, the polarisation and the wall's complex relative
+ * permittivity, goes through zero at the Brewster angle (TM), tends to -1 at grazing incidence and carries a phase of its own where
+ * the material is lossy.  One preparation of the culled sweep, one pass per chunk of wavelengths.
+ *
+ * - `params`, `fixed`, the grid role, `inv_wavelength[nf]` (`1..D2D_FREQ_MAX`, each finite and `>= 0`) and `amplitude` are as for
+ *   d2d_frequency_response_launch.  Pass a path function that holds no reflection loss of its own (D2D_FUN_RECEIVED_POWER with
+ *   r_coef = 1, or D2D_FUN_ONE), so that walls are not counted twice.
+ * - `polarization`: D2D_POL_TE (E perpendicular to the plane of incidence; for vertical antennas over a 2-D floor plan E out of the
+ *   plane, the natural case here) or D2D_POL_TM (E in the plane of incidence).
+ * - `eps[nf][n_objects][2]`: fp32 (re, im) of the complex relative permittivity of every object at every wavelength.  The time
+ *   convention is the library's, e^(-j 2 pi r / lambda): a lossy medium is eps = eps' - j eps'', so Im eps <= 0.  `n_objects` is
+ *   the resident scene's.  Rows that are all equal in bits (one permittivity for the whole band, the common case) are detected and
+ *   the product of coefficients is then formed once per contribution: the same bits by definition.
+ *
+ * The coefficient (differt2d_amd/csrc/d2d_fresnel.hpp is the definition; fp32, one rounding per operation, IEEE sqrt and division):
+ *
+ *   fresnel(er, ei, c, pol) -> (gr, gi)
+ *       if (c > 1) c = 1                                              // a NaN c stays NaN and gives (NaN, NaN)
+ *       wr = (er - 1) + c*c ; wi = ei                                 // w = eps - sin^2(theta), without forming sin^2
+ *       m  = sqrtf(wr*wr + wi*wi)
+ *       if (m == 0)        q = (0, 0)                                 // q = sqrt(w), the branch with Im q <= 0 (the decaying one)
+ *       else if (wr >= 0)  qr = sqrtf(0.5f*(m + wr)) ; qi = wi / (2.0f*qr)
+ *       else               qi = -sqrtf(0.5f*(m - wr)) ; qr = wi / (2.0f*qi)      // also for ei = +-0: total reflection, |G| = 1
+ *       TE: a = (c, 0)            TM: a = (er*c, ei*c)
+ *       n = a - q ; d = a + q ; den = d.re*d.re + d.im*d.im
+ *       if (den == 0)      (gr, gi) = (-1, 0)                         // the grazing limit
+ *       else               gr = (n.re*d.re + n.im*d.im) / den ; gi = (n.im*d.re - n.re*d.im) / den
+ *
+ * Per cell, candidates in the sweep's enumeration order, p[0] = TX and p[K+1] = RX in both grid roles, walls cand[0..K):
+ *
+ *   total = +0.0f ; re[f] = im[f] = +0.0f
+ *   for candidates:
+ *       t = valid * fun ; r = path_length(points)          // as d2d_frequency_response_launch gets them
+ *       total = total + t                                   // the fused map, bit for bit
+ *       if (t == 0) continue
+ *       a = amplitude == SQRT ? copysignf(sqrtf(fabsf(t)), t) : t
+ *       for i < K:  (ux, uy, ok_i) = unit_dir(p[i+1] - p[i])                 // d2d_steer.hpp
+ *                   (nx, ny) = unit normal of wall cand[i]                   // normalize((t_y, -t_x)) of t = dest - origin, fp32
+ *                   c_i = fabsf(ux*nx + uy*ny)                                // cos of the angle of incidence
+ *       if (any !ok_i or any c_i is NaN) continue           // no incidence angle: the path enters no plane (total has it)
+ *       for f < nf:
+ *           G = (1, +0) ; for i < K in order:  g = fresnel(eps[f][cand[i]], c_i, polarization)
+ *                                              G = (G.re*g.re - G.im*g.im, G.re*g.im + G.im*g.re)
+ *           u = r * inv_wavelength[f] ; f0 = u - floorf(u) ; (c0, s0) = phasor(f0)
+ *           zr = G.re*c0 + G.im*s0 ; zs = G.re*s0 - G.im*c0                  // G e^(-j 2 pi f0) = zr - j zs
+ *           re[f] = re[f] + a*zr ; im[f] = im[f] - a*zs
+ *
+ * `total` is the fused map bit for bit.  Plane f depends on inv_wavelength[f] and row f of eps alone; the eps of a wall that no
+ * contributing candidate touches does not matter.  With max_order = 0 the planes are d2d_frequency_response_launch's bit for bit
+ * wherever no contribution is NaN.  Values only, one GPU: no gradients with respect to eps or the geometry, no array or beam variant,
+ * no transmission through walls, no slabs of finite thickness, no roughness; RIS objects reflect like walls of their permittivity.
+ *
+ * D2D_ERR_INVALID: what d2d_frequency_response_launch refuses of the list and the amplitude; a polarization other than 0 / 1; an
+ * n_objects that is not the resident scene's; an eps component that is NaN, infinite or above 2^50 in magnitude, or Im eps > 0 (the
+ * message ends with the wavelength index and the wall index).
+ * D2D_ERR_UNSUPPORTED (the message names the reason): what d2d_frequency_response_launch refuses (sigmoid validity, MinPath /
+ * FermatPath, D2D_OUT_ADD, a function that is not fused -- the message names d2d_valid_paths and d2d_trace_paths --, a TX grid
+ * whose sweep is not culled), with outputs of 8 * nf + 4 bytes per cell plus 8 * nf * n_objects bytes for the table held against
+ * half of the free device memory -- all decided before anything is enqueued.  A refused launch leaves the previous result as it was. */
+#define D2D_POL_TE 0
+#define D2D_POL_TM 1
+int d2d_material_response_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                                 const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude, int32_t polarization,
+                                 const float* eps /* [nf][n_objects][2]: (re, im) */, int32_t n_objects);
+/* Synchronises and copies the result of the last d2d_material_response_launch that was accepted to the arrays that are not NULL
+ * (re, im: [nf][m][n]; total: [m][n]).  D2D_ERR_STATE before a launch, after a d2d_set_grid of another grid and after a
+ * d2d_set_scene of another scene (the result goes with the grid and the walls). */
+int d2d_get_material_response(d2d_ctx* ctx, float* re /* [nf][m][n] or NULL */, float* im /* same */, float* total /* [m][n] or NULL */);
+
+/* fresnel of d2d_fresnel.hpp on the device, for comparison with its host build: (gr[i], gi[i]) = fresnel(er[i], ei[i], c[i], pol). */
+int d2d_selftest_fresnel(d2d_ctx* ctx, const float* er, const float* ei, const float* c, int32_t pol, int64_t n, float* gr, float* gi);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
