@@ -164,6 +164,10 @@ SYMBOLS = [
     ("d2d_material_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     ("d2d_get_material_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_selftest_fresnel", C.c_int, [_ctx, _f32p, _f32p, _f32p, C.c_int32, C.c_int64, _f32p, _f32p]),
+    ("d2d_material_eps_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p]),
+    ("d2d_get_material_eps_vjp", C.c_int, [_ctx, C.c_void_p]),
+    ("d2d_selftest_fresnel_grad", C.c_int, [_ctx, _f32p, _f32p, _f32p, C.c_int32, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p]),
     ("d2d_frequency_response_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32]),
     ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_field_coefs_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

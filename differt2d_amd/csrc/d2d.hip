@@ -256,8 +256,20 @@ struct d2d_ctx {
         void forget() { nf = 0; }
         void drop() { out.release(); eps.release(); forget(); }
     } mat;
+    // permittivity adjoint of the material response (d2d_material_eps_vjp_launch): the cotangent planes, the permittivity table,
+    // one chunk's per-patch rows and the reduced result, kept until the next accepted launch; the scene forgets it too
+    struct EpsGrad {
+        DevBuf<float> re, im;    // [nf][m][n] each: the caller's cotangents
+        DevBuf<float> eps;       // [nf][N][2]: the permittivity table of the launch in flight
+        DevBuf<float> partial;   // [patches][MAT_CHUNK][N][2]
+        DevBuf<double> out;      // [nf][N][2]
+        int32_t nf = 0;          // rows of the last accepted launch for the CURRENT grid and scene; 0: no result
+        size_t bytes() const { return (re.n + im.n + eps.n + partial.n) * sizeof(float) + out.n * sizeof(double); }
+        void forget() { nf = 0; }
+        void drop() { re.release(); im.release(); eps.release(); partial.release(); out.release(); forget(); }
+    } eg;
     void drop_products() {  // every one of them goes with the grid
-        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop();
+        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop(); eg.drop();
     }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -808,6 +820,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->have_vjp = false;          // d_vjp was sized for (and computed from) the previous scene
     c->cg.forget();               // (... and so was the frequency response's coefficient adjoint)
     c->mat.forget();              // (... and the material response, whose table has one entry per wall)
+    c->eg.forget();               // (... and its permittivity adjoint)
     c->have_kernel_time = false;
     c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
@@ -2305,6 +2318,7 @@ constexpr SinkProduct ANGLE = {"d2d_power_angle_launch", "a host function's prof
 constexpr SinkProduct ARRAY = {"d2d_array_response_launch", "a host function's channel matrix: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrix is always overwritten", LATE};
 constexpr SinkProduct WIDE = {"d2d_array_frequency_response_launch", "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrices are always overwritten", LATE};
 constexpr SinkProduct MATERIAL = {"d2d_material_response_launch", "a host function's response: add the phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths, each times its walls' Fresnel coefficients", "the response is always overwritten", LATE};
+constexpr SinkProduct EPS_VJP = {"d2d_material_eps_vjp_launch", "a host function has no permittivities", "the gradient is always overwritten", LATE};
 constexpr SinkProduct BEAM = {"d2d_beam_response_launch", "a host function's beam response: add the beamformed phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the beam response is always overwritten", LATE};
 
 // What the products refuse of the caller's parameters before prep_sink_sweep's share.
@@ -2850,6 +2864,71 @@ int d2d_get_material_response(d2d_ctx* c, float* re, float* im, float* total) {
     return copy_out(c, {{re, o.re.p, bytes * (size_t)c->mat.nf}, {im, o.im.p, bytes * (size_t)c->mat.nf}, {total, o.total.p, bytes}});
 }
 
+// Permittivity adjoint of the material response: d2d_material_response_launch's front half (the same parameter checks, the table
+// copied during the call) and d2d_field_coefs_vjp_launch's back half (the cotangents copied before the call returns, per-patch rows,
+// the fixed-order fp64 reduction).  Per chunk of MAT_CHUNK wavelengths: zero the rows, one pass, one reduction of the chunk's
+// count * N * 2 entries (the rows keep the stride of a full chunk) into the chunk's rows of the result.  Any fused fun: the
+// amplitude does not depend on eps.
+int d2d_material_eps_vjp_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                                int32_t polarization, const float* eps, int32_t n_objects, const float* re_bar, const float* im_bar) {
+    if (!c || !fixed || !inv_wavelength || !eps || !re_bar || !im_bar) return fail(D2D_ERR_INVALID, "NULL argument");
+    SinkLaunch<d2d_ctx::EpsGrad> L(c, EPS_VJP, c->eg, fixed);
+    d2d_ctx::EpsGrad& r = c->eg;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p))) return rc;
+    if ((rc = d2d_host::material_params(inv_wavelength, nf, amplitude, polarization, eps, n_objects, c->N, err))) return fail(rc, "%s: %s", EPS_VJP.who, err.c_str());
+    if ((rc = L.device())) return rc;
+    const size_t cells = L.cells, N = (size_t)n_objects, tiles = (size_t)L.s.tiles;
+    if (!d2d_host::eps_vjp_fits(cells, nf, tiles, N, L.mem_free, r.bytes()))
+        return fail(D2D_ERR_UNSUPPORTED, "%s: cotangents of %zu cells (%zu bytes per cell), a table and a result of %zu bytes and %zu rows of %zu partial sums exceed half of the free device memory (%zu bytes free)",
+                    EPS_VJP.who, cells, 8 * (size_t)nf, 24 * (size_t)nf * N, tiles, (size_t)d2d::MAT_CHUNK * 2 * N, L.mem_free);
+    if ((rc = L.prepare())) return rc;
+    const size_t planes = (size_t)nf * cells, table = 2 * (size_t)nf * N, chunk_row = (size_t)d2d::MAT_CHUNK * 2 * N;
+    if ((rc = r.re.ensure(planes)) || (rc = r.im.ensure(planes)) || (rc = r.eps.ensure(table + 2)) || (rc = r.partial.ensure(tiles * chunk_row)) ||
+        (rc = r.out.ensure(table)))
+        return rc;
+    const bool constant = d2d_host::material_constant_band(eps, nf, n_objects);
+    HIP_TRY(hipMemcpyAsync(r.re.p, re_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.im.p, im_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (table > 0) HIP_TRY(hipMemcpyAsync(r.eps.p, eps, table * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays are free again when the call returns
+    if (N > 0 && tiles > 0) {
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::MAT_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::MAT_CHUNK);
+            d2d::EpsGradArgs g = {};
+            g.re_bar = r.re.p + (size_t)ch.first * cells;
+            g.im_bar = r.im.p + (size_t)ch.first * cells;
+            g.eps = r.eps.p + (size_t)ch.first * 2 * N;
+            g.refl = c->d_refl.p;
+            g.partial = r.partial.p;
+            g.cells = (long)cells;
+            for (int32_t j = 0; j < ch.count; ++j) g.inv[j] = inv_wavelength[ch.first + j];
+            g.nf = ch.count;
+            g.N = n_objects;
+            g.amplitude = amplitude;
+            g.pol = polarization;
+            g.constant = constant ? 1 : 0;
+            HIP_TRY(hipMemsetAsync(r.partial.p, 0, tiles * chunk_row * sizeof(float), c->stream));
+            HIP_TRY(L.pass<d2d::EpsGradSink>(g));
+            // (n_elem is the stride between rows: a full chunk's, whatever this chunk's count)
+            hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)((size_t)ch.count * 2 * N)), dim3(256), 0, c->stream, r.partial.p, (long)tiles, (int)chunk_row,
+                               r.out.p + (size_t)ch.first * 2 * N, 0);
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        HIP_TRY(hipMemsetAsync(r.out.p, 0, (table ? table : 1) * sizeof(double), c->stream));
+    }
+    r.nf = nf;
+    return D2D_OK;
+}
+
+int d2d_get_material_eps_vjp(d2d_ctx* c, double* eps_bar) {
+    if (int rc = result_state(c, c && c->have_scene && c->eg.nf >= 1 && c->eg.out.p, EPS_VJP, "result goes with the grid and the scene")) return rc;
+    if (!eps_bar) return fail(D2D_ERR_INVALID, "eps_bar is NULL");
+    return copy_out(c, {{eps_bar, c->eg.out.p, (size_t)c->eg.nf * 2 * (size_t)c->N * sizeof(double)}});
+}
+
 int d2d_valid_paths(d2d_ctx* c, const d2d_params* p, const float* fixed, int64_t* count) { return valid_paths(c, p, fixed, count); }
 
 int d2d_get_valid_paths(d2d_ctx* c, int64_t capacity, int32_t* cell, int32_t* cand, int32_t* order, float* xys, float* loss, float* valid,
@@ -3050,6 +3129,23 @@ int d2d_selftest_fresnel(d2d_ctx* c, const float* er, const float* ei, const flo
     HIP_TRY(hipStreamSynchronize(c->stream));
     float* out[2] = {gr, gi};
     for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_fresnel_grad(d2d_ctx* c, const float* er, const float* ei, const float* cs, int32_t pol, int64_t n, float* gr, float* gi, float* dr, float* di,
+                              float* ok) {
+    if (!c || !er || !ei || !cs || !gr || !gi || !dr || !di || !ok || n <= 0 || (pol != D2D_POL_TE && pol != D2D_POL_TM)) return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> din, dout;  // three inputs, five outputs, n each
+    if ((rc = din.ensure(3 * (size_t)n)) || (rc = dout.ensure(5 * (size_t)n))) return rc;
+    const float* in[3] = {er, ei, cs};
+    for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpy(din.p + (size_t)k * (size_t)n, in[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_fresnel_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, din.p, dout.p, (int)pol, (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float* out[5] = {gr, gi, dr, di, ok};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }
 

@@ -377,6 +377,27 @@ inline bool coef_vjp_fits(size_t cells, int32_t nf, size_t patches, size_t n_obj
     return n_objects <= budget / sizeof(float) / patches;
 }
 
+// ---- memory of the material response's permittivity adjoint (d2d_material_eps_vjp_launch, d2d::EpsGradSink) ------------
+// The cotangent planes take 8 nf bytes per cell, the permittivity table 8 nf bytes per object, the partial rows of one chunk
+// 4 * MAT_CHUNK * 2 bytes per patch and object and the fp64 result 16 nf bytes per object.  Refused like its siblings: above half of
+// the device memory that is free, counting what the buffers hold already as free.  No product is formed that could wrap: each share
+// is held against a quotient of what the budget has left.  (The parameters are material_params', the chunks MAT_CHUNK's.)
+inline bool eps_vjp_fits(size_t cells, int32_t nf, size_t patches, size_t n_objects, size_t mem_free, size_t held_bytes) {
+    if (nf < 1) return false;
+    size_t budget = mem_free / 2 + held_bytes / 2;
+    const size_t per_cell = 8 * (size_t)nf;
+    if (cells > budget / per_cell) return false;
+    budget -= cells * per_cell;
+    if (n_objects == 0) return true;
+    const size_t per_object = 8 * (size_t)nf + 16 * (size_t)nf;  // the table and the result
+    if (n_objects > budget / per_object) return false;
+    budget -= n_objects * per_object;
+    if (patches == 0) return true;
+    const size_t per_row = sizeof(float) * (size_t)MAT_CHUNK * 2;  // one patch's partial sums of one object
+    if (patches > budget / per_row) return false;
+    return n_objects <= budget / per_row / patches;
+}
+
 // ---- parameters and outputs of the power-angle profile (d2d_power_angle_launch, d2d::AngleSink) ---------------------
 // D2D_ERR_INVALID: an end that is neither D2D_ANGLE_AT_TX nor D2D_ANGLE_AT_RX, an origin that is NaN or outside [0, 1) turns,
 // nbins outside 1 .. D2D_ANGLE_BINS_MAX.

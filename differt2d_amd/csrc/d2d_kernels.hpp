@@ -39,6 +39,7 @@
 #include "d2d_steer.hpp"
 #include "d2d_beam.hpp"
 #include "d2d_fresnel.hpp"
+#include "d2d_fresnel_grad.hpp"
 
 namespace d2d {
 
@@ -2662,6 +2663,148 @@ struct MaterialSink {
     }
 };
 
+// EpsGradSink (d2d_material_eps_vjp_launch): the reverse-mode product of the material response with respect to the walls'
+// permittivities, for up to MAT_CHUNK wavelengths of one sweep (include/d2d.h holds the definition, d2d_fresnel_grad.hpp the
+// coefficient's derivative).  It is MaterialSink's front (the walls out of the wave-uniform code, normals and permittivities read
+// at wave-uniform addresses, the cosines per lane from seg_out) joined to CoefGradSink's back (cotangents in registers, zero for
+// lanes outside the grid; weights forced to 0.0f in lanes that do not contribute; wave_sum in wave-uniform control flow; lane 0 adds
+// to the patch's rows with a plain load-add-store: one writer per row, candidates in order, no atomics).  Per lane and j < nf, for
+// every position i < k:
+//     (g_i, d_i, ok_i) = fresnel_grad(eps[j][w_i], c_i, pol) ;  P_i = (1, +0) folded with g_o for o != i in position order
+//     Pd_i = P_i * d_i ;  E = (a*c0, -(a*s0)) ;  D = E * Pd_i ;  Wr = B.re*D.re + B.im*D.im ;  Wi = B.im*D.re - B.re*D.im
+// in fp32 without contraction (complex products as fresnel_fold forms them), and partial[tile][j][w_i][0..1] += wave_sum(Wr), wave_sum(Wi).
+// With `constant` set g_i, d_i and Pd_i are formed once per contribution from row 0, in front of the loop over j: the same values, so
+// the rows are bit-identical to the per-row route.  i and j are compile-time indices behind the wave-uniform guards i < k and j < nf.
+// The host zeroes the rows in front of every chunk's pass and reduces them in patch order into fp64 (vjp_reduce_kernel).
+struct EpsGradArgs {
+    const float* re_bar;   // [nf][cells]: this chunk's cotangent planes
+    const float* im_bar;   // [nf][cells]
+    const float* eps;      // device memory, [nf][N][2]: this chunk's rows of (re, im); row 0 alone is read when `constant`
+    const float4* refl;    // the context's wall table: row 2 w = {ox, oy, nx, ny}
+    float* partial;        // [tiles][MAT_CHUNK][N][2] per-patch sums, zeroed in front of the pass
+    long cells;            // m * n
+    float inv[MAT_CHUNK];  // turns per unit length, finite and >= 0; entries at and past nf are not read
+    int nf;                // 1 .. MAT_CHUNK
+    int N;                 // objects: the length of a row of eps
+    int amplitude;         // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int pol;               // D2D_POL_TE / D2D_POL_TM
+    int constant;          // != 0: every row of eps equals row 0 in bits
+};
+static_assert(sizeof(SweepArgs) + sizeof(EpsGradArgs) <= 4096, "power_sink_kernel's arguments must fit the 4 KiB kernel-argument segment");
+struct EpsGradSink {
+    using Args = EpsGradArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = false;
+    static constexpr bool WANTS_SEG = true;
+    float rb[MAT_CHUNK], ib[MAT_CHUNK];
+    const EpsGradArgs* x;  // the kernel argument: wave-uniform, read where it is used
+    float* row;            // partial[tile]
+    bool live;             // cell >= 0
+    __device__ __forceinline__ void begin(const EpsGradArgs& xa, long tile, int lane_cell) {
+        live = lane_cell >= 0;
+        static_for<0, MAT_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            rb[J] = ib[J] = 0.0f;
+            if (J < xa.nf && live) {
+                const size_t at = (size_t)J * (size_t)xa.cells + (size_t)lane_cell;
+                rb[J] = xa.re_bar[at];
+                ib[J] = xa.im_bar[at];
+            }
+        });
+        x = &xa;
+        row = xa.partial + (size_t)tile * (size_t)MAT_CHUNK * 2 * (size_t)xa.N;
+    }
+    // Pd_i = (product of the OTHER positions' coefficients) * d_i and ok_i for every position of the candidate, from one row of eps
+    __device__ __forceinline__ void factors(const float* erow, const int (&w)[D2D_MAX_ORDER], const float (&ci)[D2D_MAX_ORDER], int k, int pol,
+                                            float (&Pdr)[D2D_MAX_ORDER], float (&Pdi)[D2D_MAX_ORDER], bool (&okd)[D2D_MAX_ORDER]) const {
+        float gr[D2D_MAX_ORDER], gi[D2D_MAX_ORDER], dr[D2D_MAX_ORDER], di[D2D_MAX_ORDER];
+        static_for<0, D2D_MAX_ORDER>([&](auto II) {
+            constexpr int I = decltype(II)::value;
+            gr[I] = 1.0f;
+            gi[I] = dr[I] = di[I] = 0.0f;
+            okd[I] = false;
+            if (I < k) {
+                const float er = cmem(erow)[2 * w[I]], ei = cmem(erow)[2 * w[I] + 1];
+                fresnel_grad(er, ei, ci[I], pol, gr[I], gi[I], dr[I], di[I], okd[I]);
+            }
+        });
+        static_for<0, D2D_MAX_ORDER>([&](auto II) {
+            constexpr int I = decltype(II)::value;
+            Pdr[I] = Pdi[I] = 0.0f;
+            if (I < k) {
+                float Pr = 1.0f, Pi = 0.0f;
+                static_for<0, D2D_MAX_ORDER>([&](auto OO) {
+                    constexpr int O = decltype(OO)::value;
+                    if (O != I && O < k) fresnel_fold(Pr, Pi, gr[O], gi[O]);
+                });
+                fresnel_fold(Pr, Pi, dr[I], di[I]);
+                Pdr[I] = Pr;
+                Pdi[I] = Pi;
+            }
+        });
+    }
+    // seg: (p[i+1] - p[i]) for i < k of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_seg(float t, unsigned long long code, int k, float r, const float (&seg)[2 * D2D_MAX_ORDER]) {
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (k == 0 || __ballot(p) == 0ull) return;  // wave-uniform (the line of sight holds no coefficient)
+        int w[D2D_MAX_ORDER];
+        float ci[D2D_MAX_ORDER];
+        bool ok = true;
+        static_for<0, D2D_MAX_ORDER>([&](auto II) {
+            constexpr int I = decltype(II)::value;
+            w[I] = 0;
+            ci[I] = 0.0f;
+            if (I < k) {
+                w[I] = __builtin_amdgcn_readfirstlane((int)((code >> (12 * I)) & 0xfffull));
+                const float4 n = ldc4(x->refl, 2 * w[I]);
+                float ux, uy;
+                const bool oki = unit_dir(seg[2 * I], seg[2 * I + 1], ux, uy);
+                const float c = fabsf(steer_dot(ux, uy, n.z, n.w));
+                ci[I] = c;
+                ok = ok && oki && c == c;
+            }
+        });
+        const bool go = p && ok && live;  // (per lane: it becomes zero weights, never an exit)
+        const float a = x->amplitude == D2D_FIELD_AMP_SQRT ? copysignf(sqrtf(fabsf(t)), t) : t;
+        const int nf = x->nf, pol = x->pol;
+        const bool constant = x->constant != 0;
+        const size_t stride = 2 * (size_t)x->N;
+        const bool lane0 = (threadIdx.x & 63) == 0;
+        float Pdr[D2D_MAX_ORDER], Pdi[D2D_MAX_ORDER];
+        bool okd[D2D_MAX_ORDER];
+        if (constant) factors(x->eps, w, ci, k, pol, Pdr, Pdi, okd);
+        static_for<0, MAT_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            if (J < nf) {
+                if (!constant) factors(x->eps + (size_t)J * stride, w, ci, k, pol, Pdr, Pdi, okd);
+                const float u = r * x->inv[J];
+                const float f0 = u - floorf(u);
+                float c0, s0;
+                phasor(f0, c0, s0);
+                const float Er = a * c0, Ei = -(a * s0);
+                float* const out = row + (size_t)J * stride;
+                static_for<0, D2D_MAX_ORDER>([&](auto II) {
+                    constexpr int I = decltype(II)::value;
+                    if (I < k) {
+                        float Dr = Er, Di = Ei;
+                        fresnel_fold(Dr, Di, Pdr[I], Pdi[I]);
+                        const float b0 = rb[J] * Dr, b1 = ib[J] * Di, b2 = ib[J] * Dr, b3 = rb[J] * Di;
+                        const bool on = go && okd[I];
+                        const float Wr = on ? b0 + b1 : 0.0f;
+                        const float Wi = on ? b2 - b3 : 0.0f;
+                        const float Sr = wave_sum(Wr), Si = wave_sum(Wi);  // every lane of the wave is here: the exits above are wave-uniform
+                        if (lane0) {
+                            out[2 * w[I]] = out[2 * w[I]] + Sr;
+                            out[2 * w[I] + 1] = out[2 * w[I] + 1] + Si;
+                        }
+                    }
+                });
+            }
+        });
+    }
+    __device__ __forceinline__ void end(const EpsGradArgs&, long, int) const {}
+};
+
 // One candidate into a sink: a WANTS_SEG sink takes put_seg (the contribution, the candidate's code and order, the length and the
 // segments that reach its bounces), a sink that wants both the length and the directions takes put_rd, a WANTS_DIR sink the
 // contribution with the path's end directions, every other one the contribution with the candidate's code, order and length
@@ -4694,6 +4837,21 @@ __global__ void selftest_fresnel_kernel(const float* __restrict__ in, float* __r
     out[n + i] = gi;
 }
 
+// fresnel_grad (d2d_fresnel_grad.hpp) on the device, for comparison with its host build (tests/test_gpu_material_eps_vjp.py):
+// in = er, ei, c and out = gr, gi, dr, di, ok (1 or 0), n values each
+__global__ void selftest_fresnel_grad_kernel(const float* __restrict__ in, float* __restrict__ out, int pol, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float gr, gi, dr, di;
+    bool ok;
+    fresnel_grad(in[i], in[n + i], in[2 * n + i], pol, gr, gi, dr, di, ok);
+    out[i] = gr;
+    out[n + i] = gi;
+    out[2 * n + i] = dr;
+    out[3 * n + i] = di;
+    out[4 * n + i] = ok ? 1.0f : 0.0f;
+}
+
 // Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per
 // (wall w, blocker j) pair rasterises, into 64 bins of w's parametric range, where the segment e -> p is CERTAINLY
 // reported as intersecting j by the exact path (hard: hit; approx: the four activations exactly saturated), for every
@@ -4971,7 +5129,8 @@ __global__ void __launch_bounds__(64) power_vg_kernel(SweepArgs a) {
 }
 
 #ifdef D2D_AUX_KERNELS  // non-template kernels: defined once, in d2d.hip
-// Fixed-order reduction of the per-wave partials: out[e] (+)= sum_w partial[w][e], accumulated in fp64.
+// Fixed-order reduction of the per-wave partials: out[e] (+)= sum_w partial[w][e], accumulated in fp64.  n_elem is the stride
+// between rows; one block per entry, so a launch of fewer blocks reduces the leading entries of every row (d2d_material_eps_vjp_launch).
 __global__ void __launch_bounds__(256) vjp_reduce_kernel(const float* __restrict__ partial, long n_waves, int n_elem,
                                                          double* __restrict__ out, int accumulate) {
     __shared__ double sm[256];

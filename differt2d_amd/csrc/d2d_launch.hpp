@@ -49,7 +49,8 @@ D2D_DECLARE_MODE(MODE_SIG)
     X(ArraySink)     /* the array response */                                                                 \
     X(ArrayFreqSink) /* the wideband array response */                                                        \
     X(BeamSink)      /* the beam-space response */                                                            \
-    X(MaterialSink)  /* the frequency response with Fresnel reflection per wall */
+    X(MaterialSink)  /* the frequency response with Fresnel reflection per wall */                           \
+    X(EpsGradSink)   /* its adjoint w.r.t. the walls' permittivities */
 #define D2D_DECLARE_SINK(S)                                                                                                      \
     template <> hipError_t launch_sink_m<MODE_HARD, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&); \
     template <> hipError_t launch_sink_m<MODE_HSIG, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&);

@@ -199,6 +199,7 @@ class Context:
         self._wide_shape = None  # (nf, nr, nt) of the last launch_array_frequency_response that was accepted
         self._beam_shape = None  # (nf, nbr, nbt) of the last launch_beam_response that was accepted
         self._mat_nf = 0  # planes of the last launch_material_response that was accepted
+        self._eps_vjp_nf = 0  # rows of the last launch_material_eps_vjp that was accepted
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -508,6 +509,16 @@ class Context:
         L.check(self._lib.d2d_selftest_fresnel(self._ctx, *a, _polarization_id("selftest_fresnel", polarization), a[0].size, gr, gi))
         return gr, gi
 
+    def selftest_fresnel_grad(self, er, ei, c, polarization="te"):
+        """``fresnel_grad(er, ei, c, polarization)`` as the permittivity adjoint computes it on the device (include/d2d.h: must
+        equal the host build of d2d_fresnel_grad.hpp bit for bit).  Returns ``(gr, gi, dr, di, ok)``, ``ok`` as bool."""
+        a = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (er, ei, c)]
+        if any(v.size != a[0].size for v in a):
+            raise ValueError("the three inputs must have one size")
+        gr, gi, dr, di, ok = (np.empty_like(a[0]) for _ in range(5))
+        L.check(self._lib.d2d_selftest_fresnel_grad(self._ctx, *a, _polarization_id("selftest_fresnel_grad", polarization), a[0].size, gr, gi, dr, di, ok))
+        return gr, gi, dr, di, ok != 0.0
+
     def get_map(self) -> np.ndarray:
         out = np.empty(self.shape, np.float32)
         L.check(self._lib.d2d_get_map(self._ctx, out))
@@ -812,6 +823,61 @@ class Context:
         fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
         L.check(self._lib.d2d_get_material_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
         return fr
+
+    def material_eps_vjp(self, params: L.Params, fixed, inv_wavelengths, permittivity, re_bar, im_bar, polarization="te",
+                         amplitude="sqrt") -> np.ndarray:
+        """The reverse-mode product of :meth:`material_response` with respect to the walls' permittivities: ``eps_bar[f, w] =
+        dL/dRe eps[f, w] + 1j * dL/dIm eps[f, w]`` for ``dL = sum (re_bar * d re + im_bar * d im)``, complex128 ``[nf, N]``, from
+        ONE preparation of the culled sweep and, per 8 wavelengths, one kernel pass and one fixed-order fp64 reduction
+        (include/d2d.h: d2d_material_eps_vjp_launch holds the definition, differt2d_amd/csrc/d2d_fresnel_grad.hpp the derivative
+        of the coefficient).  ``eps - rate * eps_bar`` is a step of gradient descent.
+
+        ``params``, ``fixed``, ``inv_wavelengths``, ``permittivity``, ``polarization`` and ``amplitude`` are
+        :meth:`material_response`'s, refused alike; a ``permittivity`` of shape ``[N]`` stands for equal rows and the result still
+        has a row per wavelength (sum them for the gradient of the one value).  ``re_bar`` and ``im_bar`` are the cotangents of
+        the planes, ``[nf, m, n]`` (taken as fp32, copied by the call; non-finite values propagate):
+        :func:`differt2d_amd.utils.field_misfit` gives them for a least-squares fit.  Walls that no contributing path touches
+        get exactly ``+0.0``.  The same bits run to run.  A refused launch leaves the previous result readable; no other
+        product's result is touched."""
+        self.launch_material_eps_vjp(params, fixed, inv_wavelengths, permittivity, re_bar, im_bar, polarization, amplitude)
+        return self.get_material_eps_vjp()
+
+    def launch_material_eps_vjp(self, params: L.Params, fixed, inv_wavelengths, permittivity, re_bar, im_bar, polarization="te",
+                                amplitude="sqrt"):
+        """The launch of :meth:`material_eps_vjp` alone (the lists and the cotangents are copied by the call; the kernels are
+        asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        eps = np.asarray(permittivity)
+        if eps.ndim == 1:
+            eps = np.broadcast_to(eps, (max(int(inv.size), 1), eps.size))
+        if eps.ndim != 2 or eps.shape[0] != max(int(inv.size), 1):
+            raise L.D2DError(-1, f"material_eps_vjp: permittivity must be complex [N] or [nf, N] with nf = {inv.size}, got shape {tuple(eps.shape)}")
+        eps = np.ascontiguousarray(eps, dtype=np.complex64)
+        amplitude = _amplitude_id("material_eps_vjp", amplitude)
+        polarization = _polarization_id("material_eps_vjp", polarization)
+        rb = np.ascontiguousarray(re_bar, dtype=np.float32)
+        ib = np.ascontiguousarray(im_bar, dtype=np.float32)
+        planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
+        if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
+            raise L.D2DError(-1, f"material_eps_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
+        keep, table = _keep_pointer(inv, 1), _keep_pointer(eps.view(np.float32), 2)
+        if not inv.size:
+            rb = ib = keep
+        L.check(self._lib.d2d_material_eps_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size), amplitude,
+                                                      polarization, table.ctypes.data_as(C.c_void_p), int(eps.shape[1]),
+                                                      rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
+        self._eps_vjp_nf = int(inv.size)
+
+    def get_material_eps_vjp(self) -> np.ndarray:
+        """Synchronises and returns the result of the last :meth:`launch_material_eps_vjp` that was accepted: complex128
+        ``[nf, N]``."""
+        if not self._eps_vjp_nf:
+            _no_result(self._ctx, self._lib.d2d_get_material_eps_vjp, "launch_material_eps_vjp", None)
+        n = self._eps_vjp_nf * self.n_objects
+        out = np.zeros(max(n, 1), np.complex128)  # (re, im) pairs of float64: the library's layout
+        L.check(self._lib.d2d_get_material_eps_vjp(self._ctx, out.ctypes.data_as(C.c_void_p)))
+        return out[:n].reshape(self._eps_vjp_nf, self.n_objects)
 
     def field_coefs_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt") -> np.ndarray:
         """The reverse-mode product of :meth:`frequency_response` with respect to the per-object reflection coefficients:

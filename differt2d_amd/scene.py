@@ -1270,7 +1270,8 @@ class Scene(Plottable):
         walls are not counted twice: the reflection loss is the coefficients'.  Wavelengths, ``amplitude``, the path class and
         the validity as for :meth:`frequency_response_on_receivers_grid`; anything else raises :class:`D2DUnsupported`, and for
         another callable :meth:`Context.valid_paths` / :meth:`Context.trace_paths` hold every valid path and its points for a sum
-        on the host.  Values only, one GPU: no gradients with respect to the permittivity or the geometry, no array or beam
+        on the host.  Values only, one GPU: no gradients with respect to the geometry
+        (:meth:`material_response_permittivity_vjp_on_receivers_grid` has those with respect to the permittivity), no array or beam
         variant, no transmission, finite slabs or roughness.
 
         Yields ``(tx name, FrequencyResponse(re, im, total))``: ``re`` and ``im`` fp32 ``[nf, m, n]``, ``total`` fp32 ``[m, n]``,
@@ -1288,6 +1289,65 @@ class Scene(Plottable):
         ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
         return self._grid_material(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, wavelengths, inv_wavelengths,
                                    permittivity, polarization, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def _grid_material_vjp(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, re_bar, im_bar, wavelengths, inv_wavelengths, permittivity,
+                           polarization, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
+        """The two permittivity adjoints of the material response: one launch per fixed end point."""
+        convert = self._inverse_wavelengths("the material response", wavelengths, inv_wavelengths)
+        bar_of = lambda bar, pt_name: bar[pt_name] if isinstance(bar, Mapping) else bar
+
+        def prepare():
+            inv = convert()
+            eps = self._permittivity_table(permittivity, int(inv.size))
+
+            def one(ctx, params, name, xy):
+                rows = ctx.material_eps_vjp(params, xy, inv, eps, bar_of(re_bar, name), bar_of(im_bar, name), polarization, amplitude)
+                return rows if eps.ndim == 2 else rows.sum(axis=0)  # one value for the band: the rows' sum, in float64
+
+            return one
+
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the material response and its permittivity gradient come from a fused sweep (a "
+            "function from differt2d_amd.utils).  For any other callable take the sparse valid-path "
+            "records (Context.valid_paths: every valid path of every cell, with its length), their "
+            "points (Context.trace_paths) and differentiate fun's phasors times the walls' Fresnel coefficients "
+            "(utils.fresnel_coefficient) on the host",
+            "the material response covers", prepare)
+
+    def material_response_permittivity_vjp_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
+        permittivity=None, polarization: str = "te", amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0,
+        max_order: int = 1, order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The gradient of a loss on :meth:`material_response_on_receivers_grid` with respect to the complex permittivity of every
+        wall: material calibration, ``eps_r`` and ``sigma`` of the walls fitted to a measured channel.  ``re_bar`` and ``im_bar``
+        are the loss's derivatives with respect to the planes ``re`` and ``im``, ``[nf, m, n]``
+        (:func:`differt2d_amd.utils.field_misfit` gives them for a least-squares fit) -- one pair for every transmitter, or
+        mappings from the transmitters' names to their pairs.  Every other argument is the forward method's, ``permittivity=None``
+        (read from the objects) included.
+
+        Yields ``(tx name, eps_bar)``: complex128, ``dL/dRe eps + 1j * dL/dIm eps``, shaped like the permittivity that was passed
+        or read -- ``[nf, N]``, a row per wavelength, or ``[N]`` for one value per wall for the band (the rows' sum, taken in float64
+        on the host) -- so that ``eps - rate * eps_bar`` is a step of gradient descent.
+        :func:`differt2d_amd.utils.material_parameters_vjp` carries a per-wavelength ``eps_bar`` on to ``eps_r`` and the
+        conductivity.  From one sweep per 8 wavelengths (include/d2d.h: d2d_material_eps_vjp_launch holds the definition and what
+        is exact about it).  One GPU; no gradients with respect to the geometry, the wavelengths or the fixed end point, no array
+        or beam variant, no gradient of ``total``."""
+        return self._grid_material_vjp(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, re_bar, im_bar, wavelengths,
+                                       inv_wavelengths, permittivity, polarization, amplitude, path_cls, min_order, max_order, order,
+                                       filter_objects, kwargs)
+
+    def material_response_permittivity_vjp_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
+        permittivity=None, polarization: str = "te", amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0,
+        max_order: int = 1, order: Optional[int] = None, filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`material_response_permittivity_vjp_on_receivers_grid`: one result per receiver, the
+        transmitter sits at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_material_vjp(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, re_bar, im_bar, wavelengths,
+                                       inv_wavelengths, permittivity, polarization, amplitude, path_cls, min_order, max_order, order,
+                                       filter_objects, kwargs)
 
     def _grid_response_coefs_vjp(self, X, Y, fixed_items, grid_is_rx, fun_kwargs, re_bar, im_bar, wavelengths, inv_wavelengths,
                                  amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):

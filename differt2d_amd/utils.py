@@ -169,8 +169,8 @@ def field_misfit(fr, target, weights=None):
     ``L = 1/2 * sum w * |H - target|**2`` over every plane and cell, with ``H = re + 1j * im``.  ``target`` is complex
     ``[nf, m, n]`` (or broadcasts to it), ``weights`` real and non-negative with a shape that broadcasts too (``None``: 1).  Returns
     ``(loss, re_bar, im_bar)``: the loss in float64 and ``d L / d re = w * (re - target.real)``, ``d L / d im = w * (im -
-    target.imag)`` as fp32 ``[nf, m, n]`` -- what ``Context.field_coefs_vjp`` and
-    ``Scene.frequency_response_coefs_vjp_on_receivers_grid`` take.  On the host, in float64, rounded to fp32 once."""
+    target.imag)`` as fp32 ``[nf, m, n]`` -- what ``Context.field_coefs_vjp``,
+    ``Scene.frequency_response_coefs_vjp_on_receivers_grid`` and ``Context.material_eps_vjp`` take.  On the host, in float64, rounded to fp32 once."""
     re = np.asarray(fr.re, dtype=np.float64)
     im = np.asarray(fr.im, dtype=np.float64)
     t = np.broadcast_to(np.asarray(target, dtype=np.complex128), re.shape)
@@ -191,6 +191,19 @@ def complex_permittivity(eps_r, conductivity, frequency_hz):
     f = np.asarray(frequency_hz, dtype=np.float64)
     loss = np.asarray(conductivity, dtype=np.float64) / (2.0 * np.pi * f * VACUUM_PERMITTIVITY)
     return np.asarray(eps_r, dtype=np.float64) - 1j * loss
+
+
+def material_parameters_vjp(eps_bar, frequency_hz):
+    """The chain rule through :func:`complex_permittivity` for one ``eps_r`` and one conductivity per wall: ``eps_bar`` is the
+    per-wavelength gradient ``dL/dRe eps + 1j * dL/dIm eps``, complex ``[nf, N]`` (``Context.material_eps_vjp``,
+    ``Scene.material_response_permittivity_vjp_on_receivers_grid`` with a table ``[nf, N]``), ``frequency_hz`` the ``nf``
+    frequencies the rows of the table were formed at.  Returns ``(eps_r_bar, conductivity_bar)``, float64 ``[N]`` each:
+    ``eps_r_bar = sum_f Re eps_bar`` and ``conductivity_bar = sum_f -Im eps_bar / (2 pi f eps_0)``."""
+    bar = np.asarray(eps_bar, dtype=np.complex128)
+    f = np.asarray(frequency_hz, dtype=np.float64).reshape(-1)
+    if bar.ndim != 2 or bar.shape[0] != f.size:
+        raise ValueError(f"material_parameters_vjp needs eps_bar [nf, N] with a row per frequency (nf = {f.size}), got shape {tuple(bar.shape)}")
+    return bar.real.sum(axis=0), (-bar.imag / (2.0 * np.pi * f[:, None] * VACUUM_PERMITTIVITY)).sum(axis=0)
 
 
 def fresnel_coefficient(eps, cos_theta, polarization="te"):

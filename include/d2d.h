@@ -31,9 +31,9 @@ extern "C" {
                               d2d_frequency_response_launch / d2d_get_frequency_response and d2d_power_angle_launch /
                               d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response,
                               d2d_array_frequency_response_launch / d2d_get_array_frequency_response,
-                              d2d_beam_response_launch / d2d_get_beam_response and d2d_material_response_launch /
-                              d2d_get_material_response are additive: no struct, enum or existing entry point changed
-                              with them, so the version did not) */
+                              d2d_beam_response_launch / d2d_get_beam_response, d2d_material_response_launch /
+                              d2d_get_material_response and d2d_material_eps_vjp_launch / d2d_get_material_eps_vjp are
+                              additive: no struct, enum or existing entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
     D2D_OK = 0,
@@ -1011,7 +1011,7 @@ int d2d_selftest_steer(d2d_ctx* ctx, const float* dx, const float* dy, const flo
  *
  * `total` is the fused map bit for bit.  Plane f depends on inv_wavelength[f] and row f of eps alone; the eps of a wall that no
  * contributing candidate touches does not matter.  With max_order = 0 the planes are d2d_frequency_response_launch's bit for bit
- * wherever no contribution is NaN.  Values only, one GPU: no gradients with respect to eps or the geometry, no array or beam variant,
+ * wherever no contribution is NaN.  Values only, one GPU: no gradients with respect to the geometry (d2d_material_eps_vjp_launch has those with respect to eps), no array or beam variant,
  * no transmission through walls, no slabs of finite thickness, no roughness; RIS objects reflect like walls of their permittivity.
  *
  * D2D_ERR_INVALID: what d2d_frequency_response_launch refuses of the list and the amplitude; a polarization other than 0 / 1; an
@@ -1033,6 +1033,58 @@ int d2d_get_material_response(d2d_ctx* ctx, float* re /* [nf][m][n] or NULL */, 
 
 /* fresnel of d2d_fresnel.hpp on the device, for comparison with its host build: (gr[i], gi[i]) = fresnel(er[i], ei[i], c[i], pol). */
 int d2d_selftest_fresnel(d2d_ctx* ctx, const float* er, const float* ei, const float* c, int32_t pol, int64_t n, float* gr, float* gi);
+
+/* ---- material calibration: the material response's gradient with respect to the walls' permittivities (K3-E) --------------------
+ *
+ * The reverse-mode product of d2d_material_response_launch: given the cotangents re_bar, im_bar [nf][m][n] of its planes
+ * (dL = sum re_bar * dre + im_bar * dim; utils.field_misfit returns them for a least-squares misfit), eps_bar[nf][n_objects][2] =
+ * (dL/dRe eps, dL/dIm eps) of every wall at every wavelength, in fp64.  G(eps) is holomorphic, so one complex derivative per bounce
+ * (differt2d_amd/csrc/d2d_fresnel_grad.hpp is its definition) carries both components.  One preparation of the culled sweep; per
+ * chunk of 8 wavelengths one pass into per-patch rows (one writer per row, no atomics) and one fixed-order fp64 reduction of the
+ * rows: the same bits run to run.  eps <- eps - rate * (eps_bar.re + j eps_bar.im) is gradient descent.
+ *
+ * Every argument up to `n_objects` is d2d_material_response_launch's, with its checks and messages; `re_bar` and `im_bar` are
+ * copied before the call returns.  Any fused path function is accepted: the amplitude does not depend on eps.
+ *
+ *   eps_bar[f][w] = (+0.0, +0.0) for all f, w                    // fp64 [nf][n_objects][2]
+ *   for cells, for candidates in the sweep's enumeration order (walls cand[0..K), K >= 1):
+ *       t = valid * fun ; r ; seg[i] = p[i+1] - p[i]              // as d2d_material_response_launch gets them
+ *       if (t == 0) continue
+ *       c_i = |unit_dir(seg[i]) . n(cand[i])| ;  if any segment lacks a direction or any c_i is NaN: continue   // the forward's rule
+ *       a = amplitude == SQRT ? copysignf(sqrtf(fabsf(t)), t) : t
+ *       for f < nf:
+ *           (g_i, d_i, ok_i) = fresnel_grad(eps[f][cand[i]], c_i, polarization)   for i < K       // d2d_fresnel_grad.hpp
+ *           (c0, s0) = phasor(frac(r * inv_wavelength[f])) ;  E = a * (c0 - j s0)
+ *           B = re_bar[f][cell] + j im_bar[f][cell]
+ *           for i < K with ok_i:
+ *               P_i = product of g_o over the OTHER positions o != i, in position order, formed explicitly (K <= 4; nothing is divided by a g)
+ *               D   = E * (P_i * d_i)
+ *               eps_bar[f][cand[i]].re += B.re*D.re + B.im*D.im                  // dL/dRe eps
+ *               eps_bar[f][cand[i]].im += B.im*D.re - B.re*D.im                  // dL/dIm eps
+ *
+ * The terms are formed in fp32 and summed per 8 x 8 patch in fp32 (a wave's butterfly, then the patch's row), the rows in fp64: the
+ * result is the definition's up to the rounding that tests/material_eps_vjp_oracle.py bounds, not bit for bit.  A wall that occurs
+ * twice in a candidate gets both terms; the line of sight holds no coefficient and adds nothing; ok_i is false where G is defined by
+ * a special case (q = 0, the grazing limit) and has no derivative.  Row f depends on inv_wavelength[f], row f of eps and the
+ * cotangent planes f alone; a wall that no contributing candidate touches has (+0.0, +0.0).  `total` is not produced.  One GPU; no
+ * gradients with respect to the geometry, the wavelengths or the fixed end point, no array or beam variant.
+ *
+ * D2D_ERR_INVALID and D2D_ERR_UNSUPPORTED: what d2d_material_response_launch refuses, with its messages under this function's name,
+ * and NULL cotangents.  The memory rule holds the cotangents (8 * nf bytes per cell), the table and the result (24 * nf * n_objects
+ * bytes) and one chunk's rows (64 * n_objects bytes per patch) against half of the free device memory.  All decided before anything
+ * is enqueued: a refused launch leaves the previous result as it was. */
+int d2d_material_eps_vjp_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                                const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude, int32_t polarization,
+                                const float* eps /* [nf][n_objects][2]: (re, im) */, int32_t n_objects,
+                                const float* re_bar /* [nf][m][n] */, const float* im_bar /* [nf][m][n] */);
+/* Synchronises and copies the result of the last d2d_material_eps_vjp_launch that was accepted.  D2D_ERR_STATE before a launch,
+ * after a d2d_set_grid of another grid and after a d2d_set_scene of another scene (the result goes with the grid and the scene). */
+int d2d_get_material_eps_vjp(d2d_ctx* ctx, double* eps_bar /* [nf][n_objects][2] */);
+
+/* fresnel_grad of d2d_fresnel_grad.hpp on the device, for comparison with its host build:
+ * (gr[i], gi[i], dr[i], di[i], ok[i]) = fresnel_grad(er[i], ei[i], c[i], pol), ok as 1 / 0. */
+int d2d_selftest_fresnel_grad(d2d_ctx* ctx, const float* er, const float* ei, const float* c, int32_t pol, int64_t n, float* gr, float* gi,
+                              float* dr, float* di, float* ok);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
