@@ -22,6 +22,7 @@ D2D_MAX_ORDER = 4
 D2D_TOP_MAX = 8
 D2D_FIELD_AMP_SQRT, D2D_FIELD_AMP_LINEAR = 0, 1  # d2d_coherent_field_launch amplitude modes
 D2D_FREQ_MAX = 1024  # most wavelengths of one d2d_frequency_response_launch
+D2D_POS_CHUNK = 8  # wavelengths per pass of d2d_field_position_vjp_launch (part of its definition)
 D2D_ANGLE_AT_TX, D2D_ANGLE_AT_RX = 0, 1  # d2d_power_angle_launch: the end of the path whose direction is binned
 D2D_ANGLE_BINS_MAX = 4096
 D2D_ARRAY_MAX = 8  # most elements of either array of one d2d_array_response_launch
@@ -172,6 +173,9 @@ SYMBOLS = [
     ("d2d_get_frequency_response", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_field_coefs_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ("d2d_get_field_coefs_vjp", C.c_int, [_ctx, C.c_void_p]),
+    ("d2d_field_position_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("d2d_get_field_position_vjp", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("d2d_selftest_posgrad", C.c_int, [_ctx, C.c_int32, C.c_int32] + [_f32p] * 9 + [C.c_int64] + [_f32p] * 5),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),

@@ -268,8 +268,19 @@ struct d2d_ctx {
         void forget() { nf = 0; }
         void drop() { re.release(); im.release(); eps.release(); partial.release(); out.release(); forget(); }
     } eg;
+    // position adjoint of the frequency response (d2d_field_position_vjp_launch): the cotangent planes, the four planes the passes
+    // carry, the reduction's partial sums and the reduced result, kept until the next accepted launch; the scene forgets it too
+    struct PosGrad {
+        DevBuf<float> re, im;          // [nf][m][n] each: the caller's cotangents
+        DevBuf<float> cell, terms;     // [2][m][n] each: cell_bar, fixed_terms
+        DevBuf<double> part, out;      // [2][POS_REDUCE_BLOCKS], [2]: fixed_bar and the sums it is made of
+        bool have = false;             // the buffers hold the result of an accepted launch for the CURRENT grid and scene
+        size_t bytes() const { return (re.n + im.n + cell.n + terms.n) * sizeof(float); }
+        void forget() { have = false; }
+        void drop() { re.release(); im.release(); cell.release(); terms.release(); part.release(); out.release(); forget(); }
+    } pg;
     void drop_products() {  // every one of them goes with the grid
-        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop(); eg.drop();
+        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop(); eg.drop(); pg.drop();
     }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -821,6 +832,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->cg.forget();               // (... and so was the frequency response's coefficient adjoint)
     c->mat.forget();              // (... and the material response, whose table has one entry per wall)
     c->eg.forget();               // (... and its permittivity adjoint)
+    c->pg.forget();               // (... and the frequency response's position adjoint: its paths are the previous scene's)
     c->have_kernel_time = false;
     c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
@@ -2319,6 +2331,7 @@ constexpr SinkProduct ARRAY = {"d2d_array_response_launch", "a host function's c
 constexpr SinkProduct WIDE = {"d2d_array_frequency_response_launch", "a host function's channel matrices: add the steered phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the channel matrices are always overwritten", LATE};
 constexpr SinkProduct MATERIAL = {"d2d_material_response_launch", "a host function's response: add the phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths, each times its walls' Fresnel coefficients", "the response is always overwritten", LATE};
 constexpr SinkProduct EPS_VJP = {"d2d_material_eps_vjp_launch", "a host function has no permittivities", "the gradient is always overwritten", LATE};
+constexpr SinkProduct POS_VJP = {"d2d_field_position_vjp_launch", "a host function's derivative with respect to the path length is not known to the library", "the gradient is always overwritten", LATE};
 constexpr SinkProduct BEAM = {"d2d_beam_response_launch", "a host function's beam response: add the beamformed phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the beam response is always overwritten", LATE};
 
 // What the products refuse of the caller's parameters before prep_sink_sweep's share.
@@ -2415,7 +2428,7 @@ static int copy_out(d2d_ctx* c, std::initializer_list<CopyOut> copies) {
 }
 
 static_assert(d2d_host::FREQ_CHUNK == d2d::FREQ_CHUNK && d2d_host::WIDE_CHUNK == d2d::WIDE_CHUNK && d2d_host::BEAM_CHUNK == d2d::BEAM_CHUNK &&
-                  d2d_host::MAT_CHUNK == d2d::MAT_CHUNK,
+                  d2d_host::MAT_CHUNK == d2d::MAT_CHUNK && d2d_host::POS_CHUNK == d2d::POS_CHUNK,
               "d2d_host.hpp and d2d_kernels.hpp disagree");
 
 }  // namespace
@@ -2621,6 +2634,76 @@ int d2d_get_field_coefs_vjp(d2d_ctx* c, double* coef_bar) {
     if (int rc = result_state(c, c && c->have_scene && c->cg.have && c->cg.out.p, COEF_VJP, "result goes with the grid and the scene")) return rc;
     if (!coef_bar) return fail(D2D_ERR_INVALID, "coef_bar is NULL");
     return copy_out(c, {{coef_bar, c->cg.out.p, (size_t)c->N * sizeof(double)}});
+}
+
+// Position adjoint of the frequency response: ONE preparation of the culled sweep with the caller's own path function, one pass per
+// block of POS_CHUNK wavelengths -- every lane carries its cell's four running values from pass to pass through the planes, the
+// first pass starting from +0 -- then the fixed-order fp64 sums of the two fixed_terms planes.  The cotangents are copied before
+// the call returns.
+constexpr unsigned POS_REDUCE_BLOCKS = 1024;  // most partial sums per plane of the reduction's first stage
+int d2d_field_position_vjp_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                                  const float* re_bar, const float* im_bar) {
+    if (!c || !fixed || !inv_wavelength || !re_bar || !im_bar) return fail(D2D_ERR_INVALID, "NULL argument");
+    SinkLaunch<d2d_ctx::PosGrad> L(c, POS_VJP, c->pg, fixed);
+    d2d_ctx::PosGrad& r = c->pg;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p, [&] {
+            if (!p->approx) return (int)D2D_OK;
+            return fail(D2D_ERR_UNSUPPORTED,
+                        "%s covers hard validity only: a smoothed validity (hard_sigmoid, sigmoid) depends on the positions itself, and its term needs the "
+                        "reverse chain of the value+grad sweep (d2d_power_map_vg_launch); a gradient without that term is not offered",
+                        POS_VJP.who);
+        })))
+        return rc;
+    if ((rc = d2d_host::posgrad_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "%s: %s", POS_VJP.who, err.c_str());
+    if ((rc = L.device()) || (rc = L.fits(d2d_host::posgrad_bytes_per_cell(nf), r.bytes())) || (rc = L.prepare())) return rc;
+    const size_t cells = L.cells, planes = (size_t)nf * cells;
+    const unsigned blocks = (unsigned)std::min<size_t>(POS_REDUCE_BLOCKS, std::max<size_t>(1, (cells + 255) / 256));
+    if ((rc = r.re.ensure(planes)) || (rc = r.im.ensure(planes)) || (rc = r.cell.ensure(2 * cells)) || (rc = r.terms.ensure(2 * cells)) ||
+        (rc = r.part.ensure(2 * (size_t)POS_REDUCE_BLOCKS)) || (rc = r.out.ensure(2)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(r.re.p, re_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.im.p, im_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays are free again when the call returns
+    if (L.s.tiles > 0 && cells > 0) {
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::POS_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::POS_CHUNK);
+            d2d::PosGradArgs g;
+            g.re_bar = r.re.p + (size_t)ch.first * cells;
+            g.im_bar = r.im.p + (size_t)ch.first * cells;
+            g.cell_bar = r.cell.p;
+            g.fixed_terms = r.terms.p;
+            g.cells = (long)cells;
+            for (int32_t j = 0; j < d2d::POS_CHUNK; ++j) g.inv[j] = j < ch.count ? inv_wavelength[ch.first + j] : 0.0f;
+            g.nf = ch.count;
+            g.amplitude = amplitude;
+            g.fun_id = L.pp.fun_id;
+            g.h2 = L.s.a.h2;
+            g.txg = L.s.txg ? 1 : 0;
+            g.first = i == 0 ? 1 : 0;
+            HIP_TRY(L.pass<d2d::PosGradSink>(g));
+        }
+        hipLaunchKernelGGL(d2d::plane_sum_kernel<float>, dim3(blocks, 2), dim3(256), 0, c->stream, r.terms.p, (long)cells, r.part.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(d2d::plane_sum_kernel<double>, dim3(1, 2), dim3(256), 0, c->stream, r.part.p, (long)blocks, r.out.p);
+        HIP_TRY(hipGetLastError());
+    } else {  // a sweep without contributions
+        if (cells > 0) {
+            HIP_TRY(hipMemsetAsync(r.cell.p, 0, 2 * cells * sizeof(float), c->stream));
+            HIP_TRY(hipMemsetAsync(r.terms.p, 0, 2 * cells * sizeof(float), c->stream));
+        }
+        HIP_TRY(hipMemsetAsync(r.out.p, 0, 2 * sizeof(double), c->stream));
+    }
+    r.have = true;
+    return D2D_OK;
+}
+
+int d2d_get_field_position_vjp(d2d_ctx* c, float* cell_bar, float* fixed_terms, double* fixed_bar) {
+    if (int rc = result_state(c, c && c->have_scene && c->pg.have && c->pg.out.p, POS_VJP, "result goes with the grid and the scene")) return rc;
+    const d2d_ctx::PosGrad& r = c->pg;
+    const size_t bytes = 2 * (size_t)c->m * (size_t)c->n * sizeof(float);
+    return copy_out(c, {{cell_bar, r.cell.p, bytes}, {fixed_terms, r.terms.p, bytes}, {fixed_bar, r.out.p, 2 * sizeof(double)}});
 }
 
 // Power-angle build: ONE pass into the zeroed planes, every lane storing its cell's total at the end.
@@ -3145,6 +3228,25 @@ int d2d_selftest_fresnel_grad(d2d_ctx* c, const float* er, const float* ei, cons
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     float* out[5] = {gr, gi, dr, di, ok};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_posgrad(d2d_ctx* c, int32_t fun_id, int32_t amplitude, const float* t, const float* r, const float* h2, const float* inv0, const float* inv1,
+                         const float* rb0, const float* rb1, const float* ib0, const float* ib1, int64_t n, float* a, float* rho, float* kr, float* g, float* G) {
+    if (!c || !t || !r || !h2 || !inv0 || !inv1 || !rb0 || !rb1 || !ib0 || !ib1 || !a || !rho || !kr || !g || !G || n <= 0)
+        return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> din, dout;  // nine inputs, five outputs, n each
+    if ((rc = din.ensure(9 * (size_t)n)) || (rc = dout.ensure(5 * (size_t)n))) return rc;
+    const float* in[9] = {t, r, h2, inv0, inv1, rb0, rb1, ib0, ib1};
+    for (int k = 0; k < 9; ++k) HIP_TRY(hipMemcpy(din.p + (size_t)k * (size_t)n, in[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_posgrad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, din.p, dout.p, (int)fun_id, (int)amplitude,
+                       (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float* out[5] = {a, rho, kr, g, G};
     for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }

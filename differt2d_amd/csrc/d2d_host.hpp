@@ -377,6 +377,24 @@ inline bool coef_vjp_fits(size_t cells, int32_t nf, size_t patches, size_t n_obj
     return n_objects <= budget / sizeof(float) / patches;
 }
 
+// ---- parameters and memory of the frequency response's position adjoint (d2d_field_position_vjp_launch, d2d::PosGradSink) ----
+// D2D_ERR_INVALID, as the frequency response: nf outside 1 .. D2D_FREQ_MAX, an entry that is negative, NaN or infinite (the message
+// names its index; 0 is allowed), an amplitude mode that is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.  The list is not
+// read unless nf is in range.
+inline int posgrad_params(const float* inv_wavelength, int32_t nf, int32_t amplitude, std::string& err) {
+    const char* noun = "the position adjoint";
+    if (nf < 1 || nf > D2D_FREQ_MAX)
+        return err = std::string(noun) + " needs nf in 1 .. " + std::to_string(D2D_FREQ_MAX) + ", got " + std::to_string(nf), D2D_ERR_INVALID;
+    for (int32_t j = 0; j < nf; ++j)
+        if (int rc = check_inv_wavelength(noun, inv_wavelength[j], err)) return err += " at index " + std::to_string(j), rc;
+    return check_amplitude(noun, amplitude, err);
+}
+// Per cell: nf planes of re_bar and im_bar (8 nf bytes) and the four planes of cell_bar and fixed_terms (16 bytes), 4 bytes each
+// (outputs_fit; tests/native/field_position_vjp_host.cpp).  0 for an nf out of range: outputs_fit then refuses.
+inline size_t posgrad_bytes_per_cell(int32_t nf) { return nf < 1 || nf > D2D_FREQ_MAX ? 0 : 8 * (size_t)nf + 16; }
+// One pass of the sink kernel per POS_CHUNK wavelengths (chunk_plan); the block size is part of the definition (include/d2d.h).
+constexpr int32_t POS_CHUNK = D2D_POS_CHUNK;  // = d2d::POS_CHUNK (d2d_posgrad.hpp)
+
 // ---- memory of the material response's permittivity adjoint (d2d_material_eps_vjp_launch, d2d::EpsGradSink) ------------
 // The cotangent planes take 8 nf bytes per cell, the permittivity table 8 nf bytes per object, the partial rows of one chunk
 // 4 * MAT_CHUNK * 2 bytes per patch and object and the fp64 result 16 nf bytes per object.  Refused like its siblings: above half of

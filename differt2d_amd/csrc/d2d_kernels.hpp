@@ -40,6 +40,7 @@
 #include "d2d_beam.hpp"
 #include "d2d_fresnel.hpp"
 #include "d2d_fresnel_grad.hpp"
+#include "d2d_posgrad.hpp"
 
 namespace d2d {
 
@@ -2178,6 +2179,108 @@ struct CoefGradSink {
         }
     }
     __device__ __forceinline__ void end(const CoefGradArgs&, long, int) const {}
+};
+
+// PosGradSink (d2d_field_position_vjp_launch): the reverse-mode product of the frequency response with respect to the two end points
+// of every path, the cell's and the fixed one, for up to POS_CHUNK wavelengths of one sweep (include/d2d.h holds the definition,
+// d2d_posgrad.hpp its per-contribution arithmetic).  Hard validity only: a position then enters through the path length alone, and
+// d r / d p[0] = -unit(p[1] - p[0]), d r / d p[K+1] = -unit(p[K] - p[K+1]) (the interaction points are stationary).  CoefGradSink's
+// front: begin() loads the lane's cotangents re_bar[j][cell], im_bar[j][cell] into registers (zeros for lanes outside the grid,
+// cell < 0).  A per-lane back: four fp32 accumulators, the gradient with respect to the cell's position and the cell's share of the
+// gradient with respect to the fixed end point.  Per candidate that some lane of the wave has a non-zero contribution from, every
+// such lane forms G = dL/dr of the path for this block (posgrad_amp / _rho / _kr / _fold) and subtracts G times the unit direction
+// at either end, where that end has one (unit_dir of d2d_steer.hpp): no wave reduction, no atomics, no LDS.  fun_id, h2, the
+// amplitude mode and inv[] come by value in the kernel argument (scalar loads); j is a compile-time index behind the wave-uniform
+// guard j < nf, as in FreqSink.  The four planes cell_bar[2][cells], fixed_terms[2][cells] carry the running values from one
+// block's pass to the next: begin() starts from +0.0f in the first pass and from the planes afterwards, end() stores; a lane is the
+// only writer of its cell, lanes outside the grid never read or write.  cell < cells, so every address is inside the 2 * cells
+// floats of a pair of planes.
+struct PosGradArgs {
+    const float* re_bar;   // [nf][cells]: this block's cotangent planes
+    const float* im_bar;   // [nf][cells]
+    float* cell_bar;       // [2][cells]
+    float* fixed_terms;    // [2][cells]
+    long cells;            // m * n
+    float inv[POS_CHUNK];  // turns per unit length, finite and >= 0; entries at and past nf are not read
+    int nf;                // 1 .. POS_CHUNK
+    int amplitude;         // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int fun_id;            // the caller's fused path function
+    float h2;              // height * height, as the sweep has it
+    int txg;               // the cell is the transmitter: its direction is dir[0..1], the fixed end's dir[2..3]
+    int first;             // the first block's pass: the accumulators start from +0.0f
+};
+struct PosGradSink {
+    using Args = PosGradArgs;
+    static constexpr bool WANTS_R = true;
+    static constexpr bool WANTS_DIR = true;
+    static constexpr bool WANTS_SEG = false;
+    float rb[POS_CHUNK], ib[POS_CHUNK];
+    float inv[POS_CHUNK];
+    float cx, cy, fx, fy;
+    float h2;
+    int nf, amplitude, fun_id;
+    bool txg;
+    int cell;
+    __device__ __forceinline__ void begin(const PosGradArgs& x, long /*tile*/, int lane_cell) {
+        cell = lane_cell;
+        const bool live = lane_cell >= 0;
+        static_for<0, POS_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            rb[J] = ib[J] = 0.0f;
+            inv[J] = x.inv[J];
+            if (J < x.nf && live) {
+                const size_t at = (size_t)J * (size_t)x.cells + (size_t)lane_cell;
+                rb[J] = x.re_bar[at];
+                ib[J] = x.im_bar[at];
+            }
+        });
+        cx = cy = fx = fy = 0.0f;
+        if (!x.first && live) {
+            cx = x.cell_bar[lane_cell];
+            cy = x.cell_bar[(size_t)x.cells + (size_t)lane_cell];
+            fx = x.fixed_terms[lane_cell];
+            fy = x.fixed_terms[(size_t)x.cells + (size_t)lane_cell];
+        }
+        h2 = x.h2;
+        nf = x.nf;
+        amplitude = x.amplitude;
+        fun_id = x.fun_id;
+        txg = x.txg != 0;
+    }
+    // dir: {p[1] - p[0], p[K] - p[K+1]} of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_rd(float t, float r, const float (&dir)[4]) {
+        const bool p = !(t == 0.0f);  // non-zero or NaN
+        if (__ballot(p) == 0ull) return;
+        if (!(p && cell >= 0)) return;  // (per lane: nothing below crosses lanes)
+        const float a = posgrad_amp(amplitude, t);
+        const float kr = posgrad_kr(amplitude, posgrad_rho(fun_id, h2, r));
+        float g = 0.0f;
+        static_for<0, POS_CHUNK>([&](auto JJ) {
+            constexpr int J = decltype(JJ)::value;
+            if (J < nf) g = posgrad_fold(g, kr, r, inv[J], rb[J], ib[J]);
+        });
+        const float G = a * g;
+        float ucx, ucy, ufx, ufy;
+        const bool okc = unit_dir(txg ? dir[0] : dir[2], txg ? dir[1] : dir[3], ucx, ucy);
+        const bool okf = unit_dir(txg ? dir[2] : dir[0], txg ? dir[3] : dir[1], ufx, ufy);
+        if (okc) {
+            const float gx = G * ucx, gy = G * ucy;
+            cx = cx - gx;
+            cy = cy - gy;
+        }
+        if (okf) {
+            const float gx = G * ufx, gy = G * ufy;
+            fx = fx - gx;
+            fy = fy - gy;
+        }
+    }
+    __device__ __forceinline__ void end(const PosGradArgs& x, long, int) const {
+        if (cell < 0) return;
+        x.cell_bar[cell] = cx;
+        x.cell_bar[(size_t)x.cells + (size_t)cell] = cy;
+        x.fixed_terms[cell] = fx;
+        x.fixed_terms[(size_t)x.cells + (size_t)cell] = fy;
+    }
 };
 
 // AngleSink (d2d_power_angle_launch): every contribution that is not exactly zero is added to the bin of the direction in which its
@@ -4852,6 +4955,26 @@ __global__ void selftest_fresnel_grad_kernel(const float* __restrict__ in, float
     out[4 * n + i] = ok ? 1.0f : 0.0f;
 }
 
+// the position adjoint's per-contribution arithmetic (d2d_posgrad.hpp) on the device, for comparison with its host build
+// (tests/test_gpu_field_position_vjp.py): in = t, r, h2, inv0, inv1, rb0, rb1, ib0, ib1 and out = a, rho, kr, g, G, n values each,
+// g the fold over the two wavelengths in order
+__global__ void selftest_posgrad_kernel(const float* __restrict__ in, float* __restrict__ out, int fun_id, int amplitude, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float t = in[i], r = in[n + i], h2 = in[2 * n + i];
+    const float a = posgrad_amp(amplitude, t);
+    const float rho = posgrad_rho(fun_id, h2, r);
+    const float kr = posgrad_kr(amplitude, rho);
+    float g = 0.0f;
+    g = posgrad_fold(g, kr, r, in[3 * n + i], in[5 * n + i], in[7 * n + i]);
+    g = posgrad_fold(g, kr, r, in[4 * n + i], in[6 * n + i], in[8 * n + i]);
+    out[i] = a;
+    out[n + i] = rho;
+    out[2 * n + i] = kr;
+    out[3 * n + i] = g;
+    out[4 * n + i] = a * g;
+}
+
 // Shadow coverage of every wall as seen from the fixed end point `e` (the transmitter of an RX-grid sweep): one wave per
 // (wall w, blocker j) pair rasterises, into 64 bins of w's parametric range, where the segment e -> p is CERTAINLY
 // reported as intersecting j by the exact path (hard: hit; approx: the four activations exactly saturated), for every
@@ -5144,6 +5267,26 @@ __global__ void __launch_bounds__(256) vjp_reduce_kernel(const float* __restrict
         __syncthreads();
     }
     if (threadIdx.x == 0) out[e] = (accumulate ? out[e] : 0.0) + sm[0];
+}
+
+// Fixed-order fp64 sums of planes (d2d_field_position_vjp_launch: fixed_bar from the two fixed_terms planes):
+// out[y * gridDim.x + b] = sum of in[y * n + i] over the i that block b of row y owns, i = b * 256 + thread + k * gridDim.x * 256.
+// Every thread adds its elements in ascending order, the block's tree has a fixed shape and one thread writes the entry: the same
+// bits run to run, no atomics.  Two launches make a sum: float planes into gridDim.x partial sums per plane, then those (T = double,
+// one block per plane) into the result.
+template <class T>
+__global__ void __launch_bounds__(256) plane_sum_kernel(const T* __restrict__ in, long n, double* __restrict__ out) {
+    __shared__ double sm[256];
+    const T* row = in + (size_t)blockIdx.y * (size_t)n;
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += (double)row[i];
+    sm[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sm[threadIdx.x] += sm[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
 }
 
 #endif  // D2D_AUX_KERNELS

@@ -50,7 +50,8 @@ D2D_DECLARE_MODE(MODE_SIG)
     X(ArrayFreqSink) /* the wideband array response */                                                        \
     X(BeamSink)      /* the beam-space response */                                                            \
     X(MaterialSink)  /* the frequency response with Fresnel reflection per wall */                           \
-    X(EpsGradSink)   /* its adjoint w.r.t. the walls' permittivities */
+    X(EpsGradSink)   /* its adjoint w.r.t. the walls' permittivities */                                       \
+    X(PosGradSink)   /* the frequency response's adjoint w.r.t. the cell's and the fixed end point's position */
 #define D2D_DECLARE_SINK(S)                                                                                                      \
     template <> hipError_t launch_sink_m<MODE_HARD, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&); \
     template <> hipError_t launch_sink_m<MODE_HSIG, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&);

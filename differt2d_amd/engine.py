@@ -94,6 +94,14 @@ class FrequencyResponse(NamedTuple):
     total: np.ndarray  # fp32 [m, n]: the incoherent sum over all candidates, the fused map bit for bit
 
 
+class PositionGradient(NamedTuple):
+    """Result of :meth:`Context.field_position_vjp` (include/d2d.h: d2d_field_position_vjp_launch)."""
+
+    cell_bar: np.ndarray     # fp32 [m, n, 2]: dL / d (position of the cell): the receiver on an RX grid, the transmitter on a TX grid
+    fixed_terms: np.ndarray  # fp32 [m, n, 2]: the cell's share of dL / d (fixed end point)
+    fixed_bar: np.ndarray    # float64 [2]: dL / d (fixed end point), the fixed-order sum of fixed_terms over the cells
+
+
 class PowerAngleProfile(NamedTuple):
     """Result of :meth:`Context.power_angle` (include/d2d.h: d2d_power_angle_launch)."""
 
@@ -915,6 +923,64 @@ class Context:
         out = np.zeros(max(self.n_objects, 1), np.float64)
         L.check(self._lib.d2d_get_field_coefs_vjp(self._ctx, out.ctypes.data_as(C.c_void_p)))
         return out[: self.n_objects]
+
+    def field_position_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt") -> "PositionGradient":
+        """The reverse-mode product of :meth:`frequency_response` with respect to positions: for a loss ``L`` with
+        ``dL = sum (re_bar * d re + im_bar * d im)``, the gradient with respect to the position of every cell (the receiver of that
+        cell on an RX grid, the transmitter on a TX grid) and with respect to the fixed end point, from ONE preparation of the
+        culled sweep and one kernel pass per 8 wavelengths (include/d2d.h: d2d_field_position_vjp_launch holds the definition).
+        Hard validity only: a position then enters through the path length alone, and the interaction points are stationary.
+        ``params`` (any fused ``fun``), ``fixed``, ``inv_wavelengths`` and ``amplitude`` as for :meth:`frequency_response`;
+        ``re_bar`` and ``im_bar`` are the cotangents of its planes, ``[nf, m, n]`` (taken as fp32, copied by the call; non-finite
+        values propagate into their cell and ``fixed_bar``).  A refused launch leaves the previous result readable.  The resident
+        value and gradient maps, the scene VJP of :meth:`launch_vg` and the other products' results are not touched.
+
+        Returns a :class:`PositionGradient`: ``cell_bar`` and ``fixed_terms``, fp32 ``[m, n, 2]`` (indexed like
+        :meth:`get_grad_rx`; views of the library's ``[2][m][n]`` planes), defined bit for bit, and ``fixed_bar``, float64 ``[2]``, the
+        fixed-order sum of ``fixed_terms`` over the cells.  :func:`differt2d_amd.utils.field_misfit` gives the cotangents of a
+        least-squares fit (localisation), :func:`differt2d_amd.utils.wideband_power_cotangent` those of the coherent wideband
+        coverage (placement)."""
+        self.launch_field_position_vjp(params, fixed, inv_wavelengths, re_bar, im_bar, amplitude)
+        return self.get_field_position_vjp()
+
+    def launch_field_position_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt"):
+        """The launch of :meth:`field_position_vjp` alone (the list and the cotangents are copied by the call; the kernels are
+        asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        amplitude = _amplitude_id("field_position_vjp", amplitude)
+        rb = np.ascontiguousarray(re_bar, dtype=np.float32)
+        ib = np.ascontiguousarray(im_bar, dtype=np.float32)
+        planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
+        if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
+            raise L.D2DError(-1, f"field_position_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
+        keep = _keep_pointer(inv, 1)
+        if not inv.size:
+            rb = ib = keep
+        L.check(self._lib.d2d_field_position_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
+                                                        amplitude, rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
+
+    def get_field_position_vjp(self) -> "PositionGradient":
+        """Synchronises and returns the result of the last :meth:`launch_field_position_vjp` that was accepted."""
+        if not self.shape:
+            _no_result(self._ctx, self._lib.d2d_get_field_position_vjp, "launch_field_position_vjp", None, None, None)
+        planes = (2,) + tuple(self.shape)
+        cell, terms, bar = np.empty(planes, np.float32), np.empty(planes, np.float32), np.empty(2, np.float64)
+        L.check(self._lib.d2d_get_field_position_vjp(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in (cell, terms, bar))))
+        # (views of the library's [2][m][n] planes: no copy on the host)
+        return PositionGradient(cell_bar=np.moveaxis(cell, 0, -1), fixed_terms=np.moveaxis(terms, 0, -1), fixed_bar=bar)
+
+    def selftest_posgrad(self, fun_id: int, amplitude, t, r, h2, inv, rb, ib):
+        """``(a, rho, kr, g, G)`` of d2d_posgrad.hpp on the device (include/d2d.h: d2d_selftest_posgrad): ``inv``, ``rb`` and ``ib`` are
+        ``[2, n]``, the two wavelengths of the fold; the other inputs ``[n]``."""
+        t, r, h2 = (np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (t, r, h2))
+        pairs = [np.ascontiguousarray(x, dtype=np.float32).reshape(2, t.size) for x in (inv, rb, ib)]
+        if not (t.size == r.size == h2.size):
+            raise ValueError("selftest_posgrad: arrays of one size")
+        outs = [np.empty_like(t) for _ in range(5)]
+        L.check(self._lib.d2d_selftest_posgrad(self._ctx, int(fun_id), _amplitude_id("selftest_posgrad", amplitude), t, r, h2,
+                                               *(np.ascontiguousarray(p[k]) for p in pairs for k in (0, 1)), t.size, *outs))
+        return tuple(outs)
 
     def power_angle(self, params: L.Params, fixed, end, origin_turns: float, nbins: int) -> "PowerAngleProfile":
         """The power-angle profile of every cell of the resident grid: the fused sweep's contributions ``valid * fun`` binned by

@@ -180,6 +180,22 @@ def field_misfit(fr, target, weights=None):
     return loss, np.ascontiguousarray(w * dr, dtype=np.float32), np.ascontiguousarray(w * di, dtype=np.float32)
 
 
+def wideband_power_cotangent(fr, weights=None):
+    """The coherent wideband coverage of a ``FrequencyResponse`` as an objective, and its cotangents:
+    ``J = sum_cells w * mean_j |H_j|**2`` with ``H = re + 1j * im`` (:func:`wideband_power` summed over the cells), ``weights`` real
+    ``[m, n]`` (or a shape that broadcasts to it; ``None``: 1).  Returns ``(objective, re_bar, im_bar)``: ``J`` in float64 and
+    ``d J / d re = 2 w re / nf``, ``d J / d im = 2 w im / nf`` as fp32 ``[nf, m, n]`` -- what ``Context.field_position_vjp`` and
+    ``Scene.frequency_response_position_vjp_on_receivers_grid`` take: their ``fixed_bar`` is then the direction in which to move the
+    transmitter to RAISE the coverage.  On the host, in float64, rounded to fp32 once."""
+    re = np.asarray(fr.re, dtype=np.float64)
+    im = np.asarray(fr.im, dtype=np.float64)
+    nf = re.shape[0]
+    w = np.ones(re.shape[1:]) if weights is None else np.broadcast_to(np.asarray(weights, dtype=np.float64), re.shape[1:])
+    objective = float(np.sum(w * (re * re + im * im).mean(axis=0)))
+    scale = (2.0 / nf) * w
+    return objective, np.ascontiguousarray(scale * re, dtype=np.float32), np.ascontiguousarray(scale * im, dtype=np.float32)
+
+
 VACUUM_PERMITTIVITY = 8.8541878128e-12  # F/m
 
 

@@ -32,7 +32,8 @@ extern "C" {
                               d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response,
                               d2d_array_frequency_response_launch / d2d_get_array_frequency_response,
                               d2d_beam_response_launch / d2d_get_beam_response, d2d_material_response_launch /
-                              d2d_get_material_response and d2d_material_eps_vjp_launch / d2d_get_material_eps_vjp are
+                              d2d_get_material_response, d2d_material_eps_vjp_launch / d2d_get_material_eps_vjp and
+                              d2d_field_position_vjp_launch / d2d_get_field_position_vjp are
                               additive: no struct, enum or existing entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
@@ -1085,6 +1086,84 @@ int d2d_get_material_eps_vjp(d2d_ctx* ctx, double* eps_bar /* [nf][n_objects][2]
  * (gr[i], gi[i], dr[i], di[i], ok[i]) = fresnel_grad(er[i], ei[i], c[i], pol), ok as 1 / 0. */
 int d2d_selftest_fresnel_grad(d2d_ctx* ctx, const float* er, const float* ei, const float* c, int32_t pol, int64_t n, float* gr, float* gi,
                               float* dr, float* di, float* ok);
+
+/* ---- position gradients of the frequency response: its reverse-mode product with respect to the cell's position and the fixed
+ *      end point (K3-X; localisation against a measured complex channel H_meas(f_j, cell), transmitter placement for coherent
+ *      wideband coverage; additive entry points, the ABI version did not change) -------------------------------------------- */
+
+#define D2D_POS_CHUNK 8 /* wavelengths per pass of d2d_field_position_vjp_launch: part of its definition (a block's dL/dr rounds once) */
+/* Launches the position adjoint of the frequency response for the fixed end point `fixed` on the ctx stream, for the current
+ * scene, candidate mask and grid.  For hard validity and image paths a position enters the response through the path length r
+ * alone (validity is piecewise constant, every fused path function is a function of r), and the interaction points are stationary
+ * (Fermat's principle): d r / d p[0] = -unit(p[1] - p[0]), d r / d p[K+1] = -unit(p[K] - p[K+1]).
+ * K3-X `d2d::PosGradSink`, definition:
+ *
+ * - `params`, `fixed`, the role of the grid, `inv_wavelength[nf]` (`1..D2D_FREQ_MAX` entries, each finite and `>= 0`) and `amplitude` are exactly as for `d2d_frequency_response_launch`.
+ * - The cotangent planes `re_bar`, `im_bar` are host arrays, fp32 `[nf][m][n]`. They are copied before the call returns.
+ * - The validity must be hard (`params.approx == 0`). Every fused `fun_id` is accepted.
+ * - The result is the gradient of `L`, for `dL = Σ (re_bar·dre + im_bar·dim)` with `re`, `im` those of `d2d_frequency_response_launch` for the same arguments. There are three outputs.
+ * - `cell_bar[2][m][n]`, fp32: the gradient with respect to the position of every cell. On an RX grid that is the receiver of that cell; on a TX grid the transmitter.
+ * - `fixed_terms[2][m][n]`, fp32: what each cell contributes to the gradient with respect to the fixed end point.
+ * - `fixed_bar[2]`, fp64: the sum of `fixed_terms` over the cells.
+ *
+ * All arithmetic is fp32, one rounding per stated operation, no contraction. `POS_CHUNK = D2D_POS_CHUNK = 8` is the number of wavelengths per pass. It is part of the definition. Per cell:
+ *
+ *     cell_bar = fixed_terms = (+0.0f, +0.0f)
+ *     for blocks of POS_CHUNK wavelengths, in list order:
+ *       for candidates in the sweep's enumeration order:
+ *         t = valid * fun ; r = path_length(points) ; dir = {p[1]-p[0], p[K]-p[K+1]}      // as the array response gets them
+ *         if (t == 0) continue                                                             // exact zeros of either sign
+ *         a   = amplitude == SQRT ? copysignf(sqrtf(fabsf(t)), t) : t
+ *         rho = RECEIVED_POWER, RECEIVED_POWER_PER_OBJECT: -(2.0f*r) / (h2 + r*r)          // (d fun/d r) / fun ; h2 as the sweep has it
+ *               LENGTH_SQUARED: 2.0f / r ;  LENGTH: 1.0f / r ;  ONE: +0.0f
+ *         kr  = amplitude == SQRT ? 0.5f * rho : rho                                       // (d a/d r) / a
+ *         g = +0.0f
+ *         for j in the block, in order:
+ *             u = r * inv[j] ; f0 = u - floorf(u) ; (c, s) = phasor(f0) ; w = TWO_PI * inv[j]     // TWO_PI = 6.2831855f
+ *             pr = kr*c - w*s ;  pi = kr*s + w*c            // d(a e^(-j2πr/λ))/dr = a (pr - j pi)
+ *             g  = g + (re_bar[j][cell]*pr - im_bar[j][cell]*pi)
+ *         G = a * g                                         // dL/dr of this path, this block
+ *         (ucx, ucy, okc) = unit_dir(direction at the cell's end) ; (ufx, ufy, okf) = unit_dir(direction at the fixed end)   // d2d_steer.hpp, unchanged
+ *         if (okc) { cell_bar.x    = cell_bar.x    - G*ucx ;  cell_bar.y    = cell_bar.y    - G*ucy }
+ *         if (okf) { fixed_terms.x = fixed_terms.x - G*ufx ;  fixed_terms.y = fixed_terms.y - G*ufy }
+ *     fixed_bar[d] = sum over cells of (double)fixed_terms[d][cell]      // fp64, a fixed order, no atomics
+ *
+ * - The direction at the cell's end is `dir[2..3]` on an RX grid and `dir[0..1]` on a TX grid. The fixed end takes the other pair.
+ * - The per-contribution arithmetic (`a`, `rho`, `kr`, the fold over `j`, `G`) is the text of `differt2d_amd/csrc/d2d_posgrad.hpp`.
+ * - A cell that no path reaches holds exactly `+0.0` in all four entries. A path without a direction at an end adds nothing at that end.
+ * - Non-finite cotangents are not refused. A NaN contribution makes that cell's entries NaN, and thereby `fixed_bar`, and no other cell's.
+ *
+ * cell_bar and fixed_terms are defined bit for bit (tests/field_position_vjp_oracle.py restates them in NumPy); fixed_bar is a fixed-
+ * order fp64 sum: the same bits run to run and whatever ran before on the context, within (cells - 1) * 2^-53 * sum |terms| of any
+ * other summation order.  All-zero cotangents give +0.0 in every bit of the three outputs, cotangents scaled by 2 exactly doubled
+ * outputs, and appending a wavelength whose two planes are zero changes no bit.
+ *
+ * One preparation of the culled sweep and ceil(nf / D2D_POS_CHUNK) passes of one kernel, as the frequency response does it: the
+ * cotangents of a block sit in registers, every lane keeps four accumulators that the four planes carry from one pass to the next,
+ * and a fixed-order reduction sums the two fixed_terms planes.  The launch touches none of: the resident value / gradient maps, the
+ * scene VJP of d2d_power_map_vg_launch, the work history, the other products' results.
+ * D2D_ERR_INVALID: a NULL argument; nf outside 1 .. D2D_FREQ_MAX; an inv_wavelength entry that is negative, NaN or infinite (the
+ * message names its index); an unknown amplitude.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): hard_sigmoid and sigmoid validity -- a smoothed validity depends on the
+ * positions itself, and its term needs the reverse chain of the value+grad sweep (d2d_power_map_vg_launch); a gradient that silently
+ * left that term out would be a trap, so it is refused, not approximated -- and what d2d_frequency_response_launch refuses, with
+ * 8 * nf + 16 bytes per cell held against half of the free device memory.  All decided before anything is enqueued; a refused launch
+ * leaves the previous result readable.
+ * Not computed: gradients with respect to wall end points, hard_sigmoid validity, the array, beam and material variants (where the
+ * angle of incidence also moves), gradients with respect to the wavelengths, more than one GPU. */
+int d2d_field_position_vjp_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                                  const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude,
+                                  const float* re_bar /* [nf][m][n] */, const float* im_bar /* [nf][m][n] */);
+/* Synchronises and copies the result of the last accepted d2d_field_position_vjp_launch to the arrays that are not NULL.
+ * D2D_ERR_STATE before a launch and after a d2d_set_grid / d2d_set_scene of another grid or scene (the result goes with both). */
+int d2d_get_field_position_vjp(d2d_ctx* ctx, float* cell_bar /* [2][m][n] or NULL */, float* fixed_terms /* [2][m][n] or NULL */,
+                               double* fixed_bar /* [2] or NULL */);
+/* The per-contribution arithmetic of d2d_posgrad.hpp on the device, for comparison with its host build: for every i,
+ * a = posgrad_amp(amplitude, t), rho = posgrad_rho(fun_id, h2, r), kr = posgrad_kr(amplitude, rho), g = the fold of posgrad_fold
+ * over (inv0, rb0, ib0) then (inv1, rb1, ib1) from +0, and G = a * g. */
+int d2d_selftest_posgrad(d2d_ctx* ctx, int32_t fun_id, int32_t amplitude, const float* t, const float* r, const float* h2, const float* inv0,
+                         const float* inv1, const float* rb0, const float* rb1, const float* ib0, const float* ib1, int64_t n, float* a,
+                         float* rho, float* kr, float* g, float* G);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
