@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/d2d.h"
+#include "d2d_chunks.hpp"
 
 namespace d2d_host {
 
@@ -309,7 +310,7 @@ inline int freq_params(const float* inv_wavelength, int32_t nf, int32_t amplitud
 // Per cell: nf planes of re and im and one total, 4 bytes each (outputs_fit; tests/native/frequency_response_host.cpp).
 inline size_t freq_bytes_per_cell(int32_t nf) { return 8 * (size_t)nf + 4; }
 // One pass of the sink kernel per FREQ_CHUNK wavelengths (chunk_plan).
-constexpr int32_t FREQ_CHUNK = 8;  // = d2d::FREQ_CHUNK (d2d_kernels.hpp)
+using d2d::FREQ_CHUNK;
 
 // ---- parameters, outputs and launch plan of the material response (d2d_material_response_launch, d2d::MaterialSink) ---
 // D2D_ERR_INVALID, in this order: what freq_params refuses (through it); a polarization that is neither D2D_POL_TE nor D2D_POL_TM; an
@@ -361,7 +362,7 @@ inline bool material_fits(size_t cells, int32_t nf, size_t n_objects, size_t mem
     return cells <= (budget - n_objects * per_object) / freq_bytes_per_cell(nf);
 }
 // One pass of the sink kernel per MAT_CHUNK wavelengths (chunk_plan).
-constexpr int32_t MAT_CHUNK = 8;  // = d2d::MAT_CHUNK (d2d_kernels.hpp)
+using d2d::MAT_CHUNK;
 
 // ---- memory of the frequency response's coefficient adjoint (d2d_field_coefs_vjp_launch, d2d::CoefGradSink) -----------
 // The cotangent planes take 8 nf bytes per cell and the partial rows 4 bytes per patch and object.  Refused like the frequency
@@ -474,7 +475,7 @@ inline size_t wide_bytes_per_cell(int32_t nf, int32_t nt, int32_t nr) {
     return 8 * (size_t)nf * (size_t)nr * (size_t)nt + 4;
 }
 // One pass of the sink kernel per WIDE_CHUNK wavelengths (chunk_plan), each adding into the plane blocks of its chunk.
-constexpr int32_t WIDE_CHUNK = 32;  // = d2d::WIDE_CHUNK (d2d_kernels.hpp)
+using d2d::WIDE_CHUNK;
 
 // ---- parameters, outputs and launch plan of the beam-space response (d2d_beam_response_launch, d2d::BeamSink) ---------
 // D2D_ERR_INVALID: what wide_params refuses, in its order (the list, the amplitude, the element counts and lists), then nbt, then nbr
@@ -511,7 +512,7 @@ inline size_t beam_bytes_per_cell(int32_t nf, int32_t nbt, int32_t nbr) {
     return 8 * (size_t)nf * (size_t)nbr * (size_t)nbt + 4;
 }
 // One pass of the sink kernel per BEAM_CHUNK wavelengths (chunk_plan), each adding into the plane blocks of its chunk.
-constexpr int32_t BEAM_CHUNK = 64;  // = d2d::BEAM_CHUNK (d2d_kernels.hpp)
+using d2d::BEAM_CHUNK;
 
 // ---- scalar thresholds of a sweep launch (d2d::SweepArgs) -----------------------------------------------------------
 enum SweepMode { SWEEP_HARD = 0, SWEEP_HSIG = 1, SWEEP_SIG = 2 };  // = d2d::Mode (d2d_kernels.hpp)

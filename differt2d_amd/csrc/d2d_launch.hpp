@@ -20,8 +20,6 @@ template <int MODE> hipError_t launch_fwd_listed_m(bool stats, int max_order, di
 template <int MODE> hipError_t launch_fwd_grad_listed_m(int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <int MODE> hipError_t launch_fwd_split_listed_m(bool stats, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
 template <int MODE> hipError_t launch_fwd_coop_m(int max_order, int W, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a);
-template <int MODE, class Sink>
-hipError_t launch_sink_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const typename Sink::Args& x);
 #define D2D_DECLARE_MODE(M)                                                                                      \
     template <> hipError_t launch_fwd_m<M>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&);              \
     template <> hipError_t launch_fwd_grad_m<M>(int, dim3, size_t, hipStream_t, const SweepArgs&);               \
@@ -36,27 +34,7 @@ D2D_DECLARE_MODE(MODE_HARD)
 D2D_DECLARE_MODE(MODE_HSIG)
 D2D_DECLARE_MODE(MODE_SIG)
 #undef D2D_DECLARE_MODE
-// The sinks of power_sink_kernel (d2d_kernels.hpp), stated once: this list declares the per-mode launchers here and defines them
-// in d2d_sweep_tu.hip.  A new sink is one more line.  (Hard and hard_sigmoid only: launch_sink answers hipErrorInvalidValue otherwise.)
-#define D2D_SINKS(X)                                                                                          \
-    X(RecSink)       /* the record build (d2d_valid_paths) */                                                 \
-    X(BinSink)       /* the per-cell power-delay profile */                                                   \
-    X(TopSink)       /* the per-cell strongest paths */                                                       \
-    X(FieldSink)     /* the coherent field */                                                                 \
-    X(FreqSink)      /* the frequency response */                                                             \
-    X(CoefGradSink)  /* its adjoint w.r.t. the per-object reflection coefficients */                          \
-    X(AngleSink)     /* the power-angle profile */                                                            \
-    X(ArraySink)     /* the array response */                                                                 \
-    X(ArrayFreqSink) /* the wideband array response */                                                        \
-    X(BeamSink)      /* the beam-space response */                                                            \
-    X(MaterialSink)  /* the frequency response with Fresnel reflection per wall */                           \
-    X(EpsGradSink)   /* its adjoint w.r.t. the walls' permittivities */                                       \
-    X(PosGradSink)   /* the frequency response's adjoint w.r.t. the cell's and the fixed end point's position */
-#define D2D_DECLARE_SINK(S)                                                                                                      \
-    template <> hipError_t launch_sink_m<MODE_HARD, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&); \
-    template <> hipError_t launch_sink_m<MODE_HSIG, S>(bool, int, dim3, size_t, hipStream_t, const SweepArgs&, const S::Args&);
-D2D_SINKS(D2D_DECLARE_SINK)
-#undef D2D_DECLARE_SINK
+// (The sink kernel's launchers, launch_sink_m / launch_sink over D2D_SINKS, are declared with the sinks: d2d_sinks.hpp.)
 
 // ---- by-mode dispatchers ----
 // `listed`: the LISTED build (orders >= 2 from the region candidate lists, a.rl); otherwise the enumerating build, which
@@ -74,9 +52,6 @@ hipError_t launch_fwd_coop(int mode, int max_order, int W, dim3 grid, size_t lds
 hipError_t launch_txg(int mode, bool listed, bool grad, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
 // power_vg_kernel<MODE, TXG, GRADK>: exhaustive sweeps (strict_nan value+grad; "txg_exhaustive" values)
 hipError_t launch_vg(int mode, bool txg, bool grad, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a);
-// power_sink_kernel<MODE, MAXK, TXG, Sink>: the culled sweep into one of D2D_SINKS (any other mode: hipErrorInvalidValue)
-template <class Sink>
-hipError_t launch_sink(int mode, bool txg, int max_order, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const typename Sink::Args& x);
 
 // region_list_kernel<K, false, TXG>: candidate lists of order K (2..4) of level `lv` by enumeration; grid = regions x slices
 hipError_t launch_region_lists(int K, bool txg, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs& a, const RegionLevel& lv,

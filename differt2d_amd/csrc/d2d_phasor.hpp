@@ -19,9 +19,28 @@
 //
 // Accuracy over [0, 1), against float64 cos / sin of 2 pi f: the absolute error stays below 2 * 2^-24 (measured maximum
 // 1.64 * 2^-24; most of it is the rounding of 2 pi to 6.2831853f and of x, 0.37 and 0.5 units at |x| = pi / 4).
+//
+// Beside it, the two values every coherent sink forms from a contribution t and its path length r in front of the phasor:
+//   field_amp(root, t)      a = root ? copysignf(sqrtf(fabsf(t)), t) : t      the amplitude: sign(t) sqrt|t| in the SQRT mode, t itself in LINEAR
+//   turn_fraction(r, inv)   u = r * inv ;  f = u - floorf(u)                  the phase in turns: exact and in [0, 1) for every finite u >= 0, NaN otherwise
 #pragma once
 
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define D2D_PHASOR_FN __host__ __device__ __attribute__((always_inline)) inline
+#else
+#define D2D_PHASOR_FN __attribute__((always_inline)) inline
+#endif
+
 namespace d2d {
+
+D2D_PHASOR_FN float field_amp(bool root, float t) { return root ? copysignf(sqrtf(fabsf(t)), t) : t; }
+
+D2D_PHASOR_FN float turn_fraction(float r, float inv) {
+    const float u = r * inv;
+    return u - floorf(u);
+}
 
 constexpr float PHASOR_TWO_PI = 6.2831853f;
 // 1/9!, -1/7!, 1/5!, -1/3!  and  -1/10!, 1/8!, -1/6!, 1/4!, -1/2!  (decimal literals, so that any restatement reads the same fp32)

@@ -43,7 +43,7 @@ constexpr int POS_CHUNK = D2D_POS_CHUNK;  // wavelengths per pass: part of the d
 constexpr float POSGRAD_TWO_PI = 6.2831855f;
 
 // the amplitude of a contribution: the frequency response's own
-D2D_POSGRAD_FN float posgrad_amp(int amplitude, float t) { return amplitude == D2D_FIELD_AMP_SQRT ? copysignf(sqrtf(fabsf(t)), t) : t; }
+D2D_POSGRAD_FN float posgrad_amp(int amplitude, float t) { return field_amp(amplitude == D2D_FIELD_AMP_SQRT, t); }
 
 // (d fun / d r) / fun of the fused path functions
 D2D_POSGRAD_FN float posgrad_rho(int fun_id, float h2, float r) {
@@ -62,10 +62,8 @@ D2D_POSGRAD_FN float posgrad_kr(int amplitude, float rho) { return amplitude == 
 
 // one wavelength's step of the fold: g + (rb * pr - ib * pi)
 D2D_POSGRAD_FN float posgrad_fold(float g, float kr, float r, float inv, float rb, float ib) {
-    const float u = r * inv;
-    const float f0 = u - floorf(u);
     float c, s;
-    phasor(f0, c, s);
+    phasor(turn_fraction(r, inv), c, s);
     const float w = POSGRAD_TWO_PI * inv;
     const float krc = kr * c, ws = w * s, krs = kr * s, wc = w * c;
     const float pr = krc - ws, pi = krs + wc;

@@ -2,12 +2,15 @@
 // per-mode launcher (declared in d2d_launch.hpp) that d2d.hip's dispatchers call.  Compiled by the Makefile with
 //   -DD2D_TU_FAMILY={0 fwd, 1 fwd_grad, 2 fwd_split, 3 txg, 4 vg, 6 fwd / 7 fwd_grad / 8 fwd_split with the orders >= 2
 //   taken from the region lists (LISTED), 9 fwd_coop}  -DD2D_TU_MODE={0 hard, 1 hard_sigmoid, 2 sigmoid}: all 27 pairs;
-//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0), 11 the sink kernel (every sink of D2D_SINKS, d2d_launch.hpp) for modes 0 and 1 (no sigmoid instance)
+//   5 region lists and 10 NaN scan once each (-DD2D_TU_MODE=0);
+//   11 the sink kernel, one object per sink of D2D_SINKS (d2d_sinks.hpp) and mode 0 or 1 (no sigmoid instance): -DD2D_TU_SINK=<Sink>
 #include <type_traits>
 
 #include "d2d_launch.hpp"
 #if D2D_TU_FAMILY == 10
 #include "d2d_nanscan.hpp"
+#elif D2D_TU_FAMILY == 11
+#include "d2d_sinks.hpp"
 #endif
 
 #ifndef D2D_TU_FAMILY
@@ -167,13 +170,16 @@ static hipError_t launch_sink_tu(bool txg, int max_order, dim3 grid, size_t lds,
     else by_maxk(max_order, [&](auto K) { hipLaunchKernelGGL((power_sink_kernel<TU_MODE, decltype(K)::value, false, Sink>), grid, block, lds, s, a, x); });
     return hipGetLastError();
 }
-#define D2D_DEFINE_SINK(S)                                                                                                                      \
-    template <>                                                                                                                                 \
-    hipError_t launch_sink_m<TU_MODE, S>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const S::Args& x) { \
-        return launch_sink_tu<S>(txg, max_order, grid, lds, s, a, x);                                                                           \
-    }
-D2D_SINKS(D2D_DEFINE_SINK)
-#undef D2D_DEFINE_SINK
+#ifndef D2D_TU_SINK
+#error "family 11 is one object per sink: compile with -DD2D_TU_SINK=<a sink of D2D_SINKS>"
+#endif
+#define D2D_IS_TU_SINK(S) || std::is_same_v<S, D2D_TU_SINK>
+static_assert(false D2D_SINKS(D2D_IS_TU_SINK), "D2D_TU_SINK is not in D2D_SINKS (d2d_sinks.hpp): the Makefile's SINKS and that list disagree");
+#undef D2D_IS_TU_SINK
+template <>
+hipError_t launch_sink_m<TU_MODE, D2D_TU_SINK>(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const D2D_TU_SINK::Args& x) {
+    return launch_sink_tu<D2D_TU_SINK>(txg, max_order, grid, lds, s, a, x);
+}
 #else
 #error "unknown D2D_TU_FAMILY"
 #endif

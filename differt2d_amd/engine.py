@@ -161,6 +161,27 @@ def _keep_pointer(a: np.ndarray, *shape) -> np.ndarray:
     return a if a.size else np.zeros(shape, np.float32)
 
 
+def _permittivity_table(method: str, permittivity, nf: int) -> np.ndarray:
+    """The permittivities as contiguous complex64 ``[nf, N]``: ``[N]`` stands for equal rows; any other shape is refused here."""
+    eps = np.asarray(permittivity)
+    if eps.ndim == 1:
+        eps = np.broadcast_to(eps, (max(nf, 1), eps.size))
+    if eps.ndim != 2 or eps.shape[0] != max(nf, 1):
+        raise L.D2DError(-1, f"{method}: permittivity must be complex [N] or [nf, N] with nf = {nf}, got shape {tuple(eps.shape)}")
+    return np.ascontiguousarray(eps, dtype=np.complex64)
+
+
+def _cotangent_planes(method: str, re_bar, im_bar, nf: int, shape, keep: np.ndarray):
+    """The cotangents of a response's planes as contiguous fp32 ``[nf, m, n]``, refused here when either has another shape (without
+    a grid, ``shape`` empty, the library refuses before it reads anything); an empty list hands the library ``keep`` in their place."""
+    rb = np.ascontiguousarray(re_bar, dtype=np.float32)
+    ib = np.ascontiguousarray(im_bar, dtype=np.float32)
+    planes = (nf,) + tuple(shape or ())
+    if nf and shape and (rb.shape != planes or ib.shape != planes):
+        raise L.D2DError(-1, f"{method}: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
+    return (rb, ib) if nf else (keep, keep)
+
+
 def _beam_weights(name: str, w, n: int) -> np.ndarray:
     """A codebook as contiguous complex64 ``[nb, n]``: ``[n]`` is one beam; any other shape is refused here (the library sees only
     counts).  An empty codebook stays empty: the library refuses a count of 0 itself."""
@@ -771,15 +792,19 @@ class Context:
                                                         amplitude))
         self._freq_nf = int(inv.size)
 
+    def _read_frequency_response(self, getter, nf: int) -> "FrequencyResponse":
+        """``nf`` planes ``re`` / ``im`` and ``total`` of the resident grid's shape, filled by ``getter``."""
+        shape = tuple(self.shape)
+        planes = (nf,) + shape
+        fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
+        L.check(getter(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
+        return fr
+
     def get_frequency_response(self) -> "FrequencyResponse":
         """Synchronises and returns the result of the last :meth:`launch_frequency_response`."""
         if not self._freq_nf:
             _no_result(self._ctx, self._lib.d2d_get_frequency_response, "launch_frequency_response", None, None, None)
-        shape = tuple(self.shape)
-        planes = (self._freq_nf,) + shape
-        fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
-        L.check(self._lib.d2d_get_frequency_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
-        return fr
+        return self._read_frequency_response(self._lib.d2d_get_frequency_response, self._freq_nf)
 
     def material_response(self, params: L.Params, fixed, inv_wavelengths, permittivity, polarization="te",
                           amplitude="sqrt") -> "FrequencyResponse":
@@ -809,12 +834,7 @@ class Context:
         refused launch leaves the previous result readable."""
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
-        eps = np.asarray(permittivity)
-        if eps.ndim == 1:
-            eps = np.broadcast_to(eps, (max(int(inv.size), 1), eps.size))
-        if eps.ndim != 2 or eps.shape[0] != max(int(inv.size), 1):
-            raise L.D2DError(-1, f"material_response: permittivity must be complex [N] or [nf, N] with nf = {inv.size}, got shape {tuple(eps.shape)}")
-        eps = np.ascontiguousarray(eps, dtype=np.complex64)
+        eps = _permittivity_table("material_response", permittivity, int(inv.size))
         amplitude = _amplitude_id("material_response", amplitude)
         polarization = _polarization_id("material_response", polarization)
         keep, table = _keep_pointer(inv, 1), _keep_pointer(eps.view(np.float32), 2)
@@ -826,11 +846,7 @@ class Context:
         """Synchronises and returns the result of the last :meth:`launch_material_response` that was accepted."""
         if not self._mat_nf:
             _no_result(self._ctx, self._lib.d2d_get_material_response, "launch_material_response", None, None, None)
-        shape = tuple(self.shape)
-        planes = (self._mat_nf,) + shape
-        fr = FrequencyResponse(re=np.empty(planes, np.float32), im=np.empty(planes, np.float32), total=np.empty(shape, np.float32))
-        L.check(self._lib.d2d_get_material_response(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in fr)))
-        return fr
+        return self._read_frequency_response(self._lib.d2d_get_material_response, self._mat_nf)
 
     def material_eps_vjp(self, params: L.Params, fixed, inv_wavelengths, permittivity, re_bar, im_bar, polarization="te",
                          amplitude="sqrt") -> np.ndarray:
@@ -856,22 +872,11 @@ class Context:
         asynchronous, like :meth:`launch`)."""
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
-        eps = np.asarray(permittivity)
-        if eps.ndim == 1:
-            eps = np.broadcast_to(eps, (max(int(inv.size), 1), eps.size))
-        if eps.ndim != 2 or eps.shape[0] != max(int(inv.size), 1):
-            raise L.D2DError(-1, f"material_eps_vjp: permittivity must be complex [N] or [nf, N] with nf = {inv.size}, got shape {tuple(eps.shape)}")
-        eps = np.ascontiguousarray(eps, dtype=np.complex64)
+        eps = _permittivity_table("material_eps_vjp", permittivity, int(inv.size))
         amplitude = _amplitude_id("material_eps_vjp", amplitude)
         polarization = _polarization_id("material_eps_vjp", polarization)
-        rb = np.ascontiguousarray(re_bar, dtype=np.float32)
-        ib = np.ascontiguousarray(im_bar, dtype=np.float32)
-        planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
-        if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
-            raise L.D2DError(-1, f"material_eps_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
         keep, table = _keep_pointer(inv, 1), _keep_pointer(eps.view(np.float32), 2)
-        if not inv.size:
-            rb = ib = keep
+        rb, ib = _cotangent_planes("material_eps_vjp", re_bar, im_bar, int(inv.size), self.shape, keep)
         L.check(self._lib.d2d_material_eps_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size), amplitude,
                                                       polarization, table.ctypes.data_as(C.c_void_p), int(eps.shape[1]),
                                                       rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
@@ -907,14 +912,8 @@ class Context:
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
         amplitude = _amplitude_id("field_coefs_vjp", amplitude)
-        rb = np.ascontiguousarray(re_bar, dtype=np.float32)
-        ib = np.ascontiguousarray(im_bar, dtype=np.float32)
-        planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
-        if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
-            raise L.D2DError(-1, f"field_coefs_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
         keep = _keep_pointer(inv, 1)
-        if not inv.size:
-            rb = ib = keep
+        rb, ib = _cotangent_planes("field_coefs_vjp", re_bar, im_bar, int(inv.size), self.shape, keep)
         L.check(self._lib.d2d_field_coefs_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
                                                      amplitude, rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
 
@@ -949,14 +948,8 @@ class Context:
         fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
         inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
         amplitude = _amplitude_id("field_position_vjp", amplitude)
-        rb = np.ascontiguousarray(re_bar, dtype=np.float32)
-        ib = np.ascontiguousarray(im_bar, dtype=np.float32)
-        planes = (int(inv.size),) + tuple(self.shape or ())  # (without a grid the library refuses before it reads anything)
-        if inv.size and self.shape and (rb.shape != planes or ib.shape != planes):
-            raise L.D2DError(-1, f"field_position_vjp: re_bar and im_bar must have the shape {planes} of the response's planes, got {rb.shape} and {ib.shape}")
         keep = _keep_pointer(inv, 1)
-        if not inv.size:
-            rb = ib = keep
+        rb, ib = _cotangent_planes("field_position_vjp", re_bar, im_bar, int(inv.size), self.shape, keep)
         L.check(self._lib.d2d_field_position_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
                                                         amplitude, rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
 
