@@ -6,6 +6,8 @@ them exactly, shared end points (corners), tiny / huge scales, offsets, patch, a
 usage: python scripts/fuzz_parity.py [n_cases] [seed] [big]
        python scripts/fuzz_parity.py --grad [n_cases] [seed]     value + gradient: the DEFAULT (culled) sweep and, every fourth
                                                                  case, the exhaustive one against oracle/d2d_oracle_grad.c
+       --warp (after --grad, if given) replaces every case's mesh by a grid that is none (warp_grid): scrambled, sheared and
+       rotated, reversed, or with a band of 8 rows collapsed into one cell -- the oracle is per cell and takes any of them
 """
 
 import os
@@ -59,6 +61,51 @@ def random_case(rng, big=False):
     if n and rng.random() < 0.25:
         allowed = (rng.random(n) < 0.7).astype(np.uint8)
     return walls, tx, X, Y, kw, allowed
+
+
+WARPS = ("scramble", "shear", "reverse", "collapse")
+
+
+def warp_grid(X, Y, kind, seed):
+    """The mesh ``X, Y`` as a grid that is no mesh (same shape, float32): ``scramble`` permutes the cells, ``shear`` shears the
+    grid and turns it about its centre, ``reverse`` reverses rows and / or columns, ``collapse`` sets one band of 8 rows (fewer on a
+    short grid) to one of its cells.  Draws from a generator of its OWN, seeded by ``seed`` (a sequence such as ``(seed, case)``):
+    the stream that ``random_case(rng)`` consumes is the same with and without a warp."""
+    own = np.random.default_rng(seed)
+    X, Y = np.asarray(X, F), np.asarray(Y, F)
+    m, n = X.shape
+    if kind == "scramble":
+        p = own.permutation(X.size)
+        X, Y = X.reshape(-1)[p].reshape(m, n), Y.reshape(-1)[p].reshape(m, n)
+    elif kind == "shear":
+        cx, cy = 0.5 * (float(X.min()) + float(X.max())), 0.5 * (float(Y.min()) + float(Y.max()))
+        u, v = X.astype(np.float64) - cx, Y.astype(np.float64) - cy
+        th, k = own.uniform(0.0, 2.0 * np.pi), own.uniform(-0.5, 0.5)
+        c, s_ = np.cos(th), np.sin(th)
+        X, Y = cx + c * (u + k * v) - s_ * v, cy + s_ * (u + k * v) + c * v
+    elif kind == "reverse":
+        rows, cols = [(True, False), (False, True), (True, True)][int(own.integers(0, 3))]
+        X, Y = X[::-1 if rows else 1, ::-1 if cols else 1], Y[::-1 if rows else 1, ::-1 if cols else 1]
+    elif kind == "collapse":
+        r0 = int(own.integers(0, max(1, m - 7)))
+        r, c_ = int(own.integers(r0, min(m, r0 + 8))), int(own.integers(0, n))
+        X, Y = X.copy(), Y.copy()
+        X[r0:r0 + 8], Y[r0:r0 + 8] = X[r, c_], Y[r, c_]
+    else:
+        raise ValueError(f"unknown warp {kind!r}")
+    return np.ascontiguousarray(X, F), np.ascontiguousarray(Y, F)
+
+
+def warp_case(X, Y, seed, case):
+    """(--warp) the case's grid under the warp its number picks."""
+    return warp_grid(X, Y, WARPS[case % len(WARPS)], (seed, case))
+
+
+def forward_matches(got, want, kw):
+    """The forward sweep's rule: bit for bit, NaN for NaN; sigmoid within rtol 2e-5 and 1e-5 of the largest value (at least 1)."""
+    if kw["function"] == "sigmoid" and kw["approx"]:
+        return bool(np.allclose(got, want, rtol=2e-5, atol=1e-5 * max(1.0, float(np.nanmax(np.abs(want)))), equal_nan=True))
+    return bool(np.array_equal(got, want, equal_nan=True))
 
 
 def crowded_case(rng, budget=None, sigmoid=True):
@@ -172,6 +219,8 @@ KINK_MASK = True  # (cells where the oracle met a min / max tie between argument
 
 
 def main_grad(argv):
+    warp = bool(argv) and argv[0] == "--warp"
+    argv = argv[1:] if warp else argv
     n_cases = int(argv[0]) if len(argv) > 0 else 200
     seed = int(argv[1]) if len(argv) > 1 else 0
     rng = np.random.default_rng(seed)
@@ -188,6 +237,8 @@ def main_grad(argv):
                 X, Y = X[:40, :40], Y[:40, :40]
             if not crowded:
                 kw["fun"] = str(rng.choice(["received_power", "one", "length", "length_squared"]))
+            if warp:
+                X, Y = warp_case(X, Y, seed, case)
             role = L.GRID_TX if case % 3 == 2 else L.GRID_RX
             ctx.set_scene(walls)
             ctx.set_candidate_mask(allowed)
@@ -205,16 +256,19 @@ def main_grad(argv):
                       f"grid={X.shape} kw={kw} allowed={allowed is not None}: " + "; ".join(msgs), flush=True)
             if case % 200 == 199:
                 print(f"  .. {case + 1} cases, {bad} mismatches, {cells} cells compared, {nans} NaN cells, {time.time() - t0:.0f} s", flush=True)
-    print(f"grad fuzz: {n_cases} cases, {bad} mismatches, {cells} gradient cells compared, {nans} NaN cells, {time.time() - t0:.1f} s (seed {seed})")
+    print(f"grad fuzz{' (warped grids)' if warp else ''}: {n_cases} cases, {bad} mismatches, {cells} gradient cells compared, {nans} NaN cells, "
+          f"{time.time() - t0:.1f} s (seed {seed})")
     sys.exit(1 if bad else 0)
 
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--grad":
         return main_grad(sys.argv[2:])
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    big = len(sys.argv) > 3 and sys.argv[3] == "big"  # every other case has 65..139 walls
+    warp = len(sys.argv) > 1 and sys.argv[1] == "--warp"
+    argv = sys.argv[2:] if warp else sys.argv[1:]
+    n_cases = int(argv[0]) if len(argv) > 0 else 200
+    seed = int(argv[1]) if len(argv) > 1 else 0
+    big = len(argv) > 2 and argv[2] == "big"  # every other case has 65..139 walls
     rng = np.random.default_rng(seed)
     bad = 0
     t0 = time.time()
@@ -222,6 +276,8 @@ def main():
         ctx.set_option("hidden_min_tiles", 0)  # (the last-segment masks on grids this small too)
         for case in range(n_cases):
             walls, tx, X, Y, kw, allowed = random_case(rng, big=big and case % 2 == 1)
+            if warp:
+                X, Y = warp_case(X, Y, seed, case)
             ctx.set_scene(walls)
             ctx.set_candidate_mask(allowed)
             # every launch shape: patches shared between 4 waves or one wave each, identity or dearest-first order
@@ -242,11 +298,7 @@ def main():
             # second launch in a row that would use them) -- same bits
             again = ctx.power_map(tx, X, Y, grid_role=L.GRID_TX if role_tx else L.GRID_RX, **kw)
             want = CO.power_map(walls, tx, X, Y, allowed=allowed, prune=True, grid_role="tx" if role_tx else "rx", **kw)
-            if kw["function"] == "sigmoid" and kw["approx"]:
-                ok = np.allclose(got, want, rtol=2e-5, atol=1e-5 * max(1.0, float(np.nanmax(np.abs(want)))), equal_nan=True)
-            else:
-                ok = np.array_equal(got, want, equal_nan=True)
-            ok = ok and np.array_equal(got, again, equal_nan=True)
+            ok = forward_matches(got, want, kw) and np.array_equal(got, again, equal_nan=True)
             if case % 10 == 9 and not role_tx and len(walls):
                 # the instrumented build (d2d_power_map_stats) writes the product kernels' map, bit for bit
                 from differt2d_amd.engine import make_params
@@ -257,7 +309,7 @@ def main():
                 d = np.abs(got - want)
                 print(f"MISMATCH case {case} seed {seed} {'TX' if role_tx else 'RX'}-grid: N={len(walls)} grid={X.shape} kw={kw} allowed={allowed is not None} "
                       f"cells={int((~np.isclose(got, want, rtol=0, atol=0, equal_nan=True)).sum())} max={np.nanmax(d)}", flush=True)
-    print(f"fuzz: {n_cases} cases, {bad} mismatches, {time.time() - t0:.1f} s (seed {seed})")
+    print(f"fuzz{' (warped grids)' if warp else ''}: {n_cases} cases, {bad} mismatches, {time.time() - t0:.1f} s (seed {seed})")
     sys.exit(1 if bad else 0)
 
 

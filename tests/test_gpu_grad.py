@@ -486,38 +486,52 @@ def test_lattice_scenes_against_the_c_gradient_oracle(ctx):
         role = "tx" if case % 2 else "rx"
         kw = dict(min_order=0, max_order=2, approx=approx, function=function, fun=fun, alpha=float(rng.choice([100.0, 16.0])))
         value, grad, gabs, kink = CO.power_map_grad(walls, tx, X, Y, grid_role=role, with_gabs=True, with_kink=True, **kw)
-        # Which cells have a gradient worth comparing -- decided by the oracle alone: its own result must survive a nudge of
-        # the fixed end point and of the cell by one ulp.  (A lattice scene puts end points ON walls' lines: the interaction
-        # points are then rounding noise, fp32 and fp64 autodiff of oracle/ref.py disagree in the first digit, and so do any
-        # two fp32 evaluation orders.)
-        up = lambda a: np.nextafter(np.asarray(a, F), F(np.inf))
-        stable = np.ones(X.shape, bool)
-        for tx2, X2, Y2 in ((up(tx), X, Y), (tx, up(X), up(Y))):
-            v2, g2 = CO.power_map_grad(walls, tx2, X2, Y2, grid_role=role, **kw)
-            with np.errstate(invalid="ignore"):
-                stable &= np.abs(v2 - value) <= 1e-3 * np.abs(value) + 1e-9
-                stable &= (np.abs(g2 - grad) <= 1e-2 * gabs[..., None] + 1e-9).all(-1)
+        stable = _stable_under_one_ulp(walls, tx, X, Y, value, grad, gabs, role, kw)
         ctx.set_scene(walls)
         for strict in (False, True):
             got = ctx.value_and_grads(tx, X, Y, strict_nan=strict, grid_role=L.GRID_TX if role == "tx" else L.GRID_RX, **kw)
-            if function == "sigmoid":
-                np.testing.assert_allclose(got["value"], value, rtol=1e-6, atol=1e-7)
-            else:
-                assert np.array_equal(got["value"], value, equal_nan=True), (case, strict)
-            g = got["grad_rx"].astype(np.float64)
-            assert np.array_equal(np.isnan(g), np.isnan(grad)), (case, strict, kw, role, int(np.isnan(g).sum()), int(np.isnan(grad).sum()))
-            # Gradients: wherever the oracle met no tie of a minimum / maximum between arguments with different tangents.
-            # (At such a kink JAX returns the mean of the two one-sided derivatives; the image-method kernel sends the
-            # cotangent to the first of the equal arguments -- DESIGN.md, "known deviations" -- and a lattice scene is
-            # made of kinks.)  sigmoid at alpha = 100 amplifies every rounding of its argument: a wider bar there.
-            fin = np.isfinite(grad).all(-1) & np.isfinite(g).all(-1) & ~kink & stable
-            rel = 3e-4 if function == "sigmoid" else 1e-5
-            bar = rel * gabs[..., None] + rel * np.abs(grad) + 1e-6
-            bad = (np.abs(g - grad) > bar).any(-1) & fin
-            assert not bad.any(), (case, strict, kw, role, int(bad.sum()), np.argwhere(bad)[:3].tolist())
-            checked += int(fin.sum())
+            checked += _held_to_the_gradient_oracle(got, value, grad, gabs, kink, stable, function, (case, strict, kw, role))
         nan_seen += int(np.isnan(grad).any(-1).sum())
     assert nan_seen > 20 and checked > 2000
+
+
+def _stable_under_one_ulp(walls, tx, X, Y, value, grad, gabs, role, kw):
+    """Which cells have a gradient worth comparing -- decided by the oracle alone: its own result must survive a nudge of
+    the fixed end point and of the cell by one ulp.  (A lattice scene puts end points ON walls' lines: the interaction
+    points are then rounding noise, fp32 and fp64 autodiff of oracle/ref.py disagree in the first digit, and so do any
+    two fp32 evaluation orders.)"""
+    from oracle import c_oracle as CO
+
+    up = lambda a: np.nextafter(np.asarray(a, F), F(np.inf))
+    stable = np.ones(X.shape, bool)
+    for tx2, X2, Y2 in ((up(tx), X, Y), (tx, up(X), up(Y))):
+        v2, g2 = CO.power_map_grad(walls, tx2, X2, Y2, grid_role=role, **kw)
+        with np.errstate(invalid="ignore"):
+            stable &= np.abs(v2 - value) <= 1e-3 * np.abs(value) + 1e-9
+            stable &= (np.abs(g2 - grad) <= 1e-2 * gabs[..., None] + 1e-9).all(-1)
+    return stable
+
+
+def _held_to_the_gradient_oracle(got, value, grad, gabs, kink, stable, function, tag):
+    """The rule of ``test_lattice_scenes_against_the_c_gradient_oracle`` (tests/test_gpu_irregular_grids.py holds other grids to
+    it): values by bits (sigmoid: rtol 1e-6, atol 1e-7), NaN positions identical, gradients within the bar below.  Returns the
+    number of cells whose gradient was compared."""
+    if function == "sigmoid":
+        np.testing.assert_allclose(got["value"], value, rtol=1e-6, atol=1e-7)
+    else:
+        assert np.array_equal(got["value"], value, equal_nan=True), tag
+    g = got["grad_rx"].astype(np.float64)
+    assert np.array_equal(np.isnan(g), np.isnan(grad)), (tag, int(np.isnan(g).sum()), int(np.isnan(grad).sum()))
+    # Gradients: wherever the oracle met no tie of a minimum / maximum between arguments with different tangents.
+    # (At such a kink JAX returns the mean of the two one-sided derivatives; the image-method kernel sends the
+    # cotangent to the first of the equal arguments -- DESIGN.md, "known deviations" -- and a lattice scene is
+    # made of kinks.)  sigmoid at alpha = 100 amplifies every rounding of its argument: a wider bar there.
+    fin = np.isfinite(grad).all(-1) & np.isfinite(g).all(-1) & ~kink & stable
+    rel = 3e-4 if function == "sigmoid" else 1e-5
+    bar = rel * gabs[..., None] + rel * np.abs(grad) + 1e-6
+    bad = (np.abs(g - grad) > bar).any(-1) & fin
+    assert not bad.any(), (tag, int(bad.sum()), np.argwhere(bad)[:3].tolist())
+    return int(fin.sum())
 
 
 def _tight(got, want, want32, name, report):
