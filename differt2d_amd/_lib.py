@@ -176,6 +176,9 @@ SYMBOLS = [
     ("d2d_field_position_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ("d2d_get_field_position_vjp", C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("d2d_selftest_posgrad", C.c_int, [_ctx, C.c_int32, C.c_int32] + [_f32p] * 9 + [C.c_int64] + [_f32p] * 5),
+    ("d2d_field_walls_vjp_launch", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("d2d_get_field_walls_vjp", C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
+    ("d2d_selftest_wallgrad", C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int64] + [_f32p] * 5),
     ("d2d_set_theta0", C.c_int, [_ctx, C.c_void_p, C.c_int64]),
     ("d2d_comm_unique_id", C.c_int, [C.c_void_p]),
     ("d2d_comm_init", C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32]),

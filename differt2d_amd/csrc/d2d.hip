@@ -280,8 +280,19 @@ struct d2d_ctx {
         void forget() { have = false; }
         void drop() { re.release(); im.release(); cell.release(); terms.release(); part.release(); out.release(); forget(); }
     } pg;
+    // wall adjoint of the frequency response (d2d_field_walls_vjp_launch): the cotangent planes, the per-patch rows and the reduced
+    // result, kept until the next accepted launch; the scene forgets it too
+    struct WallGrad {
+        DevBuf<float> re, im;    // [nf][m][n] each: the caller's cotangents
+        DevBuf<float> partial;   // [patches][N][2]
+        DevBuf<double> out;      // [N][2]: normal_bar
+        bool have = false;       // out holds the result of an accepted launch for the CURRENT grid and scene
+        size_t bytes() const { return (re.n + im.n + partial.n) * sizeof(float); }
+        void forget() { have = false; }
+        void drop() { re.release(); im.release(); partial.release(); out.release(); forget(); }
+    } wg;
     void drop_products() {  // every one of them goes with the grid
-        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop(); eg.drop(); pg.drop();
+        prof.drop(); top.drop(); field.drop(); freq.drop(); angle.drop(); array.drop(); cg.drop(); wide.drop(); beam.drop(); mat.drop(); eg.drop(); pg.drop(); wg.drop();
     }
     void drop_records() {
         d_rec_counts.release(); d_rec_offs.release(); d_rec_cell.release(); d_rec_cand.release(); d_rec_order.release();
@@ -834,6 +845,7 @@ int d2d_set_scene(d2d_ctx* c, const float* xys, const uint8_t* kind, const float
     c->mat.forget();              // (... and the material response, whose table has one entry per wall)
     c->eg.forget();               // (... and its permittivity adjoint)
     c->pg.forget();               // (... and the frequency response's position adjoint: its paths are the previous scene's)
+    c->wg.forget();               // (... and its wall adjoint: one row per wall of the previous scene)
     c->have_kernel_time = false;
     c->for_each_set([](d2d_ctx::PrepSet& sp) { sp.cost_tiles = 0; });  // the patch-cost history describes another sweep
     c->pair_valid = false;
@@ -2333,6 +2345,7 @@ constexpr SinkProduct WIDE = {"d2d_array_frequency_response_launch", "a host fun
 constexpr SinkProduct MATERIAL = {"d2d_material_response_launch", "a host function's response: add the phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths, each times its walls' Fresnel coefficients", "the response is always overwritten", LATE};
 constexpr SinkProduct EPS_VJP = {"d2d_material_eps_vjp_launch", "a host function has no permittivities", "the gradient is always overwritten", LATE};
 constexpr SinkProduct POS_VJP = {"d2d_field_position_vjp_launch", "a host function's derivative with respect to the path length is not known to the library", "the gradient is always overwritten", LATE};
+constexpr SinkProduct WALL_VJP = {"d2d_field_walls_vjp_launch", "a host function's derivative with respect to the path length is not known to the library", "the gradient is always overwritten", LATE};
 constexpr SinkProduct BEAM = {"d2d_beam_response_launch", "a host function's beam response: add the beamformed phasors of the paths that d2d_trace_paths gives for the records of d2d_valid_paths", "the beam response is always overwritten", LATE};
 
 // What the products refuse of the caller's parameters before prep_sink_sweep's share.
@@ -2703,6 +2716,86 @@ int d2d_get_field_position_vjp(d2d_ctx* c, float* cell_bar, float* fixed_terms, 
     const d2d_ctx::PosGrad& r = c->pg;
     const size_t bytes = 2 * (size_t)c->m * (size_t)c->n * sizeof(float);
     return copy_out(c, {{cell_bar, r.cell.p, bytes}, {fixed_terms, r.terms.p, bytes}, {fixed_bar, r.out.p, 2 * sizeof(double)}});
+}
+
+// Wall adjoint of the frequency response: ONE preparation of the culled sweep with the caller's own path function, one pass per
+// block of POS_CHUNK wavelengths into the per-patch rows -- zeroed in front of the first pass, carried from pass to pass -- then the
+// fixed-order fp64 reduction of the rows.  The cotangents are copied before the call returns.
+int d2d_field_walls_vjp_launch(d2d_ctx* c, const d2d_params* p, const float* fixed, const float* inv_wavelength, int32_t nf, int32_t amplitude,
+                               const float* re_bar, const float* im_bar) {
+    if (!c || !fixed || !inv_wavelength || !re_bar || !im_bar) return fail(D2D_ERR_INVALID, "NULL argument");
+    SinkLaunch<d2d_ctx::WallGrad> L(c, WALL_VJP, c->wg, fixed);
+    d2d_ctx::WallGrad& r = c->wg;
+    std::string err;
+    int rc;
+    if ((rc = L.begin(p, [&] {
+            if (!p->approx) return (int)D2D_OK;
+            return fail(D2D_ERR_UNSUPPORTED,
+                        "%s covers hard validity only: a smoothed validity (hard_sigmoid, sigmoid) depends on the walls' end points itself, and its term needs "
+                        "the reverse chain of the value+grad sweep (d2d_power_map_vg_launch); a gradient without that term is not offered",
+                        WALL_VJP.who);
+        })))
+        return rc;
+    if ((rc = d2d_host::wallgrad_params(inv_wavelength, nf, amplitude, err))) return fail(rc, "%s: %s", WALL_VJP.who, err.c_str());
+    if ((rc = L.device())) return rc;
+    const size_t cells = L.cells, N = (size_t)c->N, tiles = (size_t)L.s.tiles;
+    if (!d2d_host::wall_vjp_fits(cells, nf, tiles, N, L.mem_free, r.bytes()))
+        return fail(D2D_ERR_UNSUPPORTED, "%s: cotangents of %zu cells (%zu bytes per cell) and %zu rows of %zu pairs of partial sums exceed half of the free device memory (%zu bytes free)",
+                    WALL_VJP.who, cells, 8 * (size_t)nf, tiles, N, L.mem_free);
+    if ((rc = L.prepare())) return rc;
+    const size_t planes = (size_t)nf * cells, row = 2 * N;
+    if ((rc = r.re.ensure(planes)) || (rc = r.im.ensure(planes)) || (rc = r.partial.ensure(tiles * row)) || (rc = r.out.ensure(row))) return rc;
+    HIP_TRY(hipMemcpyAsync(r.re.p, re_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.im.p, im_bar, planes * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays are free again when the call returns
+    if (N > 0 && tiles > 0 && cells > 0) {
+        HIP_TRY(hipMemsetAsync(r.partial.p, 0, tiles * row * sizeof(float), c->stream));
+        for (int32_t i = 0; i < d2d_host::chunks(nf, d2d::POS_CHUNK); ++i) {
+            const d2d_host::Chunk ch = d2d_host::chunk_plan(nf, i, d2d::POS_CHUNK);
+            d2d::WallGradArgs g;
+            g.re_bar = r.re.p + (size_t)ch.first * cells;
+            g.im_bar = r.im.p + (size_t)ch.first * cells;
+            g.refl = c->d_refl.p;
+            g.X = c->d_X.p;
+            g.Y = c->d_Y.p;
+            g.partial = r.partial.p;
+            g.cells = (long)cells;
+            for (int32_t j = 0; j < d2d::POS_CHUNK; ++j) g.inv[j] = j < ch.count ? inv_wavelength[ch.first + j] : 0.0f;
+            g.nf = ch.count;
+            g.N = c->N;
+            g.amplitude = amplitude;
+            g.fun_id = L.pp.fun_id;
+            g.h2 = L.s.a.h2;
+            g.txg = L.s.txg ? 1 : 0;
+            g.fx = fixed[0];
+            g.fy = fixed[1];
+            HIP_TRY(L.pass<d2d::WallGradSink>(g));
+        }
+        hipLaunchKernelGGL(d2d::vjp_reduce_kernel, dim3((unsigned)row), dim3(256), 0, c->stream, r.partial.p, (long)tiles, (int)row, r.out.p, 0);
+        HIP_TRY(hipGetLastError());
+    } else {  // a sweep without a patch, or a scene without walls
+        HIP_TRY(hipMemsetAsync(r.out.p, 0, (row ? row : 1) * sizeof(double), c->stream));
+    }
+    r.have = true;
+    return D2D_OK;
+}
+
+int d2d_get_field_walls_vjp(d2d_ctx* c, double* walls_bar, double* normal_bar) {
+    if (int rc = result_state(c, c && c->have_scene && c->wg.have && c->wg.out.p, WALL_VJP, "result goes with the grid and the scene")) return rc;
+    const size_t N = (size_t)c->N;
+    if (N == 0 || (!walls_bar && !normal_bar)) return copy_out(c, {});
+    // normal_bar, then walls_bar[w][e][d] = normal_bar[w][e] * (double)n_w[d] + 0.0 from the fp32 normals of the device's wall table
+    std::vector<double> nb(2 * N);
+    std::vector<float4> refl(walls_bar ? 2 * N : 0);
+    if (int rc = copy_out(c, {{nb.data(), c->wg.out.p, 2 * N * sizeof(double)}, {walls_bar ? refl.data() : nullptr, c->d_refl.p, 2 * N * sizeof(float4)}})) return rc;
+    if (normal_bar) memcpy(normal_bar, nb.data(), 2 * N * sizeof(double));
+    if (walls_bar)
+        for (size_t w = 0; w < N; ++w)
+            for (int e = 0; e < 2; ++e) {
+                walls_bar[4 * w + 2 * e] = nb[2 * w + e] * (double)refl[2 * w].z + 0.0;  // (+ 0.0: a zero product is +0.0)
+                walls_bar[4 * w + 2 * e + 1] = nb[2 * w + e] * (double)refl[2 * w].w + 0.0;
+            }
+    return D2D_OK;
 }
 
 // Power-angle build: ONE pass into the zeroed planes, every lane storing its cell's total at the end.
@@ -3246,6 +3339,23 @@ int d2d_selftest_posgrad(d2d_ctx* c, int32_t fun_id, int32_t amplitude, const fl
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     float* out[5] = {a, rho, kr, g, G};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return D2D_OK;
+}
+
+int d2d_selftest_wallgrad(d2d_ctx* c, const float* const* in, int64_t n, float* qx, float* qy, float* Wa, float* Wb, float* ok) {
+    if (!c || !in || !qx || !qy || !Wa || !Wb || !ok || n <= 0) return fail(D2D_ERR_INVALID, "bad argument");
+    for (int k = 0; k < 12; ++k)
+        if (!in[k]) return fail(D2D_ERR_INVALID, "bad argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    DevBuf<float> din, dout;  // twelve inputs, five outputs, n each
+    if ((rc = din.ensure(12 * (size_t)n)) || (rc = dout.ensure(5 * (size_t)n))) return rc;
+    for (int k = 0; k < 12; ++k) HIP_TRY(hipMemcpy(din.p + (size_t)k * (size_t)n, in[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(d2d::selftest_wallgrad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, din.p, dout.p, (long)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float* out[5] = {qx, qy, Wa, Wb, ok};
     for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpy(out[k], dout.p + (size_t)k * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return D2D_OK;
 }

@@ -396,6 +396,34 @@ inline size_t posgrad_bytes_per_cell(int32_t nf) { return nf < 1 || nf > D2D_FRE
 // One pass of the sink kernel per POS_CHUNK wavelengths (chunk_plan); the block size is part of the definition (include/d2d.h).
 constexpr int32_t POS_CHUNK = D2D_POS_CHUNK;  // = d2d::POS_CHUNK (d2d_posgrad.hpp)
 
+// ---- parameters and memory of the frequency response's wall adjoint (d2d_field_walls_vjp_launch, d2d::WallGradSink) ----
+// D2D_ERR_INVALID, as the position adjoint: nf outside 1 .. D2D_FREQ_MAX, an entry that is negative, NaN or infinite (the message
+// names its index; 0 is allowed), an amplitude mode that is neither D2D_FIELD_AMP_SQRT nor D2D_FIELD_AMP_LINEAR.  The list is not
+// read unless nf is in range.  (The passes are POS_CHUNK's: the block's dL/dr is the position adjoint's.)
+inline int wallgrad_params(const float* inv_wavelength, int32_t nf, int32_t amplitude, std::string& err) {
+    const char* noun = "the wall adjoint";
+    if (nf < 1 || nf > D2D_FREQ_MAX)
+        return err = std::string(noun) + " needs nf in 1 .. " + std::to_string(D2D_FREQ_MAX) + ", got " + std::to_string(nf), D2D_ERR_INVALID;
+    for (int32_t j = 0; j < nf; ++j)
+        if (int rc = check_inv_wavelength(noun, inv_wavelength[j], err)) return err += " at index " + std::to_string(j), rc;
+    return check_amplitude(noun, amplitude, err);
+}
+// The cotangent planes take 8 nf bytes per cell and the partial rows 8 bytes per patch and wall (two floats: the wall's two end
+// points).  Refused like the coefficient adjoint: above half of the device memory that is free, counting what the buffers hold
+// already as free.  No product is formed that could wrap: each share is held against a quotient of what the budget has left
+// (tests/native/field_walls_vjp_host.cpp).  An nf below 1 never fits.
+inline bool wall_vjp_fits(size_t cells, int32_t nf, size_t patches, size_t n_objects, size_t mem_free, size_t held_bytes) {
+    if (nf < 1) return false;
+    size_t budget = mem_free / 2 + held_bytes / 2;
+    const size_t per_cell = 8 * (size_t)nf;
+    if (cells > budget / per_cell) return false;
+    budget -= cells * per_cell;
+    if (patches == 0 || n_objects == 0) return true;
+    const size_t rows = budget / (2 * sizeof(float));
+    if (patches > rows) return false;
+    return n_objects <= rows / patches;
+}
+
 // ---- memory of the material response's permittivity adjoint (d2d_material_eps_vjp_launch, d2d::EpsGradSink) ------------
 // The cotangent planes take 8 nf bytes per cell, the permittivity table 8 nf bytes per object, the partial rows of one chunk
 // 4 * MAT_CHUNK * 2 bytes per patch and object and the fp64 result 16 nf bytes per object.  Refused like its siblings: above half of

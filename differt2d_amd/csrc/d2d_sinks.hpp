@@ -14,6 +14,7 @@
 #include "d2d_fresnel.hpp"
 #include "d2d_fresnel_grad.hpp"
 #include "d2d_posgrad.hpp"
+#include "d2d_wallgrad.hpp"
 
 namespace d2d {
 
@@ -1096,6 +1097,97 @@ struct EpsGradSink {
     __device__ __forceinline__ void end(const EpsGradArgs&, long, int) const {}
 };
 
+// WallGradSink (d2d_field_walls_vjp_launch): the reverse-mode product of the frequency response with respect to the two end points
+// of every wall, for up to POS_CHUNK wavelengths of one sweep (include/d2d.h holds the definition, d2d_wallgrad.hpp its per-bounce
+// arithmetic, d2d_posgrad.hpp dL/dr).  Hard validity only: a wall then enters through the path length alone, and
+// d r / d A = gam (1 - s) n, d r / d B = gam s n for every bounce on the wall (the interaction points are stationary).  EpsGradSink's
+// front: the walls out of the wave-uniform code (readfirstlane), their two table rows refl[2 w], refl[2 w + 1] read at wave-uniform
+// addresses (scalar loads), k == 0 || no_contribution as the wave-uniform exit.  PosGradSink's cotangents: begin() is load_cotangents,
+// and every contributing lane forms G = dL/dr of the path for this block (posgrad_amp / _rho / _kr / _fold).  CoefGradSink's back: per
+// bounce, the lane's weights (wallgrad_bounce; the bounce point q is rebuilt from p[0] and the segments that seg_out hands out)
+// forced to 0.0f in lanes that do not contribute, wave_sum in wave-uniform control flow, and lane 0 adds the two sums to the patch's
+// row partial[patch][w][0..1] with a plain load-add-store: one writer per row, candidates and bounces in order, no atomics -- the same
+// bits run to run.  The rows are zeroed on the stream in front of the first block's launch, accumulate over the blocks' launches and
+// are reduced in patch order into fp64 by vjp_reduce_kernel.  i and j are compile-time indices behind the wave-uniform guards i < k
+// and j < nf.  p[0] is the transmitter: `fixed` on an RX grid, the lane's cell on a TX grid (begin() loads X[cell], Y[cell]; cell <
+// cells).  Wall indices come from the sweep's own candidates, 0 <= w < N, so 2 w + 1 < 2 N: inside the table and inside a row.
+struct WallGradArgs {
+    const float* re_bar;   // [nf][cells]: this block's cotangent planes
+    const float* im_bar;   // [nf][cells]
+    const float4* refl;    // the context's wall table: row 2 w = {ox, oy, nx, ny}, row 2 w + 1 = {tx, ty, sq, len}
+    const float* X;        // [cells] the grid (read on a TX grid only)
+    const float* Y;        // [cells]
+    float* partial;        // [patches][N][2] per-patch sums, zeroed in front of the first block
+    long cells;            // m * n
+    float inv[POS_CHUNK];  // turns per unit length, finite and >= 0; entries at and past nf are not read
+    int nf;                // 1 .. POS_CHUNK
+    int N;                 // walls: a row holds 2 N floats
+    int amplitude;         // D2D_FIELD_AMP_SQRT / D2D_FIELD_AMP_LINEAR
+    int fun_id;            // the caller's fused path function
+    float h2;              // height * height, as the sweep has it
+    int txg;               // the cell is the transmitter
+    float fx, fy;          // the fixed end point
+};
+static_assert(sizeof(SweepArgs) + sizeof(WallGradArgs) <= 4096, "power_sink_kernel's arguments must fit the 4 KiB kernel-argument segment");
+struct WallGradSink {
+    using Args = WallGradArgs;
+    static constexpr bool WANTS_R = true, WANTS_DIR = false, WANTS_SEG = true;
+    float rb[POS_CHUNK], ib[POS_CHUNK];
+    const WallGradArgs* x;  // the kernel argument: wave-uniform, read where it is used
+    float* row;             // partial[tile]
+    float px, py;           // p[0] of this lane's paths
+    bool live;              // cell >= 0
+    __device__ __forceinline__ void begin(const WallGradArgs& xa, long tile, int lane_cell) {
+        live = lane_cell >= 0;
+        load_cotangents(xa.re_bar, xa.im_bar, xa.cells, xa.nf, lane_cell, rb, ib);
+        x = &xa;
+        row = xa.partial + (size_t)tile * 2 * (size_t)xa.N;
+        px = xa.fx;
+        py = xa.fy;
+        if (xa.txg != 0 && live) {
+            px = xa.X[lane_cell];
+            py = xa.Y[lane_cell];
+        }
+    }
+    // seg: (p[i+1] - p[i]) for i < k of the candidate (stale or zero where its contribution is zero)
+    __device__ __forceinline__ void put_seg(float t, unsigned long long code, int k, float r, const float (&seg)[2 * D2D_MAX_ORDER]) {
+        bool p;
+        if (k == 0 || no_contribution(t, p)) return;  // wave-uniform (the line of sight touches no wall)
+        // per lane: dL/dr of this path for this block
+        float G = 0.0f;
+        if (p) {
+            const float a = posgrad_amp(x->amplitude, t);
+            const float kr = posgrad_kr(x->amplitude, posgrad_rho(x->fun_id, x->h2, r));
+            const int nf = x->nf;
+            float g = 0.0f;
+            static_for<0, POS_CHUNK>([&](auto JJ) {
+                constexpr int J = decltype(JJ)::value;
+                if (J < nf) g = posgrad_fold(g, kr, r, x->inv[J], rb[J], ib[J]);
+            });
+            G = a * g;
+        }
+        const bool go = p && live;  // (per lane: it becomes zero weights, never an exit)
+        const bool lane0 = (threadIdx.x & 63) == 0;
+        float qx = px, qy = py;
+        static_for<0, D2D_MAX_ORDER>([&](auto II) {
+            constexpr int I = decltype(II)::value;
+            if (I < k) {
+                const int w = __builtin_amdgcn_readfirstlane((int)((code >> (12 * I)) & 0xfffull));
+                const float4 on = ldc4(x->refl, 2 * w), tt = ldc4(x->refl, 2 * w + 1);
+                float Wa, Wb;
+                const bool ok = wallgrad_bounce(G, qx, qy, seg[2 * I], seg[2 * I + 1], on.x, on.y, on.z, on.w, tt.x, tt.y, tt.z, Wa, Wb);
+                const bool count = go && ok;
+                const float Sa = wave_sum(count ? Wa : 0.0f), Sb = wave_sum(count ? Wb : 0.0f);  // every lane of the wave is here: the exits above are wave-uniform
+                if (lane0) {
+                    row[2 * w] = row[2 * w] + Sa;
+                    row[2 * w + 1] = row[2 * w + 1] + Sb;
+                }
+            }
+        });
+    }
+    __device__ __forceinline__ void end(const WallGradArgs&, long, int) const {}
+};
+
 // One candidate into a sink: a WANTS_SEG sink takes put_seg (the contribution, the candidate's code and order, the length and the
 // segments that reach its bounces), a sink that wants both the length and the directions takes put_rd, a WANTS_DIR sink the
 // contribution with the path's end directions, every other one the contribution with the candidate's code, order and length
@@ -1262,6 +1354,22 @@ __global__ void selftest_posgrad_kernel(const float* __restrict__ in, float* __r
     out[3 * n + i] = g;
     out[4 * n + i] = a * g;
 }
+
+// the wall adjoint's per-bounce arithmetic (d2d_wallgrad.hpp) on the device, for comparison with its host build
+// (tests/test_gpu_field_walls_vjp.py): in = G, qx, qy, sx, sy, ox, oy, nx, ny, tx, ty, sq and out = qx, qy after the bounce, Wa, Wb,
+// ok (1 or 0), n values each
+__global__ void selftest_wallgrad_kernel(const float* __restrict__ in, float* __restrict__ out, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float qx = in[n + i], qy = in[2 * n + i], Wa, Wb;
+    const bool ok = wallgrad_bounce(in[i], qx, qy, in[3 * n + i], in[4 * n + i], in[5 * n + i], in[6 * n + i], in[7 * n + i], in[8 * n + i], in[9 * n + i],
+                                    in[10 * n + i], in[11 * n + i], Wa, Wb);
+    out[i] = qx;
+    out[n + i] = qy;
+    out[2 * n + i] = Wa;
+    out[3 * n + i] = Wb;
+    out[4 * n + i] = ok ? 1.0f : 0.0f;
+}
 #endif  // D2D_AUX_KERNELS
 
 // ---- the launchers (host) ----
@@ -1282,7 +1390,8 @@ __global__ void selftest_posgrad_kernel(const float* __restrict__ in, float* __r
     X(BeamSink)      /* the beam-space response */                                                            \
     X(MaterialSink)  /* the frequency response with Fresnel reflection per wall */                           \
     X(EpsGradSink)   /* its adjoint w.r.t. the walls' permittivities */                                       \
-    X(PosGradSink)   /* the frequency response's adjoint w.r.t. the cell's and the fixed end point's position */
+    X(PosGradSink)   /* the frequency response's adjoint w.r.t. the cell's and the fixed end point's position */ \
+    X(WallGradSink)  /* the frequency response's adjoint w.r.t. the walls' end points */
 template <int MODE, class Sink>
 hipError_t launch_sink_m(bool txg, int max_order, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a, const typename Sink::Args& x);
 #define D2D_DECLARE_SINK(S)                                                                                                      \

@@ -102,6 +102,13 @@ class PositionGradient(NamedTuple):
     fixed_bar: np.ndarray    # float64 [2]: dL / d (fixed end point), the fixed-order sum of fixed_terms over the cells
 
 
+class WallGradient(NamedTuple):
+    """Result of :meth:`Context.field_walls_vjp` (include/d2d.h: d2d_field_walls_vjp_launch)."""
+
+    walls_bar: np.ndarray   # float64 [N, 2, 2]: dL / d (end point e of wall w), normal_bar[w, e] times the wall's fp32 unit normal
+    normal_bar: np.ndarray  # float64 [N, 2]: the sensitivity of L to moving end point A or B of wall w along the wall's unit normal
+
+
 class PowerAngleProfile(NamedTuple):
     """Result of :meth:`Context.power_angle` (include/d2d.h: d2d_power_angle_launch)."""
 
@@ -962,6 +969,52 @@ class Context:
         L.check(self._lib.d2d_get_field_position_vjp(self._ctx, *(a.ctypes.data_as(C.c_void_p) for a in (cell, terms, bar))))
         # (views of the library's [2][m][n] planes: no copy on the host)
         return PositionGradient(cell_bar=np.moveaxis(cell, 0, -1), fixed_terms=np.moveaxis(terms, 0, -1), fixed_bar=bar)
+
+    def field_walls_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt") -> "WallGradient":
+        """The reverse-mode product of :meth:`frequency_response` with respect to the end points of every wall: for a loss ``L``
+        with ``dL = sum (re_bar * d re + im_bar * d im)``, the gradient with respect to the two end points of every object of
+        the resident scene, from ONE preparation of the culled sweep and one kernel pass per 8 wavelengths (include/d2d.h:
+        d2d_field_walls_vjp_launch holds the definition).  Hard validity only: a wall then enters through the path length alone,
+        and the interaction points are stationary.  The arguments are those of :meth:`field_position_vjp`.  A refused launch
+        leaves the previous result readable.  The resident value and gradient maps, the scene VJP of :meth:`launch_vg` and the
+        other products' results are not touched.
+
+        Returns a :class:`WallGradient`: ``normal_bar``, float64 ``[N, 2]``, the sensitivity of ``L`` to moving end point ``A``
+        or ``B`` of a wall along the wall's unit normal, and ``walls_bar``, float64 ``[N, 2, 2]`` (the layout of
+        :meth:`get_scene_vjp`'s ``objects_bar``), ``normal_bar`` times the wall's fp32 unit normal.  Fixed-order sums: the same
+        bits run to run, within a derived bound of a float64 evaluation.  :func:`differt2d_amd.utils.field_misfit` gives the
+        cotangents of a least-squares fit to a measured channel (wall localisation)."""
+        self.launch_field_walls_vjp(params, fixed, inv_wavelengths, re_bar, im_bar, amplitude)
+        return self.get_field_walls_vjp()
+
+    def launch_field_walls_vjp(self, params: L.Params, fixed, inv_wavelengths, re_bar, im_bar, amplitude="sqrt"):
+        """The launch of :meth:`field_walls_vjp` alone (the list and the cotangents are copied by the call; the kernels are
+        asynchronous, like :meth:`launch`)."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.float32).reshape(2)
+        inv = np.ascontiguousarray(inv_wavelengths, dtype=np.float32).reshape(-1)
+        amplitude = _amplitude_id("field_walls_vjp", amplitude)
+        keep = _keep_pointer(inv, 1)
+        rb, ib = _cotangent_planes("field_walls_vjp", re_bar, im_bar, int(inv.size), self.shape, keep)
+        L.check(self._lib.d2d_field_walls_vjp_launch(self._ctx, C.byref(params), fixed, keep.ctypes.data_as(C.c_void_p), int(inv.size),
+                                                     amplitude, rb.ctypes.data_as(C.c_void_p), ib.ctypes.data_as(C.c_void_p)))
+
+    def get_field_walls_vjp(self) -> "WallGradient":
+        """Synchronises and returns the result of the last :meth:`launch_field_walls_vjp` that was accepted."""
+        n = self.n_objects
+        walls, normal = np.zeros((max(n, 1), 2, 2), np.float64), np.zeros((max(n, 1), 2), np.float64)
+        L.check(self._lib.d2d_get_field_walls_vjp(self._ctx, walls.ctypes.data_as(C.c_void_p), normal.ctypes.data_as(C.c_void_p)))
+        return WallGradient(walls_bar=walls[:n], normal_bar=normal[:n])
+
+    def selftest_wallgrad(self, G, qx, qy, sx, sy, ox, oy, nx, ny, tx, ty, sq):
+        """``(qx, qy, Wa, Wb, ok)`` of d2d_wallgrad.hpp's ``wallgrad_bounce`` on the device (include/d2d.h: d2d_selftest_wallgrad):
+        twelve arrays of one size."""
+        cols = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (G, qx, qy, sx, sy, ox, oy, nx, ny, tx, ty, sq)]
+        if len({c.size for c in cols}) != 1:
+            raise ValueError("selftest_wallgrad: arrays of one size")
+        ptrs = (C.c_void_p * 12)(*(c.ctypes.data for c in cols))
+        outs = [np.empty_like(cols[0]) for _ in range(5)]
+        L.check(self._lib.d2d_selftest_wallgrad(self._ctx, ptrs, cols[0].size, *outs))
+        return tuple(outs)
 
     def selftest_posgrad(self, fun_id: int, amplitude, t, r, h2, inv, rb, ib):
         """``(a, rho, kr, g, G)`` of d2d_posgrad.hpp on the device (include/d2d.h: d2d_selftest_posgrad): ``inv``, ``rb`` and ``ib`` are

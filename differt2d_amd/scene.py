@@ -1430,7 +1430,8 @@ class Scene(Plottable):
         ``(X[i, j], Y[i, j])``, ``fixed_terms[i, j]`` that cell's share of the gradient with respect to the transmitter, both fp32
         ``[m, n, 2]``, and ``fixed_bar`` their float64 sum ``[2]``, from one sweep per 8 wavelengths (include/d2d.h:
         d2d_field_position_vjp_launch holds the definition and what is exact about it).  Not computed: gradients with respect to
-        wall end points or the wavelengths, smoothed validity, the array, beam and material variants; one GPU."""
+        the wavelengths, smoothed validity, the array, beam and material variants; one GPU.  (Gradients with respect to the wall
+        end points: :meth:`frequency_response_walls_vjp_on_receivers_grid`.)"""
         return self._grid_response_position_vjp(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, re_bar, im_bar, wavelengths,
                                                 inv_wavelengths, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
 
@@ -1444,6 +1445,57 @@ class Scene(Plottable):
         TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
         return self._grid_response_position_vjp(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, re_bar, im_bar, wavelengths,
                                                 inv_wavelengths, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def _grid_response_walls_vjp(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, re_bar, im_bar, wavelengths, inv_wavelengths,
+                                 amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs):
+        """The two wall adjoints of the frequency response: one launch per fixed end point."""
+        convert = self._inverse_wavelengths("the frequency response", wavelengths, inv_wavelengths)
+        bar_of = lambda bar, pt_name: bar[pt_name] if isinstance(bar, Mapping) else bar
+
+        def prepare():
+            if logic._resolve(kwargs.get("approx")):
+                raise L.D2DUnsupported(-4, "the wall adjoint covers hard validity only (approx=False): a smoothed validity depends on "
+                                           "the walls' end points itself, and its term needs the reverse chain of the value+grad sweep")
+            inv = convert()
+            return lambda ctx, params, name, xy: ctx.field_walls_vjp(params, xy, inv, bar_of(re_bar, name), bar_of(im_bar, name), amplitude)
+
+        return self._grid_product(
+            X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, path_cls, min_order, max_order, order, filter_objects, kwargs,
+            f"fun={fun!r} is not fused natively: the wall adjoint needs the path function's derivative with "
+            "respect to the path length, which the library knows for the fused functions only (a function "
+            "from differt2d_amd.utils)",
+            "the wall adjoint covers", prepare)
+
+    def frequency_response_walls_vjp_on_receivers_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """The gradient of a loss on :meth:`frequency_response_on_receivers_grid` with respect to the end points of every wall:
+        what a fit of the walls' positions to a measured channel descends along (scene reconstruction, wall localisation).
+        ``re_bar`` and ``im_bar`` are the loss's derivatives with respect to the planes ``re`` and ``im``, ``[nf, m, n]``
+        (:func:`differt2d_amd.utils.field_misfit` gives them for a least-squares fit) -- one pair for every transmitter, or
+        mappings from the transmitters' names to their pairs.  ``fun`` (every fused function, ``received_power_per_object`` with
+        its coefficients included), ``fun_kwargs``, the wavelengths, ``amplitude`` and the path class are those of the forward
+        method; the validity must be hard (``approx=False``), anything else raises :class:`D2DUnsupported`.  Yields ``(tx name,
+        WallGradient(walls_bar, normal_bar))`` (:class:`differt2d_amd.engine.WallGradient`): ``normal_bar[w, e]`` is the
+        sensitivity of the loss to moving end point ``e`` of object ``w`` along the wall's unit normal, float64
+        ``[len(objects), 2]``, and ``walls_bar[w, e]`` that times the normal, float64 ``[len(objects), 2, 2]`` -- the gradient with
+        respect to ``objects[w].xys`` -- from one sweep per 8 wavelengths (include/d2d.h: d2d_field_walls_vjp_launch holds the
+        definition and what is exact about it).  The transmitters' results add up to the gradient of the summed loss.  Not
+        computed: smoothed validity, the array, beam and material variants, RIS angles; one GPU."""
+        return self._grid_response_walls_vjp(X, Y, list(self.transmitters.items()), True, fun, fun_kwargs, re_bar, im_bar, wavelengths,
+                                             inv_wavelengths, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
+
+    def frequency_response_walls_vjp_on_transmitters_grid(
+        self, X, Y, fun: PathFun, fun_kwargs: Optional[Mapping], re_bar, im_bar, *, wavelengths=None, inv_wavelengths=None,
+        amplitude: str = "sqrt", path_cls: type = ImagePath, min_order: int = 0, max_order: int = 1, order: Optional[int] = None,
+        filter_objects: Optional[Callable[[Object], bool]] = None, **kwargs,
+    ):
+        """Transmitter-grid twin of :meth:`frequency_response_walls_vjp_on_receivers_grid`: one result per receiver, the
+        transmitter sits at ``(X[i, j], Y[i, j])``; only where the TX-grid sweep is culled (include/d2d.h: d2d_params.grid_role)."""
+        return self._grid_response_walls_vjp(X, Y, list(self.receivers.items()), False, fun, fun_kwargs, re_bar, im_bar, wavelengths,
+                                             inv_wavelengths, amplitude, path_cls, min_order, max_order, order, filter_objects, kwargs)
 
     def _grid_angle(self, X, Y, fixed_items, grid_is_rx, fun, fun_kwargs, at, nbins, origin, path_cls, min_order, max_order, order,
                     filter_objects, kwargs):

@@ -32,8 +32,9 @@ extern "C" {
                               d2d_get_power_angle, d2d_array_response_launch / d2d_get_array_response,
                               d2d_array_frequency_response_launch / d2d_get_array_frequency_response,
                               d2d_beam_response_launch / d2d_get_beam_response, d2d_material_response_launch /
-                              d2d_get_material_response, d2d_material_eps_vjp_launch / d2d_get_material_eps_vjp and
-                              d2d_field_position_vjp_launch / d2d_get_field_position_vjp are
+                              d2d_get_material_response, d2d_material_eps_vjp_launch / d2d_get_material_eps_vjp,
+                              d2d_field_position_vjp_launch / d2d_get_field_position_vjp and
+                              d2d_field_walls_vjp_launch / d2d_get_field_walls_vjp are
                               additive: no struct, enum or existing entry point changed with them, so the version did not) */
 
 typedef enum d2d_status {
@@ -1149,8 +1150,8 @@ int d2d_selftest_fresnel_grad(d2d_ctx* ctx, const float* er, const float* ei, co
  * left that term out would be a trap, so it is refused, not approximated -- and what d2d_frequency_response_launch refuses, with
  * 8 * nf + 16 bytes per cell held against half of the free device memory.  All decided before anything is enqueued; a refused launch
  * leaves the previous result readable.
- * Not computed: gradients with respect to wall end points, hard_sigmoid validity, the array, beam and material variants (where the
- * angle of incidence also moves), gradients with respect to the wavelengths, more than one GPU. */
+ * Not computed: hard_sigmoid validity, the array, beam and material variants (where the angle of incidence also moves), gradients
+ * with respect to the wavelengths, more than one GPU.  (Gradients with respect to wall end points: d2d_field_walls_vjp_launch.) */
 int d2d_field_position_vjp_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
                                   const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude,
                                   const float* re_bar /* [nf][m][n] */, const float* im_bar /* [nf][m][n] */);
@@ -1164,6 +1165,77 @@ int d2d_get_field_position_vjp(d2d_ctx* ctx, float* cell_bar /* [2][m][n] or NUL
 int d2d_selftest_posgrad(d2d_ctx* ctx, int32_t fun_id, int32_t amplitude, const float* t, const float* r, const float* h2, const float* inv0,
                          const float* inv1, const float* rb0, const float* rb1, const float* ib0, const float* ib1, int64_t n, float* a,
                          float* rho, float* kr, float* g, float* G);
+
+/* ---- wall end-point gradients of the frequency response: its reverse-mode product with respect to the two end points of every
+ *      wall (K3-V; scene reconstruction and wall localisation against a measured complex channel H_meas(f_j, cell); additive
+ *      entry points, the ABI version did not change) --------------------------------------------------------------------------- */
+
+/* Launches the wall adjoint of the frequency response for the fixed end point `fixed` on the ctx stream, for the current scene,
+ * candidate mask and grid.
+ * K3-V `d2d::WallGradSink`, definition:
+ *
+ * - The arguments of the wall adjoint are exactly those of `d2d_field_position_vjp_launch`: `params`, `fixed[2]`, the role of the grid, `inv_wavelength[nf]` (`nf` in `1..D2D_FREQ_MAX`, each entry finite and `>= 0`), `amplitude`, and the cotangent planes `re_bar`, `im_bar`.
+ * - The cotangents are host arrays, fp32 `[nf][m][n]`. They are copied before the call returns.
+ * - Validity is hard only (`params.approx == 0`). Every fused `fun_id` is accepted; `RECEIVED_POWER_PER_OBJECT` needs its coefficients set.
+ * - For hard validity and image paths a wall enters the response through the path length `r` alone: validity is piecewise constant, every fused `fun` depends on `r` only, and per-object coefficients do not depend on geometry.
+ * - The interaction points are stationary (Fermat), so the total derivative with respect to a wall's end points is the partial derivative at a fixed position along the wall.
+ * - Take bounce `i` on wall `w` with end points `A`, `B`, `T = B − A`, and unit normal `n = normalize((T_y, −T_x))`, which is `refl[2w].zw` of the wall table. With `u_in = unit(p[i] − p[i−1])` and the relative position `s = ((p[i] − A)·T)/|T|²`: `∂r/∂A = γ (1 − s) n`, `∂r/∂B = γ s n`, `γ = 2 (u_in · n)`. The sign of `n` cancels.
+ * - The result is for `dL = Σ (re_bar·dre + im_bar·dim)`, with `re`, `im` those of `d2d_frequency_response_launch` for the same arguments. There are two outputs.
+ * - `normal_bar[w][0..1]`, fp64: `Σ_cells Σ_paths Σ_bounces on w` of `G·γ·(1−s)` and of `G·γ·s`. This is the sensitivity of `L` to moving end point `A` or `B` of wall `w` along the wall's unit normal.
+ * - `walls_bar[w][e][d] = normal_bar[w][e] · (double)n_w[d]`, fp64 `[N][2][2]`. This is the layout of `d2d_get_scene_vjp`'s `xys_bar`. The getter forms it in fp64 from the fp32 normals of the wall table, and adds `+ 0.0`: a zero product is `+0.0` whatever the normal's sign.
+ *
+ * All arithmetic is fp32, one rounding per stated operation, no contraction. Blocks hold `D2D_POS_CHUNK = 8` wavelengths. `G` rounds once per block, as in K3-X. Per contribution:
+ *
+ *     for blocks of POS_CHUNK wavelengths, in list order:
+ *       for candidates in the sweep's enumeration order (walls cand[0..K), K >= 1; the line of sight adds nothing):
+ *         t = valid * fun ; r = path_length(points) ; seg[i] = p[i+1] − p[i], i < K      // what MaterialSink gets
+ *         if (t == 0) continue
+ *         G = posgrad_amp(..) * fold of posgrad_fold over the block                      // d2d_posgrad.hpp, unchanged: dL/dr
+ *         q = p[0]                                   // the transmitter: `fixed` on an RX grid, the cell's (X, Y) on a TX grid
+ *         for i in 0..K-1:
+ *             q = q + seg[i]                         // componentwise: the bounce point, rebuilt from the hand-outs
+ *             (ux, uy, ok) = unit_dir(seg[i])        // d2d_steer.hpp, unchanged
+ *             {ox, oy, nx, ny} = refl[2w] ; {tx, ty, sq, _} = refl[2w+1] ,  w = cand[i]
+ *             gam = 2.0f * steer_dot(ux, uy, nx, ny)
+ *             s   = ((q.x − ox)*tx + (q.y − oy)*ty) / sq
+ *             wa  = G * gam ; Wb = wa * s ; Wa = wa − Wb          // Wa + Wb == wa: a rigid shift along n gets the whole term
+ *             if (ok) { row[w][0] += Wa ; row[w][1] += Wb }       // a wall that occurs twice in a candidate gets both terms
+ *     normal_bar = fixed-order fp64 sum of the per-patch rows
+ *
+ * - The bounce arithmetic (`q`, `gam`, `s`, `wa`, `Wa`, `Wb`, `ok`) is the text of `differt2d_amd/csrc/d2d_wallgrad.hpp`, which compiles for host and device.
+ * - A row is one 8 x 8 patch's fp32 sums: the contributing lanes' weights of one bounce are added over the patch's wave, and that sum is added to the row, candidates and bounces in order.
+ * - A zero-length wall has `n = (0,0)` in the table and therefore adds `±0`.
+ * - A bounce whose incoming segment has no unit vector adds nothing; `q` still advances.
+ * - Being a sum over cells, the result is defined to a derived bound against a float64 oracle, like K3-G and K3-E. It is not defined bit for bit.
+ * - The same call gives the same bits run to run, whatever ran before on the context.
+ * - All-zero cotangents give `+0.0` in every entry. Cotangents ×2 give exactly doubled entries. Appending a wavelength with zero planes changes no bit.
+ * - Walls that no contributing candidate touches are exactly `+0.0`. A sweep of order 0 alone gives all zeros.
+ * - A NaN contribution makes the entries of that candidate's walls NaN and no others.
+ *
+ * One preparation of the culled sweep and ceil(nf / D2D_POS_CHUNK) passes of one kernel: the cotangents of a block sit in registers,
+ * lane 0 of every patch's wave is the only writer of the patch's row [N][2], the rows are zeroed in front of the first pass and carried
+ * from pass to pass, and one fixed-order reduction sums them into fp64.  A sweep without a patch and a scene without walls leave zeros.
+ * The launch touches none of: the resident value / gradient maps, the scene VJP of d2d_power_map_vg_launch, the work history, the
+ * other products' results.
+ * D2D_ERR_INVALID: a NULL argument; nf outside 1 .. D2D_FREQ_MAX; an inv_wavelength entry that is negative, NaN or infinite (the
+ * message names its index); an unknown amplitude.
+ * D2D_ERR_UNSUPPORTED (the message names the reason): hard_sigmoid and sigmoid validity -- a smoothed validity depends on the walls'
+ * end points itself, and its term needs the reverse chain of the value+grad sweep (d2d_power_map_vg_launch, whose objects_bar has it
+ * for the incoherent map) -- and what d2d_frequency_response_launch refuses, with 8 * nf bytes per cell plus 8 bytes per patch and
+ * wall held against half of the free device memory.  All decided before anything is enqueued; a refused launch leaves the previous
+ * result readable.
+ * Not computed: hard_sigmoid / sigmoid validity, the array, beam and material variants (where the angle of incidence also moves),
+ * RIS angles, more than one GPU, D2D_OUT_ADD. */
+int d2d_field_walls_vjp_launch(d2d_ctx* ctx, const d2d_params* params, const float* fixed /* [2] */,
+                               const float* inv_wavelength /* [nf] */, int32_t nf, int32_t amplitude,
+                               const float* re_bar /* [nf][m][n] */, const float* im_bar /* [nf][m][n] */);
+/* Synchronises and copies the result of the last accepted d2d_field_walls_vjp_launch to the arrays that are not NULL.
+ * D2D_ERR_STATE before a launch and after a d2d_set_grid / d2d_set_scene of another grid or scene (the result goes with both). */
+int d2d_get_field_walls_vjp(d2d_ctx* ctx, double* walls_bar /* [N][2][2] or NULL */, double* normal_bar /* [N][2] or NULL */);
+/* The per-bounce arithmetic of d2d_wallgrad.hpp on the device, for comparison with its host build: in[12] = G, qx, qy, sx, sy, ox,
+ * oy, nx, ny, tx, ty, sq (n values each); for every i, wallgrad_bounce gives qx, qy after the bounce, Wa, Wb and ok as 1 / 0. */
+int d2d_selftest_wallgrad(d2d_ctx* ctx, const float* const* in /* [12] */, int64_t n, float* qx, float* qy, float* Wa, float* Wb,
+                          float* ok);
 
 /* ---- multi-GPU (one process per GPU; the reference has no multi-device code: its only batching is jax.vmap
  *      over the grid, differt2d/scene.py:1927-1932; RX rows are sharded over ranks and maps are assembled with one
